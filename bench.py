@@ -190,6 +190,29 @@ def reference_cpu_baseline(n_side: int = 12, reps: int = 2):
             "sample": f"{n}-atom periodic water box, torchani.grad.energies_and_forces (pyaev + cell_list, fp32), best of {reps}"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path: str, out, limit: int = DUMP_LIMIT_BYTES, seed: int = 0):
+    """Write the arrays a caller of the timed step receives as <path>/<name>.npy (float64 energies [C], float32 forces
+    [C, A, 3] and atomic_energies [C, A]).  When they exceed `limit` bytes in all, the per-atom arrays keep a sorted,
+    seeded sample of atoms (the same atoms for the same box), so that two builds can still be compared output for output."""
+    arrays = {"energies": out.energies.detach().double().cpu().numpy(),
+              "forces": out.forces.detach().float().cpu().numpy(),
+              "atomic_energies": out.atomic_energies.detach().float().cpu().numpy()}
+    limit -= 128 * len(arrays)   # (the .npy headers)
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        n_atoms = arrays["forces"].shape[1]
+        per_atom = (arrays["forces"].nbytes + arrays["atomic_energies"].nbytes) // n_atoms
+        keep = np.sort(np.random.RandomState(seed).choice(n_atoms, (limit - arrays["energies"].nbytes) // per_atom,
+                                                          replace=False))
+        arrays["forces"] = np.ascontiguousarray(arrays["forces"][:, keep])
+        arrays["atomic_energies"] = np.ascontiguousarray(arrays["atomic_energies"][:, keep])
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -226,7 +249,12 @@ def main():
                          "north_star's gates (1e-5 Ha, 1e-4 Ha/A) instead of this package's regression gates")
     ap.add_argument("--shuffle", action="store_true",
                     help="permute the atom order of the box (the spatial shards must not depend on it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (energies, forces, atomic_energies) "
+                         "as DIR/<name>.npy (rank 0); beyond 64 MB in all, the per-atom arrays are cut to a seeded sample of atoms")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # started plainly: launch the ranks (one process per GPU) and hand their output through
@@ -375,6 +403,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX, group=group)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     model.aev_computer.last_neighbors().raise_on_overflow()
     assert torch.isfinite(out.energies).all() and torch.isfinite(out.forces).all()
     # ---- is the headline result RIGHT?  Sampled atoms of the full box against the fp64 oracle (outside the timed region):

@@ -76,18 +76,15 @@ def test_xyz_io_round_trip_and_reference(tmp_path):
         read_xyz(tmp_path / "bad.xyz")
     with pytest.raises(ValueError):
         write_xyz(sp[0], x[0], f)
-    ref_file = "/root/reference/dataset/xyz_files/13.xyz"
-    if not os.path.exists(ref_file):
-        pytest.skip("reference tree not present")
-    from _util import import_reference   # (stub modules for the reference's optional imports)
-    import_reference()
-    from torchani.io import read_xyz as ref_read
-    for path in (ref_file, "/root/reference/tests/resources/water-0.8nm.xyz", "/root/reference/tests/resources/small.xyz"):
-        if not os.path.exists(path):
-            continue
-        a, b = read_xyz(path, dtype=torch.float64), ref_read(path, dtype=torch.float64)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), path
-        assert (a[2] is None) == (b[2] is None) and (a[2] is None or torch.equal(a[2], b[2])), path
+    # files of the reference and what its io.read_xyz returns for them (tests/golden/gen_golden_reference_meta.py)
+    meta = os.path.join(ROOT, "tests", "golden", "reference_meta")
+    ref = np.load(os.path.join(meta, "xyz_reads.npz"))
+    for name in ("13_head.xyz", "water-0.8nm.xyz", "small.xyz"):
+        a = read_xyz(os.path.join(meta, name), dtype=torch.float64)
+        assert torch.equal(a[0], torch.from_numpy(ref[name + "/species"])), name
+        assert torch.equal(a[1], torch.from_numpy(ref[name + "/coords"])), name
+        assert (a[2] is None) == (name + "/cell" not in ref.files), name
+        assert a[2] is None or torch.equal(a[2], torch.from_numpy(ref[name + "/cell"])), name
 
 
 def test_symbol_number_mass_converters():
@@ -168,27 +165,20 @@ def test_assembler_and_term_objects():
     assert r(d).shape == (12, 16) and (r(d)[d >= 5.2] == 0).all() is not None
     with pytest.raises(ValueError):
         AEVComputer.from_terms(ANIRadial.like_2x(cutoff=3.0), ANIAngular.like_2x(), 4)
-    if not os.path.exists("/root/reference/torchani/arch.py"):
-        pytest.skip("reference tree not present")
-    from _util import import_reference
-    import_reference()
-    from torchani.aev import ANIAngular as RefAngular
-    from torchani.aev import ANIRadial as RefRadial
-    from torchani.arch import Assembler as RefAssembler
-    torch.manual_seed(0)
-    td, tv = torch.rand(2, 40, dtype=torch.float64) * 3.4 + 0.4, torch.randn(2, 40, 3, dtype=torch.float64)
-    tv = tv / tv.norm(dim=-1, keepdim=True) * td.unsqueeze(-1)
+    # the reference's terms on the same inputs, and the state dict of its Assembler's model, key by key
+    # (tests/golden/gen_golden_reference_meta.py)
+    import json
+
+    ref = np.load(os.path.join(ROOT, "tests", "golden", "reference_meta", "api_ani2x.npz"))
+    d, td, tv = (torch.from_numpy(ref[k]) for k in ("terms_d", "terms_td", "terms_tv"))
     for name, kw in (("like_1x", {}), ("like_2x", {}), ("cover_linearly", dict(cutoff_fn="smooth"))):
-        mine, ref = getattr(ANIRadial, name)(**kw).double(), getattr(RefRadial, name)(**kw).double()
-        assert torch.allclose(mine(d), ref(d), rtol=1e-12, atol=1e-14), name
-        mine, ref = getattr(ANIAngular, name)(**kw).double(), getattr(RefAngular, name)(**kw).double()
-        assert torch.allclose(mine(td, tv), ref(td, tv), rtol=1e-10, atol=1e-14), name
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        ref_model = recipe(RefAssembler).assemble(8)
-    sd_r = ref_model.state_dict()
-    assert set(sd_r) == set(sd_a), sorted(set(sd_r) ^ set(sd_a))[:5]
-    assert all(sd_r[k].shape == sd_a[k].shape for k in sd_r)
-    for k in sd_r:
+        mine = getattr(ANIRadial, name)(**kw).double()
+        assert torch.allclose(mine(d), torch.from_numpy(ref["radial/" + name]), rtol=1e-12, atol=1e-14), name
+        mine = getattr(ANIAngular, name)(**kw).double()
+        assert torch.allclose(mine(td, tv), torch.from_numpy(ref["angular/" + name]), rtol=1e-10, atol=1e-14), name
+    shapes = json.loads(str(ref["meta"]))["assembler_state"]
+    assert set(shapes) == set(sd_a), sorted(set(shapes) ^ set(sd_a))[:5]
+    assert all(list(sd_a[k].shape) == shapes[k] for k in shapes)
+    for k in shapes:
         if "aev_computer" in k or k in ("atomic_numbers", "energy_shifter.self_energies"):
-            assert torch.allclose(sd_r[k].double(), sd_a[k].double()), k
+            assert torch.allclose(torch.from_numpy(ref["value/" + k]), sd_a[k].double()), k

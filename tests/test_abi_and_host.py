@@ -447,67 +447,43 @@ def test_builtin_factory_signature():
         ANI2x(dtype=torch.float64)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torchani"), reason="needs the reference tree (build container only)")
-def test_integration_section_a_against_the_live_reference():
-    """INTEGRATION.md section A, as far as it can run without a GPU: a LIVE reference model's state dict loads into
-    torchani_amd.models.ANI2x strictly (every network / self-energy key found, none unexpected), the two hot components
-    can be assigned into the reference model, and the reference's own call path then reaches our AEVComputer, which
-    refuses CPU tensors loudly (there is no fallback)."""
-    import sys
-    import types
+def _reference_meta(name):
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_meta", name))
 
-    class _Any:
-        def __class_getitem__(cls, k):
-            return cls
 
-    for name in ("h5py", "zarr"):
-        if name not in sys.modules:
-            m = types.ModuleType(name)
-            for k in ("File", "Group", "Dataset", "Datatype"):
-                setattr(m, k, type(k, (_Any,), {}))
-            sys.modules[name] = m
-    os.environ["TORCHANI_NO_WARN_EXTENSIONS"] = "1"
-    sys.path.insert(0, "/root/reference")
-    try:
-        import torchani
-        from torchani.arch import Assembler
-        from torchani.utils import SYMBOLS_2X
+def test_integration_section_a_against_the_reference_layout():
+    """INTEGRATION.md section A, as far as it can run without a GPU, against the reference package's layout recorded by
+    tests/golden/gen_golden_reference_meta.py: a state dict with the key set and shapes of a reference ANI-2x model loads
+    into torchani_amd.models.ANI2x strictly (every network / self-energy key found, none unexpected, values kept), the AEV
+    computer the reference model would call refuses CPU tensors loudly (there is no fallback), and the autograd helpers
+    have the reference's signatures and result type."""
+    import inspect
+    import json
 
-        asm = Assembler()
-        asm.set_symbols(SYMBOLS_2X)
-        asm.set_global_cutoff_fn("cosine")
-        asm.set_aev_computer(radial="ani2x", angular="ani2x", strategy="pyaev")
-        asm.set_atomic_networks(ctor="ani2x")
-        asm.set_neighborlist("all_pairs")
-        asm.set_gsaes_as_self_energies("wb97x-631gd")
-        ref = asm.assemble(8)
-        import torchani_amd
+    import torchani_amd
+    from torchani_amd.tuples import Neighbors
 
-        amd = torchani_amd.models.ANI2x(state_dict=ref.state_dict())
-        sd_ref, sd_amd = ref.state_dict(), amd.state_dict()
-        nn_keys = [k for k in sd_ref if "neural_networks" in k or "energy_shifter" in k]
-        assert len(nn_keys) == 8 * 7 * 8 + 1
-        for k in nn_keys:
-            assert torch.equal(sd_ref[k].to(sd_amd[k].dtype), sd_amd[k]), k
-        # swap the two hot components into the reference model (tests/test_neighbors.py:311-312 style)
-        ref.potentials["nnp"].aev_computer = amd.aev_computer
-        ref.potentials["nnp"].neural_networks = amd.neural_networks
-        z = torch.tensor([[6, 1, 1, 1, 1]])
-        x = torch.rand(1, 5, 3)
-        with pytest.raises(ValueError, match="ROCm device"):
-            torchani.grad.energies_and_forces(ref, z, x)
-        # the autograd helpers have the reference's signatures (names, order, defaults; this package's extra keywords come
-        # BEHIND them) and its result type
-        import inspect
-
-        for fn in ("forces", "grads", "forces_for_training", "energies_and_forces", "single_point"):
-            pr = list(inspect.signature(getattr(torchani.grad, fn)).parameters.values())
-            pa = list(inspect.signature(getattr(torchani_amd.grad, fn)).parameters.values())
-            assert [(p.name, p.default) for p in pa[:len(pr)]] == [(p.name, p.default) for p in pr], fn
-        assert torchani_amd.tuples.EnergiesForces._fields == torchani.tuples.EnergiesForces._fields
-        assert set(torchani_amd.grad.__all__) <= set(torchani.grad.__all__)
-    finally:
-        sys.path.remove("/root/reference")
+    meta = json.loads(str(_reference_meta("api_ani2x.npz")["meta"]))
+    shapes = meta["section_a_state"]
+    nn_keys = [k for k in shapes if "neural_networks" in k or "energy_shifter" in k]
+    assert len(nn_keys) == 8 * 7 * 8 + 1
+    g = torch.Generator().manual_seed(3)
+    sd_ref = {k: torch.randn(shapes[k], generator=g, dtype=getattr(torch, meta["section_a_dtypes"][k])) for k in nn_keys}
+    amd = torchani_amd.models.ANI2x(state_dict=sd_ref)
+    sd_amd = amd.state_dict()
+    for k in nn_keys:
+        assert torch.equal(sd_ref[k].to(sd_amd[k].dtype), sd_amd[k]), k
+    # the reference's potential calls aev_computer.compute_from_neighbors(elem_idxs, coords, neighbors) (potentials/nnp.py)
+    nb = Neighbors(torch.tensor([[0, 0], [1, 2]]), torch.ones(2), torch.ones(2, 3))
+    with pytest.raises(ValueError, match="ROCm device"):
+        amd.aev_computer.compute_from_neighbors(torch.tensor([[1, 0, 0]]), torch.rand(1, 3, 3), nb)
+    # the autograd helpers have the reference's signatures (names, order, defaults; this package's extra keywords come
+    # BEHIND them) and its result type
+    for fn, pr in meta["grad_signatures"].items():
+        pa = list(inspect.signature(getattr(torchani_amd.grad, fn)).parameters.values())
+        assert [[p.name, repr(p.default)] for p in pa[:len(pr)]] == pr, fn
+    assert list(torchani_amd.tuples.EnergiesForces._fields) == meta["energies_forces_fields"]
+    assert set(torchani_amd.grad.__all__) <= set(meta["grad_all"])
 
 
 def test_d3_reference_data_and_class():
@@ -538,31 +514,19 @@ def test_d3_reference_data_and_class():
         TwoBodyDispersionD3(("H", "O"), 1.0, 1.0, 0.4, 4.0, sqrt_empirical_charge=(1.0,))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/torchani/resources/c6.h5"), reason="reference tree not present")
 def test_d3_data_file_is_the_reference_table():
-    """torchani_amd/data/d3_refs.npz against the reference's resources (build container only): the HDF5 reader of
-    tests/golden/gen_golden_d3.py finds the three datasets of c6.h5 and the shipped slice equals them."""
-    import json
-    import struct
-
+    """torchani_amd/data/d3_refs.npz against the reference's resources: the c6 / cn_a / cn_b tables of its c6.h5 and the
+    constants of its atomic_constants.json, as tests/golden/gen_golden_reference_meta.py recorded them."""
     from torchani_amd.potentials import d3_reference_data
 
-    b = open("/root/reference/torchani/resources/c6.h5", "rb").read()
-    nbytes = 4 * 95 * 95 * 25
-    addrs, i = [], b.find(struct.pack("<Q", nbytes))
-    while i >= 0:
-        if b[i - 10] == 3 and b[i - 9] == 1:
-            addrs.append(struct.unpack("<Q", b[i - 8:i])[0])
-        i = b.find(struct.pack("<Q", nbytes), i + 1)
-    assert len(addrs) == 3
-    tabs = [np.frombuffer(b, dtype="<f4", count=nbytes // 4, offset=a).reshape(95, 95, 5, 5) for a in sorted(addrs)]
+    ref = _reference_meta("d3_tables.npz")
     d = d3_reference_data()
-    for ours, theirs in zip((d["c6"], d["cn_a"], d["cn_b"]), tabs):
-        assert np.array_equal(ours, theirs[:19, :19])
-    ac = json.load(open("/root/reference/torchani/resources/atomic_constants.json"))
-    for z, s_ in enumerate(d["symbols"], start=1):
-        assert abs(d["covalent_radius"][z] - ac[s_]["covalent_radius"]) < 1e-12
-        assert abs(d["sqrt_empirical_charge"][z] - ac[s_]["sqrt_empirical_charge"]) < 1e-12
+    for key in ("c6", "cn_a", "cn_b"):
+        assert ref[key].shape == (19, 19, 5, 5) and np.array_equal(d[key], ref[key]), key
+    assert list(d["symbols"]) == [str(s_) for s_ in ref["symbols"]]
+    for z in range(1, len(d["symbols"]) + 1):
+        assert abs(d["covalent_radius"][z] - ref["covalent_radius"][z - 1]) < 1e-12
+        assert abs(d["sqrt_empirical_charge"][z] - ref["sqrt_empirical_charge"][z - 1]) < 1e-12
 
 
 def test_charge_networks_pack_and_normalizer():

@@ -281,11 +281,13 @@ def test_bench_two_ranks_gloo():
     assert par["max_dE_atom"] <= par["regression_gate_dE_atom"] and par["max_dF"] <= par["regression_gate_dF"]
 
 
-def test_bench_eight_ranks_gloo_equals_one_rank():
-    """First contact with 8 ranks, as far as one GPU goes: ``bench.py --gpus 8`` (eight processes sharing the GPU over gloo,
-    a 41 472-atom box: slabs of 9.3 A against a reach of 6.1 A) -- every rank is seen, force rows travel to the two slab
+def test_bench_four_ranks_gloo_equals_one_rank():
+    """More than two ranks, as far as one GPU goes: ``bench.py --gpus 4`` (four processes sharing the GPU over gloo, a
+    41 472-atom box: slabs of 18.6 A against a reach of 6.1 A) -- every rank is seen, force rows travel to the two slab
     neighbours only, the bytes are what the plan says, rank 0's oracle sample of atoms it owns is inside the regression gates,
-    and the total energy equals the single-rank run's."""
+    and the total energy equals the single-rank run's.  (Four ranks: with this test's own process, no more than five
+    processes hold the shared GPU at once.)"""
+    world = 4
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     common = ["--steps", "2", "--warmup", "2", "--waters-side", "24", "--no-dense-stage", "--no-secondary", "--no-cpu-baseline"]
@@ -293,25 +295,25 @@ def test_bench_eight_ranks_gloo_equals_one_rank():
                         capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p1.returncode == 0, p1.stdout[-2000:] + p1.stderr[-4000:]
     one = json.loads([ln for ln in p1.stdout.splitlines() if ln.startswith("{")][0])
-    p8 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dist-backend", "gloo",
+    pw = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
                          "--parity-sample", "128"] + common, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
-    assert p8.returncode == 0, p8.stdout[-2000:] + p8.stderr[-4000:]
-    lines = [ln for ln in p8.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1, p8.stdout[-2000:]
+    assert pw.returncode == 0, pw.stdout[-2000:] + pw.stderr[-4000:]
+    lines = [ln for ln in pw.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, pw.stdout[-2000:]
     r = json.loads(lines[0])
     n = r["config"]["n_atoms"]
-    assert r["n_gpus"] == 8 and n == one["config"]["n_atoms"] == 3 * 24 ** 3
+    assert r["n_gpus"] == world and n == one["config"]["n_atoms"] == 3 * 24 ** 3
     coll = r["collective"]
-    assert coll["world_size"] == 8 and coll["collectives_per_step"] == 1
+    assert coll["world_size"] == world and coll["collectives_per_step"] == 1
     assert coll["transport"]["transport"] == "collective" and coll["transport"]["fell_back"] is None
     seen = sorted(coll["ranks_seen"], key=lambda s_: s_["rank"])
-    assert [s_["rank"] for s_ in seen] == list(range(8)) and len({s_["pid"] for s_ in seen}) == 8
+    assert [s_["rank"] for s_ in seen] == list(range(world)) and len({s_["pid"] for s_ in seen}) == world
     assert sum(s_["owned_atoms"] for s_ in seen) == n
     for s_ in seen:
-        assert sorted(s_["peers"]) == sorted({(s_["rank"] - 1) % 8, (s_["rank"] + 1) % 8}), s_
+        assert sorted(s_["peers"]) == sorted({(s_["rank"] - 1) % world, (s_["rank"] + 1) % world}), s_
         halo = s_["local_atoms"] - s_["owned_atoms"]
-        # halo force rows (3 fp32 words each) to their owners + the partial energy (two fp32 words) to the 7 other ranks
-        assert s_["sent_bytes_per_step"] == 4 * (3 * halo + 2 * 7), s_
+        # halo force rows (3 fp32 words each) to their owners + the partial energy (two fp32 words) to the other ranks
+        assert s_["sent_bytes_per_step"] == 4 * (3 * halo + 2 * (world - 1)), s_
     par = r["parity_sample"]
     assert par is not None and par["n"] == 32 and "rank 0 owns" in par["atoms_sampled_from"]
     assert par["max_dE_atom"] <= par["regression_gate_dE_atom"] and par["max_dF"] <= par["regression_gate_dF"]
