@@ -231,6 +231,25 @@ int anihip_aev_jvp(void *stream, const anihip_aev_params *p, const float *table,
                    int64_t hi, const int32_t *species, const uint32_t *meta, const float *ent,
                    const float *tangent, float *daev, uint32_t *status);
 
+/* anihip_aev_jvp for n_dir directions in one launch (direction = a grid dimension): tangent [n_dir][n_atoms][3] ->
+ * daev [n_dir][n_atoms][L], rows lo <= i < hi of every direction written.  Same grids and kernels as anihip_aev_jvp.
+ * n_dir <= 65535. */
+int anihip_aev_jvp_batched(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo,
+                           int64_t hi, const int32_t *species, const uint32_t *meta, const float *ent, int64_t n_dir,
+                           const float *tangent, float *daev, uint32_t *status);
+
+/* Second-order AEV backward, for Hessians with respect to the coordinates: for n_dir directions t[k],
+ *   out[k] += J^T dgrad[k] + (D_{t[k]} J^T) grad_aev
+ * (J = d aev / d coords over the central atoms lo <= i < hi; D_t J^T = the derivative of the backward along the motion t with
+ * grad_aev held fixed).  grad_aev [n_atoms][L], dgrad [n_dir][n_atoms][L], tangent [n_dir][n_atoms][3], out [n_dir][n_atoms][3]
+ * (accumulated with float atomics: not bit-reproducible).  An entry's displacement moves with t_j - t_i whatever its periodic
+ * image.  Any grid of the general kernels (the tuned ones included), both cutoff functions; symmetric rows (the library's
+ * builders).  n_dir <= 65535. */
+int anihip_aev_backward_second(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo,
+                               int64_t hi, const int32_t *species, const uint32_t *meta, const float *ent,
+                               const float *grad_aev, int64_t n_dir, const float *tangent, const float *dgrad, float *out,
+                               uint32_t *status);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial
@@ -450,6 +469,17 @@ int anihip_mlp_tangent_weight_grads(void *stream, const anihip_mlp_desc *d, int6
                                     const int32_t *species, const float *aev, const float *tangent,
                                     void *workspace, size_t workspace_bytes, const anihip_species_grads *grads,
                                     float *datomic_e);
+
+/* Input-space Hessian-vector products of the ensemble-mean atomic energies, for Hessians with respect to the coordinates:
+ *   out[k][i] = (1/M) sum_m H_m(aev[i]) . tangent[k][i],   H_m(x) = d^2 e_m / d aev^2 at x,
+ * for n_dir directions k and every atom i (tangent, out: [n_dir][n_atoms][aev_len]; rows of padding atoms zeroed).  It is the
+ * input gradient of S = tangent . d e / d aev: the tangent pass of anihip_mlp_tangent_weight_grads over the (direction, atom)
+ * rows, without the weight gradients, plus the layer-0 input adjoint.  The forward activations are computed once per atom and
+ * gathered per row.  Exact fp32; reads the fp32 arrays (w, wt) of any pack, ANIHIP_MLP_F16X3 packs included.
+ * n_atoms * n_dir < 2^31. */
+size_t anihip_mlp_input_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_dir);
+int anihip_mlp_input_hvp(void *stream, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species, const float *aev,
+                         int64_t n_dir, const float *tangent, void *workspace, size_t workspace_bytes, float *out);
 
 /* Refresh the packed parameter arrays of a descriptor IN PLACE (padding stays zero) from the torch.nn.Linear tensors after
  * an optimizer step -- one or two launches instead of re-packing on the host (cf. BmmAtomicNetwork packing once per model,

@@ -1,0 +1,68 @@
+"""Timings of Hessians with respect to the coordinates (grad.energies_forces_and_hessians, the batched path, and the autograd
+loop of grad.forces_and_hessians) on fixtures of tests/golden: device-synchronised, after warm-up, median of several runs.
+
+    python tools/hessian_bench.py [--runs 5] [--autograd-max 264] [--bases ch4_ani1x,dense90_ani2x,...]
+
+Prints one JSON line per case.  Seeded parameters (the fixtures' seeds): timings do not depend on the values."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def timed(fn, runs):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)) * 1e3, [round(t * 1e3, 3) for t in ts]
+
+
+def main():
+    from _util import load_golden, seeded_state
+
+    from torchani_amd import grad
+    from torchani_amd.models import ANI1x, ANI2x
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--autograd-max", type=int, default=264)
+    ap.add_argument("--bases", default="ch4_ani1x,dense90_ani2x,small_ani2x,1hz5_ani2x")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    for base in args.bases.split(","):
+        g = load_golden(base)
+        ctor = ANI2x if g["kind"] == "ani2x" else ANI1x
+        model = ctor(state_dict=seeded_state(g["kind"], 8, g["seed"]), device=dev, periodic_table_index=False,
+                     cutoff_fn=g["cutoff_fn"], row_capacity=256)
+        sp = torch.from_numpy(g["species"].astype(np.int64)).to(dev)
+        x = torch.from_numpy(g["coords"]).to(dev)
+        A = int((sp >= 0).sum())
+        row = {"case": base, "atoms": A}
+        row["batched_ms"], row["batched_runs"] = timed(lambda: grad.energies_forces_and_hessians(model, sp, x),
+                                                       max(1, args.runs if A < 500 else 3))
+        if A <= args.autograd_max:
+            def loop():
+                xs = x.detach().clone().requires_grad_(True)
+                grad.forces_and_hessians(model((sp, xs)).energies, xs)
+            row["autograd_ms"], row["autograd_runs"] = timed(loop, max(1, args.runs if A < 100 else 3))
+            row["speedup"] = round(row["autograd_ms"] / row["batched_ms"], 2)
+        print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip"]
 HEADERS = ["anihip_common.h", "train.h", "mlp_fused.h", "mlp_prep.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -174,6 +174,14 @@ def lib() -> C.CDLL:
     L.anihip_aev_forward_update.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.anihip_aev_backward.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp]
     L.anihip_aev_jvp.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.anihip_aev_jvp_batched.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.anihip_aev_jvp_batched.restype = C.c_int
+    L.anihip_aev_backward_second.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.anihip_aev_backward_second.restype = C.c_int
+    L.anihip_mlp_input_hvp_workspace_bytes.restype = sz
+    L.anihip_mlp_input_hvp_workspace_bytes.argtypes = [C.POINTER(MlpDesc), i64, i64]
+    L.anihip_mlp_input_hvp.argtypes = [vp, C.POINTER(MlpDesc), i64, vp, vp, i64, vp, vp, sz, vp]
+    L.anihip_mlp_input_hvp.restype = C.c_int
     L.anihip_aev_backward_virial.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.anihip_mlp_workspace_bytes.restype = sz
     L.anihip_mlp_workspace_bytes.argtypes = [C.POINTER(MlpDesc), i64]
@@ -226,6 +234,7 @@ EXPORTED_SYMBOLS = [
     "anihip_mlp_tangent_workspace_bytes", "anihip_mlp_tangent_weight_grads", "anihip_pair_xtb_repulsion",
     "anihip_pair_d3", "anihip_pair_analytic", "anihip_energy_forces_finish", "anihip_mlp_pack_bytes", "anihip_mlp_pack",
     "anihip_nbr_rows_to_half_workspace_bytes", "anihip_nbr_rows_to_half",
+    "anihip_aev_jvp_batched", "anihip_aev_backward_second", "anihip_mlp_input_hvp_workspace_bytes", "anihip_mlp_input_hvp",
 ]
 
 

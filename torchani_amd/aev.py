@@ -9,6 +9,7 @@ from __future__ import annotations
 import math
 import typing as tp
 import warnings
+import weakref
 
 import torch
 from torch import Tensor
@@ -133,24 +134,44 @@ class ANIAngular(_AngularTerms):
 
 
 class _AEVBackwardFunction(torch.autograd.Function):
-    """grad_aev -> grad_coords = J^T grad_aev as a differentiable function of grad_aev: its own backward is the
+    """(grad_aev, coords) -> grad_coords = J^T grad_aev as a differentiable function of grad_aev: its own backward is the
     forward-mode product J u (anihip_aev_jvp), the reference's cuaev double backward (CuaevDoubleAutograd,
-    csrc/cuaev.cpp:141-186, csrc/aev.cu:1986-2015) that training on forces needs.  Like the reference it returns the
-    derivative with respect to grad_aev only (no third order, no second-order term for the coordinates)."""
+    csrc/cuaev.cpp:141-186, csrc/aev.cu:1986-2015) that training on forces needs.  ``coords`` is given (not None) only
+    when the networks are frozen (_AEVFunction.backward): then the backward also returns the coordinate term
+    (D_w J^T) grad_aev of the second derivative (anihip_aev_backward_second) -- Hessians and Hessian-vector products.
+    Force training (trainable parameters) passes None: the derivative with respect to grad_aev only, like the reference."""
 
     @staticmethod
-    def forward(ctx, grad_aev: Tensor, eng, nbrs, species32: Tensor) -> Tensor:
+    def forward(ctx, grad_aev: Tensor, coords: tp.Optional[Tensor], eng, nbrs, species32: Tensor) -> Tensor:
         g = grad_aev.detach().to(torch.float32).contiguous()
         ctx.eng, ctx.nbrs, ctx.species32 = eng, nbrs, species32
         ctx.g_dtype, ctx.g_shape = grad_aev.dtype, grad_aev.shape
+        # (a first-order backward never records this Function: ctx and g die with the call)
+        ctx.g = g if coords is not None else None
+        ctx.c_dtype = None if coords is None else coords.dtype
         C, A = species32.shape
         return eng.backward(species32, nbrs, g).view(C, A, 3)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_force: Tensor):
-        jt = ctx.eng.jvp(ctx.species32, ctx.nbrs, grad_force.contiguous())
-        return jt.view(ctx.g_shape).to(ctx.g_dtype), None, None, None
+        w = grad_force.contiguous()
+        jt = ctx.eng.jvp(ctx.species32, ctx.nbrs, w) if ctx.needs_input_grad[0] else None
+        dc = None
+        if ctx.g is not None and ctx.needs_input_grad[1]:
+            C, A = ctx.species32.shape
+            dc = ctx.eng.backward_second(ctx.species32, ctx.nbrs, ctx.g, w.view(1, C * A, 3)).view(C, A, 3).to(ctx.c_dtype)
+        return (None if jt is None else jt.view(ctx.g_shape).to(ctx.g_dtype)), dc, None, None, None
+
+
+def _second_order_coords(ctx) -> tp.Optional[Tensor]:
+    """The coordinates for the coordinate term of the second derivative: only under create_graph=True, only when the networks
+    reading these AEVs are frozen (_MLPFunction marks the node), and only while the caller's coordinates are alive (they are
+    held by weak reference: a first-order call keeps nothing more alive than before)."""
+    if not (torch.is_grad_enabled() and getattr(ctx, "frozen_nets", False)):
+        return None
+    ref = getattr(ctx, "coords_ref", None)
+    return None if ref is None else ref()
 
 
 class _AEVFunction(torch.autograd.Function):
@@ -164,13 +185,14 @@ class _AEVFunction(torch.autograd.Function):
         aev = eng.forward(species32, nbrs)
         ctx.eng, ctx.nbrs, ctx.species32 = eng, nbrs, species32
         ctx.in_dtype = coords.dtype
+        ctx.coords_ref = weakref.ref(coords)
         computer._last_neighbors = nbrs
         return aev.view(species32.shape[0], species32.shape[1], eng.L).to(coords.dtype)
 
     @staticmethod
     def backward(ctx, grad_aev: Tensor):
         # (through a Function of its own so that create_graph=True can differentiate the forces once more)
-        gc = _AEVBackwardFunction.apply(grad_aev, ctx.eng, ctx.nbrs, ctx.species32)
+        gc = _AEVBackwardFunction.apply(grad_aev, _second_order_coords(ctx), ctx.eng, ctx.nbrs, ctx.species32)
         return gc.to(ctx.in_dtype), None, None, None, None
 
 
@@ -190,7 +212,7 @@ class _AEVFromRowsFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_aev: Tensor):
-        gc = _AEVBackwardFunction.apply(grad_aev, ctx.eng, ctx.nbrs, ctx.species32)
+        gc = _AEVBackwardFunction.apply(grad_aev, None, ctx.eng, ctx.nbrs, ctx.species32)
         return gc.to(ctx.in_dtype), None, None, None
 
 

@@ -278,9 +278,13 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
     AevArgs a, const float *__restrict__ tab, int64_t lo, int64_t hi,
     const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
     const float4 *__restrict__ ent, float *__restrict__ aev, uint32_t *__restrict__ slab_mask,
-    const float *__restrict__ tang)
+    const float *__restrict__ tang, int64_t dir_t, int64_t dir_o)
 {
     static_assert(NA % 4 == 0 && NZ % 4 == 0 && NA * NZ == 32, "angular tiling");
+    // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y reads tangent + y dir_t, writes
+    // aev + y dir_o
+    tang += (size_t)blockIdx.y * dir_t;
+    aev += (size_t)blockIdx.y * dir_o;
     constexpr int AQ = NA / 4, ZQ = NZ / 4;
     __shared__ float4 s_ang[FWD_WPB][MAXA];   // ux uy uz r
     __shared__ float s_afc[FWD_WPB][MAXA];    // fc(r, Rca)
@@ -1592,6 +1596,9 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
 int aev_forward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                         const int32_t *species, const uint32_t *meta, const float *ent, float *aev, const float *tangent,
                         uint32_t *slab_mask);
+int aev_jvp_generic_dirs(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+                         const int32_t *species, const uint32_t *meta, const float *ent, float *daev, const float *tangent,
+                         int n_dir, int64_t dir_t, int64_t n_atoms);
 int aev_backward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                          const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
                          float *grad_coords, double *virial, bool fixed);
@@ -1779,10 +1786,37 @@ extern "C" int anihip_aev_jvp(void *stream, const anihip_aev_params *p, const fl
     dim3 grid(persistent_blocks(hi - lo, FWD_WPB, 4)), block(FWD_WPB * WAVE);
     if (p->n_shf_a == 8)
         hipLaunchKernelGGL((k_aev_fwd<8, 4, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
-                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent);
+                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, (int64_t)0, (int64_t)0);
     else
         hipLaunchKernelGGL((k_aev_fwd<4, 8, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
-                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent);
+                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, (int64_t)0, (int64_t)0);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    (void)status;
+    return 0;
+}
+
+extern "C" int anihip_aev_jvp_batched(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                                      int64_t lo, int64_t hi, const int32_t *species, const uint32_t *meta,
+                                      const float *ent, int64_t n_dir, const float *tangent, float *daev, uint32_t *status)
+{
+    ANIHIP_REQUIRE(p && table && species && meta && ent && tangent && daev, "null pointer argument");
+    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
+    ANIHIP_REQUIRE(0 <= n_dir && n_dir <= 65535, "n_dir must be 0..65535 (got %lld)", (long long)n_dir);
+    if (hi == lo || n_dir == 0) return 0;
+    const int64_t dir_t = 3 * n_atoms;
+    if (!tuned_grid(p))
+        return aev_jvp_generic_dirs((hipStream_t)stream, p, table, lo, hi, species, meta, ent, daev, tangent, (int)n_dir, dir_t,
+                                    n_atoms);
+    AevArgs a;
+    if (int rc = make_args(p, &a)) return rc;
+    const int64_t dir_o = n_atoms * (int64_t)a.L;
+    dim3 grid(persistent_blocks(hi - lo, FWD_WPB, 4), (unsigned)n_dir), block(FWD_WPB * WAVE);
+    if (p->n_shf_a == 8)
+        hipLaunchKernelGGL((k_aev_fwd<8, 4, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
+                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, dir_t, dir_o);
+    else
+        hipLaunchKernelGGL((k_aev_fwd<4, 8, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
+                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, dir_t, dir_o);
     ANIHIP_CHECK_HIP(hipGetLastError());
     (void)status;
     return 0;

@@ -121,8 +121,13 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
                                                                 const uint32_t *__restrict__ meta,
                                                                 const float4 *__restrict__ ent, float *__restrict__ aev,
                                                                 const float *__restrict__ tangent,
-                                                                uint32_t *__restrict__ slab_mask)
+                                                                uint32_t *__restrict__ slab_mask, int64_t dir_t,
+                                                                int64_t dir_o)
 {
+    if (JVP) {   // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y
+        tangent += (size_t)blockIdx.y * dir_t;
+        aev += (size_t)blockIdx.y * dir_o;
+    }
     __shared__ float4 s_ur[GEN_WPB][MAXR];
     __shared__ float2 s_fca[GEN_WPB][MAXR];
     __shared__ float2 s_fcr[GEN_WPB][MAXR];
@@ -458,10 +463,26 @@ int aev_forward_generic(hipStream_t stream, const anihip_aev_params *p, const fl
     const dim3 grid(gen_blocks(hi - lo)), block(GEN_WPB * WAVE);
     if (tangent)
         hipLaunchKernelGGL(k_aev_fwd_gen<true>, grid, block, 0, stream, a, table, lo, hi, species, meta, (const float4 *)ent, aev,
-                           tangent, slab_mask);
+                           tangent, slab_mask, (int64_t)0, (int64_t)0);
     else
         hipLaunchKernelGGL(k_aev_fwd_gen<false>, grid, block, 0, stream, a, table, lo, hi, species, meta, (const float4 *)ent,
-                           aev, tangent, slab_mask);
+                           aev, tangent, slab_mask, (int64_t)0, (int64_t)0);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// n_dir directions at once (anihip_aev_jvp_batched): tangent [n_dir][n_atoms][3] -> daev [n_dir][n_atoms][L], direction =
+// blockIdx.y
+int aev_jvp_generic_dirs(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+                         const int32_t *species, const uint32_t *meta, const float *ent, float *daev, const float *tangent,
+                         int n_dir, int64_t dir_t, int64_t n_atoms)
+{
+    GenArgs a;
+    if (int rc = gen_args(p, &a)) return rc;
+    if (hi == lo || n_dir == 0) return 0;
+    const dim3 grid(gen_blocks(hi - lo), (unsigned)n_dir), block(GEN_WPB * WAVE);
+    hipLaunchKernelGGL(k_aev_fwd_gen<true>, grid, block, 0, stream, a, table, lo, hi, species, meta, (const float4 *)ent, daev,
+                       tangent, (uint32_t *)nullptr, dir_t, n_atoms * (int64_t)a.L);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

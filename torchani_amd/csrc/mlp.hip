@@ -91,6 +91,8 @@ struct GemmArgs {
     int a_tm_h[MAX_S];     //      and per-species row width H_s
     const float *Z;        // tangent pass: zdot (same leading dimension as Y)
     float *C2;             // tangent pass: second output (same leading dimension as C)
+    const int *y_gather;   // tangent pass over (direction, atom) rows (anihip_mlp_input_hvp): sorted row -> row of Y / X (the
+                           // activations of its atom); NULL: the same row.  Z, C, C2 are always indexed by the row itself
     // training passes of GELU networks (act = ANIHIP_ACT_GELU): GELU' cannot be recovered from the stored activation
     // (x Phi(x) is not monotonic), so the forward keeps the PRE-activations too: Xout (EPI_BIAS_CELU, laid out like C) and
     // the passes that need activation derivatives read them back: X (laid out like Y)
@@ -301,7 +303,8 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_gemm(GemmArgs g)
             } else if (EPI == EPI_TANGENT || EPI == EPI_ADJ_P || EPI == EPI_ADJ_Q) {
                 // act'(x) and act''(x): CELU from the stored activation y, GELU from the stored pre-activation
                 const int64_t ic = (int64_t)(p0 + row) * g.ldc + (int64_t)bb * pr.c_boff + col;
-                const int64_t iy = (int64_t)(p0 + row) * g.ldy + (int64_t)bb * pr.c_boff + col;
+                const int64_t iz = (int64_t)(p0 + row) * g.ldy + (int64_t)bb * pr.c_boff + col;
+                const int64_t iy = g.y_gather ? (int64_t)g.y_gather[p0 + row] * g.ldy + (int64_t)bb * pr.c_boff + col : iz;
                 float c1, c2;
                 act_derivs(g.act, g.Y[iy], g.X ? g.X[iy] : 0.f, g.inv_alpha, c1, c2);
                 if (EPI == EPI_TANGENT) {
@@ -309,7 +312,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_gemm(GemmArgs g)
                     g.C2[ic] = c1 * v;
                 } else if (EPI == EPI_ADJ_P) {
                     g.C[ic] = v * c1;
-                    g.C2[ic] = v * c2 * g.Z[iy];
+                    g.C2[ic] = v * c2 * g.Z[iz];
                 } else {
                     g.C[ic] += v * c1;
                 }
@@ -1603,6 +1606,7 @@ struct HeadTangentArgs {
     float inv_alpha;
     int act_kind;
     const float *zpre;            // pre-activations of the last hidden layer (GELU)
+    const int *y_gather;          // sorted row -> row of act / zpre (anihip_mlp_input_hvp), or NULL: the same row
 };
 
 __global__ __launch_bounds__(256) void k_head_tangent(HeadTangentArgs h)
@@ -1616,13 +1620,14 @@ __global__ __launch_bounds__(256) void k_head_tangent(HeadTangentArgs h)
         while (s + 1 < h.S && p >= h.ctl[CTL_OFF + s + 1]) ++s;
         const int Hp = h.Hp[s];
         float part = 0.f;
+        const int64_t py = h.y_gather ? (int64_t)h.y_gather[p] : p;
         for (int m = 0; m < h.M; ++m) {
             const float *w = h.w[s] + (int64_t)m * Hp;
             for (int o = lane; o < Hp; o += WAVE) {
-                const int64_t idx = p * h.ld + m * Hp + o;
-                const float y = h.act[idx], zd = h.zd[idx];
+                const int64_t idx = p * h.ld + m * Hp + o, idy = py * h.ld + m * Hp + o;
+                const float y = h.act[idy], zd = h.zd[idx];
                 float c1, c2;
-                act_derivs(h.act_kind, y, h.zpre ? h.zpre[idx] : 0.f, h.inv_alpha, c1, c2);
+                act_derivs(h.act_kind, y, h.zpre ? h.zpre[idy] : 0.f, h.inv_alpha, c1, c2);
                 const float mu = invM * w[o];
                 h.P[idx] = mu * c1;
                 h.Q[idx] = mu * c2 * zd;
@@ -2794,6 +2799,111 @@ extern "C" int anihip_mlp_weight_grads(void *stream_, const anihip_mlp_desc *d, 
     return 0;
 }
 
+// ---- the tangent pass, shared by anihip_mlp_tangent_weight_grads and anihip_mlp_input_hvp ----------------------------
+// rows: the sorted rows of ctl (atoms of the call, or (direction, atom) rows of the HVP); a_gather: sorted row -> row of the
+// tangent (layer 0); y_gather: sorted row -> row of the kept activations (NULL: the row itself)
+struct TangentPass {
+    const anihip_mlp_desc *d;
+    MlpWorkspace *w;
+    const int *ctl, *a_gather, *y_gather;
+    int64_t n;
+    float **zd, **ad, **P, **Q;
+};
+
+static int tp_width_max(const anihip_mlp_desc *d, int l)
+{
+    int mx = 0;
+    for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l] ? mx : d->net[s].dims[l];
+    return mx;
+}
+
+static GemmArgs tp_gemm_base(const TangentPass &t)
+{
+    GemmArgs g{};
+    g.ctl = t.ctl; g.S = t.d->num_species; g.alpha = t.d->celu_alpha; g.inv_alpha = 1.0f / t.d->celu_alpha;
+    g.nrow_tiles_ub = (int)((t.n + BM - 1) / BM) + t.d->num_species;
+    g.amax_in = g.amax_out = -1;
+    g.act = t.d->activation;
+    g.y_gather = t.y_gather;
+    return g;
+}
+
+// zdot_l = W_l adot_{l-1}, adot_l = c'(z_l) zdot_l   (adot_0 = tangent rows)
+static void tangent_forward(hipStream_t stream, const TangentPass &t, const float *tangent)
+{
+    const anihip_mlp_desc *d = t.d;
+    const int S = d->num_species, M = d->n_members, nh = d->net[0].n_layers - 1, L = d->aev_len;
+    const MlpWorkspace &w = *t.w;
+    for (int l = 0; l < nh; ++l) {
+        GemmArgs g = tp_gemm_base(t);
+        g.C = t.zd[l]; g.C2 = t.ad[l]; g.ldc = w.ld[l]; g.Y = w.act[l]; g.ldy = w.ld[l]; g.X = w.zp[l];
+        if (l == 0) {
+            g.A = tangent; g.lda = L; g.a_gather = t.a_gather; g.batch = 1;
+            g.ncol_max = (tp_width_max(d, 1) * M + BN - 1) / BN;
+        } else {
+            g.A = t.ad[l - 1]; g.lda = w.ld[l - 1]; g.batch = M;
+            g.ncol_max = (tp_width_max(d, l + 1) + BN - 1) / BN;
+        }
+        for (int s = 0; s < S; ++s) {
+            const anihip_species_net &nn = d->net[s];
+            GemmProblem &p = g.prob[s];
+            p.B = nn.w[l];
+            if (l == 0) {
+                p.K = nn.dims[0]; p.N = nn.dims[1] * M; p.ldb = p.N;
+            } else {
+                p.K = nn.dims[l]; p.N = nn.dims[l + 1]; p.ldb = p.N;
+                p.a_boff = nn.dims[l]; p.c_boff = nn.dims[l + 1];
+                p.b_stride = (int64_t)p.K * p.N;
+            }
+        }
+        launch_gemm_fp32<EPI_TANGENT>(stream, g);
+    }
+}
+
+// output layer: adjoint seeds p, q of the last hidden layer (and d atomic_e per atom, datomic_e non-NULL)
+static void tangent_head(hipStream_t stream, const TangentPass &t, float *datomic_e)
+{
+    const anihip_mlp_desc *d = t.d;
+    const int S = d->num_species, nl = d->net[0].n_layers, nh = nl - 1;
+    const MlpWorkspace &w = *t.w;
+    HeadTangentArgs h{};
+    for (int s = 0; s < S; ++s) { h.w[s] = d->net[s].w[nl - 1]; h.Hp[s] = d->net[s].dims[nl - 1]; }
+    h.ctl = t.ctl; h.perm = w.perm; h.act = w.act[nh - 1]; h.zd = t.zd[nh - 1]; h.ad = t.ad[nh - 1];
+    h.P = t.P[nh - 1]; h.Q = t.Q[nh - 1]; h.ld = w.ld[nh - 1]; h.datomic_e = datomic_e; h.S = S; h.M = d->n_members;
+    h.inv_alpha = 1.0f / d->celu_alpha; h.act_kind = d->activation; h.zpre = w.zp[nh - 1];
+    h.y_gather = t.y_gather;
+    int64_t blocks = (t.n + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(k_head_tangent, dim3((unsigned)blocks), dim3(256), 0, stream, h);
+}
+
+// adjoints of layer l - 1 from those of layer l:  mu = W^T p -> (p, mu c'' zdot);  nu = W^T q -> q += nu c'
+static void tangent_adjoint(hipStream_t stream, const TangentPass &t, int l)
+{
+    const anihip_mlp_desc *d = t.d;
+    const int S = d->num_species, M = d->n_members;
+    const MlpWorkspace &w = *t.w;
+    for (int pass = 0; pass < 2; ++pass) {
+        GemmArgs g = tp_gemm_base(t);
+        g.A = pass == 0 ? t.P[l] : t.Q[l]; g.lda = w.ld[l]; g.batch = M;
+        g.C = pass == 0 ? t.P[l - 1] : t.Q[l - 1]; g.C2 = t.Q[l - 1]; g.ldc = w.ld[l - 1];
+        g.Y = w.act[l - 1]; g.Z = t.zd[l - 1]; g.ldy = w.ld[l - 1]; g.X = w.zp[l - 1];
+        g.ncol_max = (tp_width_max(d, l) + BN - 1) / BN;
+        for (int s = 0; s < S; ++s) {
+            const anihip_species_net &nn = d->net[s];
+            GemmProblem &p = g.prob[s];
+            p.B = nn.wt[l];
+            p.K = nn.dims[l + 1]; p.N = nn.dims[l]; p.ldb = p.N;
+            p.a_boff = nn.dims[l + 1]; p.c_boff = nn.dims[l];
+            p.b_stride = (int64_t)p.K * p.N;
+        }
+        if (pass == 0)
+            launch_gemm_fp32<EPI_ADJ_P>(stream, g);
+        else
+            launch_gemm_fp32<EPI_ADJ_Q>(stream, g);
+    }
+}
+
 extern "C" size_t anihip_mlp_tangent_workspace_bytes(const anihip_mlp_desc *d, int64_t n_central)
 {
     if (!d || n_central < 0) return 0;
@@ -2830,59 +2940,14 @@ extern "C" int anihip_mlp_tangent_weight_grads(void *stream_, const anihip_mlp_d
     float *buf[4][ANIHIP_MAX_LAYERS];
     mlp_tangent_carve(d, n, (char *)workspace, &w, buf);
     float **zd = buf[0], **ad = buf[1], **P = buf[2], **Q = buf[3];
-    const float alpha = d->celu_alpha, inv_alpha = 1.0f / d->celu_alpha;
 
     // 1. bucket by species, activations a_l (datomic_e doubles as the array whose padding entries get zeroed)
     if (int rc = train_forward(stream, d, n_atoms, lo, hi, species, aev, w, datomic_e, nullptr)) return rc;
-    const int nrow_ub = (int)((n + BM - 1) / BM) + S;
-    auto width_max = [&](int l) {
-        int mx = 0;
-        for (int s = 0; s < S; ++s) mx = mx > d->net[s].dims[l] ? mx : d->net[s].dims[l];
-        return mx;
-    };
-    auto gemm_base = [&]() {
-        GemmArgs g{};
-        g.ctl = w.ctl; g.S = S; g.alpha = alpha; g.inv_alpha = inv_alpha; g.nrow_tiles_ub = nrow_ub;
-        g.amax_in = g.amax_out = -1;
-        g.act = d->activation;
-        return g;
-    };
+    TangentPass tp{d, &w, w.ctl, w.perm, nullptr, n, zd, ad, P, Q};
     // 2. tangents: zdot_l = W_l adot_{l-1}, adot_l = c'(z_l) zdot_l   (adot_0 = tangent rows)
-    for (int l = 0; l < nh; ++l) {
-        GemmArgs g = gemm_base();
-        g.C = zd[l]; g.C2 = ad[l]; g.ldc = w.ld[l]; g.Y = w.act[l]; g.ldy = w.ld[l]; g.X = w.zp[l];
-        if (l == 0) {
-            g.A = tangent; g.lda = L; g.a_gather = w.perm; g.batch = 1;
-            g.ncol_max = (width_max(1) * M + BN - 1) / BN;
-        } else {
-            g.A = ad[l - 1]; g.lda = w.ld[l - 1]; g.batch = M;
-            g.ncol_max = (width_max(l + 1) + BN - 1) / BN;
-        }
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.w[l];
-            if (l == 0) {
-                p.K = nn.dims[0]; p.N = nn.dims[1] * M; p.ldb = p.N;
-            } else {
-                p.K = nn.dims[l]; p.N = nn.dims[l + 1]; p.ldb = p.N;
-                p.a_boff = nn.dims[l]; p.c_boff = nn.dims[l + 1];
-                p.b_stride = (int64_t)p.K * p.N;
-            }
-        }
-        launch_gemm_fp32<EPI_TANGENT>(stream, g);
-    }
+    tangent_forward(stream, tp, tangent);
     // 3. output layer: adjoint seeds p, q of the last hidden layer, d atomic_e, d w_out (d b_out = 0)
-    {
-        HeadTangentArgs h{};
-        for (int s = 0; s < S; ++s) { h.w[s] = d->net[s].w[nl - 1]; h.Hp[s] = d->net[s].dims[nl - 1]; }
-        h.ctl = w.ctl; h.perm = w.perm; h.act = w.act[nh - 1]; h.zd = zd[nh - 1]; h.ad = ad[nh - 1];
-        h.P = P[nh - 1]; h.Q = Q[nh - 1]; h.ld = w.ld[nh - 1]; h.datomic_e = datomic_e; h.S = S; h.M = M;
-        h.inv_alpha = inv_alpha; h.act_kind = d->activation; h.zpre = w.zp[nh - 1];
-        int64_t blocks = (n + 3) / 4;
-        if (blocks > 256 * 8) blocks = 256 * 8;
-        hipLaunchKernelGGL(k_head_tangent, dim3((unsigned)blocks), dim3(256), 0, stream, h);
-    }
+    tangent_head(stream, tp, datomic_e);
     const int cr_chunks = (int)((n + CR_ROWS - 1) / CR_ROWS) + S;
     auto col_reduce = [&](const float *X, int64_t ldx, int l_out, bool weights, float scale) {
         ColReduceArgs c{};
@@ -2931,25 +2996,125 @@ extern "C" int anihip_mlp_tangent_weight_grads(void *stream_, const anihip_mlp_d
             hipLaunchKernelGGL(k_wgrad, dim3((unsigned)total), dim3(256), 0, stream, a);
         }
         if (l == 0) break;
-        for (int pass = 0; pass < 2; ++pass) {   // mu = W^T p -> (p, mu c'' zdot);  nu = W^T q -> q += nu c'
-            GemmArgs g = gemm_base();
-            g.A = pass == 0 ? P[l] : Q[l]; g.lda = w.ld[l]; g.batch = M;
-            g.C = pass == 0 ? P[l - 1] : Q[l - 1]; g.C2 = Q[l - 1]; g.ldc = w.ld[l - 1];
-            g.Y = w.act[l - 1]; g.Z = zd[l - 1]; g.ldy = w.ld[l - 1]; g.X = w.zp[l - 1];
-            g.ncol_max = (width_max(l) + BN - 1) / BN;
-            for (int s = 0; s < S; ++s) {
-                const anihip_species_net &nn = d->net[s];
-                GemmProblem &p = g.prob[s];
-                p.B = nn.wt[l];
-                p.K = nn.dims[l + 1]; p.N = nn.dims[l]; p.ldb = p.N;
-                p.a_boff = nn.dims[l + 1]; p.c_boff = nn.dims[l];
-                p.b_stride = (int64_t)p.K * p.N;
-            }
-            if (pass == 0)
-                launch_gemm_fp32<EPI_ADJ_P>(stream, g);
-            else
-                launch_gemm_fp32<EPI_ADJ_Q>(stream, g);
+        tangent_adjoint(stream, tp, l);   // mu = W^T p -> (p, mu c'' zdot);  nu = W^T q -> q += nu c'
+    }
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- network input HVP ------------------------------------------------------------------------------------------------
+// (direction, atom) rows of one HVP call: sorted row q = p * n_dir + k for the atom at sorted position p and direction k, so
+// the rows of a species are contiguous like its atoms; the control block of the rows is the atoms' scaled by n_dir
+__global__ __launch_bounds__(256) void k_hvp_rows(const int *ctl, const int *perm, int S, int n_dir, int64_t n_atoms,
+                                                  int *rctl, int *rperm, int *ygather)
+{
+    const int64_t total = (int64_t)ctl[CTL_OFF + S] * n_dir;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        int trun = 0;
+        for (int t = 0; t < S; ++t) {
+            const int cnt = ctl[CTL_CNT + t] * n_dir;
+            rctl[CTL_CNT + t] = cnt;
+            rctl[CTL_OFF + t] = ctl[CTL_OFF + t] * n_dir;
+            rctl[CTL_TILE + t] = trun;
+            trun += (cnt + BM - 1) / BM;
         }
+        rctl[CTL_OFF + S] = (int)total;
+        rctl[CTL_TILE + S] = trun;
+    }
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = q / n_dir, k = q - p * n_dir;
+        rperm[q] = (int)(k * n_atoms + perm[p]);
+        ygather[q] = (int)p;
+    }
+}
+
+// workspace: the atoms' inference workspace (activations kept, once per atom) + the rows' control block, permutation and
+// activation gather + zdot, adot, p, q per hidden layer and row
+static size_t mlp_hvp_carve(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_dir, char *base, MlpWorkspace *w,
+                            float *(*buf)[ANIHIP_MAX_LAYERS], float **atomic_e, int **rctl, int **rperm, int **ygather)
+{
+    size_t off = align256(mlp_carve(d, n_atoms, base, w));
+    off = carve_zp(d, n_atoms, base, off, w);
+    const int64_t rows = n_atoms * n_dir;
+    auto take = [&](size_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += align256(bytes);
+        return p;
+    };
+    float *ae = (float *)take(sizeof(float) * (size_t)(n_atoms + 1));
+    int *rc = (int *)take(sizeof(int) * CTL_WORDS);
+    int *rp = (int *)take(sizeof(int) * (size_t)(rows + 1));
+    int *yg = (int *)take(sizeof(int) * (size_t)(rows + 1));
+    if (atomic_e) { *atomic_e = ae; *rctl = rc; *rperm = rp; *ygather = yg; }
+    const int nh = d->net[0].n_layers - 1;
+    for (int k = 0; k < 4; ++k)
+        for (int l = 0; l < nh; ++l) {
+            int mx = 0;
+            for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
+            float *b = (float *)take(sizeof(float) * (size_t)mx * d->n_members * (size_t)(rows + 1));
+            if (buf) buf[k][l] = b;
+        }
+    return off;
+}
+
+extern "C" size_t anihip_mlp_input_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_dir)
+{
+    if (!d || n_atoms < 0 || n_dir < 0) return 0;
+    return mlp_hvp_carve(d, n_atoms, n_dir, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int anihip_mlp_input_hvp(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species,
+                                    const float *aev, int64_t n_dir, const float *tangent, void *workspace,
+                                    size_t workspace_bytes, float *out)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_desc(d)) return rc;
+    ANIHIP_REQUIRE(species && aev && tangent && workspace && out, "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_dir >= 0, "negative size");
+    ANIHIP_REQUIRE(n_atoms * n_dir < ((int64_t)1 << 31) - 1, "n_atoms * n_dir must stay below 2^31 (got %lld)",
+                   (long long)(n_atoms * n_dir));
+    const int S = d->num_species, M = d->n_members, nl = d->net[0].n_layers, nh = nl - 1, L = d->aev_len;
+    const int64_t rows = n_atoms * n_dir;
+    if (rows == 0) return 0;
+    ANIHIP_REQUIRE(workspace_bytes >= mlp_hvp_carve(d, n_atoms, n_dir, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                    nullptr),
+                   "workspace too small (anihip_mlp_input_hvp_workspace_bytes)");
+    MlpWorkspace w;
+    float *buf[4][ANIHIP_MAX_LAYERS];
+    float *atomic_e;
+    int *rctl, *rperm, *ygather;
+    mlp_hvp_carve(d, n_atoms, n_dir, (char *)workspace, &w, buf, &atomic_e, &rctl, &rperm, &ygather);
+    // (rows of padding atoms are never bucketed: they stay zero)
+    zero_words_async(stream, out, sizeof(float) * (size_t)rows * L);
+    // 1. the atoms: species buckets, exact-fp32 forward with the activations kept -- once per atom, not per direction
+    if (int rc = train_forward(stream, d, n_atoms, 0, n_atoms, species, aev, w, atomic_e, nullptr)) return rc;
+    // 2. the (direction, atom) rows
+    zero_words_async(stream, rctl, sizeof(int) * CTL_WORDS);
+    int64_t blocks = (rows + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_hvp_rows, dim3((unsigned)blocks), dim3(256), 0, stream, w.ctl, w.perm, S, (int)n_dir, n_atoms, rctl,
+                       rperm, ygather);
+    // 3. the tangent pass over the rows (activations gathered per row), without the weight gradients
+    TangentPass tp{d, &w, rctl, rperm, ygather, rows, buf[0], buf[1], buf[2], buf[3]};
+    tangent_forward(stream, tp, tangent);
+    tangent_head(stream, tp, nullptr);
+    for (int l = nh - 1; l >= 1; --l) tangent_adjoint(stream, tp, l);
+    // 4. the layer-0 input adjoint: out = W_0^T q_0 (q_0 = d S / d z_0 carries the 1 / M of the ensemble mean)
+    {
+        const int K0p = ((L + 31) / 32) * 32;
+        GemmArgs g = tp_gemm_base(tp);
+        g.y_gather = nullptr;
+        g.A = buf[3][0]; g.lda = w.ld[0]; g.a_gather = nullptr; g.batch = 1;
+        g.C = out; g.ldc = L; g.c_scatter = rperm; g.n_store = L;
+        g.ncol_max = (K0p + BN - 1) / BN;
+        for (int s = 0; s < S; ++s) {
+            const anihip_species_net &nn = d->net[s];
+            GemmProblem &p = g.prob[s];
+            p.B = nn.wt[0];
+            p.K = nn.dims[1] * M; p.N = K0p; p.ldb = p.N;
+            p.a_boff = 0; p.c_boff = 0; p.b_stride = 0;
+        }
+        launch_gemm_fp32<EPI_SCATTER>(stream, g);
     }
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;

@@ -353,6 +353,40 @@ class AevEngine:
             _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(t), _ptr(out), _ptr(nbrs.status)))
         return out
 
+    def jvp_batched(self, species: Tensor, nbrs: NeighborRows, tangent: Tensor) -> Tensor:
+        """J t[k] [K, N, L] for K coordinate directions tangent [K, N, 3] in one launch (anihip_aev_jvp_batched)."""
+        _require_cuda(species, tangent)
+        n = species.numel()
+        t = tangent.detach().to(torch.float32).contiguous()
+        K = t.shape[0]
+        assert t.numel() == 3 * n * K
+        out = torch.zeros((K, n, self.L), dtype=torch.float32, device=species.device)
+        _lib.check(_lib.lib().anihip_aev_jvp_batched(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, nbrs.lo, nbrs.hi, _ptr(species),
+            _ptr(nbrs.meta), _ptr(nbrs.ent), K, _ptr(t), _ptr(out), _ptr(nbrs.status)))
+        return out
+
+    def backward_second(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor, tangent: Tensor,
+                        dgrad: tp.Optional[Tensor] = None) -> Tensor:
+        """out[k] = J^T dgrad[k] + (D_{tangent[k]} J^T) grad_aev  [K, N, 3] (anihip_aev_backward_second): the derivative of
+        the backward along K coordinate directions; dgrad None = zeros."""
+        _require_cuda(species, grad_aev, tangent, dgrad)
+        if not nbrs.symmetric:
+            raise NotImplementedError("second derivatives need symmetric neighbor rows (the library's own builders)")
+        n = species.numel()
+        g = grad_aev.detach().to(torch.float32).contiguous()
+        t = tangent.detach().to(torch.float32).contiguous()
+        K = t.shape[0]
+        assert g.numel() == n * self.L and t.numel() == 3 * n * K
+        dg = (torch.zeros((K, n, self.L), dtype=torch.float32, device=species.device) if dgrad is None
+              else dgrad.detach().to(torch.float32).contiguous())
+        assert dg.numel() == K * n * self.L
+        out = torch.zeros((K, n, 3), dtype=torch.float32, device=species.device)
+        _lib.check(_lib.lib().anihip_aev_backward_second(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, nbrs.lo, nbrs.hi, _ptr(species),
+            _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(g), K, _ptr(t), _ptr(dg), _ptr(out), _ptr(nbrs.status)))
+        return out
+
     def backward(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor,
                  grad_coords: tp.Optional[Tensor] = None, shard_rows: bool = False,
                  virial: tp.Optional[Tensor] = None, slab_mask: tp.Optional[Tensor] = None,
@@ -813,6 +847,23 @@ class PackedNetworks:
             _ptr(de)))
         gw, gb = self._unpack_grads(buf, sizes, offs)
         return gw, gb, de
+
+    def input_hvp(self, species: Tensor, aev: Tensor, tangent: Tensor) -> Tensor:
+        """(1/M) sum_m H_m(aev_i) tangent[k, i]  [K, N, L]: input-space Hessian-vector products of the ensemble-mean atomic
+        energies for K AEV-space tangents [K, N, L] (anihip_mlp_input_hvp; exact fp32, activations once per atom)."""
+        _require_cuda(species, aev, tangent)
+        n = species.numel()
+        dev = aev.device
+        a = aev.detach().to(torch.float32).contiguous()
+        t = tangent.detach().to(torch.float32).contiguous()
+        K = t.shape[0]
+        assert a.numel() == n * self.aev_len and t.numel() == K * n * self.aev_len
+        L = _lib.lib()
+        ws = torch.empty(L.anihip_mlp_input_hvp_workspace_bytes(C.byref(self.desc), n, K), dtype=torch.uint8, device=dev)
+        out = torch.empty((K, n, self.aev_len), dtype=torch.float32, device=dev)
+        _lib.check(L.anihip_mlp_input_hvp(_stream(), C.byref(self.desc), n, _ptr(species), _ptr(a), K, _ptr(t), _ptr(ws),
+                                          ws.numel(), _ptr(out)))
+        return out
 
     def flat_grad_target(self, w_ptr, b_ptr, member_stride: int):
         """anihip_species_grads table for gradients that go straight into a flat buffer (torchani_amd.optim.Adam):

@@ -1,10 +1,18 @@
-"""Autograd helpers with the reference's names and behaviour (torchani/grad.py:42-86,263-399).
+"""Autograd helpers with the reference's names and behaviour (torchani/grad.py:42-399).
 
-Hessians (grad.py:86-150,239-260) need second derivatives with respect to the coordinates, which the HIP engine does
-not provide (its second-order pass serves training on forces: parameters only): ``hessians`` / ``forces_and_hessians``
-raise and say so.  NOT here (removed in round 3 as outside the hot path, SURVEY section 2 "OUT OF SCOPE"): the reference's
-``vibrational_analysis`` / ``VibAnalysis`` (grad.py:153-236), a numerical Hessian, and the modules ``torchani.units``,
-``torchani.cutoffs`` (the cutoff envelopes live in the AEV kernels: ``AEVComputer(..., cutoff_fn="cosine" | "smooth")``,
+Hessians with respect to the coordinates (grad.py:86-150,239-260) come in two forms:
+
+* ``hessians`` / ``forces_and_hessians``: through autograd like the reference -- one Hessian-vector product per force
+  component.  Forces taken with ``create_graph=True`` from a model with FROZEN parameters are differentiable with respect to
+  the coordinates: ``torch.autograd.grad((F * w).sum(), x) == -H w`` for any ``w``.  Each product runs the batched AEV JVP,
+  the network input HVP and the second-order AEV backward of the HIP engine (include/anihip.h).
+* ``energies_forces_and_hessians``: the batched path -- neighbor rows, AEVs and d E / d aev once, then the unit directions
+  of all molecules in chunks of K (``hessian_chunk_size``, from a fixed memory budget) through the same three kernels.
+
+Models with enabled pair potentials (xTB repulsion, D3) have no second derivative in the pair kernels: every Hessian entry
+point raises NotImplementedError naming the potential.  ``vibrational_analysis`` and ``VibAnalysis`` (grad.py:153-236) are
+host-side; unit conversions live in ``torchani_amd.units``.  NOT here: a numerical Hessian, the modules ``torchani.cutoffs``
+(the cutoff envelopes live in the AEV kernels: ``AEVComputer(..., cutoff_fn="cosine" | "smooth")``,
 ``constants.cutoff_kernel_name``) and ``torchani.sae`` (``nn.SelfEnergy`` is the energy shifter of the models).
 """
 from __future__ import annotations
@@ -15,7 +23,8 @@ import typing as tp
 import torch
 from torch import Tensor
 
-from .tuples import EnergiesForces
+from .tuples import EnergiesForces, EnergiesForcesHessians, ForcesHessians, VibAnalysis
+from . import units as _units
 
 
 def forces(energies: Tensor, coordinates: Tensor, retain_graph: tp.Optional[bool] = None,
@@ -37,7 +46,8 @@ def grads(scalars: Tensor, coords: Tensor, retain_graph: tp.Optional[bool] = Non
 
 
 __all__ = ["single_point", "forces_for_training", "energies_and_forces", "forces", "grads", "calc_forces", "calc_grads",
-           "hessians", "forces_and_hessians", "energies_forces_and_hessians"]   # (the last three raise: see the module docstring)
+           "hessians", "forces_and_hessians", "energies_forces_and_hessians", "calc_hessians", "calc_forces_and_hessians",
+           "vibrational_analysis"]
 
 calc_forces = forces
 calc_grads = grads
@@ -50,11 +60,164 @@ def forces_for_training(energies: Tensor, coordinates: Tensor) -> Tensor:
 
 
 def _no_hessians(*args, **kwargs):
-    raise NotImplementedError("hessians need second derivatives with respect to the coordinates, which the HIP engine "
-                              "does not provide")
+    # (single_point(hessians=True) is not wired up yet: use energies_forces_and_hessians / forces_and_hessians)
+    raise NotImplementedError("single_point(hessians=True) is not available: use grad.energies_forces_and_hessians or "
+                              "grad.forces_and_hessians")
 
 
-forces_and_hessians = hessians = energies_forces_and_hessians = _no_hessians
+def hessians(forces: Tensor, coordinates: Tensor, retain_graph: tp.Optional[bool] = None) -> Tensor:
+    """d^2 E / d x^2 [C, 3A, 3A] from forces taken with create_graph=True (grad.py:108-145): one Hessian-vector product per
+    force component through autograd.  Padding atoms give zero rows and columns."""
+    if not coordinates.requires_grad:
+        raise ValueError("'coordinates' passed to `torchani.grad.hessians` must require grad")
+    if not coordinates.is_leaf:
+        raise ValueError("'coordinates' passed to `torchani.grad` functions must be a 'leaf' Tensor"
+                         "(i.e. must not have been modified prior to being used as an input).")
+    if not forces.requires_grad:
+        raise RuntimeError("these forces carry no graph: take them with create_graph=True (grad.forces_and_hessians)")
+    C, A, D = forces.shape
+    n = A * D
+    flat = forces.reshape(C, n).unbind(dim=1)
+    cols = []
+    for j, comp in enumerate(flat):
+        keep = retain_graph if j == n - 1 else True
+        (gj,) = torch.autograd.grad([comp.sum()], [coordinates], retain_graph=keep, allow_unused=True)
+        if gj is None:
+            # (trainable parameters: the forces' second-order graph leads to the parameters, not to the coordinates)
+            raise RuntimeError("these forces do not depend on the coordinates to second order: Hessians through autograd "
+                               "need a model with frozen parameters (requires_grad_(False)); "
+                               "grad.energies_forces_and_hessians serves any model")
+        cols.append(gj.reshape(C, 1, n))
+    return -torch.cat(cols, dim=1)
+
+
+def forces_and_hessians(energies: Tensor, coordinates: Tensor, retain_graph: tp.Optional[bool] = None) -> ForcesHessians:
+    """ForcesHessians(forces, hessians) through autograd (grad.py:86-103)."""
+    f = forces(energies, coordinates, retain_graph=True, create_graph=True)
+    return ForcesHessians(f, hessians(f, coordinates, retain_graph=retain_graph))
+
+
+calc_hessians = hessians
+calc_forces_and_hessians = forces_and_hessians
+
+# device memory one chunk of directions of energies_forces_and_hessians may take
+HESSIAN_BUDGET_BYTES = 1 << 30
+
+
+def hessian_direction_bytes(n_rows: int, aev_len: int, hvp_row_bytes: int) -> int:
+    """Device bytes one direction of energies_forces_and_hessians costs over n_rows = C * A atom rows: its tangent and
+    output (3 floats each), J t and H_net J t (aev_len floats each), and the network HVP workspace of its rows."""
+    return n_rows * (4 * 6 + 8 * aev_len + hvp_row_bytes)
+
+
+def hessian_chunk_size(n_molecules: int, n_atoms: int, aev_len: int, hvp_row_bytes: int,
+                       budget: int = HESSIAN_BUDGET_BYTES) -> int:
+    """K: unit directions per chunk of energies_forces_and_hessians, from the fixed memory budget (never from a user
+    option): as many as fit, at least 1, at most the 3A directions of a molecule."""
+    per = hessian_direction_bytes(n_molecules * n_atoms, aev_len, hvp_row_bytes)
+    return int(max(1, min(3 * n_atoms, budget // max(per, 1))))
+
+
+def _enabled_pair_potentials(model) -> tp.List[str]:
+    pots = getattr(model, "potentials", None)
+    if pots is None:
+        return []
+    return [type(p).__name__ for name, p in pots.items() if name != "nnp" and getattr(p, "_enabled", False)]
+
+
+def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, retain_graph: bool = False, *,
+                                 cell: tp.Optional[Tensor] = None,
+                                 pbc: tp.Optional[Tensor] = None) -> EnergiesForcesHessians:
+    """EnergiesForcesHessians(energies, forces, hessians [C, 3A, 3A]) of a model, batched (grad.py:239-260 computes the
+    same through 3A autograd products).  The neighbor rows, AEVs and d E / d aev are computed once; then unit direction j
+    (atom j // 3, component j % 3 of EVERY molecule of the batch at once) runs through anihip_aev_jvp_batched,
+    anihip_mlp_input_hvp and anihip_aev_backward_second in chunks of K = hessian_chunk_size(...) directions: ceil(3A / K)
+    calls per stage.  Energies and forces are those of grad.energies_and_forces.  Results are detached (any model: frozen
+    or trainable parameters); ``retain_graph`` is accepted for the reference's signature."""
+    pots = _enabled_pair_potentials(model)
+    if pots:
+        raise NotImplementedError(f"the pair potential(s) {', '.join(pots)} have no second derivative with respect to the "
+                                  "coordinates: Hessians of this model are not available")
+    ef = energies_and_forces(model, species, coordinates, cell, pbc, keep_vars=False)
+    with torch.no_grad():
+        aevc = model.aev_computer
+        elem = model._elem_idxs(species)
+        species32 = elem.to(torch.int32).contiguous()
+        c32 = coordinates.detach().to(torch.float32).contiguous()
+        pbc_t = None if pbc is None else tuple(bool(b) for b in pbc.tolist())
+        nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_t)
+        nbrs.raise_on_overflow()
+        eng = aevc.engine()
+        aev = eng.forward(species32, nbrs)
+        packed = model.neural_networks._pack(coordinates.device)
+        _, g, _ = packed.forward_backward(species32, aev, want_grad=True)
+        Cn, A = species32.shape
+        N = Cn * A
+        row_bytes = -(-_hvp_row_bytes(packed, N) // N)
+        K = hessian_chunk_size(Cn, A, eng.L, row_bytes)
+        n = 3 * A
+        H = torch.zeros((Cn, n, n), dtype=torch.float32, device=coordinates.device)
+        rows = torch.arange(Cn, device=coordinates.device) * A
+        for j0 in range(0, n, K):
+            j1 = min(n, j0 + K)
+            k = torch.arange(j1 - j0, device=coordinates.device)
+            t = torch.zeros((j1 - j0, N, 3), dtype=torch.float32, device=coordinates.device)
+            jj = k + j0
+            t[k.view(-1, 1), (rows.view(1, -1) + (jj // 3).view(-1, 1)), (jj % 3).view(-1, 1)] = 1.0
+            daev = eng.jvp_batched(species32, nbrs, t)
+            hv = packed.input_hvp(species32, aev, daev.view(j1 - j0, N, eng.L))
+            del daev
+            out = eng.backward_second(species32, nbrs, g, t, hv)   # [K, N, 3]: columns j0..j1 of every molecule
+            H[:, :, j0:j1] = out.view(j1 - j0, Cn, n).permute(1, 2, 0)
+    return EnergiesForcesHessians(ef.energies, ef.forces, H.to(coordinates.dtype))
+
+
+def _hvp_row_bytes(packed, n_rows: int) -> int:
+    """Workspace bytes of ONE direction of anihip_mlp_input_hvp over n_rows atoms (the query is linear in the directions)."""
+    import ctypes
+
+    from . import _lib
+
+    L = _lib.lib()
+    one = L.anihip_mlp_input_hvp_workspace_bytes(ctypes.byref(packed.desc), n_rows, 1)
+    two = L.anihip_mlp_input_hvp_workspace_bytes(ctypes.byref(packed.desc), n_rows, 2)
+    return max(int(two - one), 1)
+
+
+def vibrational_analysis(masses: Tensor, hessian: Tensor, mode_kind: str = "mdu", unit: str = "cm^-1") -> VibAnalysis:
+    """Harmonic frequencies, normal modes, force constants and reduced masses of ONE molecule (grad.py:153-236).
+
+    masses [1, A] (amu), hessian [1, 3A, 3A] (Hartree / Angstrom^2).  The generalized eigenproblem H q = w^2 T q
+    (T = the masses on the diagonal, three times each) is solved as the symmetric problem T^-1/2 H T^-1/2 q' = w^2 q'.
+    mode_kind: "mdu" mass-deweighted unnormalized (ASE), "mdn" mass-deweighted normalized (Gaussian, ORCA), "mwn"
+    mass-weighted normalized.  Imaginary frequencies come out negative.  Force constants (mDyne / Angstrom) and reduced
+    masses (amu) as in Gaussian.  unit: "cm^-1" or "meV"."""
+    if unit == "cm^-1":
+        to_unit = _units.sqrt_mhessian2invcm
+    elif unit == "meV":
+        to_unit = _units.sqrt_mhessian2milliev
+    else:
+        raise ValueError("Only meV and cm^-1 are supported right now")
+    assert hessian.shape[0] == 1, "Currently only supporting computing one molecule a time"
+    w = masses.sqrt().reciprocal().repeat_interleave(3, dim=1)[0]   # [3A]
+    mh = hessian[0] * w.unsqueeze(0) * w.unsqueeze(1)
+    evals, evecs = torch.linalg.eigh(mh)
+    mw = evecs.transpose(0, 1)                     # row k = mass-weighted mode k (orthonormal)
+    md = mw * w.unsqueeze(0)                       # mass-deweighted, unnormalized
+    inv_norm = md.norm(dim=1).reciprocal()         # sqrt(amu)
+    rmasses = inv_norm ** 2
+    fconstants = _units.mhessian2fconst(evals) * rmasses
+    kind = mode_kind.lower()
+    if kind in ("mdn", "mass-deweighted-normalized"):
+        modes = md * inv_norm.unsqueeze(1)
+    elif kind in ("mdu", "mass-deweighted-unnormalized"):
+        modes = md
+    elif kind in ("mwn", "mass-weighted-normalized"):
+        modes = mw
+    else:
+        raise ValueError(f"Incorrect mode kind {mode_kind}")
+    freqs = to_unit(evals.abs().sqrt() / (2 * math.pi) * torch.sign(evals))
+    return VibAnalysis(freqs, modes.reshape(evals.numel(), -1, 3), fconstants, rmasses)
 
 
 def energies_and_forces(model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None,

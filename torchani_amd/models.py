@@ -114,13 +114,16 @@ class ANI(torch.nn.Module):
         if ensemble_values:
             energies = energies.unsqueeze(0)
         extra = None
+        frozen = True   # (networks without trainable parameters: the pair terms guard their missing second derivative)
         if self.potentials["nnp"]._enabled:
             aevs = self.aev_computer(elem_idxs, coords, cell, pbc)
             energies = energies + self.neural_networks(elem_idxs, aevs, atomic, ensemble_values)
             extra = self._scalars_from_aevs(elem_idxs, aevs, charge)
+            frozen = getattr(aevs.grad_fn, "frozen_nets", True)
         for name, pot in self.potentials.items():   # pair potentials on the same neighbor rows (arch.py:329-346)
             if name == "nnp" or not pot._enabled:
                 continue
+            pot._second_order_guard = frozen
             species32 = elem_idxs.to(torch.int32).contiguous()
             nbrs = self.aev_computer.last_neighbors() if self.potentials["nnp"]._enabled else None
             if nbrs is None or pot.cutoff > self.aev_computer.radial.cutoff + 1e-6 or getattr(pot, "needs_all_rows", False):

@@ -102,6 +102,35 @@ class _MLPBackwardFunction(torch.autograd.Function):
         return (d_go, None, None, None, None, *flat)
 
 
+class _MLPInputGradFunction(torch.autograd.Function):
+    """(grad_out, coords) -> grad_aev = grad_out * d e / d aev of FROZEN networks, differentiable: its backward for an
+    incoming v [C, A, L] returns sum_L v g to grad_out and, to the coordinates, J^T (grad_out H_net v) -- the network input
+    HVP (anihip_mlp_input_hvp) taken back through the AEV backward.  The AEVs are recomputed from the AEV node's rows (only
+    when a second derivative is actually taken)."""
+
+    @staticmethod
+    def forward(ctx, grad_out: Tensor, coords: Tensor, node, packed: PackedNetworks, g_unit: Tensor, shape) -> Tensor:
+        go = grad_out.detach().to(torch.float32).reshape(-1, 1)
+        ctx.node, ctx.packed, ctx.g_unit, ctx.go, ctx.shape = node, packed, g_unit, go, shape
+        ctx.go_shape, ctx.go_dtype, ctx.c_dtype = grad_out.shape, grad_out.dtype, coords.dtype
+        return (g_unit * go).view(shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v: Tensor):
+        node, g_unit = ctx.node, ctx.g_unit
+        v32 = v.to(torch.float32).reshape(g_unit.shape)
+        d_go = (v32 * g_unit).sum(dim=-1).view(ctx.go_shape).to(ctx.go_dtype) if ctx.needs_input_grad[0] else None
+        dc = None
+        if ctx.needs_input_grad[1]:
+            species32 = node.species32
+            a32 = node.eng.forward(species32, node.nbrs)
+            hv = ctx.packed.input_hvp(species32, a32, v32.unsqueeze(0))[0] * ctx.go
+            C, A = species32.shape
+            dc = node.eng.backward(species32, node.nbrs, hv.contiguous()).view(C, A, 3).to(ctx.c_dtype)
+        return d_go, dc, None, None, None, None
+
+
 class _MLPFunction(torch.autograd.Function):
     """params = the Linear parameters in the order member -> species -> layer -> (weight, bias)."""
 
@@ -121,6 +150,15 @@ class _MLPFunction(torch.autograd.Function):
             ae, g, me = packed.forward_backward(species32, a32, want_grad=need_grad, want_members=want_members)
         ctx.g = g
         ctx.train = train
+        # the AEV node (aev._AEVFunction) learns whether its networks are frozen: only then does a create_graph=True backward
+        # give the forces a coordinate dependence (Hessians); force training keeps its first-order AEV graph
+        node = aevs.grad_fn if aevs.requires_grad else None
+        if node is not None and hasattr(node, "coords_ref"):
+            node.frozen_nets = not train and not want_members
+        else:
+            node = None
+        ctx.aev_node = node if (need_grad and not want_members) else None
+        ctx.packed = packed if ctx.aev_node is not None else None
         ctx.flat_target = getattr(packed, "flat_target", None) if train else None
         ctx.flat_verify = getattr(packed, "flat_verify", None) if ctx.flat_target is not None else None
         ctx.aev_grad = aevs.requires_grad
@@ -181,6 +219,14 @@ class _MLPFunction(torch.autograd.Function):
             return (ga, None, None, None, *flat)
         if ctx.g is None:
             raise RuntimeError("AEVs did not require grad in forward")
+        node = ctx.aev_node
+        coords = node.coords_ref() if (node is not None and torch.is_grad_enabled()) else None
+        if coords is not None:
+            # create_graph=True with frozen parameters and AEVs of this package's AEVComputer: d E / d aev stays
+            # differentiable with respect to the coordinates (network input HVP) and to grad_out.  Nothing more is kept by
+            # a first-order call: the AEVs are recomputed from the AEV node's rows when a second derivative is taken
+            g = _MLPInputGradFunction.apply(grad_out, coords, node, ctx.packed, ctx.g, ctx.shape)
+            return (g.to(ctx.in_dtype), None, None, None, *([None] * len(ctx.param_dtypes)))
         if torch.is_grad_enabled() and grad_out.requires_grad:
             raise RuntimeError("second-order gradients need trainable parameters (requires_grad) in the HIP engine")
         g = ctx.g.view(ctx.shape) * grad_out.to(torch.float32).unsqueeze(-1)

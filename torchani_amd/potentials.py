@@ -18,6 +18,7 @@ import ctypes as C
 import math
 import os
 import typing as tp
+import weakref
 
 import numpy as np
 import torch
@@ -49,15 +50,38 @@ class _PairEnergy(torch.autograd.Function):
         grad = torch.zeros((Cn * A, 3), dtype=torch.float32, device=coords.device)
         pot.accumulate(species32, nbrs, atomic, grad)
         ctx.save_for_backward(grad)
-        ctx.shape, ctx.dtype = coords.shape, coords.dtype
+        ctx.shape, ctx.dtype, ctx.pot = coords.shape, coords.dtype, pot
+        # (held weakly: a first-order call keeps nothing alive; the guard below needs the coordinates as an input)
+        ctx.coords_ref = weakref.ref(coords) if getattr(pot, "_second_order_guard", True) else None
         return atomic.view(Cn, A).to(torch.float64).sum(dim=1)
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, g: Tensor):
         (grad,) = ctx.saved_tensors
         Cn, A = ctx.shape[0], ctx.shape[1]
-        return (grad.view(Cn, A, 3) * g.view(Cn, 1, 1).to(grad.dtype)).to(ctx.dtype), None, None, None
+        with torch.no_grad():
+            gc = (grad.view(Cn, A, 3) * g.view(Cn, 1, 1).to(grad.dtype)).to(ctx.dtype)
+        # create_graph=True: pair.hip has no second derivative with respect to the coordinates -- never drop the term
+        # silently, raise when it is taken.  (Not when the model's networks train: force training differentiates the forces
+        # with respect to the parameters, which the pair term does not depend on.)
+        coords = ctx.coords_ref() if (torch.is_grad_enabled() and ctx.coords_ref is not None) else None
+        if coords is not None and coords.requires_grad:
+            gc = _PairNoSecondOrder.apply(gc, coords, type(ctx.pot).__name__)
+        return gc, None, None, None
+
+
+class _PairNoSecondOrder(torch.autograd.Function):
+    """Identity whose derivative raises: the pair kernels have no second derivative with respect to the coordinates."""
+
+    @staticmethod
+    def forward(ctx, gc: Tensor, coords: Tensor, name: str) -> Tensor:
+        ctx.name = name
+        return gc.clone()
+
+    @staticmethod
+    def backward(ctx, _v: Tensor):
+        raise NotImplementedError(f"the pair potential {ctx.name} has no second derivative with respect to the coordinates "
+                                  "(Hessians of models with enabled pair potentials are not available)")
 
 
 class _Standalone:

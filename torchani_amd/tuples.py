@@ -87,3 +87,27 @@ class ForceStdev(tp.NamedTuple):
     magnitudes: Tensor
     relative_stdev: Tensor
     relative_range: Tensor
+
+
+class EnergiesForcesHessians(tp.NamedTuple):
+    """What grad.energies_forces_and_hessians returns (torchani/tuples.py:18-21): hessians [C, 3A, 3A]."""
+
+    energies: Tensor
+    forces: Tensor
+    hessians: Tensor
+
+
+class ForcesHessians(tp.NamedTuple):
+    """What grad.forces_and_hessians returns (torchani/tuples.py:24-26)."""
+
+    forces: Tensor
+    hessians: Tensor
+
+
+class VibAnalysis(tp.NamedTuple):
+    """Frequencies, normal modes, force constants and reduced masses of grad.vibrational_analysis (torchani/tuples.py:36-42)."""
+
+    freqs: Tensor
+    modes: Tensor
+    fconstants: Tensor
+    rmasses: Tensor
