@@ -540,6 +540,18 @@ int anihip_pair_analytic(void *stream, int32_t kind, int64_t n_atoms, int64_t lo
                          float cutoff, int32_t cutoff_kind, int32_t flags, float *atomic_e, float *grad_coords,
                          double *virial);
 
+/* Hessian-vector products of anihip_pair_analytic's energy, for Hessians with respect to the coordinates: for n_dir
+ * directions t[k],  out[k] += H t[k]  over the central atoms lo <= i < hi, with H = d^2 E / d coords^2 of the pair energies
+ * of those rows.  Same kind, rows, pair_table, extra, cutoff, cutoff_kind and ANIHIP_PAIR_NO_CLAMP as anihip_pair_analytic;
+ * tangent and out are device float [n_dir][n_atoms][3].  Per pair, with d = r_j - r_i, r = |d|, u = d / r and
+ * e(r) = base(r) fc(r):  (H t)_i = sum_{j in row i} (e''(r) u u^T + e'(r) / r (I - u u^T)) (t_i - t_j)  -- a periodic
+ * image of atom i itself contributes nothing.  Symmetric rows only (ANIHIP_PAIR_PUSH is refused); no atomics,
+ * deterministic. */
+int anihip_pair_analytic_hvp(void *stream, int32_t kind, int64_t n_atoms, int64_t lo, int64_t hi, const int32_t *species,
+                             const uint32_t *meta, const float *ent, const float *pair_table, const float *extra,
+                             float cutoff, int32_t cutoff_kind, int32_t flags, int64_t n_dir, const float *tangent,
+                             float *out);
+
 /* DFT-D3(BJ) two-body dispersion (potentials/dftd3.py:113-330 TwoBodyDispersionD3, damping :44-110 BeckeJohnsonDamp;
  * envelope and per-atom halves as above), distances in Bohr:
  *   CN_i   = sum_j 1 / (1 + exp(-16 (4/3 (Rcov_a + Rcov_b) / d_ij - 1)))                     (all neighbors of the row)

@@ -2,8 +2,11 @@
 loop of grad.forces_and_hessians) on fixtures of tests/golden: device-synchronised, after warm-up, median of several runs.
 
     python tools/hessian_bench.py [--runs 5] [--autograd-max 264] [--bases ch4_ani1x,dense90_ani2x,...]
+                                  [--kind fixture|ani2xr|anir2s]
 
-Prints one JSON line per case.  Seeded parameters (the fixtures' seeds): timings do not depend on the values."""
+Prints one JSON line per case.  Seeded parameters (the fixtures' seeds): timings do not depend on the values.
+``--kind ani2xr`` / ``anir2s`` times that architecture (networks plus the xTB repulsion term) on the fixtures'
+coordinates instead of the fixture's own ANI-2x / ANI-1x model."""
 from __future__ import annotations
 
 import argparse
@@ -36,23 +39,33 @@ def main():
     from _util import load_golden, seeded_state
 
     from torchani_amd import grad
-    from torchani_amd.models import ANI1x, ANI2x
+    from torchani_amd.models import ANI1x, ANI2x, ANI2xr, ANIr2s
+    from torchani_amd.weights import arch_spec
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--autograd-max", type=int, default=264)
     ap.add_argument("--bases", default="ch4_ani1x,dense90_ani2x,small_ani2x,1hz5_ani2x")
+    ap.add_argument("--kind", default="fixture", choices=("fixture", "ani2xr", "anir2s"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for base in args.bases.split(","):
         g = load_golden(base)
-        ctor = ANI2x if g["kind"] == "ani2x" else ANI1x
-        model = ctor(state_dict=seeded_state(g["kind"], 8, g["seed"]), device=dev, periodic_table_index=False,
-                     cutoff_fn=g["cutoff_fn"], row_capacity=256)
-        sp = torch.from_numpy(g["species"].astype(np.int64)).to(dev)
+        species = g["species"].astype(np.int64)
+        if args.kind == "fixture":
+            ctor = ANI2x if g["kind"] == "ani2x" else ANI1x
+            model = ctor(state_dict=seeded_state(g["kind"], 8, g["seed"]), device=dev, periodic_table_index=False,
+                         cutoff_fn=g["cutoff_fn"], row_capacity=256)
+        else:
+            ctor = ANI2xr if args.kind == "ani2xr" else ANIr2s
+            model = ctor(state_dict=seeded_state(args.kind, 8, g["seed"]), device=dev, periodic_table_index=False,
+                         neighborlist="batch", row_capacity=256)
+            symbols = arch_spec(args.kind)[0]
+            species = np.asarray([symbols.index(s) for s in g["symbols"]] + [-1])[species]   # (-1 stays -1)
+        sp = torch.from_numpy(species).to(dev)
         x = torch.from_numpy(g["coords"]).to(dev)
         A = int((sp >= 0).sum())
-        row = {"case": base, "atoms": A}
+        row = {"case": base, "model": g["kind"] if args.kind == "fixture" else args.kind, "atoms": A}
         row["batched_ms"], row["batched_runs"] = timed(lambda: grad.energies_forces_and_hessians(model, sp, x),
                                                        max(1, args.runs if A < 500 else 3))
         if A <= args.autograd_max:

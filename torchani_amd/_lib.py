@@ -212,6 +212,8 @@ def lib() -> C.CDLL:
     L.anihip_pair_xtb_repulsion.restype = C.c_int
     L.anihip_pair_analytic.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp, vp, vp, C.c_float, i32, i32, vp, vp, vp]
     L.anihip_pair_analytic.restype = C.c_int
+    L.anihip_pair_analytic_hvp.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp, vp, vp, C.c_float, i32, i32, i64, vp, vp]
+    L.anihip_pair_analytic_hvp.restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
     for name in ("anihip_aev_table_pack", "anihip_nbr_build_batch", "anihip_nbr_build_cell", "anihip_nbr_from_half",
@@ -235,6 +237,7 @@ EXPORTED_SYMBOLS = [
     "anihip_pair_d3", "anihip_pair_analytic", "anihip_energy_forces_finish", "anihip_mlp_pack_bytes", "anihip_mlp_pack",
     "anihip_nbr_rows_to_half_workspace_bytes", "anihip_nbr_rows_to_half",
     "anihip_aev_jvp_batched", "anihip_aev_backward_second", "anihip_mlp_input_hvp_workspace_bytes", "anihip_mlp_input_hvp",
+    "anihip_pair_analytic_hvp",
 ]
 
 

@@ -132,6 +132,155 @@ __global__ __launch_bounds__(256) void k_pair(int64_t lo, int64_t hi, const int3
     }
 }
 
+// ---- Hessian-vector products of the closed-form pair terms ------------------------------------------------------
+// For a pair with d = r_j - r_i, r = |d|, u = d / r and e(r) = base(r) fc(r), d^2 e / d d^2 = B = a I + c u u^T with
+// a = e'(r) / r, c = e''(r) - a.  On symmetric rows atom i owns every pair of its row in full (as in k_pair's gradient), so
+//   (H v)_i = sum_{j in row i} B_ij (v_i - v_j)
+// and a periodic image of i itself (j == i) contributes v_i - v_i = 0, which is the second derivative of a constant.
+
+// bare pair energy and its first and second derivatives with respect to r [Angstrom] (the same forms as pair_eval)
+template <int KIND>
+__device__ __forceinline__ void pair_eval2(const float4 p, const PairExtra &x, float r, float &base, float &dbase,
+                                           float &d2base)
+{
+    constexpr float B2 = A2B * A2B;
+    if constexpr (KIND == ANIHIP_PAIR_XTB) {            // f = y / d exp(-s d^k): f' = f g, f'' = f (g^2 + g'), g = -1/d - s k d^(k-1)
+        const float rb = r * A2B, irb = 1.0f / rb;
+        const float pw = __builtin_amdgcn_exp2f(p.z * __builtin_amdgcn_logf(rb));   // rb^k
+        const float ex = __expf(-p.y * pw);
+        base = p.x / rb * ex;
+        const float g = -irb - p.y * p.z * pw * irb;
+        const float dg = (1.0f - p.y * p.z * (p.z - 1.0f) * pw) * irb * irb;
+        dbase = base * g * A2B;
+        d2base = base * (g * g + dg) * B2;
+    } else if constexpr (KIND == ANIHIP_PAIR_ZBL) {     // f = cl phi(s d), cl = Za Zb / d
+        const float rb = r * A2B, irb = 1.0f / rb, xr = rb * p.y;
+        float phi = 0.f, dphi = 0.f, d2phi = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float t = x.v[i] * __expf(-x.v[4 + i] * xr);
+            phi += t;
+            dphi -= x.v[4 + i] * t;
+            d2phi += x.v[4 + i] * x.v[4 + i] * t;
+        }
+        const float cl = p.x * irb;
+        base = cl * phi;
+        dbase = cl * (p.y * dphi - phi * irb) * A2B;
+        d2base = cl * (p.y * p.y * d2phi - 2.0f * p.y * dphi * irb + 2.0f * phi * irb * irb) * B2;
+    } else if constexpr (KIND == ANIHIP_PAIR_LJ) {      // d^2 / dr^2 x^n = n (n + 1) x^n / r^2
+        const float ir = 1.0f / r, xs = p.y * ir, x2 = xs * xs, x6 = x2 * x2 * x2, x12 = x6 * x6;
+        base = p.x * (p.z * x12 + p.w * x6);
+        dbase = -p.x * (12.0f * p.z * x12 + 6.0f * p.w * x6) * ir;
+        d2base = p.x * (156.0f * p.z * x12 + 42.0f * p.w * x6) * ir * ir;
+    } else {                                            // f = qq (d^2 + h^2)^-1/2: f'' = qq is^3 (3 d^2 is^2 - 1)
+        const float rb = r * A2B;
+        const float is = __builtin_amdgcn_rsqf(rb * rb + p.y * p.y), is3 = is * is * is;
+        base = p.x * is;
+        dbase = -p.x * rb * is3 * A2B;
+        d2base = p.x * is3 * (3.0f * rb * rb * is * is - 1.0f) * B2;
+    }
+}
+
+// envelope and its first and second derivatives (cutoffs.py:74-101; the smooth one's max(eps, .) guard as in k_pair: both
+// derivatives are 0 beyond it, and fc im^2 is formed first so that fc = 0 never meets an overflowed power of im)
+__device__ __forceinline__ void envelope2(float r, float inv_rc, float rev_rc, float pi_rc, int smooth, float &fc,
+                                          float &dfc, float &d2fc)
+{
+    if (smooth) {
+        const float q = r * inv_rc, m1 = (1.0f - q) * (1.0f + q);
+        const float im = 1.0f / fmaxf(1e-10f, m1);
+        fc = __expf(1.0f - im);
+        if (m1 - 1e-10f >= 0.0f) {
+            const float irc2 = inv_rc * inv_rc, fi2 = fc * im * im, s = r * r * irc2;
+            dfc = -2.0f * r * irc2 * fi2;
+            d2fc = fi2 * irc2 * (4.0f * s * im * im - 8.0f * s * im - 2.0f);
+        } else {
+            dfc = 0.f;
+            d2fc = 0.f;
+        }
+    } else {
+        const float cs = __builtin_amdgcn_cosf(r * rev_rc);
+        fc = 0.5f * cs + 0.5f;
+        dfc = -0.5f * pi_rc * __builtin_amdgcn_sinf(r * rev_rc);
+        d2fc = -0.5f * pi_rc * pi_rc * cs;
+    }
+}
+
+// out[k] += H t[k] for k < n_dir.  One wave per central atom, lane = neighbor, as k_pair: each lane evaluates its pair's
+// (a, c, u) once, in registers (up to HVP_ROUNDS x 64 neighbors = ANIHIP_MAX_RAD, every row of the library's builders),
+// then for every direction gathers t[k][j], applies B and the wave sums give (H t[k])_i.  No atomics: deterministic.
+constexpr int HVP_ROUNDS = (MAXR + WAVE - 1) / WAVE;
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, int64_t hi,
+                                                  const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
+                                                  const float4 *__restrict__ ent, const float *__restrict__ tab,
+                                                  PairExtra extra, float cutoff, int smooth, int clamp_r, int64_t n_dir,
+                                                  const float *__restrict__ tangent, float *__restrict__ out)
+{
+    const int lane = lane_id();
+    const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const size_t stride = (size_t)n_atoms * 3;
+    const float inv_rc = 1.0f / cutoff, rev_rc = 0.5f / cutoff, pi_rc = 3.14159265358979f / cutoff;
+    for (int64_t i = lo + blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); i < hi; i += nw) {
+        const int si = species[i];
+        if (si < 0) continue;
+        const uint32_t start = meta[(size_t)i * META_W], c = meta[(size_t)i * META_W + 1];
+        const int nR = (int)(c & 0xFFFFu) + (int)(c >> 16);
+        for (int b0 = 0; b0 < nR; b0 += HVP_ROUNDS * WAVE) {   // (one pass for every row of at most ANIHIP_MAX_RAD entries)
+            float ba[HVP_ROUNDS], bc[HVP_ROUNDS], ux[HVP_ROUNDS], uy[HVP_ROUNDS], uz[HVP_ROUNDS];
+            int jj[HVP_ROUNDS];   // (atom indices have 28 bits: IDX_MASK)
+#pragma unroll
+            for (int q = 0; q < HVP_ROUNDS; ++q) {
+                ba[q] = 0.f; bc[q] = 0.f; ux[q] = 0.f; uy[q] = 0.f; uz[q] = 0.f;
+                jj[q] = (int)i;   // (an empty slot gathers v_i and adds B (v_i - v_i) with B = 0)
+                const int k = b0 + q * WAVE + lane;
+                if (k >= nR) continue;
+                const float4 d = ent[start + k];
+                const uint32_t w = __float_as_uint(d.w);
+                const int sj = (int)(w >> 28);
+                const int j = (int)(w & IDX_MASK);
+                if (j >= n_atoms) continue;
+                const float r2 = d.x * d.x + d.y * d.y + d.z * d.z;
+                const float inv = __builtin_amdgcn_rsqf(r2);
+                const float r = clamp_r ? fmaxf(r2 * inv, 1e-7f) : r2 * inv;   // (core.py:138-139 clamp)
+                if (r > cutoff) continue;
+                float fc, dfc, d2fc;
+                envelope2(r, inv_rc, rev_rc, pi_rc, smooth, fc, dfc, d2fc);
+                const float4 p = reinterpret_cast<const float4 *>(tab)[si * 8 + sj];
+                float base, dbase, d2base;
+                pair_eval2<KIND>(p, extra, r, base, dbase, d2base);
+                const float e1 = dbase * fc + base * dfc;
+                const float e2 = d2base * fc + 2.0f * dbase * dfc + base * d2fc;
+                ba[q] = e1 / r;
+                bc[q] = e2 - ba[q];
+                ux[q] = d.x * inv; uy[q] = d.y * inv; uz[q] = d.z * inv;
+                jj[q] = j;
+            }
+            for (int64_t kd = 0; kd < n_dir; ++kd) {
+                const float *tk = tangent + (size_t)kd * stride;
+                const float vx = tk[3 * i], vy = tk[3 * i + 1], vz = tk[3 * i + 2];
+                float hx = 0.f, hy = 0.f, hz = 0.f;
+#pragma unroll
+                for (int q = 0; q < HVP_ROUNDS; ++q) {
+                    if (b0 + q * WAVE >= nR) break;   // (wave-uniform)
+                    const float *tj = tk + 3 * (size_t)jj[q];
+                    const float dx = vx - tj[0], dy = vy - tj[1], dz = vz - tj[2];
+                    const float cu = bc[q] * (ux[q] * dx + uy[q] * dy + uz[q] * dz);
+                    hx += ba[q] * dx + cu * ux[q];
+                    hy += ba[q] * dy + cu * uy[q];
+                    hz += ba[q] * dz + cu * uz[q];
+                }
+                hx = wave_sum(hx); hy = wave_sum(hy); hz = wave_sum(hz);
+                if (lane == 0) {
+                    float *o = out + (size_t)kd * stride + 3 * i;
+                    o[0] += hx; o[1] += hy; o[2] += hz;
+                }
+            }
+        }
+    }
+}
+
 // ---- DFT-D3(BJ) two-body dispersion (potentials/dftd3.py:113-330) -------------------------------------------------
 // Three passes over the rows, one wave per central atom, lane = neighbor, all gathers (the rows are full and symmetric):
 //   k_d3_cn     CN_i = sum_j count(d_ij)                                                    (:256-279 _coordnums)
@@ -386,6 +535,44 @@ extern "C" int anihip_pair_analytic(void *stream, int32_t kind, int64_t n_atoms,
         default: ANIHIP_LAUNCH_PAIR(ANIHIP_PAIR_COULOMB); break;
     }
 #undef ANIHIP_LAUNCH_PAIR
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_pair_analytic_hvp(void *stream, int32_t kind, int64_t n_atoms, int64_t lo, int64_t hi,
+                                        const int32_t *species, const uint32_t *meta, const float *ent,
+                                        const float *pair_table, const float *extra, float cutoff, int32_t cutoff_kind,
+                                        int32_t flags, int64_t n_dir, const float *tangent, float *out)
+{
+    ANIHIP_REQUIRE(species && meta && ent && pair_table, "null pointer argument");
+    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
+    ANIHIP_REQUIRE(n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
+    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
+    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
+    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
+    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
+    ANIHIP_REQUIRE(!(flags & ANIHIP_PAIR_PUSH),
+                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    ANIHIP_REQUIRE(n_dir >= 0, "n_dir must not be negative");
+    if (hi == lo || n_dir == 0) return 0;
+    ANIHIP_REQUIRE(tangent && out, "null pointer argument");
+    int64_t blocks = (hi - lo + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    PairExtra x{};
+    if (extra)
+        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
+    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
+    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
+#define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
+    hipLaunchKernelGGL((k_pair_hvp<K>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_atoms, lo, hi,     \
+                       species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r, n_dir, tangent, out)
+    switch (kind) {
+        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
+        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;
+        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_LJ); break;
+        default: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_COULOMB); break;
+    }
+#undef ANIHIP_LAUNCH_PAIR_HVP
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

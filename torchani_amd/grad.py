@@ -9,8 +9,10 @@ Hessians with respect to the coordinates (grad.py:86-150,239-260) come in two fo
 * ``energies_forces_and_hessians``: the batched path -- neighbor rows, AEVs and d E / d aev once, then the unit directions
   of all molecules in chunks of K (``hessian_chunk_size``, from a fixed memory budget) through the same three kernels.
 
-Models with enabled pair potentials (xTB repulsion, D3) have no second derivative in the pair kernels: every Hessian entry
-point raises NotImplementedError naming the potential.  ``vibrational_analysis`` and ``VibAnalysis`` (grad.py:153-236) are
+The closed-form pair potentials (xTB repulsion, ZBL, Lennard-Jones, fixed-charge Coulomb / MNOK: ANI-2xr, ANI-r2s and
+models built with ``add_pair_potential``) add their Hessian-vector products (anihip_pair_analytic_hvp) on both paths, and a
+standalone pair potential may stand in for the model.  D3 dispersion (ANI-2dr) has no second derivative here: every Hessian
+entry point raises NotImplementedError naming it.  ``vibrational_analysis`` and ``VibAnalysis`` (grad.py:153-236) are
 host-side; unit conversions live in ``torchani_amd.units``.  NOT here: a numerical Hessian, the modules ``torchani.cutoffs``
 (the cutoff envelopes live in the AEV kernels: ``AEVComputer(..., cutoff_fn="cosine" | "smooth")``,
 ``constants.cutoff_kernel_name``) and ``torchani.sae`` (``nn.SelfEnergy`` is the energy shifter of the models).
@@ -118,11 +120,33 @@ def hessian_chunk_size(n_molecules: int, n_atoms: int, aev_len: int, hvp_row_byt
     return int(max(1, min(3 * n_atoms, budget // max(per, 1))))
 
 
-def _enabled_pair_potentials(model) -> tp.List[str]:
-    pots = getattr(model, "potentials", None)
-    if pots is None:
-        return []
-    return [type(p).__name__ for name, p in pots.items() if name != "nnp" and getattr(p, "_enabled", False)]
+def _pair_potentials_without_hessians(model) -> tp.List[str]:
+    """Names of the enabled pair potentials of a model (or of a standalone potential) that have no second derivative
+    with respect to the coordinates: TwoBodyDispersionD3 (its coordination-number coupling)."""
+    from .potentials import _AnalyticPair, _Standalone
+
+    if isinstance(model, _Standalone):
+        pots = [model]
+    else:
+        pots = [p for name, p in getattr(model, "potentials", {}).items() if name != "nnp" and getattr(p, "_enabled", False)]
+    return [type(p).__name__ for p in pots if not isinstance(p, _AnalyticPair)]
+
+
+def _analytic_pair_rows(model, species32: Tensor, c32: Tensor, cell, pbc, aev_rows) -> tp.List[tuple]:
+    """(potential, rows) of every enabled closed-form pair potential of a model, on the rows its forward uses: the AEV's
+    rows, or the potential's own (model._pair_rows) when its cutoff is larger or infinite.  Overflowed rows raise."""
+    out = []
+    for name, pot in model.potentials.items():
+        if name == "nnp" or not pot._enabled:
+            continue
+        rows = aev_rows
+        if rows is None or pot.cutoff > model.aev_computer.radial.cutoff + 1e-6:
+            rows = model._pair_rows(pot, species32, c32, cell, pbc)
+            if rows.overflowed():
+                raise RuntimeError(f"pair potential {name!r}: an atom has more than {rows.row_cap} neighbors inside its "
+                                   f"cutoff ({pot.cutoff} A): its Hessian would be wrong")
+        out.append((pot, rows))
+    return out
 
 
 def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, retain_graph: bool = False, *,
@@ -131,43 +155,69 @@ def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, re
     """EnergiesForcesHessians(energies, forces, hessians [C, 3A, 3A]) of a model, batched (grad.py:239-260 computes the
     same through 3A autograd products).  The neighbor rows, AEVs and d E / d aev are computed once; then unit direction j
     (atom j // 3, component j % 3 of EVERY molecule of the batch at once) runs through anihip_aev_jvp_batched,
-    anihip_mlp_input_hvp and anihip_aev_backward_second in chunks of K = hessian_chunk_size(...) directions: ceil(3A / K)
-    calls per stage.  Energies and forces are those of grad.energies_and_forces.  Results are detached (any model: frozen
-    or trainable parameters); ``retain_graph`` is accepted for the reference's signature."""
-    pots = _enabled_pair_potentials(model)
+    anihip_mlp_input_hvp, anihip_aev_backward_second and, per enabled closed-form pair potential,
+    anihip_pair_analytic_hvp, in chunks of K = hessian_chunk_size(...) directions: ceil(3A / K) calls per stage.  A
+    standalone pair potential (``torchani_amd.potentials``) may stand in for the model, on its own rows.  Energies and
+    forces are those of grad.energies_and_forces.  Results are detached (any model: frozen or trainable parameters);
+    ``retain_graph`` is accepted for the reference's signature."""
+    from .potentials import _Standalone
+
+    pots = _pair_potentials_without_hessians(model)
     if pots:
         raise NotImplementedError(f"the pair potential(s) {', '.join(pots)} have no second derivative with respect to the "
                                   "coordinates: Hessians of this model are not available")
     ef = energies_and_forces(model, species, coordinates, cell, pbc, keep_vars=False)
+    standalone = isinstance(model, _Standalone)
     with torch.no_grad():
-        aevc = model.aev_computer
-        elem = model._elem_idxs(species)
-        species32 = elem.to(torch.int32).contiguous()
         c32 = coordinates.detach().to(torch.float32).contiguous()
         pbc_t = None if pbc is None else tuple(bool(b) for b in pbc.tolist())
-        nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_t)
-        nbrs.raise_on_overflow()
-        eng = aevc.engine()
-        aev = eng.forward(species32, nbrs)
-        packed = model.neural_networks._pack(coordinates.device)
-        _, g, _ = packed.forward_backward(species32, aev, want_grad=True)
+        if standalone:
+            species32 = model._to_elem_idxs(species, True).to(torch.int32).contiguous()
+            rows = model._standalone_rows(species32, c32, cell, pbc)
+            if rows.overflowed():
+                raise RuntimeError(f"{type(model).__name__}: an atom has more than {rows.row_cap} neighbors inside the "
+                                   f"cutoff ({model.cutoff} A): its Hessian would be wrong")
+            pairs = [(model, rows)]
+            nnp = False
+        else:
+            species32 = model._elem_idxs(species).to(torch.int32).contiguous()
+            nnp = model.potentials["nnp"]._enabled
+            nbrs = None
+            if nnp:
+                aevc = model.aev_computer
+                nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_t)
+                nbrs.raise_on_overflow()
+                eng = aevc.engine()
+                aev = eng.forward(species32, nbrs)
+                packed = model.neural_networks._pack(coordinates.device)
+                _, g, _ = packed.forward_backward(species32, aev, want_grad=True)
+            pairs = _analytic_pair_rows(model, species32, c32, cell, pbc, nbrs)
         Cn, A = species32.shape
         N = Cn * A
-        row_bytes = -(-_hvp_row_bytes(packed, N) // N)
-        K = hessian_chunk_size(Cn, A, eng.L, row_bytes)
+        if nnp:
+            row_bytes = -(-_hvp_row_bytes(packed, N) // N)
+            K = hessian_chunk_size(Cn, A, eng.L, row_bytes)
+        else:
+            K = hessian_chunk_size(Cn, A, 0, 0)
         n = 3 * A
         H = torch.zeros((Cn, n, n), dtype=torch.float32, device=coordinates.device)
-        rows = torch.arange(Cn, device=coordinates.device) * A
+        mol0 = torch.arange(Cn, device=coordinates.device) * A
         for j0 in range(0, n, K):
             j1 = min(n, j0 + K)
             k = torch.arange(j1 - j0, device=coordinates.device)
             t = torch.zeros((j1 - j0, N, 3), dtype=torch.float32, device=coordinates.device)
             jj = k + j0
-            t[k.view(-1, 1), (rows.view(1, -1) + (jj // 3).view(-1, 1)), (jj % 3).view(-1, 1)] = 1.0
-            daev = eng.jvp_batched(species32, nbrs, t)
-            hv = packed.input_hvp(species32, aev, daev.view(j1 - j0, N, eng.L))
-            del daev
-            out = eng.backward_second(species32, nbrs, g, t, hv)   # [K, N, 3]: columns j0..j1 of every molecule
+            t[k.view(-1, 1), (mol0.view(1, -1) + (jj // 3).view(-1, 1)), (jj % 3).view(-1, 1)] = 1.0
+            if nnp:
+                daev = eng.jvp_batched(species32, nbrs, t)
+                hv = packed.input_hvp(species32, aev, daev.view(j1 - j0, N, eng.L))
+                del daev
+                out = eng.backward_second(species32, nbrs, g, t, hv)   # [K, N, 3]: columns j0..j1 of every molecule
+                del hv
+            else:
+                out = torch.zeros_like(t)
+            for pot, rows in pairs:
+                pot.hvp(species32, rows, t, out)
             H[:, :, j0:j1] = out.view(j1 - j0, Cn, n).permute(1, 2, 0)
     return EnergiesForcesHessians(ef.energies, ef.forces, H.to(coordinates.dtype))
 

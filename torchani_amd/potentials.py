@@ -6,8 +6,9 @@ Mirrors torchani/potentials/xtb.py:17-77 (RepulsionXTB: constructor, buffers ``y
 pair energies), torchani/potentials/dftd3.py:44-330 (BeckeJohnsonDamp, TwoBodyDispersionD3: constructor,
 ``from_functional``, coordination numbers, C6 interpolation, pair energies) and the shared machinery of
 torchani/potentials/core.py:103-207 (cutoff envelope, ``atomic`` halves, sum per molecule).  The arithmetic runs in
-libanihip (anihip_pair_xtb_repulsion, anihip_pair_d3, csrc/pair.hip) on neighbor rows of the engine; there is no eager
-fallback.
+libanihip (anihip_pair_analytic, anihip_pair_d3, csrc/pair.hip) on neighbor rows of the engine; there is no eager
+fallback.  Forces taken with ``create_graph=True`` are differentiable once more with respect to the coordinates for the
+closed-form potentials (anihip_pair_analytic_hvp: Hessians, grad.py); D3 raises there.
 
 (The GELU / bias-free networks of those models run through the fused network kernel, torchani_amd.models.ANI2xr /
 ANI2dr.)
@@ -53,25 +54,61 @@ class _PairEnergy(torch.autograd.Function):
         ctx.shape, ctx.dtype, ctx.pot = coords.shape, coords.dtype, pot
         # (held weakly: a first-order call keeps nothing alive; the guard below needs the coordinates as an input)
         ctx.coords_ref = weakref.ref(coords) if getattr(pot, "_second_order_guard", True) else None
+        # the rows of the second derivative, like the AEV node's (the networks' rows are the same object)
+        ctx.rows = (species32, nbrs) if ctx.coords_ref is not None else None
         return atomic.view(Cn, A).to(torch.float64).sum(dim=1)
 
     @staticmethod
     def backward(ctx, g: Tensor):
         (grad,) = ctx.saved_tensors
         Cn, A = ctx.shape[0], ctx.shape[1]
-        with torch.no_grad():
-            gc = (grad.view(Cn, A, 3) * g.view(Cn, 1, 1).to(grad.dtype)).to(ctx.dtype)
-        # create_graph=True: pair.hip has no second derivative with respect to the coordinates -- never drop the term
-        # silently, raise when it is taken.  (Not when the model's networks train: force training differentiates the forces
-        # with respect to the parameters, which the pair term does not depend on.)
+        # create_graph=True: the force term is differentiable in the coordinates through the pair kernels' Hessian-vector
+        # product (closed-form pair terms); D3 has no second derivative there -- never drop the term silently, raise when
+        # it is taken.  (Not when the model's networks train: force training differentiates the forces with respect to the
+        # parameters, which the pair term does not depend on.)
         coords = ctx.coords_ref() if (torch.is_grad_enabled() and ctx.coords_ref is not None) else None
         if coords is not None and coords.requires_grad:
-            gc = _PairNoSecondOrder.apply(gc, coords, type(ctx.pot).__name__)
+            if isinstance(ctx.pot, _AnalyticPair):
+                species32, nbrs = ctx.rows
+                return _PairForce.apply(g, coords, grad, ctx.pot, species32, nbrs), None, None, None
+            with torch.no_grad():
+                gc = (grad.view(Cn, A, 3) * g.view(Cn, 1, 1).to(grad.dtype)).to(ctx.dtype)
+            return _PairNoSecondOrder.apply(gc, coords, type(ctx.pot).__name__), None, None, None
+        with torch.no_grad():
+            gc = (grad.view(Cn, A, 3) * g.view(Cn, 1, 1).to(grad.dtype)).to(ctx.dtype)
         return gc, None, None, None
 
 
+class _PairForce(torch.autograd.Function):
+    """(g, coords) -> g * d E_pair / d coords per molecule, differentiable in the coordinates: its backward is the pair
+    Hessian-vector product (anihip_pair_analytic_hvp with one direction) scaled per molecule by g.  Recorded only by a
+    backward with create_graph=True: a first-order call launches nothing new."""
+
+    @staticmethod
+    def forward(ctx, g: Tensor, coords: Tensor, grad: Tensor, pot: "_AnalyticPair", species32: Tensor,
+                nbrs: NeighborRows) -> Tensor:
+        Cn, A = species32.shape
+        ctx.save_for_backward(g, grad)
+        ctx.pot, ctx.species32, ctx.nbrs, ctx.c_dtype = pot, species32, nbrs, coords.dtype
+        return (grad.view(Cn, A, 3) * g.detach().view(Cn, 1, 1).to(grad.dtype)).to(coords.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, w: Tensor):
+        g, grad = ctx.saved_tensors
+        Cn, A = ctx.species32.shape
+        dg = dc = None
+        if ctx.needs_input_grad[0]:
+            dg = (grad.view(Cn, A, 3).to(torch.float64) * w.to(torch.float64)).sum(dim=(1, 2)).to(g.dtype)
+        if ctx.needs_input_grad[1]:
+            out = torch.zeros((1, Cn * A, 3), dtype=torch.float32, device=w.device)
+            ctx.pot.hvp(ctx.species32, ctx.nbrs, w.detach().to(torch.float32).contiguous().view(1, Cn * A, 3), out)
+            dc = (out.view(Cn, A, 3) * g.detach().view(Cn, 1, 1).to(torch.float32)).to(ctx.c_dtype)
+        return dg, dc, None, None, None, None
+
+
 class _PairNoSecondOrder(torch.autograd.Function):
-    """Identity whose derivative raises: the pair kernels have no second derivative with respect to the coordinates."""
+    """Identity whose derivative raises: D3 has no second derivative with respect to the coordinates here."""
 
     @staticmethod
     def forward(ctx, gc: Tensor, coords: Tensor, name: str) -> Tensor:
@@ -81,7 +118,7 @@ class _PairNoSecondOrder(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _v: Tensor):
         raise NotImplementedError(f"the pair potential {ctx.name} has no second derivative with respect to the coordinates "
-                                  "(Hessians of models with enabled pair potentials are not available)")
+                                  "(Hessians of models with it enabled are not available)")
 
 
 class _Standalone:
@@ -126,6 +163,7 @@ class _Standalone:
             self.accumulate(species32, rows, a, None)
             e = a.view(species32.shape)
         else:
+            self._second_order_guard = True   # (no networks around it: the coordinates' second derivative is always taken)
             e = self.compute_from_rows(species32, coords, rows)
         if not torch.cuda.is_current_stream_capturing() and rows.overflowed():   # (the builder zeroed the row)
             raise RuntimeError(f"{type(self).__name__}: an atom has more than {_lib.MAX_RAD} neighbors inside the cutoff "
@@ -202,6 +240,28 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
             _stream(), self.kind, species32.numel(), nbrs.lo, nbrs.hi, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent),
             _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
             _lib.CUTOFF_KINDS[self.cutoff_fn], flags, _ptr(atomic_e), _ptr(grad_coords), _ptr(virial)))
+
+    def hvp(self, species32: Tensor, nbrs: NeighborRows, tangent: Tensor, out: Tensor,
+            cutoff: tp.Optional[float] = None) -> None:
+        """out [K, N, 3] += H tangent[k] for the K directions tangent [K, N, 3] (float32), H = the second derivative of the
+        pair energies of the central atoms of nbrs with respect to the coordinates (anihip_pair_analytic_hvp).  Symmetric
+        rows only."""
+        _require_cuda(species32, tangent, out)
+        n = species32.numel()
+        K = tangent.shape[0]
+        if tangent.dtype != torch.float32 or out.dtype != torch.float32 or not (tangent.is_contiguous() and out.is_contiguous()):
+            raise ValueError("tangent and out must be contiguous float32 tensors")
+        if tangent.numel() != 3 * n * K or out.numel() != 3 * n * K:
+            raise ValueError(f"tangent and out must be [K, {n}, 3]")
+        cut = self.cutoff if cutoff is None else cutoff
+        if math.isinf(cut):
+            cut = 1e30
+        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
+        ex = self._extra()
+        _lib.check(_lib.lib().anihip_pair_analytic_hvp(
+            _stream(), self.kind, n, nbrs.lo, nbrs.hi, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent),
+            _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
+            _lib.CUTOFF_KINDS[self.cutoff_fn], flags, K, _ptr(tangent), _ptr(out)))
 
     def compute_from_rows(self, species32: Tensor, coords: Tensor, nbrs: NeighborRows) -> Tensor:
         """Molecular energies [C] (float64), differentiable with respect to coords."""
