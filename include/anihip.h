@@ -250,6 +250,51 @@ int anihip_aev_backward_second(void *stream, const anihip_aev_params *p, const f
                                const float *grad_aev, int64_t n_dir, const float *tangent, const float *dgrad, float *out,
                                uint32_t *status);
 
+/* ---------------------------------------------------------------------------------------------
+ * Block-sparse Hessians (grad.energies_forces_and_sparse_hessians).  The AEV of atom i depends on R(i) = {i} U its row
+ * (periodic images folded onto atom indices), so d^2 E / d r_a d r_j is non-zero only for j in P(a) = U_{i in R(a)} R(i).
+ * A unit direction (atom a, component c) is worked as ITEM ROWS (direction 3 a + c, central atom i) for i in R(a): the
+ * tangent e_c on atom a is implicit; row_dir[q] = 3 a + c (flattened atom index a), row_atom[q] = i.  Symmetric rows only.
+ *
+ * R lists, two calls: roff NULL -> rcnt[a] = |R(a)| (0 for padding); then, with roff [n_atoms + 1] = the exclusive scan of
+ * rcnt, rlist[roff[a] ..] = a followed by the other atoms of R(a) (each once). */
+int anihip_hess_sparse_rlist(void *stream, int64_t n_atoms, const int32_t *species, const uint32_t *meta, const float *ent,
+                             const int64_t *roff, int32_t *rcnt, int32_t *rlist);
+
+/* The block pattern, two calls: poff NULL -> pcnt[a] = |P(a)|; then, with poff [n_atoms + 1] the exclusive scan of pcnt and
+ * nnz = poff[n_atoms], index (int64 [2][nnz]) gets the pattern BY COLUMNS: for p in poff[a] .. poff[a + 1],
+ * index[1][p] = a and index[0][p] runs over P(a) ascending.  The pattern is symmetric.  |P(a)| above 4096 (far beyond
+ * rows of ANIHIP_MAX_RAD entries) sets bit 0 of *status. */
+int anihip_hess_sparse_pattern(void *stream, int64_t n_atoms, const int64_t *roff, const int32_t *rlist, const int64_t *poff,
+                               int64_t nnz, int32_t *pcnt, int64_t *index, uint32_t *status);
+
+/* The item rows of the direction atoms n0 <= a < n1: 3 sum_a |R(a)| rows written to row_atom / row_dir, the items (a, i)
+ * ordered by the species of i (rows of a species contiguous, species ascending), three rows (c = 0, 1, 2) per item.
+ * scratch: num_species (n1 - n0) + 1 ints.  One launch, one block. */
+int anihip_hess_sparse_items(void *stream, int32_t num_species, int64_t n0, int64_t n1, const int32_t *species,
+                             const int64_t *roff, const int32_t *rlist, int32_t *scratch, int32_t *row_atom, int32_t *row_dir);
+
+/* anihip_aev_jvp over item rows: daev [n_rows][L], row q = d aev_{row_atom[q]} along the unit tangent of row_dir[q].  Every
+ * grid through the general kernel (the tuned grids included), both cutoff functions. */
+int anihip_aev_jvp_items(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                         const int32_t *species, const uint32_t *meta, const float *ent, int64_t n_rows,
+                         const int32_t *row_atom, const int32_t *row_dir, float *daev);
+
+/* anihip_aev_backward_second over item rows: out[row_dir[q] - dir0] += J_i^T dgrad[q] + (D_t J_i^T) grad_aev for the central
+ * atom i = row_atom[q] and the unit tangent t of row_dir[q]; dgrad [n_rows][L], out [n_dir][n_atoms][3] (float atomics);
+ * rows whose slab falls outside 0 .. n_dir are skipped. */
+int anihip_aev_backward_second_items(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                                     const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
+                                     int64_t n_rows, const int32_t *row_atom, const int32_t *row_dir, int64_t dir0,
+                                     int64_t n_dir, const float *dgrad, float *out);
+
+/* Pattern blocks of the entries p0 <= p < p1 (the columns of a chunk's direction atoms) out of the scratch
+ * [n_dir][n_atoms][3] whose slab 3 a + c - dir0 holds column (a, c) of H:  blocks[p][y][c] = scratch[3 a + c - dir0][j][y]
+ * for j = index[0][p], a = index[1][p]; those scratch positions are written back to zero (the caller zeroes the scratch
+ * once, never per chunk). */
+int anihip_hess_sparse_extract(void *stream, int64_t n_atoms, int64_t p0, int64_t p1, const int64_t *index, int64_t nnz,
+                               int64_t dir0, int64_t n_dir, float *scratch, float *blocks);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial
@@ -481,6 +526,17 @@ size_t anihip_mlp_input_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_
 int anihip_mlp_input_hvp(void *stream, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species, const float *aev,
                          int64_t n_dir, const float *tangent, void *workspace, size_t workspace_bytes, float *out);
 
+/* anihip_mlp_input_hvp over explicit rows (block-sparse Hessians): out[q] = (1/M) sum_m H_m(aev[row_atom[q]]) . tangent[q]
+ * (tangent, out: [n_rows][aev_len]).  The rows must be ordered so that the rows of a species are contiguous, species
+ * ascending (anihip_hess_sparse_items).  anihip_mlp_rows_hvp_prepare runs the exact-fp32 forward over the atoms once and
+ * keeps the activations in the workspace; anihip_mlp_rows_hvp then serves any number of row sets of at most n_rows rows
+ * (the workspace size of the largest) from the same workspace.  n_rows < 2^31. */
+size_t anihip_mlp_rows_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_rows);
+int anihip_mlp_rows_hvp_prepare(void *stream, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species,
+                                const float *aev, void *workspace, size_t workspace_bytes);
+int anihip_mlp_rows_hvp(void *stream, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species, int64_t n_rows,
+                        const int32_t *row_atom, const float *tangent, void *workspace, size_t workspace_bytes, float *out);
+
 /* Refresh the packed parameter arrays of a descriptor IN PLACE (padding stays zero) from the torch.nn.Linear tensors after
  * an optimizer step -- one or two launches instead of re-packing on the host (cf. BmmAtomicNetwork packing once per model,
  * nn/_infer.py:141-161).  ANIHIP_MLP_FP32: w / wt / bias.  ANIHIP_MLP_F16X3 (round 5): every layout anihip_mlp_pack derives
@@ -551,6 +607,15 @@ int anihip_pair_analytic_hvp(void *stream, int32_t kind, int64_t n_atoms, int64_
                              const uint32_t *meta, const float *ent, const float *pair_table, const float *extra,
                              float cutoff, int32_t cutoff_kind, int32_t flags, int64_t n_dir, const float *tangent,
                              float *out);
+
+/* anihip_pair_analytic_hvp over item rows (block-sparse Hessians): out[row_dir[q] - dir0][i] += (H t)_i for the central atom
+ * i = row_atom[q] and the unit tangent t of row_dir[q] (out [n_dir][n_atoms][3]; an item row names each (direction, atom)
+ * once: no atomics).  The pair cutoff must not exceed the radial cutoff the rows were built with; rows whose slab falls
+ * outside 0 .. n_dir are skipped. */
+int anihip_pair_analytic_hvp_items(void *stream, int32_t kind, int64_t n_atoms, const int32_t *species, const uint32_t *meta,
+                                   const float *ent, const float *pair_table, const float *extra, float cutoff,
+                                   int32_t cutoff_kind, int32_t flags, int64_t n_rows, const int32_t *row_atom,
+                                   const int32_t *row_dir, int64_t dir0, int64_t n_dir, float *out);
 
 /* DFT-D3(BJ) two-body dispersion (potentials/dftd3.py:113-330 TwoBodyDispersionD3, damping :44-110 BeckeJohnsonDamp;
  * envelope and per-atom halves as above), distances in Bohr:

@@ -2,11 +2,13 @@
 loop of grad.forces_and_hessians) on fixtures of tests/golden: device-synchronised, after warm-up, median of several runs.
 
     python tools/hessian_bench.py [--runs 5] [--autograd-max 264] [--bases ch4_ani1x,dense90_ani2x,...]
-                                  [--kind fixture|ani2xr|anir2s]
+                                  [--kind fixture|ani2xr|anir2s] [--sparse [--dense-max 1000]]
 
 Prints one JSON line per case.  Seeded parameters (the fixtures' seeds): timings do not depend on the values.
 ``--kind ani2xr`` / ``anir2s`` times that architecture (networks plus the xTB repulsion term) on the fixtures'
-coordinates instead of the fixture's own ANI-2x / ANI-1x model."""
+coordinates instead of the fixture's own ANI-2x / ANI-1x model.  ``--sparse`` times the block-sparse path
+(grad.energies_forces_and_sparse_hessians) and the dense batched path in the same run (the dense one only up to
+``--dense-max`` atoms), with the fixture's cell and pbc, the number of stored blocks and the peak device memory of each."""
 from __future__ import annotations
 
 import argparse
@@ -47,6 +49,8 @@ def main():
     ap.add_argument("--autograd-max", type=int, default=264)
     ap.add_argument("--bases", default="ch4_ani1x,dense90_ani2x,small_ani2x,1hz5_ani2x")
     ap.add_argument("--kind", default="fixture", choices=("fixture", "ani2xr", "anir2s"))
+    ap.add_argument("--sparse", action="store_true", help="block-sparse path beside the dense one")
+    ap.add_argument("--dense-max", type=int, default=1000, help="--sparse: largest system the dense path is timed on")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for base in args.bases.split(","):
@@ -66,6 +70,28 @@ def main():
         x = torch.from_numpy(g["coords"]).to(dev)
         A = int((sp >= 0).sum())
         row = {"case": base, "model": g["kind"] if args.kind == "fixture" else args.kind, "atoms": A}
+        if args.sparse:
+            cell = None if g["cell"] is None else torch.from_numpy(g["cell"]).to(dev)
+            pbc = None if g["pbc"] is None else torch.from_numpy(np.asarray(g["pbc"])).to(dev)
+            runs = max(1, args.runs if A < 5000 else 2)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            out = grad.energies_forces_and_sparse_hessians(model, sp, x, cell=cell, pbc=pbc)
+            row["nnz"] = out.hessians.nnz
+            row["sparse_peak_gib"] = round(torch.cuda.max_memory_allocated() / 2**30, 3)
+            del out
+            row["sparse_ms"], row["sparse_runs"] = timed(
+                lambda: grad.energies_forces_and_sparse_hessians(model, sp, x, cell=cell, pbc=pbc), runs)
+            if A <= args.dense_max:
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                grad.energies_forces_and_hessians(model, sp, x, cell=cell, pbc=pbc)
+                row["dense_peak_gib"] = round(torch.cuda.max_memory_allocated() / 2**30, 3)
+                row["dense_ms"], row["dense_runs"] = timed(
+                    lambda: grad.energies_forces_and_hessians(model, sp, x, cell=cell, pbc=pbc), runs)
+                row["dense_over_sparse"] = round(row["dense_ms"] / row["sparse_ms"], 2)
+            print(json.dumps(row), flush=True)
+            continue
         row["batched_ms"], row["batched_runs"] = timed(lambda: grad.energies_forces_and_hessians(model, sp, x),
                                                        max(1, args.runs if A < 500 else 3))
         if A <= args.autograd_max:

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip"]
 HEADERS = ["anihip_common.h", "train.h", "mlp_fused.h", "mlp_prep.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -214,6 +214,23 @@ def lib() -> C.CDLL:
     L.anihip_pair_analytic.restype = C.c_int
     L.anihip_pair_analytic_hvp.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp, vp, vp, C.c_float, i32, i32, i64, vp, vp]
     L.anihip_pair_analytic_hvp.restype = C.c_int
+    L.anihip_hess_sparse_rlist.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.anihip_hess_sparse_pattern.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.anihip_hess_sparse_items.argtypes = [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.anihip_hess_sparse_extract.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp]
+    L.anihip_aev_jvp_items.argtypes = [vp, C.POINTER(AevParams), vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.anihip_aev_backward_second_items.argtypes = [vp, C.POINTER(AevParams), vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, i64,
+                                                   vp, vp]
+    L.anihip_mlp_rows_hvp_workspace_bytes.restype = sz
+    L.anihip_mlp_rows_hvp_workspace_bytes.argtypes = [C.POINTER(MlpDesc), i64, i64]
+    L.anihip_mlp_rows_hvp_prepare.argtypes = [vp, C.POINTER(MlpDesc), i64, vp, vp, vp, sz]
+    L.anihip_mlp_rows_hvp.argtypes = [vp, C.POINTER(MlpDesc), i64, vp, i64, vp, vp, vp, sz, vp]
+    L.anihip_pair_analytic_hvp_items.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, C.c_float, i32, i32, i64, vp, vp, i64, i64,
+                                                 vp]
+    for name in ("anihip_hess_sparse_rlist", "anihip_hess_sparse_pattern", "anihip_hess_sparse_items",
+                 "anihip_hess_sparse_extract", "anihip_aev_jvp_items", "anihip_aev_backward_second_items",
+                 "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items"):
+        getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
     for name in ("anihip_aev_table_pack", "anihip_nbr_build_batch", "anihip_nbr_build_cell", "anihip_nbr_from_half",
@@ -238,6 +255,9 @@ EXPORTED_SYMBOLS = [
     "anihip_nbr_rows_to_half_workspace_bytes", "anihip_nbr_rows_to_half",
     "anihip_aev_jvp_batched", "anihip_aev_backward_second", "anihip_mlp_input_hvp_workspace_bytes", "anihip_mlp_input_hvp",
     "anihip_pair_analytic_hvp",
+    "anihip_hess_sparse_rlist", "anihip_hess_sparse_pattern", "anihip_hess_sparse_items", "anihip_hess_sparse_extract",
+    "anihip_aev_jvp_items", "anihip_aev_backward_second_items", "anihip_mlp_rows_hvp_workspace_bytes",
+    "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items",
 ]
 
 

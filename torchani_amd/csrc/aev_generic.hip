@@ -115,16 +115,20 @@ __device__ __forceinline__ void gen_stage_row(const GenArgs &a, const GenHdr &h,
 // slab_mask (optional, rows of at most 1024 columns): bit j of slab_mask[i] <=> columns 32 j .. 32 j + 31 of row i can be
 // non-zero -- PLAIN column order (a general grid has no 16 / 32-column blocks to line up with slabs: a block of a present
 // species (pair) flags every slab it overlaps); the networks' layer 0 skips the slabs no atom of a tile flags.
-template <bool JVP>
+// ITEMS (anihip_aev_jvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi instead of atoms: central
+// atom row_atom[q], output row q, and the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), zero elsewhere.
+template <bool JVP, bool ITEMS = false>
 __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const float *__restrict__ tab, int64_t lo,
                                                                 int64_t hi, const int32_t *__restrict__ species,
                                                                 const uint32_t *__restrict__ meta,
                                                                 const float4 *__restrict__ ent, float *__restrict__ aev,
                                                                 const float *__restrict__ tangent,
                                                                 uint32_t *__restrict__ slab_mask, int64_t dir_t,
-                                                                int64_t dir_o)
+                                                                int64_t dir_o, const int32_t *__restrict__ row_atom = nullptr,
+                                                                const int32_t *__restrict__ row_dir = nullptr)
 {
-    if (JVP) {   // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y
+    static_assert(JVP || !ITEMS, "item rows are JVP rows");
+    if (JVP && !ITEMS) {   // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y
         tangent += (size_t)blockIdx.y * dir_t;
         aev += (size_t)blockIdx.y * dir_o;
     }
@@ -142,19 +146,26 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
         const int j0 = c0 >> 5, j1 = (c1 - 1) >> 5;
         return (j1 >= 31 ? 0xFFFFFFFFu : ((1u << (j1 + 1)) - 1u)) & ~((1u << j0) - 1u);
     };
-    for (int64_t i = lo + blockIdx.x * (int64_t)GEN_WPB + wib; i < hi; i += nw) {
-        float *out = aev + (size_t)i * a.L;   // (the caller's pointer is that of row 0, also for a shard's [hi - lo, L] buffer)
+    for (int64_t q = lo + blockIdx.x * (int64_t)GEN_WPB + wib; q < hi; q += nw) {
+        const int64_t i = ITEMS ? (int64_t)row_atom[q] : q;
+        float *out = aev + (size_t)q * a.L;   // (the caller's pointer is that of row 0, also for a shard's [hi - lo, L] buffer)
         GenHdr h = gen_hdr(meta, i);
         if (species[i] < 0) { h.nA = 0; h.nF = 0; h.pkA = 0ull; h.pkF = 0ull; }
         uint32_t flags = 0u;
         // (every element of the row is written exactly once: blocks without a neighbor (pair) as zeros)
         if (h.nA + h.nF > 0) gen_stage_row(a, h, ent, st);
         if (JVP && h.nA + h.nF > 0) {
-            const float tix = tangent[3 * i], tiy = tangent[3 * i + 1], tiz = tangent[3 * i + 2];
+            int da = -1, dc = 0;   // ITEMS: d' = e_dc ([j == da] - [i == da])
+            if (ITEMS) { da = row_dir[q] / 3; dc = row_dir[q] - 3 * da; }
+            auto tang = [&](size_t n, int k) {
+                if (ITEMS) return (int64_t)n == da && k == dc ? 1.0f : 0.0f;
+                return tangent[3 * n + k];
+            };
+            const float tix = tang(i, 0), tiy = tang(i, 1), tiz = tang(i, 2);
             for (int e = lane; e < h.nA + h.nF; e += WAVE) {
                 const size_t jn = (size_t)st.jat[e];
                 const float4 U = st.ur[e];
-                const float dx = tangent[3 * jn] - tix, dy = tangent[3 * jn + 1] - tiy, dz = tangent[3 * jn + 2] - tiz;
+                const float dx = tang(jn, 0) - tix, dy = tang(jn, 1) - tiy, dz = tang(jn, 2) - tiz;
                 const float rd = U.x * dx + U.y * dy + U.z * dz, ir = 1.0f / U.w;
                 td[e] = make_float4((dx - U.x * rd) * ir, (dy - U.y * rd) * ir, (dz - U.z * rd) * ir, rd);
             }
@@ -262,7 +273,7 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
             }
             o1 += n1;
         }
-        if (slab_mask && lane == 0) slab_mask[i] = flags;
+        if (!ITEMS && slab_mask && lane == 0) slab_mask[i] = flags;
         wave_sync();
     }
 }
@@ -483,6 +494,22 @@ int aev_jvp_generic_dirs(hipStream_t stream, const anihip_aev_params *p, const f
     const dim3 grid(gen_blocks(hi - lo), (unsigned)n_dir), block(GEN_WPB * WAVE);
     hipLaunchKernelGGL(k_aev_fwd_gen<true>, grid, block, 0, stream, a, table, lo, hi, species, meta, (const float4 *)ent, daev,
                        tangent, (uint32_t *)nullptr, dir_t, n_atoms * (int64_t)a.L);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// item rows lo <= q < hi (anihip_aev_jvp_items): daev [q][L] = d aev_{row_atom[q]} along e_c on atom a, row_dir[q] = 3 a + c
+int aev_jvp_generic_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+                          const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
+                          const int32_t *row_dir, float *daev)
+{
+    GenArgs a;
+    if (int rc = gen_args(p, &a)) return rc;
+    if (hi == lo) return 0;
+    const dim3 grid(gen_blocks(hi - lo)), block(GEN_WPB * WAVE);
+    hipLaunchKernelGGL((k_aev_fwd_gen<true, true>), grid, block, 0, stream, a, table, lo, hi, species, meta,
+                       (const float4 *)ent, daev, (const float *)nullptr, (uint32_t *)nullptr, (int64_t)0, (int64_t)0,
+                       row_atom, row_dir);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -112,13 +112,20 @@ __device__ __forceinline__ void hess_pair(bool same, int t, int n1, int n2, int 
 
 __device__ __forceinline__ int hess_triu(int S, int a, int b) { return a * S - (a * (a - 1)) / 2 + (b - a); }
 
+// ITEMS (anihip_aev_backward_second_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi: central
+// atom row_atom[q], dgrad row q, the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), output slab
+// row_dir[q] - dir0 of out [n_dir][n_atoms][3]; blockIdx.y = 0.
+template <bool ITEMS>
 __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const float *__restrict__ tab, int64_t n_atoms,
                                                              int64_t lo, int64_t hi, const int32_t *__restrict__ species,
                                                              const uint32_t *__restrict__ meta,
                                                              const float4 *__restrict__ ent,
                                                              const float *__restrict__ grad_aev,
                                                              const float *__restrict__ tangent,
-                                                             const float *__restrict__ dgrad, float *__restrict__ out)
+                                                             const float *__restrict__ dgrad, float *__restrict__ out,
+                                                             const int32_t *__restrict__ row_atom,
+                                                             const int32_t *__restrict__ row_dir, int64_t dir0,
+                                                             int64_t n_slabs)
 {
     __shared__ float4 s_u[HESS_WPB][MAXR];     // unit vector, r
     __shared__ float4 s_ud[HESS_WPB][MAXR];    // its derivative along the direction: u', r'
@@ -131,23 +138,37 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
     int *sj = s_j[wib];
     float *gx = s_g[wib][0], *gy = s_g[wib][1], *gz = s_g[wib][2];
     const int64_t dir = blockIdx.y;
-    const float *tg = tangent + (size_t)dir * 3 * n_atoms;
-    const float *dg = dgrad + (size_t)dir * n_atoms * a.L;
+    const float *tg = ITEMS ? nullptr : tangent + (size_t)dir * 3 * n_atoms;
+    const float *dg = ITEMS ? dgrad : dgrad + (size_t)dir * n_atoms * a.L;
     float *o = out + (size_t)dir * 3 * n_atoms;
     const int64_t nw = (int64_t)gridDim.x * HESS_WPB;
     const int nAZ = a.nA * a.nZ;
-    for (int64_t i = lo + blockIdx.x * (int64_t)HESS_WPB + wib; i < hi; i += nw) {
+    for (int64_t q = lo + blockIdx.x * (int64_t)HESS_WPB + wib; q < hi; q += nw) {
+        const int64_t i = ITEMS ? (int64_t)row_atom[q] : q;
         if (species[i] < 0) continue;
         const HessHdr h = hess_hdr(meta, i);
         const int nR = h.nA + h.nF;
         if (nR == 0) continue;
-        const float tix = tg[3 * i], tiy = tg[3 * i + 1], tiz = tg[3 * i + 2];
+        int64_t da = -1;   // ITEMS: t = e_dc on atom da
+        int dc = 0;
+        if (ITEMS) {
+            const int64_t slab = row_dir[q] - dir0;
+            if (slab < 0 || slab >= n_slabs) continue;   // (a row outside the caller's slabs)
+            da = row_dir[q] / 3;
+            dc = row_dir[q] - 3 * (int)da;
+            o = out + (size_t)slab * 3 * n_atoms;
+        }
+        auto tang = [&](size_t n, int k) {
+            if (ITEMS) return (int64_t)n == da && k == dc ? 1.0f : 0.0f;
+            return tg[3 * n + k];
+        };
+        const float tix = tang(i, 0), tiy = tang(i, 1), tiz = tang(i, 2);
         for (int e = lane; e < nR; e += WAVE) {
             const float4 d = ent[h.start + e];
             const float r = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z), ir = 1.0f / r;
             const float ux = d.x * ir, uy = d.y * ir, uz = d.z * ir;
             const int jn = (int)(__float_as_uint(d.w) & IDX_MASK);
-            const float dx = tg[3 * (size_t)jn] - tix, dy = tg[3 * (size_t)jn + 1] - tiy, dz = tg[3 * (size_t)jn + 2] - tiz;
+            const float dx = tang(jn, 0) - tix, dy = tang(jn, 1) - tiy, dz = tang(jn, 2) - tiz;
             const float rd = ux * dx + uy * dy + uz * dz;
             su[e] = make_float4(ux, uy, uz, r);
             sud[e] = make_float4((dx - ux * rd) * ir, (dy - uy * rd) * ir, (dz - uz * rd) * ir, rd);
@@ -159,7 +180,7 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
         }
         wave_sync();
         const float *w = grad_aev + (size_t)i * a.L;
-        const float *wd = dg + (size_t)i * a.L;
+        const float *wd = dg + (size_t)q * a.L;
         float ox = 0.f, oy = 0.f, oz = 0.f;   // minus the tangent part of the gradient on the central atom, per lane
         // ---- radial (lane = neighbor) ----
         for (int e = lane; e < nR; e += WAVE) {
@@ -293,8 +314,42 @@ extern "C" int anihip_aev_backward_second(void *stream, const anihip_aev_params 
     int64_t b = (hi - lo + HESS_WPB - 1) / HESS_WPB;
     if (b > 1024) b = 1024;
     const dim3 grid((unsigned)b, (unsigned)n_dir), block(HESS_WPB * WAVE);
-    hipLaunchKernelGGL(k_aev_bwd2, grid, block, 0, (hipStream_t)stream, a, table, n_atoms, lo, hi, species, meta,
-                       (const float4 *)ent, grad_aev, tangent, dgrad, out);
+    hipLaunchKernelGGL(k_aev_bwd2<false>, grid, block, 0, (hipStream_t)stream, a, table, n_atoms, lo, hi, species, meta,
+                       (const float4 *)ent, grad_aev, tangent, dgrad, out, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                       (int64_t)0, (int64_t)0);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_aev_backward_second_items(void *stream, const anihip_aev_params *p, const float *table,
+                                                int64_t n_atoms, const int32_t *species, const uint32_t *meta,
+                                                const float *ent, const float *grad_aev, int64_t n_rows,
+                                                const int32_t *row_atom, const int32_t *row_dir, int64_t dir0,
+                                                int64_t n_dir, const float *dgrad, float *out)
+{
+    ANIHIP_REQUIRE(p && table && species && meta && ent && grad_aev && row_atom && row_dir && dgrad && out,
+                   "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0 && n_dir >= 0, "negative size");
+    ANIHIP_REQUIRE(p->num_species >= 1 && p->num_species <= MAX_S - 1, "num_species must be 1..7");
+    ANIHIP_REQUIRE(p->n_shf_r >= 1 && p->n_shf_r <= 32 && p->n_shf_a >= 1 && p->n_shf_a <= 16 && p->n_shf_z >= 1 &&
+                       p->n_shf_z <= 16,
+                   "symmetry-function grid outside n_shf_r <= 32, n_shf_a <= 16, n_shf_z <= 16 (got %d, %d x %d)",
+                   p->n_shf_r, p->n_shf_a, p->n_shf_z);
+    ANIHIP_REQUIRE(p->cutoff_kind == ANIHIP_CUTOFF_COSINE || p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH,
+                   "cutoff_kind must be ANIHIP_CUTOFF_COSINE or ANIHIP_CUTOFF_SMOOTH");
+    if (n_rows == 0) return 0;
+    HessArgs a;
+    a.S = p->num_species;
+    a.nR = p->n_shf_r; a.nA = p->n_shf_a; a.nZ = p->n_shf_z;
+    a.radlen = a.S * a.nR;
+    a.L = a.radlen + (a.S * (a.S + 1) / 2) * a.nA * a.nZ;
+    a.Rcr = p->Rcr; a.Rca = p->Rca; a.EtaR = p->EtaR; a.EtaA = p->EtaA; a.Zeta = p->Zeta;
+    a.smooth = p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH;
+    int64_t b = (n_rows + HESS_WPB - 1) / HESS_WPB;
+    if (b > 4096) b = 4096;
+    hipLaunchKernelGGL(k_aev_bwd2<true>, dim3((unsigned)b), dim3(HESS_WPB * WAVE), 0, (hipStream_t)stream, a, table, n_atoms,
+                       (int64_t)0, n_rows, species, meta, (const float4 *)ent, grad_aev, (const float *)nullptr, dgrad, out,
+                       row_atom, row_dir, dir0, n_dir);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -3119,3 +3119,156 @@ extern "C" int anihip_mlp_input_hvp(void *stream_, const anihip_mlp_desc *d, int
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// ---- network input HVP over explicit rows (sparse Hessians) ---------------------------------------------------------------
+// The caller's rows are already ordered so that the rows of a species are contiguous (species ascending); row q reads the
+// kept activations of atom row_atom[q] through its sorted position.  k_rows_pos: pos[perm[p]] = p once per call;
+// k_rows_ctl: the rows' control block (the species runs found by binary search), the identity gather / scatter and the
+// activation gather.
+__global__ __launch_bounds__(256) void k_rows_pos(const int *ctl, const int *perm, int S, int *pos)
+{
+    const int64_t total = ctl[CTL_OFF + S];
+    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x)
+        pos[perm[p]] = (int)p;
+}
+
+__global__ __launch_bounds__(256) void k_rows_ctl(int S, int64_t n_rows, const int32_t *species, const int32_t *row_atom,
+                                                  const int *pos, int *rctl, int *rid, int *ygather)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        auto first = [&](int t) {   // first row of species >= t
+            int64_t lo = 0, hi = n_rows;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) / 2;
+                if (species[row_atom[mid]] < t) lo = mid + 1; else hi = mid;
+            }
+            return (int)lo;
+        };
+        int trun = 0;
+        for (int t = 0; t < S; ++t) {
+            const int o = first(t), cnt = first(t + 1) - o;
+            rctl[CTL_CNT + t] = cnt;
+            rctl[CTL_OFF + t] = o;
+            rctl[CTL_TILE + t] = trun;
+            trun += (cnt + BM - 1) / BM;
+        }
+        rctl[CTL_OFF + S] = (int)n_rows;
+        rctl[CTL_TILE + S] = trun;
+    }
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n_rows; q += (int64_t)gridDim.x * blockDim.x) {
+        rid[q] = (int)q;
+        ygather[q] = pos[row_atom[q]];
+    }
+}
+
+// workspace: the atoms' part (inference workspace with the activations kept, per-atom energies, sorted positions) first --
+// it does not depend on n_rows, so anihip_mlp_rows_hvp_prepare fills it once per call -- then the rows' part
+static size_t mlp_rows_carve(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_rows, char *base, MlpWorkspace *w,
+                             float *(*buf)[ANIHIP_MAX_LAYERS], float **atomic_e, int **pos, int **rctl, int **rid,
+                             int **ygather)
+{
+    size_t off = align256(mlp_carve(d, n_atoms, base, w));
+    off = carve_zp(d, n_atoms, base, off, w);
+    auto take = [&](size_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += align256(bytes);
+        return p;
+    };
+    float *ae = (float *)take(sizeof(float) * (size_t)(n_atoms + 1));
+    int *ps = (int *)take(sizeof(int) * (size_t)(n_atoms + 1));
+    int *rc = (int *)take(sizeof(int) * CTL_WORDS);
+    int *ri = (int *)take(sizeof(int) * (size_t)(n_rows + 1));
+    int *yg = (int *)take(sizeof(int) * (size_t)(n_rows + 1));
+    if (atomic_e) { *atomic_e = ae; *pos = ps; *rctl = rc; *rid = ri; *ygather = yg; }
+    const int nh = d->net[0].n_layers - 1;
+    for (int k = 0; k < 4; ++k)
+        for (int l = 0; l < nh; ++l) {
+            int mx = 0;
+            for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
+            float *b = (float *)take(sizeof(float) * (size_t)mx * d->n_members * (size_t)(n_rows + 1));
+            if (buf) buf[k][l] = b;
+        }
+    return off;
+}
+
+extern "C" size_t anihip_mlp_rows_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_rows)
+{
+    if (!d || n_atoms < 0 || n_rows < 0) return 0;
+    return mlp_rows_carve(d, n_atoms, n_rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int anihip_mlp_rows_hvp_prepare(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species,
+                                           const float *aev, void *workspace, size_t workspace_bytes)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_desc(d)) return rc;
+    ANIHIP_REQUIRE(species && aev && workspace, "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_atoms < ((int64_t)1 << 31) - 1, "n_atoms must be 0 .. 2^31 - 2");
+    ANIHIP_REQUIRE(workspace_bytes >= mlp_rows_carve(d, n_atoms, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                     nullptr, nullptr),
+                   "workspace too small (anihip_mlp_rows_hvp_workspace_bytes)");
+    if (n_atoms == 0) return 0;
+    MlpWorkspace w;
+    float *buf[4][ANIHIP_MAX_LAYERS];
+    float *atomic_e;
+    int *pos, *rctl, *rid, *ygather;
+    mlp_rows_carve(d, n_atoms, 0, (char *)workspace, &w, buf, &atomic_e, &pos, &rctl, &rid, &ygather);
+    // species buckets, exact-fp32 forward with the activations kept, once per call
+    if (int rc = train_forward(stream, d, n_atoms, 0, n_atoms, species, aev, w, atomic_e, nullptr)) return rc;
+    int64_t blocks = (n_atoms + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_rows_pos, dim3((unsigned)blocks), dim3(256), 0, stream, w.ctl, w.perm, d->num_species, pos);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_mlp_rows_hvp(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species,
+                                   int64_t n_rows, const int32_t *row_atom, const float *tangent, void *workspace,
+                                   size_t workspace_bytes, float *out)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_desc(d)) return rc;
+    ANIHIP_REQUIRE(species && row_atom && tangent && workspace && out, "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
+    ANIHIP_REQUIRE(n_rows < ((int64_t)1 << 31) - 1, "n_rows must stay below 2^31 (got %lld)", (long long)n_rows);
+    const int S = d->num_species, M = d->n_members, nl = d->net[0].n_layers, nh = nl - 1, L = d->aev_len;
+    if (n_rows == 0) return 0;
+    ANIHIP_REQUIRE(workspace_bytes >= mlp_rows_carve(d, n_atoms, n_rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                     nullptr, nullptr),
+                   "workspace too small (anihip_mlp_rows_hvp_workspace_bytes)");
+    MlpWorkspace w;
+    float *buf[4][ANIHIP_MAX_LAYERS];
+    float *atomic_e;
+    int *pos, *rctl, *rid, *ygather;
+    mlp_rows_carve(d, n_atoms, n_rows, (char *)workspace, &w, buf, &atomic_e, &pos, &rctl, &rid, &ygather);
+    zero_words_async(stream, out, sizeof(float) * (size_t)n_rows * L);
+    zero_words_async(stream, rctl, sizeof(int) * CTL_WORDS);
+    int64_t blocks = (n_rows + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_rows_ctl, dim3((unsigned)blocks), dim3(256), 0, stream, S, n_rows, species, row_atom, pos, rctl,
+                       rid, ygather);
+    // the tangent pass over the rows (activations gathered per row), without the weight gradients
+    TangentPass tp{d, &w, rctl, rid, ygather, n_rows, buf[0], buf[1], buf[2], buf[3]};
+    tangent_forward(stream, tp, tangent);
+    tangent_head(stream, tp, nullptr);
+    for (int l = nh - 1; l >= 1; --l) tangent_adjoint(stream, tp, l);
+    // the layer-0 input adjoint: out = W_0^T q_0
+    {
+        const int K0p = ((L + 31) / 32) * 32;
+        GemmArgs g = tp_gemm_base(tp);
+        g.y_gather = nullptr;
+        g.A = buf[3][0]; g.lda = w.ld[0]; g.a_gather = nullptr; g.batch = 1;
+        g.C = out; g.ldc = L; g.c_scatter = rid; g.n_store = L;
+        g.ncol_max = (K0p + BN - 1) / BN;
+        for (int s = 0; s < S; ++s) {
+            const anihip_species_net &nn = d->net[s];
+            GemmProblem &p = g.prob[s];
+            p.B = nn.wt[0];
+            p.K = nn.dims[1] * M; p.N = K0p; p.ldb = p.N;
+            p.a_boff = 0; p.c_boff = 0; p.b_stride = 0;
+        }
+        launch_gemm_fp32<EPI_SCATTER>(stream, g);
+    }
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}

@@ -211,20 +211,34 @@ __device__ __forceinline__ void envelope2(float r, float inv_rc, float rev_rc, f
 // then for every direction gathers t[k][j], applies B and the wave sums give (H t[k])_i.  No atomics: deterministic.
 constexpr int HVP_ROUNDS = (MAXR + WAVE - 1) / WAVE;
 
-template <int KIND>
+// ITEMS (anihip_pair_analytic_hvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi: central atom
+// row_atom[q], ONE direction, the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), output slab row_dir[q] - dir0
+// of out [n_dir][n_atoms][3] (an item row names each (direction, atom) once: still no atomics).
+template <int KIND, bool ITEMS = false>
 __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, int64_t hi,
                                                   const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
                                                   const float4 *__restrict__ ent, const float *__restrict__ tab,
                                                   PairExtra extra, float cutoff, int smooth, int clamp_r, int64_t n_dir,
-                                                  const float *__restrict__ tangent, float *__restrict__ out)
+                                                  const float *__restrict__ tangent, float *__restrict__ out,
+                                                  const int32_t *__restrict__ row_atom = nullptr,
+                                                  const int32_t *__restrict__ row_dir = nullptr, int64_t dir0 = 0)
 {
     const int lane = lane_id();
     const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
     const size_t stride = (size_t)n_atoms * 3;
     const float inv_rc = 1.0f / cutoff, rev_rc = 0.5f / cutoff, pi_rc = 3.14159265358979f / cutoff;
-    for (int64_t i = lo + blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); i < hi; i += nw) {
+    for (int64_t qi = lo + blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); qi < hi; qi += nw) {
+        const int64_t i = ITEMS ? (int64_t)row_atom[qi] : qi;
         const int si = species[i];
         if (si < 0) continue;
+        int64_t da = -1, slab = 0;   // ITEMS: t = e_dc on atom da, written to slab
+        int dc = 0;
+        if (ITEMS) {
+            slab = row_dir[qi] - dir0;
+            if (slab < 0 || slab >= n_dir) continue;   // (a row outside the caller's slabs)
+            da = row_dir[qi] / 3;
+            dc = row_dir[qi] - 3 * (int)da;
+        }
         const uint32_t start = meta[(size_t)i * META_W], c = meta[(size_t)i * META_W + 1];
         const int nR = (int)(c & 0xFFFFu) + (int)(c >> 16);
         for (int b0 = 0; b0 < nR; b0 += HVP_ROUNDS * WAVE) {   // (one pass for every row of at most ANIHIP_MAX_RAD entries)
@@ -257,15 +271,18 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
                 ux[q] = d.x * inv; uy[q] = d.y * inv; uz[q] = d.z * inv;
                 jj[q] = j;
             }
-            for (int64_t kd = 0; kd < n_dir; ++kd) {
-                const float *tk = tangent + (size_t)kd * stride;
-                const float vx = tk[3 * i], vy = tk[3 * i + 1], vz = tk[3 * i + 2];
+            for (int64_t kd = 0; kd < (ITEMS ? 1 : n_dir); ++kd) {
+                const float *tk = ITEMS ? nullptr : tangent + (size_t)kd * stride;
+                auto tang = [&](int64_t n, int k) {
+                    if (ITEMS) return n == da && k == dc ? 1.0f : 0.0f;
+                    return tk[3 * n + k];
+                };
+                const float vx = tang(i, 0), vy = tang(i, 1), vz = tang(i, 2);
                 float hx = 0.f, hy = 0.f, hz = 0.f;
 #pragma unroll
                 for (int q = 0; q < HVP_ROUNDS; ++q) {
                     if (b0 + q * WAVE >= nR) break;   // (wave-uniform)
-                    const float *tj = tk + 3 * (size_t)jj[q];
-                    const float dx = vx - tj[0], dy = vy - tj[1], dz = vz - tj[2];
+                    const float dx = vx - tang(jj[q], 0), dy = vy - tang(jj[q], 1), dz = vz - tang(jj[q], 2);
                     const float cu = bc[q] * (ux[q] * dx + uy[q] * dy + uz[q] * dz);
                     hx += ba[q] * dx + cu * ux[q];
                     hy += ba[q] * dy + cu * uy[q];
@@ -273,7 +290,7 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
                 }
                 hx = wave_sum(hx); hy = wave_sum(hy); hz = wave_sum(hz);
                 if (lane == 0) {
-                    float *o = out + (size_t)kd * stride + 3 * i;
+                    float *o = out + (size_t)(ITEMS ? slab : kd) * stride + 3 * i;
                     o[0] += hx; o[1] += hy; o[2] += hz;
                 }
             }
@@ -566,6 +583,44 @@ extern "C" int anihip_pair_analytic_hvp(void *stream, int32_t kind, int64_t n_at
 #define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
     hipLaunchKernelGGL((k_pair_hvp<K>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_atoms, lo, hi,     \
                        species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r, n_dir, tangent, out)
+    switch (kind) {
+        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
+        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;
+        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_LJ); break;
+        default: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_COULOMB); break;
+    }
+#undef ANIHIP_LAUNCH_PAIR_HVP
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_pair_analytic_hvp_items(void *stream, int32_t kind, int64_t n_atoms, const int32_t *species,
+                                              const uint32_t *meta, const float *ent, const float *pair_table,
+                                              const float *extra, float cutoff, int32_t cutoff_kind, int32_t flags,
+                                              int64_t n_rows, const int32_t *row_atom, const int32_t *row_dir, int64_t dir0,
+                                              int64_t n_dir, float *out)
+{
+    ANIHIP_REQUIRE(species && meta && ent && pair_table && row_atom && row_dir && out, "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0 && n_dir >= 0, "negative size");
+    ANIHIP_REQUIRE(n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
+    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
+    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
+    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
+    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
+    ANIHIP_REQUIRE(!(flags & ANIHIP_PAIR_PUSH),
+                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    if (n_rows == 0 || n_dir == 0) return 0;
+    int64_t blocks = (n_rows + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    PairExtra x{};
+    if (extra)
+        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
+    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
+    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
+#define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
+    hipLaunchKernelGGL((k_pair_hvp<K, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_atoms,       \
+                       (int64_t)0, n_rows, species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r,   \
+                       n_dir, (const float *)nullptr, out, row_atom, row_dir, dir0)
     switch (kind) {
         case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
         case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;

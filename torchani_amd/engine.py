@@ -84,6 +84,84 @@ def rows_to_half(nbrs: NeighborRows, n_atoms: int) -> tp.Tuple[Tensor, Tensor, T
     return idx, dist, diff
 
 
+class SparsePattern(tp.NamedTuple):
+    """Structure of a block-sparse Hessian over the rows of a call (hessian_pattern): R(a) = {a} U row(a) as CSR
+    (roff [N + 1] int64, rlist int32), the block pattern P(a) = U_{i in R(a)} R(i) by columns (poff [N + 1] int64, index
+    int64 [2, nnz]: the entries of column a are poff[a] .. poff[a + 1], rows ascending) and host copies of the offsets."""
+
+    roff: Tensor
+    rlist: Tensor
+    poff: Tensor
+    index: Tensor
+    roff_host: np.ndarray
+    poff_host: np.ndarray
+
+    @property
+    def nnz(self) -> int:
+        return int(self.poff_host[-1])
+
+
+def _exclusive_scan(counts: Tensor) -> Tensor:
+    out = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts, 0, out=out[1:])
+    return out
+
+
+def hessian_pattern(species: Tensor, nbrs: NeighborRows) -> SparsePattern:
+    """R lists and block pattern of the flattened atoms (anihip_hess_sparse_rlist, anihip_hess_sparse_pattern; two calls
+    each, count then fill; two host syncs).  Symmetric rows only."""
+    _require_cuda(species)
+    if not nbrs.symmetric:
+        raise NotImplementedError("sparse Hessians need symmetric neighbor rows (the library's own builders)")
+    L = _lib.lib()
+    n = species.numel()
+    dev = species.device
+    rcnt = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(L.anihip_hess_sparse_rlist(_stream(), n, _ptr(species), _ptr(nbrs.meta), _ptr(nbrs.ent), None, _ptr(rcnt),
+                                          None))
+    roff = _exclusive_scan(rcnt)
+    roff_host = roff.cpu().numpy()
+    rlist = torch.empty(max(int(roff_host[-1]), 1), dtype=torch.int32, device=dev)
+    _lib.check(L.anihip_hess_sparse_rlist(_stream(), n, _ptr(species), _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(roff), None,
+                                          _ptr(rlist)))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    pcnt = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(L.anihip_hess_sparse_pattern(_stream(), n, _ptr(roff), _ptr(rlist), None, 0, _ptr(pcnt), None,
+                                            _ptr(status)))
+    poff = _exclusive_scan(pcnt)
+    poff_host = poff.cpu().numpy()
+    if int(status.item()):
+        raise RuntimeError("sparse Hessian pattern: an atom couples to more than 4096 atoms")
+    nnz = int(poff_host[-1])
+    index = torch.empty((2, nnz), dtype=torch.int64, device=dev)
+    if nnz:
+        _lib.check(L.anihip_hess_sparse_pattern(_stream(), n, _ptr(roff), _ptr(rlist), _ptr(poff), nnz, None,
+                                                _ptr(index), _ptr(status)))
+    return SparsePattern(roff, rlist, poff, index, roff_host, poff_host)
+
+
+def hessian_items(species: Tensor, pat: SparsePattern, num_species: int, n0: int, n1: int) -> tp.Tuple[Tensor, Tensor]:
+    """(row_atom, row_dir) int32 [3 sum_{n0 <= a < n1} |R(a)|]: the item rows of the direction atoms n0 .. n1, the rows of a
+    species contiguous (anihip_hess_sparse_items)."""
+    dev = species.device
+    n_rows = 3 * int(pat.roff_host[n1] - pat.roff_host[n0])
+    row_atom = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+    row_dir = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+    scratch = torch.empty(num_species * (n1 - n0) + 1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().anihip_hess_sparse_items(_stream(), num_species, n0, n1, _ptr(species), _ptr(pat.roff),
+                                                   _ptr(pat.rlist), _ptr(scratch), _ptr(row_atom), _ptr(row_dir)))
+    return row_atom[:n_rows], row_dir[:n_rows]
+
+
+def hessian_extract(pat: SparsePattern, n0: int, n1: int, scratch: Tensor, blocks: Tensor) -> None:
+    """blocks of the columns of the direction atoms n0 .. n1 out of scratch [K, N, 3] (slab 3 a + c - 3 n0 = column (a, c)),
+    writing zeros back to exactly the positions read (anihip_hess_sparse_extract)."""
+    n = scratch.shape[1]
+    _lib.check(_lib.lib().anihip_hess_sparse_extract(
+        _stream(), n, int(pat.poff_host[n0]), int(pat.poff_host[n1]), _ptr(pat.index), pat.nnz, 3 * n0, scratch.shape[0],
+        _ptr(scratch), _ptr(blocks)))
+
+
 class AevEngine:
     """Neighbor rows + AEV forward/backward for one set of AEV constants."""
 
@@ -386,6 +464,35 @@ class AevEngine:
             _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, nbrs.lo, nbrs.hi, _ptr(species),
             _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(g), K, _ptr(t), _ptr(dg), _ptr(out), _ptr(nbrs.status)))
         return out
+
+    def jvp_items(self, species: Tensor, nbrs: NeighborRows, row_atom: Tensor, row_dir: Tensor) -> Tensor:
+        """daev [R, L] over item rows (anihip_aev_jvp_items): row q = d aev_{row_atom[q]} along the unit direction
+        row_dir[q] = 3 a + c (component c of flattened atom a)."""
+        _require_cuda(species, row_atom, row_dir)
+        n = species.numel()
+        R = row_atom.numel()
+        out = torch.empty((R, self.L), dtype=torch.float32, device=species.device)
+        _lib.check(_lib.lib().anihip_aev_jvp_items(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, _ptr(species), _ptr(nbrs.meta),
+            _ptr(nbrs.ent), R, _ptr(row_atom), _ptr(row_dir), _ptr(out)))
+        return out
+
+    def backward_second_items(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor, row_atom: Tensor,
+                              row_dir: Tensor, dir0: int, dgrad: Tensor, out: Tensor) -> None:
+        """out[row_dir[q] - dir0] += J_i^T dgrad[q] + (D_t J_i^T) grad_aev over item rows (anihip_aev_backward_second_items);
+        out [K, N, 3] float32, dgrad [R, L]."""
+        _require_cuda(species, grad_aev, row_atom, row_dir, dgrad, out)
+        if not nbrs.symmetric:
+            raise NotImplementedError("second derivatives need symmetric neighbor rows (the library's own builders)")
+        n = species.numel()
+        R = row_atom.numel()
+        grad_aev = grad_aev.detach().to(torch.float32).contiguous()
+        assert grad_aev.numel() == n * self.L
+        assert dgrad.dtype == torch.float32 and dgrad.is_contiguous() and dgrad.numel() == R * self.L
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[1:] == (n, 3)
+        _lib.check(_lib.lib().anihip_aev_backward_second_items(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, _ptr(species), _ptr(nbrs.meta),
+            _ptr(nbrs.ent), _ptr(grad_aev), R, _ptr(row_atom), _ptr(row_dir), dir0, out.shape[0], _ptr(dgrad), _ptr(out)))
 
     def backward(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor,
                  grad_coords: tp.Optional[Tensor] = None, shard_rows: bool = False,
@@ -863,6 +970,38 @@ class PackedNetworks:
         out = torch.empty((K, n, self.aev_len), dtype=torch.float32, device=dev)
         _lib.check(L.anihip_mlp_input_hvp(_stream(), C.byref(self.desc), n, _ptr(species), _ptr(a), K, _ptr(t), _ptr(ws),
                                           ws.numel(), _ptr(out)))
+        return out
+
+    def rows_hvp_row_bytes(self, n_atoms: int) -> int:
+        """Workspace bytes one row of anihip_mlp_rows_hvp costs (the query is linear in the rows)."""
+        L = _lib.lib()
+        one = L.anihip_mlp_rows_hvp_workspace_bytes(C.byref(self.desc), n_atoms, 1)
+        two = L.anihip_mlp_rows_hvp_workspace_bytes(C.byref(self.desc), n_atoms, 2)
+        return max(int(two - one), 1)
+
+    def rows_hvp_prepare(self, species: Tensor, aev: Tensor, max_rows: int) -> Tensor:
+        """Workspace of rows_hvp for row sets of at most max_rows rows, with the exact-fp32 forward over the atoms run
+        once and its activations kept (anihip_mlp_rows_hvp_prepare)."""
+        _require_cuda(species, aev)
+        n = species.numel()
+        assert aev.dtype == torch.float32 and aev.is_contiguous() and aev.numel() == n * self.aev_len
+        L = _lib.lib()
+        ws = torch.empty(L.anihip_mlp_rows_hvp_workspace_bytes(C.byref(self.desc), n, max_rows), dtype=torch.uint8,
+                         device=aev.device)
+        _lib.check(L.anihip_mlp_rows_hvp_prepare(_stream(), C.byref(self.desc), n, _ptr(species), _ptr(aev), _ptr(ws),
+                                                 ws.numel()))
+        return ws
+
+    def rows_hvp(self, species: Tensor, ws: Tensor, row_atom: Tensor, tangent: Tensor) -> Tensor:
+        """(1/M) sum_m H_m(aev_{row_atom[q]}) tangent[q]  [R, L] over explicit rows, the rows of a species contiguous
+        (anihip_mlp_rows_hvp; exact fp32; ws from rows_hvp_prepare)."""
+        _require_cuda(species, ws, row_atom, tangent)
+        n = species.numel()
+        R = row_atom.numel()
+        assert tangent.dtype == torch.float32 and tangent.is_contiguous() and tangent.numel() == R * self.aev_len
+        out = torch.empty((R, self.aev_len), dtype=torch.float32, device=tangent.device)
+        _lib.check(_lib.lib().anihip_mlp_rows_hvp(_stream(), C.byref(self.desc), n, _ptr(species), R, _ptr(row_atom),
+                                                  _ptr(tangent), _ptr(ws), ws.numel(), _ptr(out)))
         return out
 
     def flat_grad_target(self, w_ptr, b_ptr, member_stride: int):

@@ -8,6 +8,8 @@ Hessians with respect to the coordinates (grad.py:86-150,239-260) come in two fo
   the network input HVP and the second-order AEV backward of the HIP engine (include/anihip.h).
 * ``energies_forces_and_hessians``: the batched path -- neighbor rows, AEVs and d E / d aev once, then the unit directions
   of all molecules in chunks of K (``hessian_chunk_size``, from a fixed memory budget) through the same three kernels.
+* ``energies_forces_and_sparse_hessians``: the block-sparse path for large systems (``tuples.BlockHessian``) -- each unit
+  direction is worked only on the central atoms whose AEV it moves, and only the blocks inside the cutoff pattern are kept.
 
 The closed-form pair potentials (xTB repulsion, ZBL, Lennard-Jones, fixed-charge Coulomb / MNOK: ANI-2xr, ANI-r2s and
 models built with ``add_pair_potential``) add their Hessian-vector products (anihip_pair_analytic_hvp) on both paths, and a
@@ -25,7 +27,7 @@ import typing as tp
 import torch
 from torch import Tensor
 
-from .tuples import EnergiesForces, EnergiesForcesHessians, ForcesHessians, VibAnalysis
+from .tuples import BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians, ForcesHessians, VibAnalysis
 from . import units as _units
 
 
@@ -220,6 +222,110 @@ def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, re
                 pot.hvp(species32, rows, t, out)
             H[:, :, j0:j1] = out.view(j1 - j0, Cn, n).permute(1, 2, 0)
     return EnergiesForcesHessians(ef.energies, ef.forces, H.to(coordinates.dtype))
+
+
+def _sparse_hessian_pairs(model) -> tp.List[tp.Any]:
+    """The enabled closed-form pair potentials of a model, for energies_forces_and_sparse_hessians: each must reach no
+    further than the AEV radial cutoff (its pairs then sit in the AEV's rows and its Hessian in their pattern)."""
+    rc = float(model.aev_computer.radial.cutoff)
+    out = []
+    for name, pot in model.potentials.items():
+        if name == "nnp" or not pot._enabled:
+            continue
+        if math.isinf(pot.cutoff) or pot.cutoff > rc + 1e-6:
+            raise ValueError(f"pair potential {name!r} ({type(pot).__name__}) has cutoff {pot.cutoff} A, beyond the AEV radial "
+                             f"cutoff {rc} A: its Hessian is dense, use grad.energies_forces_and_hessians")
+        out.append(pot)
+    return out
+
+
+def sparse_hessian_chunks(roff_host, n_rows_budget: int, max_atoms: int) -> tp.List[tp.Tuple[int, int]]:
+    """Direction-atom ranges [n0, n1) of energies_forces_and_sparse_hessians: each holds at most n_rows_budget item rows
+    (3 |R(a)| per atom a; at least one atom per chunk) and at most max_atoms atoms; ranges without rows are dropped."""
+    import numpy as np
+
+    cum = 3 * np.asarray(roff_host, dtype=np.int64)
+    N = cum.size - 1
+    out = []
+    n0 = 0
+    while n0 < N:
+        n1 = int(np.searchsorted(cum, cum[n0] + n_rows_budget, side="right")) - 1
+        n1 = max(n0 + 1, min(n1, n0 + max_atoms, N))
+        if cum[n1] > cum[n0]:
+            out.append((n0, n1))
+        n0 = n1
+    return out
+
+
+def energies_forces_and_sparse_hessians(model, species: Tensor, coordinates: Tensor, *, cell: tp.Optional[Tensor] = None,
+                                        pbc: tp.Optional[Tensor] = None) -> EnergiesForcesSparseHessians:
+    """EnergiesForcesSparseHessians(energies, forces, hessians: BlockHessian) of a model: the Hessian with respect to the
+    coordinates as 3 x 3 blocks over the pattern P(a) = U_{i in R(a)} R(i), R(i) = {i} U the neighbor row of i (ANI is
+    local: no other block can be non-zero).  Unit direction (atom a, component c) is worked on the item rows (direction,
+    i), i in R(a), only: anihip_aev_jvp_items, anihip_mlp_rows_hvp (activations computed once per call),
+    anihip_aev_backward_second_items and anihip_pair_analytic_hvp_items scatter into a [K, N, 3] scratch zeroed once, and
+    anihip_hess_sparse_extract moves each chunk's pattern blocks out and zeroes exactly those positions.  Chunks of
+    direction atoms hold at most HESSIAN_BUDGET_BYTES of item-row buffers.  Energies and forces are those of
+    grad.energies_and_forces; the blocks are float32 and agree with energies_forces_and_hessians to fp32 rounding.
+
+    Covered: the networks plus closed-form pair potentials whose cutoff is at most the AEV radial cutoff (ANI-1x, ANI-2x,
+    ANI-2xr), both envelopes, any AEV grid, PBC, batches.  A larger or infinite pair cutoff (ANI-r2s) raises ValueError;
+    D3 (ANI-2dr) raises NotImplementedError; standalone pair potentials are not served."""
+    import numpy as np
+
+    from .engine import hessian_extract, hessian_items, hessian_pattern
+    from .potentials import _Standalone
+
+    if isinstance(model, _Standalone):
+        raise NotImplementedError("sparse Hessians are not available for a standalone pair potential: use "
+                                  "grad.energies_forces_and_hessians")
+    pots = _pair_potentials_without_hessians(model)
+    if pots:
+        raise NotImplementedError(f"the pair potential(s) {', '.join(pots)} have no second derivative with respect to the "
+                                  "coordinates: Hessians of this model are not available")
+    pairs = _sparse_hessian_pairs(model)
+    ef = energies_and_forces(model, species, coordinates, cell, pbc, keep_vars=False)
+    dev = coordinates.device
+    with torch.no_grad():
+        c32 = coordinates.detach().to(torch.float32).contiguous()
+        pbc_t = None if pbc is None else tuple(bool(b) for b in pbc.tolist())
+        species32 = model._elem_idxs(species).to(torch.int32).contiguous()
+        aevc = model.aev_computer
+        eng = aevc.engine()
+        nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_t)
+        nbrs.raise_on_overflow()
+        Cn, A = species32.shape
+        N = Cn * A
+        pat = hessian_pattern(species32, nbrs)
+        nnp = model.potentials["nnp"]._enabled
+        per_row = 8
+        if nnp:
+            aev = eng.forward(species32, nbrs)
+            packed = model.neural_networks._pack(dev)
+            _, g, _ = packed.forward_backward(species32, aev, want_grad=True)
+            per_row += 8 * eng.L + packed.rows_hvp_row_bytes(N)
+        max_r = int(np.diff(pat.roff_host).max()) if N else 0
+        budget = max(HESSIAN_BUDGET_BYTES // per_row, 3 * max_r)
+        chunks = sparse_hessian_chunks(pat.roff_host, budget, max(1, HESSIAN_BUDGET_BYTES // (36 * max(N, 1))))
+        blocks = torch.zeros((pat.nnz, 3, 3), dtype=torch.float32, device=dev)
+        if chunks:
+            rows_max = max(3 * int(pat.roff_host[n1] - pat.roff_host[n0]) for n0, n1 in chunks)
+            K = max(3 * (n1 - n0) for n0, n1 in chunks)
+            scratch = torch.zeros((K, N, 3), dtype=torch.float32, device=dev)
+            ws = packed.rows_hvp_prepare(species32, aev, rows_max) if nnp else None
+            S = int(eng.params.num_species)
+            for n0, n1 in chunks:
+                row_atom, row_dir = hessian_items(species32, pat, S, n0, n1)
+                if nnp:
+                    daev = eng.jvp_items(species32, nbrs, row_atom, row_dir)
+                    hv = packed.rows_hvp(species32, ws, row_atom, daev)
+                    del daev
+                    eng.backward_second_items(species32, nbrs, g, row_atom, row_dir, 3 * n0, hv, scratch)
+                    del hv
+                for pot in pairs:
+                    pot.hvp_items(species32, nbrs, row_atom, row_dir, 3 * n0, scratch)
+                hessian_extract(pat, n0, n1, scratch, blocks)
+    return EnergiesForcesSparseHessians(ef.energies, ef.forces, BlockHessian(pat.index, blocks, Cn, A))
 
 
 def _hvp_row_bytes(packed, n_rows: int) -> int:

@@ -263,6 +263,24 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
             _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
             _lib.CUTOFF_KINDS[self.cutoff_fn], flags, K, _ptr(tangent), _ptr(out)))
 
+    def hvp_items(self, species32: Tensor, nbrs: NeighborRows, row_atom: Tensor, row_dir: Tensor, dir0: int,
+                  out: Tensor) -> None:
+        """out[row_dir[q] - dir0][i] += (H e)_i over item rows (central atom i = row_atom[q], unit direction row_dir[q] =
+        3 a + c) of a block-sparse Hessian (anihip_pair_analytic_hvp_items); out [K, N, 3] float32.  Symmetric rows whose
+        radial cutoff is at least the potential's."""
+        _require_cuda(species32, row_atom, row_dir, out)
+        n = species32.numel()
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.shape[1:] != (n, 3):
+            raise ValueError(f"out must be a contiguous float32 [K, {n}, 3] tensor")
+        if math.isinf(self.cutoff):
+            raise ValueError("an infinite cutoff has no sparse Hessian")
+        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
+        ex = self._extra()
+        _lib.check(_lib.lib().anihip_pair_analytic_hvp_items(
+            _stream(), self.kind, n, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(self.table(species32.device)),
+            None if ex is None else ex.ctypes.data, float(self.cutoff), _lib.CUTOFF_KINDS[self.cutoff_fn], flags,
+            row_atom.numel(), _ptr(row_atom), _ptr(row_dir), dir0, out.shape[0], _ptr(out)))
+
     def compute_from_rows(self, species32: Tensor, coords: Tensor, nbrs: NeighborRows) -> Tensor:
         """Molecular energies [C] (float64), differentiable with respect to coords."""
         return _PairEnergy.apply(coords, self, species32, nbrs)

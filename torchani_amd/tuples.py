@@ -1,4 +1,4 @@
-"""Named tuples returned by the public API (mirrors torchani/tuples.py:32-36,92-96)."""
+"""Named tuples returned by the public API (mirrors torchani/tuples.py:32-36,92-96), and the block-sparse Hessian."""
 from __future__ import annotations
 
 import typing as tp
@@ -111,3 +111,68 @@ class VibAnalysis(tp.NamedTuple):
     modes: Tensor
     fconstants: Tensor
     rmasses: Tensor
+
+
+class BlockHessian:
+    """Block-sparse Hessian with respect to the coordinates of a batch (grad.energies_forces_and_sparse_hessians).
+
+    index: int64 [2, nnz] of flattened atom indices c * A + a; blocks: [nnz, 3, 3] with
+    blocks[p][x, y] = d^2 E / d r_{index[0, p], x} d r_{index[1, p], y}.  The pattern is symmetric ((i, j) and (j, i) are both
+    stored), never crosses molecules and holds no padding atom.  The engine stores it by columns: the entries with
+    index[1] = a are contiguous, index[0] ascending."""
+
+    def __init__(self, index: Tensor, blocks: Tensor, n_molecules: int, n_atoms: int) -> None:
+        if index.dim() != 2 or index.shape[0] != 2 or blocks.shape != (index.shape[1], 3, 3):
+            raise ValueError("index must be [2, nnz] and blocks [nnz, 3, 3]")
+        self.index = index
+        self.blocks = blocks
+        self.n_molecules = int(n_molecules)
+        self.n_atoms = int(n_atoms)
+
+    @property
+    def nnz(self) -> int:
+        return int(self.index.shape[1])
+
+    def __repr__(self) -> str:
+        return f"BlockHessian(n_molecules={self.n_molecules}, n_atoms={self.n_atoms}, nnz={self.nnz})"
+
+    def to_dense(self) -> Tensor:
+        """[C, 3A, 3A]: the layout of grad.energies_forces_and_hessians (zeros outside the pattern)."""
+        import torch
+
+        C, A = self.n_molecules, self.n_atoms
+        H = torch.zeros((C, A, 3, A, 3), dtype=self.blocks.dtype, device=self.blocks.device)
+        i, j = self.index[0], self.index[1]
+        H[i // A, i % A, :, j % A, :] = self.blocks
+        return H.reshape(C, 3 * A, 3 * A)
+
+    def to_sparse_coo(self) -> Tensor:
+        """Coalesced torch sparse COO tensor [C 3A, C 3A] of the scalar entries (row 3 (c A + a) + x)."""
+        import torch
+
+        n = 3 * self.n_molecules * self.n_atoms
+        x = torch.arange(3, device=self.index.device)
+        rows = (3 * self.index[0]).view(-1, 1, 1) + x.view(1, 3, 1)
+        cols = (3 * self.index[1]).view(-1, 1, 1) + x.view(1, 1, 3)
+        idx = torch.stack([rows.expand(-1, 3, 3).reshape(-1), cols.expand(-1, 3, 3).reshape(-1)])
+        return torch.sparse_coo_tensor(idx, self.blocks.reshape(-1), (n, n)).coalesce()
+
+    def matvec(self, v: Tensor) -> Tensor:
+        """H v for v of C * A * 3 elements ([C, A, 3], [C, 3A] or flat): the result has v's shape."""
+        import torch
+
+        N = self.n_molecules * self.n_atoms
+        if v.numel() != 3 * N:
+            raise ValueError(f"v must hold {3 * N} elements (C * A * 3)")
+        vf = v.reshape(N, 3).to(self.blocks.dtype)
+        prod = torch.bmm(self.blocks, vf[self.index[1]].unsqueeze(-1)).squeeze(-1)
+        out = torch.zeros((N, 3), dtype=self.blocks.dtype, device=self.blocks.device).index_add_(0, self.index[0], prod)
+        return out.reshape(v.shape)
+
+
+class EnergiesForcesSparseHessians(tp.NamedTuple):
+    """What grad.energies_forces_and_sparse_hessians returns: hessians is a BlockHessian."""
+
+    energies: Tensor
+    forces: Tensor
+    hessians: BlockHessian
