@@ -295,6 +295,34 @@ int anihip_aev_backward_second_items(void *stream, const anihip_aev_params *p, c
 int anihip_hess_sparse_extract(void *stream, int64_t n_atoms, int64_t p0, int64_t p1, const int64_t *index, int64_t nnz,
                                int64_t dir0, int64_t n_dir, float *scratch, float *blocks);
 
+/* Lowest normal modes of block-sparse Hessians (grad.sparse_vibrational_analysis): the operator
+ *   A = M^-1/2 ((H + H^T) / 2) M^-1/2
+ * of a tuples.BlockHessian in a layout of its own (csrc/hess_modes.hip).
+ *
+ * anihip_block_hessian_prepare, once per call.  index int64 [2][nnz] BY COLUMNS (index[1] non-decreasing, index[0] strictly
+ * ascending inside a column), blocks fp32 [nnz][3][3] (blocks[p][x][y] = d^2 E / d r_{index[0][p], x} d r_{index[1][p], y}),
+ * masses fp64 [n_atoms] (amu; read only for atoms that hold blocks).  Writes coff int64 [n_atoms + 1] (the entries of column
+ * a are coff[a] .. coff[a + 1]), rows int32 [nnz] = index[0], partner int64 [nnz] (the entry of the transposed block),
+ * ablocks fp32 [nnz][3][3] = (B_ja + B_aj^T) / (2 sqrt(m_j m_a)) for the entry p = (row j, column a), diag int64 [n_atoms]
+ * (the entry of atom a's diagonal block, -1 if it has none: a padding atom) and gersh fp64 [n_atoms] (the largest of the
+ * Gershgorin row sums sum_{j, y} |A_{(a x), (j y)}| of atom a's three rows).  *status (zeroed by the caller) gets
+ * ANIHIP_BLOCK_HESSIAN_BAD_INDEX for an index out of 0 .. n_atoms or not sorted by columns, ANIHIP_BLOCK_HESSIAN_NO_PARTNER
+ * for a block whose transpose is not stored and ANIHIP_BLOCK_HESSIAN_NO_DIAGONAL for an atom with blocks but no diagonal
+ * block; the affected outputs are zero.  The index is not read by anihip_block_hessian_spmm.
+ *
+ * anihip_block_hessian_spmm: y = A x for m vectors, 1 <= m <= ANIHIP_BLOCK_HESSIAN_MAX_VECTORS; x, y fp32 [n_atoms][3][m]
+ * (vector index fastest), y OVERWRITTEN (rows of atoms without blocks are zero).  Row a of y is a sum over column a's blocks
+ * (A is symmetric) in fp64, written once: no atomics, bit-identical run to run. */
+#define ANIHIP_BLOCK_HESSIAN_MAX_VECTORS 64
+#define ANIHIP_BLOCK_HESSIAN_BAD_INDEX 1u
+#define ANIHIP_BLOCK_HESSIAN_NO_PARTNER 2u
+#define ANIHIP_BLOCK_HESSIAN_NO_DIAGONAL 4u
+int anihip_block_hessian_prepare(void *stream, int64_t n_atoms, int64_t nnz, const int64_t *index, const float *blocks,
+                                 const double *masses, int64_t *coff, int32_t *rows, int64_t *partner, float *ablocks,
+                                 double *gersh, int64_t *diag, uint32_t *status);
+int anihip_block_hessian_spmm(void *stream, int64_t n_atoms, int32_t m, const int64_t *coff, const int32_t *rows,
+                              const float *ablocks, const float *x, float *y);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -2,13 +2,16 @@
 loop of grad.forces_and_hessians) on fixtures of tests/golden: device-synchronised, after warm-up, median of several runs.
 
     python tools/hessian_bench.py [--runs 5] [--autograd-max 264] [--bases ch4_ani1x,dense90_ani2x,...]
-                                  [--kind fixture|ani2xr|anir2s] [--sparse [--dense-max 1000]]
+                                  [--kind fixture|ani2xr|anir2s] [--sparse [--dense-max 1000] [--modes 10,50]]
 
 Prints one JSON line per case.  Seeded parameters (the fixtures' seeds): timings do not depend on the values.
 ``--kind ani2xr`` / ``anir2s`` times that architecture (networks plus the xTB repulsion term) on the fixtures'
 coordinates instead of the fixture's own ANI-2x / ANI-1x model.  ``--sparse`` times the block-sparse path
 (grad.energies_forces_and_sparse_hessians) and the dense batched path in the same run (the dense one only up to
-``--dense-max`` atoms), with the fixture's cell and pbc, the number of stored blocks and the peak device memory of each."""
+``--dense-max`` atoms), with the fixture's cell and pbc, the number of stored blocks and the peak device memory of each.
+``--modes K[,K2..]`` adds grad.sparse_vibrational_analysis on that sparse Hessian: solver time and iterations for each K,
+the time per call of anihip_block_hessian_spmm at m = 1, 8, 32, 64 beside m calls of BlockHessian.matvec, and (up to
+``--dense-max`` atoms) the dense route: to_dense, mass weighting and fp64 torch.linalg.eigh."""
 from __future__ import annotations
 
 import argparse
@@ -37,6 +40,50 @@ def timed(fn, runs):
     return float(np.median(ts)) * 1e3, [round(t * 1e3, 3) for t in ts]
 
 
+def modes_row(H, g, sp, ks, runs, dense):
+    """Timings of grad.sparse_vibrational_analysis and its operator on a BlockHessian."""
+    from torchani_amd import grad
+    from torchani_amd.engine import block_hessian_prepare, block_hessian_spmm
+    from torchani_amd.extras.io import PERIODIC_TABLE
+    from torchani_amd.utils import atomic_numbers_to_masses
+
+    dev = sp.device
+    z = torch.tensor([PERIODIC_TABLE.index(s) for s in g["symbols"]], device=dev)
+    masses = atomic_numbers_to_masses(torch.where(sp >= 0, z[sp.clamp(min=0)], torch.full_like(sp, -1)),
+                                      dtype=torch.float64)
+    row = {}
+    for k in ks:
+        va = grad.sparse_vibrational_analysis(masses, H, k)
+        row[f"modes{k}_ms"], row[f"modes{k}_runs"] = timed(lambda: grad.sparse_vibrational_analysis(masses, H, k), runs)
+        row[f"modes{k}_iter"] = va.n_iter
+        row[f"modes{k}_lowest"] = [round(v, 6) for v in va.eigenvalues[0, :3].tolist()]
+    op = block_hessian_prepare(H.index, H.blocks, masses.reshape(-1))
+    row["prepare_ms"], _ = timed(lambda: block_hessian_prepare(H.index, H.blocks, masses.reshape(-1)), runs)
+    N = sp.numel()
+    for m in (1, 8, 32, 64):
+        X = torch.randn((N, 3, m), device=dev)
+        Y = torch.empty_like(X)
+        reps = 20
+
+        def calls():
+            for _ in range(reps):
+                block_hessian_spmm(op, X, Y)
+        row[f"spmm_m{m}_ms"] = round(timed(calls, runs)[0] / reps, 4)
+        cols = [X[:, :, i].contiguous() for i in range(m)]
+
+        def matvecs():
+            for v in cols:
+                H.matvec(v)
+        row[f"matvec_x{m}_ms"] = round(timed(matvecs, max(1, runs // 2))[0], 3)
+    if dense:
+        def eigh():
+            D = H.to_dense().double()
+            w = masses.rsqrt().repeat_interleave(3, dim=1)
+            return torch.linalg.eigh(0.5 * (D + D.transpose(1, 2)) * w.unsqueeze(2) * w.unsqueeze(1))
+        row["dense_eigh_ms"], _ = timed(eigh, max(1, runs // 2))
+    return row
+
+
 def main():
     from _util import load_golden, seeded_state
 
@@ -51,6 +98,7 @@ def main():
     ap.add_argument("--kind", default="fixture", choices=("fixture", "ani2xr", "anir2s"))
     ap.add_argument("--sparse", action="store_true", help="block-sparse path beside the dense one")
     ap.add_argument("--dense-max", type=int, default=1000, help="--sparse: largest system the dense path is timed on")
+    ap.add_argument("--modes", default="", help="--sparse: lowest normal modes, K[,K2..] of them")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for base in args.bases.split(","):
@@ -82,6 +130,9 @@ def main():
             del out
             row["sparse_ms"], row["sparse_runs"] = timed(
                 lambda: grad.energies_forces_and_sparse_hessians(model, sp, x, cell=cell, pbc=pbc), runs)
+            if args.modes:
+                row.update(modes_row(grad.energies_forces_and_sparse_hessians(model, sp, x, cell=cell, pbc=pbc).hessians,
+                                     g, sp, [int(k) for k in args.modes.split(",")], runs, A <= args.dense_max))
             if A <= args.dense_max:
                 torch.cuda.synchronize()
                 torch.cuda.reset_peak_memory_stats()

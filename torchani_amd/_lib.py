@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip"]
 HEADERS = ["anihip_common.h", "train.h", "mlp_fused.h", "mlp_prep.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -39,6 +39,8 @@ MLP_FLAG_SHAPED = 4096   # one fused launch per species with compile-time networ
 MLP_FLAG_BWD_TWO_PRODUCTS = 2048   # off by default: two-product backward GEMMs of the large-system path (include/anihip.h)
 ABI_VERSION = 12
 REPACK_FUSED_ONLY = 1
+BLOCK_HESSIAN_MAX_VECTORS = 64   # ANIHIP_BLOCK_HESSIAN_MAX_VECTORS
+BLOCK_HESSIAN_BAD_INDEX, BLOCK_HESSIAN_NO_PARTNER, BLOCK_HESSIAN_NO_DIAGONAL = 1, 2, 4
 
 
 class AevParams(C.Structure):
@@ -231,6 +233,10 @@ def lib() -> C.CDLL:
                  "anihip_hess_sparse_extract", "anihip_aev_jvp_items", "anihip_aev_backward_second_items",
                  "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items"):
         getattr(L, name).restype = C.c_int
+    L.anihip_block_hessian_prepare.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_block_hessian_prepare.restype = C.c_int
+    L.anihip_block_hessian_spmm.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
+    L.anihip_block_hessian_spmm.restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
     for name in ("anihip_aev_table_pack", "anihip_nbr_build_batch", "anihip_nbr_build_cell", "anihip_nbr_from_half",
@@ -258,6 +264,7 @@ EXPORTED_SYMBOLS = [
     "anihip_hess_sparse_rlist", "anihip_hess_sparse_pattern", "anihip_hess_sparse_items", "anihip_hess_sparse_extract",
     "anihip_aev_jvp_items", "anihip_aev_backward_second_items", "anihip_mlp_rows_hvp_workspace_bytes",
     "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items",
+    "anihip_block_hessian_prepare", "anihip_block_hessian_spmm",
 ]
 
 

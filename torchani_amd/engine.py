@@ -162,6 +162,71 @@ def hessian_extract(pat: SparsePattern, n0: int, n1: int, scratch: Tensor, block
         _ptr(scratch), _ptr(blocks)))
 
 
+class BlockOperator(tp.NamedTuple):
+    """The mass-weighted, symmetrized operator A = M^-1/2 ((H + H^T) / 2) M^-1/2 of a BlockHessian in the layout of
+    anihip_block_hessian_spmm (block_hessian_prepare): column offsets coff [N + 1] int64, rows int32 [nnz], the transpose
+    partner of each entry int64 [nnz], ablocks fp32 [nnz, 3, 3] (entry p = (row j, column a) holds A_ja), the entry of each
+    atom's diagonal block diag int64 [N] (-1: padding) and the per-atom Gershgorin row-sum bound gersh fp64 [N]."""
+
+    coff: Tensor
+    rows: Tensor
+    partner: Tensor
+    ablocks: Tensor
+    diag: Tensor
+    gersh: Tensor
+
+    @property
+    def n_atoms(self) -> int:
+        return int(self.diag.numel())
+
+
+def block_hessian_prepare(index: Tensor, blocks: Tensor, masses: Tensor) -> BlockOperator:
+    """anihip_block_hessian_prepare over a column-sorted index int64 [2, nnz], blocks fp32 [nnz, 3, 3] and masses [N] (amu);
+    one host sync for the status word.  Raises ValueError for an index out of range or not sorted by columns, a block whose
+    transpose is missing, or an atom with blocks but no diagonal block."""
+    _require_cuda(index, blocks, masses)
+    dev = blocks.device
+    n = masses.numel()
+    nnz = int(index.shape[1])
+    index = index.to(torch.int64).contiguous()
+    blocks = blocks.to(torch.float32).contiguous()
+    masses = masses.to(torch.float64).contiguous()
+    coff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    rows = torch.empty(nnz, dtype=torch.int32, device=dev)
+    partner = torch.empty(nnz, dtype=torch.int64, device=dev)
+    ablocks = torch.empty((nnz, 3, 3), dtype=torch.float32, device=dev)
+    diag = torch.empty(n, dtype=torch.int64, device=dev)
+    gersh = torch.empty(n, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().anihip_block_hessian_prepare(
+        _stream(), n, nnz, _ptr(index), _ptr(blocks), _ptr(masses), _ptr(coff), _ptr(rows), _ptr(partner), _ptr(ablocks),
+        _ptr(gersh), _ptr(diag), _ptr(status)))
+    st = int(status.item())
+    if st & _lib.BLOCK_HESSIAN_BAD_INDEX:
+        raise ValueError("BlockHessian index out of range or not sorted by columns")
+    if st & _lib.BLOCK_HESSIAN_NO_PARTNER:
+        raise ValueError("BlockHessian pattern is not symmetric: a block (i, j) is stored without (j, i)")
+    if st & _lib.BLOCK_HESSIAN_NO_DIAGONAL:
+        raise ValueError("BlockHessian has an atom with off-diagonal blocks but no diagonal block")
+    return BlockOperator(coff, rows, partner, ablocks, diag, gersh)
+
+
+def block_hessian_spmm(op: BlockOperator, x: Tensor, out: tp.Optional[Tensor] = None) -> Tensor:
+    """Y = A X (anihip_block_hessian_spmm) for X fp32 [N, 3, m] (or any shape of N * 3 * m elements, vector index fastest),
+    1 <= m <= 64; Y has X's shape."""
+    _require_cuda(x)
+    n = op.n_atoms
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() % (3 * max(n, 1)):
+        raise ValueError(f"x must be contiguous float32 of N * 3 * m elements (N = {n})")
+    m = x.numel() // (3 * n) if n else 1
+    if not 1 <= m <= _lib.BLOCK_HESSIAN_MAX_VECTORS:
+        raise ValueError(f"anihip_block_hessian_spmm takes 1 .. {_lib.BLOCK_HESSIAN_MAX_VECTORS} vectors, got {m}")
+    y = torch.empty_like(x) if out is None else out
+    _lib.check(_lib.lib().anihip_block_hessian_spmm(_stream(), n, m, _ptr(op.coff), _ptr(op.rows), _ptr(op.ablocks), _ptr(x),
+                                                    _ptr(y)))
+    return y
+
+
 class AevEngine:
     """Neighbor rows + AEV forward/backward for one set of AEV constants."""
 

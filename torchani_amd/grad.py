@@ -15,7 +15,8 @@ The closed-form pair potentials (xTB repulsion, ZBL, Lennard-Jones, fixed-charge
 models built with ``add_pair_potential``) add their Hessian-vector products (anihip_pair_analytic_hvp) on both paths, and a
 standalone pair potential may stand in for the model.  D3 dispersion (ANI-2dr) has no second derivative here: every Hessian
 entry point raises NotImplementedError naming it.  ``vibrational_analysis`` and ``VibAnalysis`` (grad.py:153-236) are
-host-side; unit conversions live in ``torchani_amd.units``.  NOT here: a numerical Hessian, the modules ``torchani.cutoffs``
+host-side; ``sparse_vibrational_analysis`` finds the lowest modes of a ``BlockHessian`` on the device (anihip_block_hessian_spmm
+under the solver of ``torchani_amd.modes``); unit conversions live in ``torchani_amd.units``.  NOT here: a numerical Hessian, the modules ``torchani.cutoffs``
 (the cutoff envelopes live in the AEV kernels: ``AEVComputer(..., cutoff_fn="cosine" | "smooth")``,
 ``constants.cutoff_kernel_name``) and ``torchani.sae`` (``nn.SelfEnergy`` is the energy shifter of the models).
 """
@@ -27,7 +28,8 @@ import typing as tp
 import torch
 from torch import Tensor
 
-from .tuples import BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians, ForcesHessians, VibAnalysis
+from .tuples import (BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians, ForcesHessians,
+                     SparseVibAnalysis, VibAnalysis)
 from . import units as _units
 
 
@@ -374,6 +376,190 @@ def vibrational_analysis(masses: Tensor, hessian: Tensor, mode_kind: str = "mdu"
         raise ValueError(f"Incorrect mode kind {mode_kind}")
     freqs = to_unit(evals.abs().sqrt() / (2 * math.pi) * torch.sign(evals))
     return VibAnalysis(freqs, modes.reshape(evals.numel(), -1, 3), fconstants, rmasses)
+
+
+SPARSE_MODES_SEED = 20261015   # start vectors of sparse_vibrational_analysis (fixed: results repeat exactly)
+
+
+def _modes_outputs(evals: Tensor, mw: Tensor, w: Tensor, mode_kind: str, to_unit):
+    """vibrational_analysis's outputs from eigenvalues [C, k] and mass-weighted unit modes mw [C, k, 3A]; w [C, 3A] = m^-1/2
+    (0 on padding)."""
+    md = mw * w.unsqueeze(1)
+    inv_norm = md.norm(dim=2).reciprocal()
+    rmasses = inv_norm ** 2
+    fconstants = _units.mhessian2fconst(evals) * rmasses
+    kind = mode_kind.lower()
+    if kind in ("mdn", "mass-deweighted-normalized"):
+        modes = md * inv_norm.unsqueeze(2)
+    elif kind in ("mdu", "mass-deweighted-unnormalized"):
+        modes = md
+    elif kind in ("mwn", "mass-weighted-normalized"):
+        modes = mw
+    else:
+        raise ValueError(f"Incorrect mode kind {mode_kind}")
+    freqs = to_unit(evals.abs().sqrt() / (2 * math.pi) * torch.sign(evals))
+    return freqs, modes, fconstants, rmasses
+
+
+def _rigid_basis(masses: Tensor, real: Tensor, coordinates: tp.Optional[Tensor], rotations: bool) -> Tensor:
+    """[C, 3A, 6 or 3] mass-weighted rigid-body motions over the real atoms: sqrt(m_a) e_x and sqrt(m_a) e_x x (r_a - com)."""
+    C, A = masses.shape
+    sm = torch.where(real, masses, torch.zeros_like(masses)).sqrt()                     # [C, A]
+    eye = torch.eye(3, dtype=masses.dtype, device=masses.device)
+    vecs = [sm[:, :, None] * eye[x] for x in range(3)]                                  # [C, A, 3] each
+    if rotations:
+        m = sm ** 2
+        r = coordinates.to(masses.dtype)
+        com = (m.unsqueeze(2) * r).sum(1, keepdim=True) / m.sum(1, keepdim=True).clamp_min(1e-300).unsqueeze(2)
+        d = (r - com) * real.unsqueeze(2)
+        vecs += [sm.unsqueeze(2) * torch.cross(eye[x].expand_as(d), d, dim=2) for x in range(3)]
+    return torch.stack([v.reshape(C, 3 * A) for v in vecs], dim=2)
+
+
+def sparse_vibrational_analysis(masses: Tensor, hessian: BlockHessian, n_modes: int = 20, *, mode_kind: str = "mdu",
+                                unit: str = "cm^-1", project_rigid: bool = False, coordinates: tp.Optional[Tensor] = None,
+                                pbc: tp.Optional[Tensor] = None, tol: float = 1e-6, max_iter: int = 1000,
+                                check: bool = True) -> SparseVibAnalysis:
+    """The n_modes lowest normal modes of each molecule of a block-sparse Hessian (grad.energies_forces_and_sparse_hessians):
+    the eigenproblem of vibrational_analysis, A = M^-1/2 ((H + H^T) / 2) M^-1/2 over each molecule's real atoms, solved
+    without forming A.  masses [C, A] (amu).  A padding atom is one without a diagonal block: it is excluded and its mode
+    components are zero; a real atom whose mass is not positive and finite raises ValueError.
+
+    anihip_block_hessian_prepare turns the blocks into the operator once (symmetrized, mass-weighted, the Gershgorin bound
+    ||A||_G of each molecule); modes.lobpcg then touches A only through anihip_block_hessian_spmm, one product for all
+    molecules.  A molecule with at most 3 (n_modes + guard) degrees of freedom is solved densely on the device
+    (modes.dense_eigenpairs).  Every pair must reach ||A q - theta q|| <= tol ||A||_G; otherwise RuntimeError after
+    max_iter iterations, or with check=False the unconverged pairs are returned.
+
+    project_rigid=True removes the rigid-body motions in mass-weighted space: the 3 translations, and the 3 rotations about
+    the centre of mass when no axis of pbc is periodic (they need coordinates [C, A, 3]); the modes returned are the lowest
+    orthogonal to them.  The default keeps the spectrum of vibrational_analysis, which does not project.  Outputs:
+    tuples.SparseVibAnalysis (fp64; freqs, modes, fconstants and rmasses as vibrational_analysis, mode_kind and unit
+    alike)."""
+    from . import modes as _modes
+    from .engine import _require_cuda, block_hessian_prepare, block_hessian_spmm
+
+    if unit == "cm^-1":
+        to_unit = _units.sqrt_mhessian2invcm
+    elif unit == "meV":
+        to_unit = _units.sqrt_mhessian2milliev
+    else:
+        raise ValueError("Only meV and cm^-1 are supported right now")
+    if mode_kind.lower() not in ("mdn", "mass-deweighted-normalized", "mdu", "mass-deweighted-unnormalized", "mwn",
+                                 "mass-weighted-normalized"):
+        raise ValueError(f"Incorrect mode kind {mode_kind}")
+    if not isinstance(hessian, BlockHessian):
+        raise TypeError("hessian must be a tuples.BlockHessian (grad.vibrational_analysis takes dense Hessians)")
+    C, A = hessian.n_molecules, hessian.n_atoms
+    if tuple(masses.shape) != (C, A):
+        raise ValueError(f"masses must be [C, A] = [{C}, {A}], got {list(masses.shape)}")
+    if n_modes < 1:
+        raise ValueError("n_modes must be at least 1")
+    if not tol > 0 or max_iter < 1:
+        raise ValueError("tol must be positive and max_iter at least 1")
+    periodic = pbc is not None and bool(torch.as_tensor(pbc).any())
+    if project_rigid and not periodic and (coordinates is None or tuple(coordinates.shape) != (C, A, 3)):
+        raise ValueError("project_rigid=True without periodic axes removes rotations: pass coordinates [C, A, 3]")
+    _require_cuda(masses, hessian.index, hessian.blocks, coordinates)
+    dev = masses.device
+    N = C * A
+    index, blocks = hessian.index, hessian.blocks
+    with torch.no_grad():
+        if hessian.nnz > 1:
+            key = index[1] * N + index[0]
+            unsorted, crossing = torch.stack([(key[1:] <= key[:-1]).any(), (index[0] // A != index[1] // A).any()]).tolist()
+            if crossing:
+                raise ValueError("BlockHessian blocks couple different molecules")
+            if unsorted:   # a hand-built Hessian: put it in column order once (the engine's own output already is)
+                order = torch.argsort(key)
+                index, blocks = index[:, order], blocks[order]
+        m64 = masses.detach().to(torch.float64)
+        op = block_hessian_prepare(index, blocks, m64.reshape(-1))
+        real = (op.diag >= 0).view(C, A)
+        bad = real & ~(torch.isfinite(m64) & (m64 > 0))
+        w_atom = torch.where(real & ~bad, m64.clamp_min(1e-300).rsqrt(), torch.zeros_like(m64))
+        w = w_atom.repeat_interleave(3, dim=1)                                          # [C, 3A]
+        bound = op.gersh.view(C, A).amax(dim=1)
+        dofmask = w > 0
+        R = None
+        if project_rigid:
+            R = _rigid_basis(m64, real, None if coordinates is None else coordinates.detach(), not periodic)
+            R, _, _ = _modes.svqb(R)
+            R, _, vr = _modes.svqb(R)
+            n_rigid = vr.sum(dim=1)
+        else:
+            n_rigid = torch.zeros(C, dtype=torch.int64, device=dev)
+        avail = 3 * real.sum(dim=1) - n_rigid
+        any_bad, avail_h = bool(bad.any()), avail.cpu()
+        if any_bad:
+            raise ValueError("masses must be positive and finite on every real atom (an atom with a diagonal block)")
+        if n_modes > int(avail_h.min()):
+            raise ValueError(f"n_modes = {n_modes} exceeds the {int(avail_h.min())} degrees of freedom of a molecule")
+        k = n_modes + max(4, n_modes // 4)
+        dense = avail_h <= 3 * k
+        sel_d = torch.nonzero(dense).reshape(-1).tolist()
+        sel_l = torch.nonzero(~dense).reshape(-1).tolist()
+
+        def operator(sel):
+            full = len(sel) == C
+            sel_t = torch.tensor(sel, dtype=torch.int64, device=dev)
+            Rs = None if R is None else R[sel_t]
+
+            def project(V):
+                return V - Rs @ (Rs.transpose(1, 2) @ V)
+
+            def apply(V):
+                outs = []
+                for c0 in range(0, V.shape[2], _modes.MAX_VECTORS):
+                    Vc = V[:, :, c0:c0 + _modes.MAX_VECTORS]
+                    if full:
+                        X = Vc.to(torch.float32).contiguous()
+                    else:
+                        X = torch.zeros((C, 3 * A, Vc.shape[2]), dtype=torch.float32, device=dev)
+                        X[sel_t] = Vc.to(torch.float32)
+                    Y = block_hessian_spmm(op, X)
+                    outs.append((Y if full else Y[sel_t]).to(torch.float64))
+                return torch.cat(outs, dim=2)
+
+            if Rs is None:
+                return apply, None, sel_t
+            return (lambda V: project(apply(project(V)))), project, sel_t
+
+        evals = torch.zeros((C, n_modes), dtype=torch.float64, device=dev)
+        vecs = torch.zeros((C, 3 * A, n_modes), dtype=torch.float64, device=dev)
+        res = torch.zeros((C, n_modes), dtype=torch.float64, device=dev)
+        n_iter = 0
+        if sel_d:
+            apply, project, sel_t = operator(sel_d)
+            mask = dofmask[sel_t]
+            rank = torch.cumsum(mask.to(torch.int64), dim=1) - 1
+            d = int(mask.sum(dim=1).max())
+            E = torch.zeros((len(sel_d), 3 * A, d), dtype=torch.float64, device=dev)
+            ci, ii = torch.nonzero(mask, as_tuple=True)
+            E[ci, ii, rank[ci, ii]] = 1.0
+            if project is not None:
+                E = project(E)
+            r = _modes.dense_eigenpairs(apply, E, n_modes, bound[sel_t])
+            evals[sel_t], vecs[sel_t], res[sel_t] = r.eigenvalues, r.vectors, r.residuals
+        if sel_l:
+            apply, project, sel_t = operator(sel_l)
+            g = torch.Generator(device=dev).manual_seed(SPARSE_MODES_SEED)
+            X0 = torch.randn((len(sel_l), 3 * A, k), dtype=torch.float64, device=dev, generator=g)
+            X0 = X0 * dofmask[sel_t].unsqueeze(2)
+            r = _modes.lobpcg(apply, X0, n_modes, tol * bound[sel_t], bound[sel_t], max_iter, project=project)
+            evals[sel_t], vecs[sel_t] = r.eigenvalues[:, :n_modes], r.vectors[:, :, :n_modes]
+            res[sel_t] = r.residuals[:, :n_modes]
+            n_iter = r.n_iter
+        if check:
+            rel = (res / bound.clamp_min(1e-300).unsqueeze(1)).max(dim=1).values
+            worst = int(rel.argmax())
+            if float(rel[worst]) > tol:
+                raise RuntimeError(f"sparse_vibrational_analysis did not converge in max_iter = {max_iter} iterations: worst "
+                                   f"residual {float(res[worst].max()):.3e} = {float(rel[worst]):.2e} ||A||_G in molecule "
+                                   f"{worst} (tol {tol:g}); raise max_iter or pass check=False")
+        mw = vecs.transpose(1, 2)
+        freqs, modes, fconstants, rmasses = _modes_outputs(evals, mw, w, mode_kind, to_unit)
+    return SparseVibAnalysis(freqs, modes.reshape(C, n_modes, A, 3), fconstants, rmasses, evals, res, n_iter)
 
 
 def energies_and_forces(model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None,

@@ -113,6 +113,21 @@ class VibAnalysis(tp.NamedTuple):
     rmasses: Tensor
 
 
+class SparseVibAnalysis(tp.NamedTuple):
+    """What grad.sparse_vibrational_analysis returns for C molecules and k modes: freqs [C, k], modes [C, k, A, 3],
+    fconstants [C, k] and rmasses [C, k] as in VibAnalysis (zero on padding atoms), eigenvalues [C, k] of the mass-weighted
+    Hessian (fp64, Hartree / (amu Angstrom^2), ascending), residuals [C, k] = ||A q - theta q|| of the mass-weighted unit
+    modes q, and n_iter, the solver's iteration count (0 when every molecule was solved densely)."""
+
+    freqs: Tensor
+    modes: Tensor
+    fconstants: Tensor
+    rmasses: Tensor
+    eigenvalues: Tensor
+    residuals: Tensor
+    n_iter: int
+
+
 class BlockHessian:
     """Block-sparse Hessian with respect to the coordinates of a batch (grad.energies_forces_and_sparse_hessians).
 
