@@ -295,6 +295,44 @@ int anihip_aev_backward_second_items(void *stream, const anihip_aev_params *p, c
 int anihip_hess_sparse_extract(void *stream, int64_t n_atoms, int64_t p0, int64_t p1, const int64_t *index, int64_t nnz,
                                int64_t dir0, int64_t n_dir, float *scratch, float *blocks);
 
+/* ---------------------------------------------------------------------------------------------
+ * Strain second derivatives (grad.energies_forces_and_strain_hessians).  Coordinates are row vectors; the system is strained
+ * by a 3 x 3 matrix S as x -> x S, cell -> cell S, so every pair displacement d (any periodic image) becomes d S.  At S = I,
+ * for strain direction k = 3 a + b the tangent of every entry is d' = d_a e_b (it replaces t_j - t_i of a coordinate
+ * direction), and
+ *   strain_hessians[c][a][b][p][q] = d^2 E_c / d S_ab d S_pq = sum over the rows of molecule c and their pairs of
+ *                                    d_a ((d E_i / d d)')_b along the tangent of (p, q),
+ *   internal_strain[c][i][y][a][b] = d^2 E_c / d x_iy d S_ab = K_k[i][y] + delta_ya (d E / d x_i)_b,
+ * where K_k = J^T (H_net J d') + (D_d' J^T) g is the mixed derivative with the displacements taken in the strained frame
+ * (what these entry points scatter); the force term is the caller's.  Strain item rows: row_dir[q] = k in 0 .. 8, row_atom[q] =
+ * the central atom i.  ss is double [n_atoms / atoms_per_mol][9][9] (ss[c][3 a + b][3 p + q]), accumulated with fp64
+ * atomics; out is float [9][n_atoms][3].  Symmetric rows only.
+ *
+ * anihip_aev_jvp over strain item rows: daev [n_rows][L], row q = d aev_{row_atom[q]} / d S_k.  Every grid through the
+ * general kernel, both cutoff functions. */
+int anihip_aev_jvp_strain_items(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                                const int32_t *species, const uint32_t *meta, const float *ent, int64_t n_rows,
+                                const int32_t *row_atom, const int32_t *row_dir, float *daev);
+
+/* anihip_aev_backward_second over strain item rows: out[k][.] += K_k of the central atom i = row_atom[q] (float atomics, as
+ * the item rows of block-sparse Hessians), dgrad [n_rows][L] = H_net J d' of the row; and
+ * ss[i / atoms_per_mol][3 x + y][k] += sum_e d_{e,x} ((d E_i / d d_e)')_y (one fp64 atomic per component and row).  Rows with
+ * row_dir outside 0 .. 8 are skipped.  atoms_per_mol divides n_atoms. */
+int anihip_aev_backward_second_strain_items(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                                            int64_t atoms_per_mol, const int32_t *species, const uint32_t *meta,
+                                            const float *ent, const float *grad_aev, int64_t n_rows, const int32_t *row_atom,
+                                            const int32_t *row_dir, const float *dgrad, float *out, double *ss);
+
+/* anihip_pair_analytic_hvp along the 9 strain directions, over the central atoms lo <= i < hi (same kind, rows, tables,
+ * cutoff and flags as anihip_pair_analytic):  out[k][i] += -sum_j B_ij d'_ij  (B = d^2 e / d d^2 of the pair; no atomics),
+ * ss[mol][3 x + y][3 p + q] += sum_pairs d_x (B d'_pq)_y / 2 (each row owns half of each of its pairs), and, when virial is
+ * not NULL, virial[mol][3 x + y] += sum_pairs (d e / d d)_y d_x / 2 = d E / d S_xy; mol = i / atoms_per_mol.  A periodic
+ * image of atom i itself does contribute here.  Symmetric rows only. */
+int anihip_pair_analytic_hvp_strain(void *stream, int32_t kind, int64_t n_atoms, int64_t atoms_per_mol, int64_t lo,
+                                    int64_t hi, const int32_t *species, const uint32_t *meta, const float *ent,
+                                    const float *pair_table, const float *extra, float cutoff, int32_t cutoff_kind,
+                                    int32_t flags, float *out, double *ss, double *virial);
+
 /* Lowest normal modes of block-sparse Hessians (grad.sparse_vibrational_analysis): the operator
  *   A = M^-1/2 ((H + H^T) / 2) M^-1/2
  * of a tuples.BlockHessian in a layout of its own (csrc/hess_modes.hip).

@@ -3,6 +3,7 @@ loop of grad.forces_and_hessians) on fixtures of tests/golden: device-synchronis
 
     python tools/hessian_bench.py [--runs 5] [--autograd-max 264] [--bases ch4_ani1x,dense90_ani2x,...]
                                   [--kind fixture|ani2xr|anir2s] [--sparse [--dense-max 1000] [--modes 10,50]]
+                                  [--strain [--strain-budgets 4,16]]
 
 Prints one JSON line per case.  Seeded parameters (the fixtures' seeds): timings do not depend on the values.
 ``--kind ani2xr`` / ``anir2s`` times that architecture (networks plus the xTB repulsion term) on the fixtures'
@@ -11,7 +12,10 @@ coordinates instead of the fixture's own ANI-2x / ANI-1x model.  ``--sparse`` ti
 ``--dense-max`` atoms), with the fixture's cell and pbc, the number of stored blocks and the peak device memory of each.
 ``--modes K[,K2..]`` adds grad.sparse_vibrational_analysis on that sparse Hessian: solver time and iterations for each K,
 the time per call of anihip_block_hessian_spmm at m = 1, 8, 32, 64 beside m calls of BlockHessian.matvec, and (up to
-``--dense-max`` atoms) the dense route: to_dense, mass weighting and fp64 torch.linalg.eigh."""
+``--dense-max`` atoms) the dense route: to_dense, mass weighting and fp64 torch.linalg.eigh.  ``--strain`` times
+grad.energies_forces_and_strain_hessians with the fixture's cell and pbc: peak device memory, the number of atom chunks
+under the default budget (grad.HESSIAN_BUDGET_BYTES) and, with ``--strain-budgets 4,16`` (GiB), the same call under larger
+budgets."""
 from __future__ import annotations
 
 import argparse
@@ -99,6 +103,8 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="block-sparse path beside the dense one")
     ap.add_argument("--dense-max", type=int, default=1000, help="--sparse: largest system the dense path is timed on")
     ap.add_argument("--modes", default="", help="--sparse: lowest normal modes, K[,K2..] of them")
+    ap.add_argument("--strain", action="store_true", help="strain second derivatives instead of coordinate Hessians")
+    ap.add_argument("--strain-budgets", default="", help="--strain: also time under these chunk budgets [GiB]")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for base in args.bases.split(","):
@@ -118,6 +124,29 @@ def main():
         x = torch.from_numpy(g["coords"]).to(dev)
         A = int((sp >= 0).sum())
         row = {"case": base, "model": g["kind"] if args.kind == "fixture" else args.kind, "atoms": A}
+        if args.strain:
+            cell = None if g["cell"] is None else torch.from_numpy(g["cell"]).to(dev)
+            pbc = None if g["pbc"] is None else torch.from_numpy(np.asarray(g["pbc"])).to(dev)
+            runs = max(1, args.runs if A < 5000 else 3)
+            L_aev = model.aev_computer.engine().L
+            row_bytes = model.neural_networks._pack(dev).rows_hvp_row_bytes(sp.numel())
+            default = grad.HESSIAN_BUDGET_BYTES
+            for gib in [None] + [float(b) for b in args.strain_budgets.split(",") if b]:
+                budget = default if gib is None else int(gib * 2**30)
+                grad.HESSIAN_BUDGET_BYTES = budget
+                try:
+                    key = "strain" if gib is None else f"strain_{gib:g}gib"
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    grad.energies_forces_and_strain_hessians(model, sp, x, cell=cell, pbc=pbc)
+                    row[key + "_peak_gib"] = round(torch.cuda.max_memory_allocated() / 2**30, 3)
+                    row[key + "_chunks"] = -(-A // grad.strain_hessian_chunk_atoms(L_aev, row_bytes, budget))
+                    row[key + "_ms"], row[key + "_runs"] = timed(
+                        lambda: grad.energies_forces_and_strain_hessians(model, sp, x, cell=cell, pbc=pbc), runs)
+                finally:
+                    grad.HESSIAN_BUDGET_BYTES = default
+            print(json.dumps(row), flush=True)
+            continue
         if args.sparse:
             cell = None if g["cell"] is None else torch.from_numpy(g["cell"]).to(dev)
             pbc = None if g["pbc"] is None else torch.from_numpy(np.asarray(g["pbc"])).to(dev)

@@ -233,6 +233,14 @@ def lib() -> C.CDLL:
                  "anihip_hess_sparse_extract", "anihip_aev_jvp_items", "anihip_aev_backward_second_items",
                  "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items"):
         getattr(L, name).restype = C.c_int
+    L.anihip_aev_jvp_strain_items.argtypes = [vp, C.POINTER(AevParams), vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.anihip_aev_backward_second_strain_items.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, vp, vp, vp, vp, i64, vp, vp,
+                                                          vp, vp, vp]
+    L.anihip_pair_analytic_hvp_strain.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, C.c_float, i32, i32, vp, vp,
+                                                  vp]
+    for name in ("anihip_aev_jvp_strain_items", "anihip_aev_backward_second_strain_items",
+                 "anihip_pair_analytic_hvp_strain"):
+        getattr(L, name).restype = C.c_int
     L.anihip_block_hessian_prepare.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.anihip_block_hessian_prepare.restype = C.c_int
     L.anihip_block_hessian_spmm.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
@@ -265,6 +273,7 @@ EXPORTED_SYMBOLS = [
     "anihip_aev_jvp_items", "anihip_aev_backward_second_items", "anihip_mlp_rows_hvp_workspace_bytes",
     "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items",
     "anihip_block_hessian_prepare", "anihip_block_hessian_spmm",
+    "anihip_aev_jvp_strain_items", "anihip_aev_backward_second_strain_items", "anihip_pair_analytic_hvp_strain",
 ]
 
 

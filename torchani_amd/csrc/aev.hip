@@ -1602,6 +1602,9 @@ int aev_jvp_generic_dirs(hipStream_t stream, const anihip_aev_params *p, const f
 int aev_jvp_generic_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                           const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
                           const int32_t *row_dir, float *daev);
+int aev_jvp_generic_strain_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+                                 const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
+                                 const int32_t *row_dir, float *daev);
 int aev_backward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                          const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
                          float *grad_coords, double *virial, bool fixed);
@@ -1834,6 +1837,17 @@ extern "C" int anihip_aev_jvp_items(void *stream, const anihip_aev_params *p, co
     ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
     if (n_rows == 0) return 0;
     return aev_jvp_generic_items((hipStream_t)stream, p, table, 0, n_rows, species, meta, ent, row_atom, row_dir, daev);
+}
+
+extern "C" int anihip_aev_jvp_strain_items(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                                           const int32_t *species, const uint32_t *meta, const float *ent, int64_t n_rows,
+                                           const int32_t *row_atom, const int32_t *row_dir, float *daev)
+{
+    ANIHIP_REQUIRE(p && table && species && meta && ent && row_atom && row_dir && daev, "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
+    if (n_rows == 0) return 0;
+    return aev_jvp_generic_strain_items((hipStream_t)stream, p, table, 0, n_rows, species, meta, ent, row_atom, row_dir,
+                                        daev);
 }
 
 static int aev_backward(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo,

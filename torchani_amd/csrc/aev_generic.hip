@@ -117,7 +117,9 @@ __device__ __forceinline__ void gen_stage_row(const GenArgs &a, const GenHdr &h,
 // species (pair) flags every slab it overlaps); the networks' layer 0 skips the slabs no atom of a tile flags.
 // ITEMS (anihip_aev_jvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi instead of atoms: central
 // atom row_atom[q], output row q, and the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), zero elsewhere.
-template <bool JVP, bool ITEMS = false>
+// STRAIN (anihip_aev_jvp_strain_items, strain second derivatives; item rows): row_dir[q] = 3 a + b names the strain
+// direction S_ab, and every entry moves with its own displacement, d' = d_a e_b, whatever its periodic image.
+template <bool JVP, bool ITEMS = false, bool STRAIN = false>
 __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const float *__restrict__ tab, int64_t lo,
                                                                 int64_t hi, const int32_t *__restrict__ species,
                                                                 const uint32_t *__restrict__ meta,
@@ -128,6 +130,7 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
                                                                 const int32_t *__restrict__ row_dir = nullptr)
 {
     static_assert(JVP || !ITEMS, "item rows are JVP rows");
+    static_assert(ITEMS || !STRAIN, "strain rows are item rows");
     if (JVP && !ITEMS) {   // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y
         tangent += (size_t)blockIdx.y * dir_t;
         aev += (size_t)blockIdx.y * dir_o;
@@ -165,7 +168,14 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
             for (int e = lane; e < h.nA + h.nF; e += WAVE) {
                 const size_t jn = (size_t)st.jat[e];
                 const float4 U = st.ur[e];
-                const float dx = tang(jn, 0) - tix, dy = tang(jn, 1) - tiy, dz = tang(jn, 2) - tiz;
+                float dx, dy, dz;
+                if (STRAIN) {   // d' = d_a e_b: component a of the entry's displacement, moved along b
+                    const float4 d = ent[h.start + e];
+                    const float s = da == 0 ? d.x : (da == 1 ? d.y : d.z);
+                    dx = dc == 0 ? s : 0.f; dy = dc == 1 ? s : 0.f; dz = dc == 2 ? s : 0.f;
+                } else {
+                    dx = tang(jn, 0) - tix; dy = tang(jn, 1) - tiy; dz = tang(jn, 2) - tiz;
+                }
                 const float rd = U.x * dx + U.y * dy + U.z * dz, ir = 1.0f / U.w;
                 td[e] = make_float4((dx - U.x * rd) * ir, (dy - U.y * rd) * ir, (dz - U.z * rd) * ir, rd);
             }
@@ -508,6 +518,22 @@ int aev_jvp_generic_items(hipStream_t stream, const anihip_aev_params *p, const 
     if (hi == lo) return 0;
     const dim3 grid(gen_blocks(hi - lo)), block(GEN_WPB * WAVE);
     hipLaunchKernelGGL((k_aev_fwd_gen<true, true>), grid, block, 0, stream, a, table, lo, hi, species, meta,
+                       (const float4 *)ent, daev, (const float *)nullptr, (uint32_t *)nullptr, (int64_t)0, (int64_t)0,
+                       row_atom, row_dir);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// strain item rows lo <= q < hi (anihip_aev_jvp_strain_items): daev [q][L] = d aev_{row_atom[q]} / d S_ab, row_dir[q] = 3 a + b
+int aev_jvp_generic_strain_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+                                 const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
+                                 const int32_t *row_dir, float *daev)
+{
+    GenArgs a;
+    if (int rc = gen_args(p, &a)) return rc;
+    if (hi == lo) return 0;
+    const dim3 grid(gen_blocks(hi - lo)), block(GEN_WPB * WAVE);
+    hipLaunchKernelGGL((k_aev_fwd_gen<true, true, true>), grid, block, 0, stream, a, table, lo, hi, species, meta,
                        (const float4 *)ent, daev, (const float *)nullptr, (uint32_t *)nullptr, (int64_t)0, (int64_t)0,
                        row_atom, row_dir);
     ANIHIP_CHECK_HIP(hipGetLastError());

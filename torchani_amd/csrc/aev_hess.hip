@@ -115,7 +115,13 @@ __device__ __forceinline__ int hess_triu(int S, int a, int b) { return a * S - (
 // ITEMS (anihip_aev_backward_second_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi: central
 // atom row_atom[q], dgrad row q, the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), output slab
 // row_dir[q] - dir0 of out [n_dir][n_atoms][3]; blockIdx.y = 0.
-template <bool ITEMS>
+// STRAIN (anihip_aev_backward_second_strain_items, strain second derivatives; item rows, n_slabs = 9): row_dir[q] = 3 a + b
+// names the strain direction S_ab and the output slab, every entry moves with d' = d_a e_b (replacing t_j - t_i), and the
+// row also adds sum_e d_{e,x} g_{e,y} -- g = the tangent part of d E_i / d d_e, i.e. the derivative of the row's virial
+// along S_ab -- to ss[i / atoms_per_mol][3 x + y][3 a + b] (one wave sum per component, one fp64 atomic per component and
+// row).  The mode has no tangent array and no slab offset: `tangent` carries ss (double [C][9][9]) and `dir0` carries
+// atoms_per_mol, so that the kernel's signature, and with it the code of the other instantiations, stays as it was.
+template <bool ITEMS, bool STRAIN = false>
 __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const float *__restrict__ tab, int64_t n_atoms,
                                                              int64_t lo, int64_t hi, const int32_t *__restrict__ species,
                                                              const uint32_t *__restrict__ meta,
@@ -127,6 +133,7 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
                                                              const int32_t *__restrict__ row_dir, int64_t dir0,
                                                              int64_t n_slabs)
 {
+    static_assert(ITEMS || !STRAIN, "strain rows are item rows");
     __shared__ float4 s_u[HESS_WPB][MAXR];     // unit vector, r
     __shared__ float4 s_ud[HESS_WPB][MAXR];    // its derivative along the direction: u', r'
     __shared__ float4 s_fcr[HESS_WPB][MAXR];   // radial envelope fc, fc', fc''
@@ -139,6 +146,8 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
     float *gx = s_g[wib][0], *gy = s_g[wib][1], *gz = s_g[wib][2];
     const int64_t dir = blockIdx.y;
     const float *tg = ITEMS ? nullptr : tangent + (size_t)dir * 3 * n_atoms;
+    double *ss = STRAIN ? reinterpret_cast<double *>(const_cast<float *>(tangent)) : nullptr;
+    const int64_t atoms_per_mol = STRAIN ? dir0 : 1;
     const float *dg = ITEMS ? dgrad : dgrad + (size_t)dir * n_atoms * a.L;
     float *o = out + (size_t)dir * 3 * n_atoms;
     const int64_t nw = (int64_t)gridDim.x * HESS_WPB;
@@ -152,7 +161,7 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
         int64_t da = -1;   // ITEMS: t = e_dc on atom da
         int dc = 0;
         if (ITEMS) {
-            const int64_t slab = row_dir[q] - dir0;
+            const int64_t slab = row_dir[q] - (STRAIN ? 0 : dir0);
             if (slab < 0 || slab >= n_slabs) continue;   // (a row outside the caller's slabs)
             da = row_dir[q] / 3;
             dc = row_dir[q] - 3 * (int)da;
@@ -168,7 +177,13 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
             const float r = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z), ir = 1.0f / r;
             const float ux = d.x * ir, uy = d.y * ir, uz = d.z * ir;
             const int jn = (int)(__float_as_uint(d.w) & IDX_MASK);
-            const float dx = tang(jn, 0) - tix, dy = tang(jn, 1) - tiy, dz = tang(jn, 2) - tiz;
+            float dx, dy, dz;
+            if (STRAIN) {   // d' = d_a e_b (a = da, b = dc)
+                const float sa = da == 0 ? d.x : (da == 1 ? d.y : d.z);
+                dx = dc == 0 ? sa : 0.f; dy = dc == 1 ? sa : 0.f; dz = dc == 2 ? sa : 0.f;
+            } else {
+                dx = tang(jn, 0) - tix; dy = tang(jn, 1) - tiy; dz = tang(jn, 2) - tiz;
+            }
             const float rd = ux * dx + uy * dy + uz * dz;
             su[e] = make_float4(ux, uy, uz, r);
             sud[e] = make_float4((dx - ux * rd) * ir, (dy - uy * rd) * ir, (dz - uz * rd) * ir, rd);
@@ -267,11 +282,31 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
         }
         wave_sync();
         // ---- push: every neighbor its sum, the central atom minus the total ----
+        float vs[STRAIN ? 9 : 1];   // STRAIN: this lane's part of sum_e d_x g_y, component 3 x + y
+#pragma unroll
+        for (int c = 0; c < (STRAIN ? 9 : 1); ++c) vs[c] = 0.f;
         for (int e = lane; e < nR; e += WAVE) {
             const size_t jn = (size_t)sj[e];
             atomicAdd(o + 3 * jn, gx[e]);
             atomicAdd(o + 3 * jn + 1, gy[e]);
             atomicAdd(o + 3 * jn + 2, gz[e]);
+            if (STRAIN) {
+                const float4 d = ent[h.start + e];
+                const float dd[3] = {d.x, d.y, d.z}, gg[3] = {gx[e], gy[e], gz[e]};
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+#pragma unroll
+                    for (int y = 0; y < 3; ++y) vs[(STRAIN ? 3 * x + y : 0)] += dd[x] * gg[y];
+            }
+        }
+        if (STRAIN) {   // lane c < 9 keeps the row's component c and adds it to ss[mol][c][row direction]
+            float mine = 0.f;
+#pragma unroll
+            for (int c = 0; c < (STRAIN ? 9 : 1); ++c) {
+                const float t = wave_sum(vs[c]);
+                if (lane == c) mine = t;
+            }
+            if (lane < 9) atomicAdd(ss + (size_t)(i / atoms_per_mol) * 81 + 9 * lane + row_dir[q], (double)mine);
         }
         const float tx = wave_sum(ox), ty = wave_sum(oy), tz = wave_sum(oz);
         if (lane == 0) {
@@ -350,6 +385,42 @@ extern "C" int anihip_aev_backward_second_items(void *stream, const anihip_aev_p
     hipLaunchKernelGGL(k_aev_bwd2<true>, dim3((unsigned)b), dim3(HESS_WPB * WAVE), 0, (hipStream_t)stream, a, table, n_atoms,
                        (int64_t)0, n_rows, species, meta, (const float4 *)ent, grad_aev, (const float *)nullptr, dgrad, out,
                        row_atom, row_dir, dir0, n_dir);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_aev_backward_second_strain_items(void *stream, const anihip_aev_params *p, const float *table,
+                                                       int64_t n_atoms, int64_t atoms_per_mol, const int32_t *species,
+                                                       const uint32_t *meta, const float *ent, const float *grad_aev,
+                                                       int64_t n_rows, const int32_t *row_atom, const int32_t *row_dir,
+                                                       const float *dgrad, float *out, double *ss)
+{
+    ANIHIP_REQUIRE(p && table && species && meta && ent && grad_aev && row_atom && row_dir && dgrad && out && ss,
+                   "null pointer argument");
+    ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
+    ANIHIP_REQUIRE(atoms_per_mol >= 1 && n_atoms % atoms_per_mol == 0,
+                   "atoms_per_mol must be >= 1 and divide n_atoms (got %lld, %lld)", (long long)atoms_per_mol,
+                   (long long)n_atoms);
+    ANIHIP_REQUIRE(p->num_species >= 1 && p->num_species <= MAX_S - 1, "num_species must be 1..7");
+    ANIHIP_REQUIRE(p->n_shf_r >= 1 && p->n_shf_r <= 32 && p->n_shf_a >= 1 && p->n_shf_a <= 16 && p->n_shf_z >= 1 &&
+                       p->n_shf_z <= 16,
+                   "symmetry-function grid outside n_shf_r <= 32, n_shf_a <= 16, n_shf_z <= 16 (got %d, %d x %d)",
+                   p->n_shf_r, p->n_shf_a, p->n_shf_z);
+    ANIHIP_REQUIRE(p->cutoff_kind == ANIHIP_CUTOFF_COSINE || p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH,
+                   "cutoff_kind must be ANIHIP_CUTOFF_COSINE or ANIHIP_CUTOFF_SMOOTH");
+    if (n_rows == 0) return 0;
+    HessArgs a;
+    a.S = p->num_species;
+    a.nR = p->n_shf_r; a.nA = p->n_shf_a; a.nZ = p->n_shf_z;
+    a.radlen = a.S * a.nR;
+    a.L = a.radlen + (a.S * (a.S + 1) / 2) * a.nA * a.nZ;
+    a.Rcr = p->Rcr; a.Rca = p->Rca; a.EtaR = p->EtaR; a.EtaA = p->EtaA; a.Zeta = p->Zeta;
+    a.smooth = p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH;
+    int64_t b = (n_rows + HESS_WPB - 1) / HESS_WPB;
+    if (b > 4096) b = 4096;
+    hipLaunchKernelGGL((k_aev_bwd2<true, true>), dim3((unsigned)b), dim3(HESS_WPB * WAVE), 0, (hipStream_t)stream, a, table,
+                       n_atoms, (int64_t)0, n_rows, species, meta, (const float4 *)ent, grad_aev,
+                       reinterpret_cast<const float *>(ss), dgrad, out, row_atom, row_dir, atoms_per_mol, (int64_t)9);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

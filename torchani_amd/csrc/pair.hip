@@ -214,7 +214,16 @@ constexpr int HVP_ROUNDS = (MAXR + WAVE - 1) / WAVE;
 // ITEMS (anihip_pair_analytic_hvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi: central atom
 // row_atom[q], ONE direction, the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), output slab row_dir[q] - dir0
 // of out [n_dir][n_atoms][3] (an item row names each (direction, atom) once: still no atomics).
-template <int KIND, bool ITEMS = false>
+// STRAIN (anihip_pair_analytic_hvp_strain, strain second derivatives): central atoms lo <= i < hi, the n_dir = 9 strain
+// directions S_ab (k = 3 a + b), each pair moving with d' = d_a e_b:  out[k][i] += -sum_j B_ij d'_ij (no atomics).  Each lane
+// also keeps, over its pairs, M_xp = sum d_x d_p a / 2 (the pair virial) and the fully symmetric
+// T_xypq = sum c r^2 u_x u_y u_p u_q / 2 (6 + 15 numbers); the strain-strain term
+//   ss[mol][3 x + y][3 p + q] += sum_pairs d_x (B d'_pq)_y / 2 = delta_yq M_xp + T_xypq
+// and virial[mol][3 x + y] += M_xy are added per molecule (mol = i / atoms_per_mol) with one wave reduction and fp64 atomics
+// whenever the wave's molecule changes.  The mode has no tangent array and no item rows: `tangent` carries ss (double
+// [C][9][9]), `row_atom` carries virial (double [C][9] or null) and `dir0` carries atoms_per_mol, so that the kernel's
+// signature, and with it the code of the other instantiations, stays as it was.
+template <int KIND, bool ITEMS = false, bool STRAIN = false>
 __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, int64_t hi,
                                                   const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
                                                   const float4 *__restrict__ ent, const float *__restrict__ tab,
@@ -223,12 +232,55 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
                                                   const int32_t *__restrict__ row_atom = nullptr,
                                                   const int32_t *__restrict__ row_dir = nullptr, int64_t dir0 = 0)
 {
+    static_assert(!(ITEMS && STRAIN), "strain directions run over the central atoms");
     const int lane = lane_id();
     const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
     const size_t stride = (size_t)n_atoms * 3;
     const float inv_rc = 1.0f / cutoff, rev_rc = 0.5f / cutoff, pi_rc = 3.14159265358979f / cutoff;
+    double *ss = STRAIN ? reinterpret_cast<double *>(const_cast<float *>(tangent)) : nullptr;
+    double *virial = STRAIN ? reinterpret_cast<double *>(const_cast<int32_t *>(row_atom)) : nullptr;
+    const int64_t atoms_per_mol = STRAIN ? dir0 : 1;
+    constexpr int NS = STRAIN ? 21 : 1;
+    float sm[NS];   // STRAIN: M (6, pairs x <= p) then T (15, by the powers of x and y)
+    if (STRAIN) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) sm[c] = 0.f;
+    }
+    int64_t mol = -1;
+    auto flush = [&]() {   // (wave-uniform) the lane partials of molecule `mol` into ss / virial, then zero them
+#pragma unroll
+        for (int c = 0; c < NS; ++c) sm[c] = wave_sum(sm[c]);
+        for (int l = lane; l < 81; l += WAVE) {   // (81 components over the 64 lanes)
+            const int xy = l / 9, pq = l - 9 * xy;
+            const int x = xy / 3, y = xy - 3 * x, pp = pq / 3, qq = pq - 3 * pp;
+            const int lo_ = min(x, pp), hi_ = max(x, pp);
+            const int im = lo_ * 3 - (lo_ * (lo_ - 1)) / 2 + (hi_ - lo_);
+            const int nx = (x == 0) + (y == 0) + (pp == 0) + (qq == 0), ny = (x == 1) + (y == 1) + (pp == 1) + (qq == 1);
+            const int it = nx * 5 - (nx * (nx - 1)) / 2 + ny;
+            float mv = 0.f, tv = 0.f;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) mv = c == im ? sm[c] : mv;
+#pragma unroll
+            for (int c = 0; c < 15; ++c) tv = c == it ? sm[(STRAIN ? 6 + c : 0)] : tv;
+            atomicAdd(ss + (size_t)mol * 81 + l, (double)((y == qq ? mv : 0.f) + tv));
+            if (virial && pq == 0) {   // (l = 0, 9, .., 72: component xy of the virial = M_xy)
+                const int lm = min(x, y), hm = max(x, y);
+                const int iv = lm * 3 - (lm * (lm - 1)) / 2 + (hm - lm);
+                float vv = 0.f;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) vv = c == iv ? sm[c] : vv;
+                atomicAdd(virial + (size_t)mol * 9 + xy, (double)vv);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NS; ++c) sm[c] = 0.f;
+    };
     for (int64_t qi = lo + blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); qi < hi; qi += nw) {
         const int64_t i = ITEMS ? (int64_t)row_atom[qi] : qi;
+        if (STRAIN && i / atoms_per_mol != mol) {
+            if (mol >= 0) flush();
+            mol = i / atoms_per_mol;
+        }
         const int si = species[i];
         if (si < 0) continue;
         int64_t da = -1, slab = 0;   // ITEMS: t = e_dc on atom da, written to slab
@@ -243,10 +295,12 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
         const int nR = (int)(c & 0xFFFFu) + (int)(c >> 16);
         for (int b0 = 0; b0 < nR; b0 += HVP_ROUNDS * WAVE) {   // (one pass for every row of at most ANIHIP_MAX_RAD entries)
             float ba[HVP_ROUNDS], bc[HVP_ROUNDS], ux[HVP_ROUNDS], uy[HVP_ROUNDS], uz[HVP_ROUNDS];
+            float rr[STRAIN ? HVP_ROUNDS : 1];   // STRAIN: r (d = r u)
             int jj[HVP_ROUNDS];   // (atom indices have 28 bits: IDX_MASK)
 #pragma unroll
             for (int q = 0; q < HVP_ROUNDS; ++q) {
                 ba[q] = 0.f; bc[q] = 0.f; ux[q] = 0.f; uy[q] = 0.f; uz[q] = 0.f;
+                if (STRAIN) rr[(STRAIN ? q : 0)] = 0.f;
                 jj[q] = (int)i;   // (an empty slot gathers v_i and adds B (v_i - v_i) with B = 0)
                 const int k = b0 + q * WAVE + lane;
                 if (k >= nR) continue;
@@ -270,11 +324,29 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
                 bc[q] = e2 - ba[q];
                 ux[q] = d.x * inv; uy[q] = d.y * inv; uz[q] = d.z * inv;
                 jj[q] = j;
+                if (STRAIN) {
+                    rr[(STRAIN ? q : 0)] = r;
+                    const float w1 = 0.5f * ba[q] * r * r, w2 = 0.5f * bc[q] * r * r;
+                    const float u3[3] = {ux[q], uy[q], uz[q]};
+                    int c = 0;
+#pragma unroll
+                    for (int x = 0; x < 3; ++x)
+#pragma unroll
+                        for (int pp = x; pp < 3; ++pp) sm[(STRAIN ? c++ : 0)] += w1 * u3[x] * u3[pp];
+                    const float px[5] = {1.f, ux[q], ux[q] * ux[q], ux[q] * ux[q] * ux[q], ux[q] * ux[q] * ux[q] * ux[q]};
+                    const float py[5] = {1.f, uy[q], uy[q] * uy[q], uy[q] * uy[q] * uy[q], uy[q] * uy[q] * uy[q] * uy[q]};
+                    const float pz[5] = {1.f, uz[q], uz[q] * uz[q], uz[q] * uz[q] * uz[q], uz[q] * uz[q] * uz[q] * uz[q]};
+#pragma unroll
+                    for (int nx = 0; nx <= 4; ++nx)
+#pragma unroll
+                        for (int ny = 0; ny <= 4 - nx; ++ny) sm[(STRAIN ? c++ : 0)] += w2 * px[nx] * py[ny] * pz[4 - nx - ny];
+                }
             }
             for (int64_t kd = 0; kd < (ITEMS ? 1 : n_dir); ++kd) {
                 const float *tk = ITEMS ? nullptr : tangent + (size_t)kd * stride;
                 auto tang = [&](int64_t n, int k) {
                     if (ITEMS) return n == da && k == dc ? 1.0f : 0.0f;
+                    if (STRAIN) return 0.0f;   // (no tangent array)
                     return tk[3 * n + k];
                 };
                 const float vx = tang(i, 0), vy = tang(i, 1), vz = tang(i, 2);
@@ -282,7 +354,14 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
 #pragma unroll
                 for (int q = 0; q < HVP_ROUNDS; ++q) {
                     if (b0 + q * WAVE >= nR) break;   // (wave-uniform)
-                    const float dx = vx - tang(jj[q], 0), dy = vy - tang(jj[q], 1), dz = vz - tang(jj[q], 2);
+                    float dx, dy, dz;
+                    if (STRAIN) {   // t_i - t_j = -d' = -d_a e_b, direction kd = 3 a + b
+                        const int sa = (int)kd / 3, sb = (int)kd - 3 * sa;
+                        const float m = -(sa == 0 ? ux[q] : (sa == 1 ? uy[q] : uz[q])) * rr[(STRAIN ? q : 0)];
+                        dx = sb == 0 ? m : 0.f; dy = sb == 1 ? m : 0.f; dz = sb == 2 ? m : 0.f;
+                    } else {
+                        dx = vx - tang(jj[q], 0); dy = vy - tang(jj[q], 1); dz = vz - tang(jj[q], 2);
+                    }
                     const float cu = bc[q] * (ux[q] * dx + uy[q] * dy + uz[q] * dz);
                     hx += ba[q] * dx + cu * ux[q];
                     hy += ba[q] * dy + cu * uy[q];
@@ -296,6 +375,7 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
             }
         }
     }
+    if (STRAIN && mol >= 0) flush();
 }
 
 // ---- DFT-D3(BJ) two-body dispersion (potentials/dftd3.py:113-330) -------------------------------------------------
@@ -621,6 +701,47 @@ extern "C" int anihip_pair_analytic_hvp_items(void *stream, int32_t kind, int64_
     hipLaunchKernelGGL((k_pair_hvp<K, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_atoms,       \
                        (int64_t)0, n_rows, species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r,   \
                        n_dir, (const float *)nullptr, out, row_atom, row_dir, dir0)
+    switch (kind) {
+        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
+        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;
+        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_LJ); break;
+        default: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_COULOMB); break;
+    }
+#undef ANIHIP_LAUNCH_PAIR_HVP
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_pair_analytic_hvp_strain(void *stream, int32_t kind, int64_t n_atoms, int64_t atoms_per_mol, int64_t lo,
+                                               int64_t hi, const int32_t *species, const uint32_t *meta, const float *ent,
+                                               const float *pair_table, const float *extra, float cutoff,
+                                               int32_t cutoff_kind, int32_t flags, float *out, double *ss, double *virial)
+{
+    ANIHIP_REQUIRE(species && meta && ent && pair_table && out && ss, "null pointer argument");
+    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
+    ANIHIP_REQUIRE(atoms_per_mol >= 1 && n_atoms % atoms_per_mol == 0,
+                   "atoms_per_mol must be >= 1 and divide n_atoms (got %lld, %lld)", (long long)atoms_per_mol,
+                   (long long)n_atoms);
+    ANIHIP_REQUIRE(n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
+    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
+    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
+    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
+    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
+    ANIHIP_REQUIRE(!(flags & ANIHIP_PAIR_PUSH),
+                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    if (hi == lo) return 0;
+    int64_t blocks = (hi - lo + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    PairExtra x{};
+    if (extra)
+        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
+    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
+    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
+#define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
+    hipLaunchKernelGGL((k_pair_hvp<K, false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,        \
+                       n_atoms, lo, hi, species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r,      \
+                       (int64_t)9, reinterpret_cast<const float *>(ss), out, reinterpret_cast<const int32_t *>(virial),   \
+                       (const int32_t *)nullptr, atoms_per_mol)
     switch (kind) {
         case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
         case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;

@@ -559,6 +559,37 @@ class AevEngine:
             _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, _ptr(species), _ptr(nbrs.meta),
             _ptr(nbrs.ent), _ptr(grad_aev), R, _ptr(row_atom), _ptr(row_dir), dir0, out.shape[0], _ptr(dgrad), _ptr(out)))
 
+    def jvp_strain_items(self, species: Tensor, nbrs: NeighborRows, row_atom: Tensor, row_dir: Tensor) -> Tensor:
+        """daev [R, L] over strain item rows (anihip_aev_jvp_strain_items): row q = d aev_{row_atom[q]} / d S_ab,
+        row_dir[q] = 3 a + b (x -> x S, cell -> cell S)."""
+        _require_cuda(species, row_atom, row_dir)
+        n = species.numel()
+        R = row_atom.numel()
+        out = torch.empty((R, self.L), dtype=torch.float32, device=species.device)
+        _lib.check(_lib.lib().anihip_aev_jvp_strain_items(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, _ptr(species), _ptr(nbrs.meta),
+            _ptr(nbrs.ent), R, _ptr(row_atom), _ptr(row_dir), _ptr(out)))
+        return out
+
+    def backward_second_strain_items(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor, row_atom: Tensor,
+                                     row_dir: Tensor, dgrad: Tensor, out: Tensor, ss: Tensor) -> None:
+        """out [9, N, 3] += the strained-frame mixed derivative of the rows' atoms, ss [C, 9, 9] (float64) += their
+        strain-strain contraction (anihip_aev_backward_second_strain_items); dgrad [R, L] = H_net J d' of the rows."""
+        _require_cuda(species, grad_aev, row_atom, row_dir, dgrad, out, ss)
+        if not nbrs.symmetric:
+            raise NotImplementedError("second derivatives need symmetric neighbor rows (the library's own builders)")
+        n = species.numel()
+        R = row_atom.numel()
+        grad_aev = grad_aev.detach().to(torch.float32).contiguous()
+        assert grad_aev.numel() == n * self.L
+        assert dgrad.dtype == torch.float32 and dgrad.is_contiguous() and dgrad.numel() == R * self.L
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (9, n, 3)
+        assert ss.dtype == torch.float64 and ss.is_contiguous() and ss.shape[1:] == (9, 9) and n % ss.shape[0] == 0
+        _lib.check(_lib.lib().anihip_aev_backward_second_strain_items(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, n // ss.shape[0], _ptr(species),
+            _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(grad_aev), R, _ptr(row_atom), _ptr(row_dir), _ptr(dgrad), _ptr(out),
+            _ptr(ss)))
+
     def backward(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor,
                  grad_coords: tp.Optional[Tensor] = None, shard_rows: bool = False,
                  virial: tp.Optional[Tensor] = None, slab_mask: tp.Optional[Tensor] = None,

@@ -10,6 +10,9 @@ Hessians with respect to the coordinates (grad.py:86-150,239-260) come in two fo
   of all molecules in chunks of K (``hessian_chunk_size``, from a fixed memory budget) through the same three kernels.
 * ``energies_forces_and_sparse_hessians``: the block-sparse path for large systems (``tuples.BlockHessian``) -- each unit
   direction is worked only on the central atoms whose AEV it moves, and only the blocks inside the cutoff pattern are kept.
+* ``energies_forces_and_strain_hessians``: second derivatives with respect to the strain (x -> x S, cell -> cell S) -- the
+  strain-strain block, the internal-strain tensor and the per-molecule virial, from 9 strain directions whatever the
+  number of atoms; ``elastic_constants`` turns them into clamped- or relaxed-ion elastic constants.
 
 The closed-form pair potentials (xTB repulsion, ZBL, Lennard-Jones, fixed-charge Coulomb / MNOK: ANI-2xr, ANI-r2s and
 models built with ``add_pair_potential``) add their Hessian-vector products (anihip_pair_analytic_hvp) on both paths, and a
@@ -28,8 +31,8 @@ import typing as tp
 import torch
 from torch import Tensor
 
-from .tuples import (BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians, ForcesHessians,
-                     SparseVibAnalysis, VibAnalysis)
+from .tuples import (BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians,
+                     EnergiesForcesStrainHessians, ForcesHessians, SparseVibAnalysis, VibAnalysis)
 from . import units as _units
 
 
@@ -328,6 +331,192 @@ def energies_forces_and_sparse_hessians(model, species: Tensor, coordinates: Ten
                     pot.hvp_items(species32, nbrs, row_atom, row_dir, 3 * n0, scratch)
                 hessian_extract(pat, n0, n1, scratch, blocks)
     return EnergiesForcesSparseHessians(ef.energies, ef.forces, BlockHessian(pat.index, blocks, Cn, A))
+
+
+def strain_hessian_chunk_atoms(aev_len: int, hvp_row_bytes: int, budget: int = HESSIAN_BUDGET_BYTES) -> int:
+    """Atoms per chunk of energies_forces_and_strain_hessians (9 item rows each) from the memory budget: per row its
+    row_atom / row_dir, J d', H_net J d' and the gathered d E / d aev (aev_len floats each) and the network HVP workspace."""
+    return int(max(1, budget // (9 * (8 + 12 * aev_len + hvp_row_bytes))))
+
+
+def energies_forces_and_strain_hessians(model, species: Tensor, coordinates: Tensor, *, cell: tp.Optional[Tensor] = None,
+                                        pbc: tp.Optional[Tensor] = None) -> EnergiesForcesStrainHessians:
+    """EnergiesForcesStrainHessians(energies, forces, virial, strain_hessians, internal_strain) of a model: the second
+    derivatives of E(x S, cell S) with respect to the strain S (coordinates are row vectors; x -> x S, cell -> cell S) at
+    S = I, per molecule:
+
+    * virial [C, 3, 3] = d E_c / d S_ab;
+    * strain_hessians [C, 3, 3, 3, 3] = d^2 E_c / d S_ab d S_pq, all 81 components (rotations included);
+    * internal_strain [C, A, 3, 3, 3] = d^2 E_c / d x_iy d S_ab, x the unstrained coordinates.
+
+    Only 9 directions, whatever the number of atoms: the item rows (k, i), k = 3 a + b in 0 .. 8 over every real atom i,
+    run through anihip_aev_jvp_strain_items, anihip_mlp_rows_hvp (activations computed once per call) and
+    anihip_aev_backward_second_strain_items, in chunks of atoms (rows of a species contiguous) holding at most
+    HESSIAN_BUDGET_BYTES of row buffers; each enabled closed-form pair potential adds anihip_pair_analytic_hvp_strain on the
+    rows its forward uses.  The kernels give the strained-frame mixed derivative K; internal_strain adds
+    delta_ya (d E / d x_i)_b from the forces.  Molecules without a cell are allowed (S then scales the coordinates).  A
+    standalone pair potential may stand in for the model.  Energies and forces are those of grad.energies_and_forces;
+    results are detached, in the coordinates' dtype.  D3 (ANI-2dr) raises NotImplementedError."""
+    from .potentials import _Standalone
+
+    pots = _pair_potentials_without_hessians(model)
+    if pots:
+        raise NotImplementedError(f"the pair potential(s) {', '.join(pots)} have no second derivative with respect to the "
+                                  "coordinates: strain second derivatives of this model are not available")
+    ef = energies_and_forces(model, species, coordinates, cell, pbc, keep_vars=False)
+    dev = coordinates.device
+    with torch.no_grad():
+        c32 = coordinates.detach().to(torch.float32).contiguous()
+        pbc_t = None if pbc is None else tuple(bool(b) for b in pbc.tolist())
+        nnp = False
+        if isinstance(model, _Standalone):
+            species32 = model._to_elem_idxs(species, True).to(torch.int32).contiguous()
+            rows = model._standalone_rows(species32, c32, cell, pbc)
+            if rows.overflowed():
+                raise RuntimeError(f"{type(model).__name__}: an atom has more than {rows.row_cap} neighbors inside the "
+                                   f"cutoff ({model.cutoff} A): its strain derivatives would be wrong")
+            pairs = [(model, rows)]
+        else:
+            species32 = model._elem_idxs(species).to(torch.int32).contiguous()
+            nnp = model.potentials["nnp"]._enabled
+            nbrs = None
+            if nnp:
+                aevc = model.aev_computer
+                nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_t)
+                nbrs.raise_on_overflow()
+                eng = aevc.engine()
+                aev = eng.forward(species32, nbrs)
+                packed = model.neural_networks._pack(dev)
+                _, g, _ = packed.forward_backward(species32, aev, want_grad=True)
+            pairs = _analytic_pair_rows(model, species32, c32, cell, pbc, nbrs)
+        Cn, A = species32.shape
+        N = Cn * A
+        out = torch.zeros((9, N, 3), dtype=torch.float32, device=dev)
+        ss = torch.zeros((Cn, 9, 9), dtype=torch.float64, device=dev)
+        vir = torch.zeros((Cn, 9), dtype=torch.float64, device=dev)
+        if nnp and N:
+            flat = species32.view(-1)
+            real = torch.nonzero(flat >= 0).view(-1)
+            atoms = real[torch.argsort(flat[real], stable=True)].to(torch.int32)   # (rows of a species contiguous)
+            g = g.reshape(N, eng.L)
+            chunk = strain_hessian_chunk_atoms(eng.L, packed.rows_hvp_row_bytes(N), HESSIAN_BUDGET_BYTES)
+            n_real = atoms.numel()
+            ws = packed.rows_hvp_prepare(species32, aev, 9 * min(chunk, max(n_real, 1)))
+            dirs = torch.arange(9, dtype=torch.int32, device=dev)
+            for a0 in range(0, n_real, chunk):
+                at = atoms[a0:a0 + chunk]
+                row_atom = at.repeat_interleave(9)
+                row_dir = dirs.repeat(at.numel())
+                daev = eng.jvp_strain_items(species32, nbrs, row_atom, row_dir)
+                # d E_i / d S_k = g_i . d aev_i / d S_k: the per-molecule virial of the networks
+                ra = row_atom.long()
+                dE = (daev * g.index_select(0, ra)).sum(dim=1)
+                vir.view(-1).index_add_(0, (ra // A) * 9 + row_dir.long(), dE.double())
+                del dE
+                hv = packed.rows_hvp(species32, ws, row_atom, daev)
+                del daev
+                eng.backward_second_strain_items(species32, nbrs, g, row_atom, row_dir, hv, out, ss)
+                del hv
+        for pot, rows in pairs:
+            pot.hvp_strain(species32, rows, out, ss, vir)
+        dt = coordinates.dtype
+        K = out.view(3, 3, Cn, A, 3).permute(2, 3, 4, 0, 1).to(dt)   # [C, A, y, a, b]
+        dEdx = -ef.forces.detach().to(dt)
+        eye = torch.eye(3, dtype=dt, device=dev)
+        internal = K + eye.view(1, 1, 3, 3, 1) * dEdx.view(Cn, A, 1, 1, 3)
+        return EnergiesForcesStrainHessians(ef.energies, ef.forces, vir.view(Cn, 3, 3).to(dt),
+                                            ss.view(Cn, 3, 3, 3, 3).to(dt), internal.contiguous())
+
+
+# Voigt order of elastic_constants: xx, yy, zz, yz, xz, xy
+VOIGT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
+
+
+def voigt_projector(dtype: torch.dtype = torch.float64, device: tp.Optional[torch.device] = None) -> Tensor:
+    """P [6, 9]: a symmetric strain in Voigt form (engineering shears, e_4 = 2 eps_yz) as the 9 components S_ab it moves,
+    so that d^2 E / d e_I d e_J = P W P^T for W = d^2 E / d S d S [9, 9]."""
+    P = torch.zeros((6, 9), dtype=dtype, device=device)
+    for I, (a, b) in enumerate(VOIGT_PAIRS):
+        if a == b:
+            P[I, 3 * a + a] = 1.0
+        else:
+            P[I, 3 * a + b] = 0.5
+            P[I, 3 * b + a] = 0.5
+    return P
+
+
+def _translations(active: Tensor) -> Tensor:
+    """Orthonormal rigid translations [C, 3A, 3] over the active atoms [C, A] (zero on the others)."""
+    Cn, A = active.shape
+    w = active.to(torch.float64)
+    w = w / w.sum(dim=1, keepdim=True).clamp(min=1.0).sqrt()
+    T = torch.zeros((Cn, A, 3, 3), dtype=torch.float64, device=active.device)
+    for y in range(3):
+        T[:, :, y, y] = w
+    return T.view(Cn, 3 * A, 3)
+
+
+def elastic_constants(result: EnergiesForcesStrainHessians, cell: Tensor, *, hessians: tp.Optional[Tensor] = None,
+                      relaxed: bool = False, unit: str = "GPa", pbc: tp.Optional[Tensor] = None) -> Tensor:
+    """Elastic constants [C, 6, 6] in Voigt order xx, yy, zz, yz, xz, xy (engineering shears) from
+    energies_forces_and_strain_hessians.  Full pbc only: a missing cell, or a ``pbc`` with a non-periodic direction, raises
+    ValueError (``pbc`` None: the cell is taken as periodic in all three directions).
+
+    Clamped-ion (Born) constants: (1/V) P W P^T with W = strain_hessians [9, 9] and P = voigt_projector().  With
+    ``relaxed=True`` the internal relaxation is subtracted: C - Xi^T H^+ Xi / V, where Xi [3A, 6] is the strained-frame mixed
+    derivative (internal_strain minus its force term delta_ya (d E / d x_i)_b) projected on symmetric strain and H is the
+    dense Hessian [C, 3A, 3A] ``hessians`` (e.g. grad.energies_forces_and_hessians(...).hessians).  H^+ is the pseudo-inverse
+    in fp64 on the complement of the three rigid translations of the atoms H or Xi touch (padding atoms are left out).
+
+    These are second derivatives of the energy.  At a non-zero stress they differ from the stress-strain coefficients by
+    terms in the stress, and a relaxed-ion value is only meaningful at a relaxed geometry (zero forces, H positive
+    semidefinite on the complement of the translations).  unit: "GPa" or "Hartree/A^3"."""
+    if cell is None:
+        raise ValueError("elastic constants need a periodic cell")
+    if pbc is not None and not bool(torch.as_tensor(pbc).all()):
+        raise ValueError("elastic constants need periodic boundary conditions in all three directions")
+    if unit == "GPa":
+        scale = _units.HARTREE_PER_ANGSTROM3_TO_GPA
+    elif unit in ("Hartree/A^3", "hartree/angstrom^3"):
+        scale = 1.0
+    else:
+        raise ValueError(f"unknown unit {unit!r}: 'GPa' or 'Hartree/A^3'")
+    W = result.strain_hessians.detach().to(torch.float64)
+    Cn = W.shape[0]
+    dev = W.device
+    cell64 = cell.detach().to(device=dev, dtype=torch.float64)
+    if cell64.dim() == 2:
+        cell64 = cell64.unsqueeze(0).expand(Cn, 3, 3)
+    V = torch.linalg.det(cell64).abs()
+    if bool((V <= 0).any()):
+        raise ValueError("the cell has zero volume")
+    P = voigt_projector(torch.float64, dev)
+    Wf = W.reshape(Cn, 9, 9)
+    out = P @ Wf @ P.T / V.view(Cn, 1, 1)
+    if relaxed:
+        if hessians is None:
+            raise ValueError("relaxed=True needs the dense Hessian: pass hessians=energies_forces_and_hessians(...).hessians")
+        A = result.internal_strain.shape[1]
+        H = hessians.detach().to(device=dev, dtype=torch.float64)
+        if H.shape != (Cn, 3 * A, 3 * A):
+            raise ValueError(f"hessians must be [{Cn}, {3 * A}, {3 * A}]")
+        H = 0.5 * (H + H.transpose(1, 2))
+        eye = torch.eye(3, dtype=torch.float64, device=dev)
+        F = result.forces.detach().to(device=dev, dtype=torch.float64)
+        K = result.internal_strain.detach().to(torch.float64) + eye.view(1, 1, 3, 3, 1) * F.view(Cn, A, 1, 1, 3)
+        Xi = K.reshape(Cn, 3 * A, 9) @ P.T   # [C, 3A, 6]
+        active = (H.view(Cn, A, 3, 3 * A).abs().sum(dim=(2, 3)) > 0) | (Xi.view(Cn, A, 18).abs().sum(dim=2) > 0)
+        T = _translations(active)
+        Pr = torch.eye(3 * A, dtype=torch.float64, device=dev).unsqueeze(0) - T @ T.transpose(1, 2)
+        Hp = Pr @ H @ Pr
+        lam, U = torch.linalg.eigh(Hp)
+        big = lam.abs().amax(dim=1, keepdim=True)
+        keep = lam.abs() > 1e-10 * big.clamp(min=torch.finfo(torch.float64).tiny)
+        inv = torch.where(keep, 1.0 / torch.where(keep, lam, torch.ones_like(lam)), torch.zeros_like(lam))
+        X = Pr @ Xi
+        UX = U.transpose(1, 2) @ X
+        out = out - (UX.transpose(1, 2) @ (inv.unsqueeze(2) * UX)) / V.view(Cn, 1, 1)
+    return out * scale
 
 
 def _hvp_row_bytes(packed, n_rows: int) -> int:

@@ -281,6 +281,29 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
             None if ex is None else ex.ctypes.data, float(self.cutoff), _lib.CUTOFF_KINDS[self.cutoff_fn], flags,
             row_atom.numel(), _ptr(row_atom), _ptr(row_dir), dir0, out.shape[0], _ptr(out)))
 
+    def hvp_strain(self, species32: Tensor, nbrs: NeighborRows, out: Tensor, ss: Tensor, virial: Tensor,
+                   cutoff: tp.Optional[float] = None) -> None:
+        """Strain second derivatives of the pair energies of the central atoms of nbrs (anihip_pair_analytic_hvp_strain):
+        out [9, N, 3] float32 += -sum_j B_ij d'_ij along the strain directions S_ab (k = 3 a + b, d' = d_a e_b), ss
+        [C, 9, 9] float64 += d^2 E_c / d S d S and virial [C, 9] float64 += d E_c / d S.  Symmetric rows only."""
+        _require_cuda(species32, out, ss, virial)
+        n = species32.numel()
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != (9, n, 3):
+            raise ValueError(f"out must be a contiguous float32 [9, {n}, 3] tensor")
+        nc = ss.shape[0]
+        if ss.dtype != torch.float64 or virial.dtype != torch.float64 or ss.shape != (nc, 9, 9) or \
+                virial.shape != (nc, 9) or nc == 0 or n % nc:
+            raise ValueError("ss [C, 9, 9] and virial [C, 9] must be float64, C dividing the atoms")
+        cut = self.cutoff if cutoff is None else cutoff
+        if math.isinf(cut):
+            cut = 1e30
+        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
+        ex = self._extra()
+        _lib.check(_lib.lib().anihip_pair_analytic_hvp_strain(
+            _stream(), self.kind, n, n // nc, nbrs.lo, nbrs.hi, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent),
+            _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
+            _lib.CUTOFF_KINDS[self.cutoff_fn], flags, _ptr(out), _ptr(ss), _ptr(virial)))
+
     def compute_from_rows(self, species32: Tensor, coords: Tensor, nbrs: NeighborRows) -> Tensor:
         """Molecular energies [C] (float64), differentiable with respect to coords."""
         return _PairEnergy.apply(coords, self, species32, nbrs)

@@ -191,3 +191,15 @@ class EnergiesForcesSparseHessians(tp.NamedTuple):
     energies: Tensor
     forces: Tensor
     hessians: BlockHessian
+
+
+class EnergiesForcesStrainHessians(tp.NamedTuple):
+    """What grad.energies_forces_and_strain_hessians returns.  With the strain x -> x S, cell -> cell S at S = I:
+    virial [C, 3, 3] = d E_c / d S (per molecule), strain_hessians [C, 3, 3, 3, 3] = d^2 E_c / d S_ab d S_pq (all 81
+    components, rotations included) and internal_strain [C, A, 3, 3, 3] = d^2 E_c / d x_iy d S_ab (x unstrained)."""
+
+    energies: Tensor
+    forces: Tensor
+    virial: Tensor
+    strain_hessians: Tensor
+    internal_strain: Tensor

@@ -21,6 +21,8 @@ ANGSTROM_TO_METER = 1e-10
 NEWTON_TO_MILLIDYNE = 1e8                    # 1 N = 1e5 dyne = 1e8 mDyne
 HARTREE_TO_KCALPERMOL = HARTREE_TO_JOULE * JOULE_TO_KCAL * AVOGADROS_NUMBER
 HARTREE_TO_KJOULEPERMOL = HARTREE_TO_JOULE * AVOGADROS_NUMBER / 1000
+# energy density Hartree / Angstrom^3 -> GPa (elastic constants, stress)
+HARTREE_PER_ANGSTROM3_TO_GPA = HARTREE_TO_JOULE / ANGSTROM_TO_METER ** 3 / 1e9
 EV_TO_KCALPERMOL = EV_TO_JOULE * JOULE_TO_KCAL * AVOGADROS_NUMBER
 EV_TO_KJOULEPERMOL = EV_TO_JOULE * AVOGADROS_NUMBER / 1000
 DEBYE_TO_ELECTRON_ANGSTROM = 0.2081943       # 1 D = 0.2081943 e Angstrom
@@ -86,6 +88,10 @@ def hartree2kcalpermol(x):
 def ea2debye(x):
     """Dipole in e Angstrom -> Debye."""
     return x / DEBYE_TO_ELECTRON_ANGSTROM
+
+
+def hartree_per_angstrom3_to_gpa(x):
+    return x * HARTREE_PER_ANGSTROM3_TO_GPA
 
 
 # older names of the reference
