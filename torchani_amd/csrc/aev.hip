@@ -19,6 +19,7 @@
 //   is expanded as cos(theta)cos(ShfZ)+sin(theta)sin(ShfZ) with cos(theta)=0.95 cos(angle), which
 //   is algebraically identical to acos + cos (aev/_terms.py:339-343) and needs no acos.
 #include "anihip_common.h"
+#include "hess_rows.h"
 
 namespace anihip {
 
@@ -1599,12 +1600,9 @@ int aev_forward_generic(hipStream_t stream, const anihip_aev_params *p, const fl
 int aev_jvp_generic_dirs(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                          const int32_t *species, const uint32_t *meta, const float *ent, float *daev, const float *tangent,
                          int n_dir, int64_t dir_t, int64_t n_atoms);
-int aev_jvp_generic_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+int aev_jvp_generic_items(hipStream_t stream, Dir M, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                           const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
                           const int32_t *row_dir, float *daev);
-int aev_jvp_generic_strain_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
-                                 const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
-                                 const int32_t *row_dir, float *daev);
 int aev_backward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                          const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
                          float *grad_coords, double *virial, bool fixed);
@@ -1836,7 +1834,8 @@ extern "C" int anihip_aev_jvp_items(void *stream, const anihip_aev_params *p, co
     ANIHIP_REQUIRE(p && table && species && meta && ent && row_atom && row_dir && daev, "null pointer argument");
     ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
     if (n_rows == 0) return 0;
-    return aev_jvp_generic_items((hipStream_t)stream, p, table, 0, n_rows, species, meta, ent, row_atom, row_dir, daev);
+    return aev_jvp_generic_items((hipStream_t)stream, Dir::Item, p, table, 0, n_rows, species, meta, ent, row_atom, row_dir,
+                                 daev);
 }
 
 extern "C" int anihip_aev_jvp_strain_items(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
@@ -1846,8 +1845,8 @@ extern "C" int anihip_aev_jvp_strain_items(void *stream, const anihip_aev_params
     ANIHIP_REQUIRE(p && table && species && meta && ent && row_atom && row_dir && daev, "null pointer argument");
     ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
     if (n_rows == 0) return 0;
-    return aev_jvp_generic_strain_items((hipStream_t)stream, p, table, 0, n_rows, species, meta, ent, row_atom, row_dir,
-                                        daev);
+    return aev_jvp_generic_items((hipStream_t)stream, Dir::Strain, p, table, 0, n_rows, species, meta, ent, row_atom,
+                                 row_dir, daev);
 }
 
 static int aev_backward(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo,

@@ -14,40 +14,14 @@
 // Maths restated from the reference (paths relative to /root/reference/torchani/): aev/_terms.py:99-104,171-186 (radial),
 // :34-55,324-325,339-343 (angular; cos(theta - ShfZ) expanded with cos(theta) = 0.95 cos(angle)), cutoffs.py:71-101,
 // aev/_computer.py:302-350 (layout); the derivatives are the chain rule on those expressions.
-#include "anihip_common.h"
+#include "aev_gen.h"
+#include "hess_rows.h"
 
 namespace anihip {
 
 constexpr int GEN_WPB = 4;
 constexpr float G_LOG2E = 1.4426950408889634f;
 constexpr float G_PI = 3.14159265358979323846f;
-constexpr int GEN_MAXA = 16, GEN_MAXZ = 16, GEN_MAXR = 32;
-
-struct GenArgs {
-    int S, nR, nA, nZ, L, radlen;
-    float Rcr, Rca, EtaR, EtaA, Zeta;
-    int smooth;
-};
-
-struct GenHdr {
-    uint32_t start;
-    int nA, nF;
-    uint64_t pkA, pkF;
-};
-
-__device__ __forceinline__ GenHdr gen_hdr(const uint32_t *meta, int64_t i)
-{
-    const uint32_t *m = meta + (size_t)i * META_W;
-    GenHdr h;
-    h.start = m[0];
-    h.nA = (int)(m[1] & 0xFFFFu);
-    h.nF = (int)(m[1] >> 16);
-    h.pkA = (uint64_t)m[2] | ((uint64_t)m[3] << 32);
-    h.pkF = (uint64_t)m[4] | ((uint64_t)m[5] << 32);
-    return h;
-}
-
-__device__ __forceinline__ int gen_cnt(uint64_t pk, int t) { return (int)((pk >> (8 * t)) & 255u); }
 
 // {fc, d fc / d r} of either cutoff envelope
 __device__ __forceinline__ float2 gen_cutoff(float r, float rc, bool smooth)
@@ -63,24 +37,6 @@ __device__ __forceinline__ float2 gen_cutoff(float r, float rc, bool smooth)
     const float x = r / rc;   // cutoffs.py:71-81; cosf / sinf of the hardware take revolutions
     return make_float2(0.5f * __builtin_amdgcn_cosf(0.5f * x) + 0.5f, -0.5f * G_PI / rc * __builtin_amdgcn_sinf(0.5f * x));
 }
-
-// (j, k) of the t-th pair of a block: rectangle for two species, row-major upper triangle inside one
-__device__ __forceinline__ void gen_pair(bool same, int t, int n1, int n2, int &j, int &k)
-{
-    if (!same) {
-        j = t / n2;
-        k = t - j * n2;
-    } else {   // t = j (2 n - j - 1) / 2 + (k - j - 1), 0 <= j < k < n
-        const float nn = (float)(2 * n1 - 1);
-        j = (int)((nn - sqrtf(fmaxf(nn * nn - 8.0f * (float)t, 0.f))) * 0.5f);
-        j = max(0, min(j, n1 - 2));
-        while (j > 0 && (j * (2 * n1 - j - 1)) / 2 > t) --j;
-        while (((j + 1) * (2 * n1 - j - 2)) / 2 <= t) ++j;
-        k = j + 1 + (t - (j * (2 * n1 - j - 1)) / 2);
-    }
-}
-
-__device__ __forceinline__ int gen_triu(int S, int a, int b) { return a * S - (a * (a - 1)) / 2 + (b - a); }
 
 // ---- staging of a row: unit vector + distance, angular cutoff (value, derivative) ------------------------------------
 struct GenStage {
@@ -115,11 +71,10 @@ __device__ __forceinline__ void gen_stage_row(const GenArgs &a, const GenHdr &h,
 // slab_mask (optional, rows of at most 1024 columns): bit j of slab_mask[i] <=> columns 32 j .. 32 j + 31 of row i can be
 // non-zero -- PLAIN column order (a general grid has no 16 / 32-column blocks to line up with slabs: a block of a present
 // species (pair) flags every slab it overlaps); the networks' layer 0 skips the slabs no atom of a tile flags.
-// ITEMS (anihip_aev_jvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi instead of atoms: central
-// atom row_atom[q], output row q, and the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), zero elsewhere.
-// STRAIN (anihip_aev_jvp_strain_items, strain second derivatives; item rows): row_dir[q] = 3 a + b names the strain
-// direction S_ab, and every entry moves with its own displacement, d' = d_a e_b, whatever its periodic image.
-template <bool JVP, bool ITEMS = false, bool STRAIN = false>
+// M (hess_rows.h): the JVP's direction.  Item (anihip_aev_jvp_items, sparse Hessians) and Strain (anihip_aev_jvp_strain_items,
+// strain second derivatives): the wave's index q runs over item rows lo <= q < hi instead of atoms, central atom
+// row_atom[q], output row q.  (M is not used when JVP is off.)
+template <bool JVP, Dir M = Dir::Dense>
 __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const float *__restrict__ tab, int64_t lo,
                                                                 int64_t hi, const int32_t *__restrict__ species,
                                                                 const uint32_t *__restrict__ meta,
@@ -129,8 +84,7 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
                                                                 int64_t dir_o, const int32_t *__restrict__ row_atom = nullptr,
                                                                 const int32_t *__restrict__ row_dir = nullptr)
 {
-    static_assert(JVP || !ITEMS, "item rows are JVP rows");
-    static_assert(ITEMS || !STRAIN, "strain rows are item rows");
+    constexpr bool ITEMS = JVP && M != Dir::Dense;
     if (JVP && !ITEMS) {   // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y
         tangent += (size_t)blockIdx.y * dir_t;
         aev += (size_t)blockIdx.y * dir_o;
@@ -158,24 +112,12 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_fwd_gen(GenArgs a, const
         // (every element of the row is written exactly once: blocks without a neighbor (pair) as zeros)
         if (h.nA + h.nF > 0) gen_stage_row(a, h, ent, st);
         if (JVP && h.nA + h.nF > 0) {
-            int da = -1, dc = 0;   // ITEMS: d' = e_dc ([j == da] - [i == da])
-            if (ITEMS) { da = row_dir[q] / 3; dc = row_dir[q] - 3 * da; }
-            auto tang = [&](size_t n, int k) {
-                if (ITEMS) return (int64_t)n == da && k == dc ? 1.0f : 0.0f;
-                return tangent[3 * n + k];
-            };
-            const float tix = tang(i, 0), tiy = tang(i, 1), tiz = tang(i, 2);
+            const DirRow row = ITEMS ? dir_item(row_atom, row_dir, q, 0) : DirRow{i, 0, -1, 0};
+            const float3 ti = dir_tangent3<M>(tangent, row, i);
             for (int e = lane; e < h.nA + h.nF; e += WAVE) {
-                const size_t jn = (size_t)st.jat[e];
-                const float4 U = st.ur[e];
-                float dx, dy, dz;
-                if (STRAIN) {   // d' = d_a e_b: component a of the entry's displacement, moved along b
-                    const float4 d = ent[h.start + e];
-                    const float s = da == 0 ? d.x : (da == 1 ? d.y : d.z);
-                    dx = dc == 0 ? s : 0.f; dy = dc == 1 ? s : 0.f; dz = dc == 2 ? s : 0.f;
-                } else {
-                    dx = tang(jn, 0) - tix; dy = tang(jn, 1) - tiy; dz = tang(jn, 2) - tiz;
-                }
+                const float4 U = st.ur[e], d = ent[h.start + e];
+                const float3 dp = dir_dprime<M>(tangent, row, ti, st.jat[e], make_float3(d.x, d.y, d.z));
+                const float dx = dp.x, dy = dp.y, dz = dp.z;
                 const float rd = U.x * dx + U.y * dy + U.z * dz, ir = 1.0f / U.w;
                 td[e] = make_float4((dx - U.x * rd) * ir, (dy - U.y * rd) * ir, (dz - U.z * rd) * ir, rd);
             }
@@ -454,24 +396,6 @@ static int gen_blocks(int64_t n_central)
     return (int)b;
 }
 
-static int gen_args(const anihip_aev_params *p, GenArgs *a)
-{
-    ANIHIP_REQUIRE(p->num_species >= 1 && p->num_species <= MAX_S - 1, "num_species must be 1..7");
-    ANIHIP_REQUIRE(p->n_shf_r >= 1 && p->n_shf_r <= GEN_MAXR && p->n_shf_a >= 1 && p->n_shf_a <= GEN_MAXA &&
-                       p->n_shf_z >= 1 && p->n_shf_z <= GEN_MAXZ,
-                   "symmetry-function grid outside n_shf_r <= 32, n_shf_a <= 16, n_shf_z <= 16 (got %d, %d x %d)",
-                   p->n_shf_r, p->n_shf_a, p->n_shf_z);
-    a->S = p->num_species;
-    a->nR = p->n_shf_r; a->nA = p->n_shf_a; a->nZ = p->n_shf_z;
-    a->radlen = a->S * a->nR;
-    a->L = a->radlen + (a->S * (a->S + 1) / 2) * a->nA * a->nZ;
-    a->Rcr = p->Rcr; a->Rca = p->Rca; a->EtaR = p->EtaR; a->EtaA = p->EtaA; a->Zeta = p->Zeta;
-    ANIHIP_REQUIRE(p->cutoff_kind == ANIHIP_CUTOFF_COSINE || p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH,
-                   "cutoff_kind must be ANIHIP_CUTOFF_COSINE or ANIHIP_CUTOFF_SMOOTH");
-    a->smooth = p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH;
-    return 0;
-}
-
 // (called by anihip_aev_forward / anihip_aev_backward* of aev.hip for grids the tuned kernels do not cover)
 int aev_forward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                         const int32_t *species, const uint32_t *meta, const float *ent, float *aev, const float *tangent,
@@ -508,8 +432,9 @@ int aev_jvp_generic_dirs(hipStream_t stream, const anihip_aev_params *p, const f
     return 0;
 }
 
-// item rows lo <= q < hi (anihip_aev_jvp_items): daev [q][L] = d aev_{row_atom[q]} along e_c on atom a, row_dir[q] = 3 a + c
-int aev_jvp_generic_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
+// item rows lo <= q < hi, M = Dir::Item (anihip_aev_jvp_items) or Dir::Strain (anihip_aev_jvp_strain_items): daev [q][L] =
+// d aev_{row_atom[q]} along e_c on atom a / along S_ac, row_dir[q] = 3 a + c
+int aev_jvp_generic_items(hipStream_t stream, Dir M, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                           const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
                           const int32_t *row_dir, float *daev)
 {
@@ -517,25 +442,9 @@ int aev_jvp_generic_items(hipStream_t stream, const anihip_aev_params *p, const 
     if (int rc = gen_args(p, &a)) return rc;
     if (hi == lo) return 0;
     const dim3 grid(gen_blocks(hi - lo)), block(GEN_WPB * WAVE);
-    hipLaunchKernelGGL((k_aev_fwd_gen<true, true>), grid, block, 0, stream, a, table, lo, hi, species, meta,
-                       (const float4 *)ent, daev, (const float *)nullptr, (uint32_t *)nullptr, (int64_t)0, (int64_t)0,
-                       row_atom, row_dir);
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// strain item rows lo <= q < hi (anihip_aev_jvp_strain_items): daev [q][L] = d aev_{row_atom[q]} / d S_ab, row_dir[q] = 3 a + b
-int aev_jvp_generic_strain_items(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
-                                 const int32_t *species, const uint32_t *meta, const float *ent, const int32_t *row_atom,
-                                 const int32_t *row_dir, float *daev)
-{
-    GenArgs a;
-    if (int rc = gen_args(p, &a)) return rc;
-    if (hi == lo) return 0;
-    const dim3 grid(gen_blocks(hi - lo)), block(GEN_WPB * WAVE);
-    hipLaunchKernelGGL((k_aev_fwd_gen<true, true, true>), grid, block, 0, stream, a, table, lo, hi, species, meta,
-                       (const float4 *)ent, daev, (const float *)nullptr, (uint32_t *)nullptr, (int64_t)0, (int64_t)0,
-                       row_atom, row_dir);
+    hipLaunchKernelGGL((M == Dir::Strain ? k_aev_fwd_gen<true, Dir::Strain> : k_aev_fwd_gen<true, Dir::Item>), grid, block, 0,
+                       stream, a, table, lo, hi, species, meta, (const float4 *)ent, daev, (const float *)nullptr,
+                       (uint32_t *)nullptr, (int64_t)0, (int64_t)0, row_atom, row_dir);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -17,7 +17,8 @@
 // One wave per (central atom, direction): blockIdx.y = direction.  Same row format, same push of the per-neighbor sums
 // (LDS ds_add_f32, then one global float atomic per component per neighbor) as the first-order general kernel; any grid
 // the general kernels serve, the tuned ANI-1x / ANI-2x grids included (their tables hold the plain shifts as well).
-#include "anihip_common.h"
+#include "aev_gen.h"
+#include "hess_rows.h"
 
 namespace anihip {
 
@@ -25,12 +26,6 @@ constexpr int HESS_WPB = 2;
 constexpr float H_LOG2E = 1.4426950408889634f;
 constexpr float H_LN2 = 0.6931471805599453f;
 constexpr float H_PI = 3.14159265358979323846f;
-
-struct HessArgs {
-    int S, nR, nA, nZ, L, radlen;
-    float Rcr, Rca, EtaR, EtaA, Zeta;
-    int smooth;
-};
 
 // ---- dual numbers: v + d eps, eps^2 = 0 ----------------------------------------------------------------------------
 struct Dual {
@@ -76,53 +71,14 @@ __device__ __forceinline__ float3 hess_cutoff(float r, float rc, bool smooth)
     return make_float3(0.5f * c + 0.5f, -0.5f * k * s, -0.5f * k * k * c);
 }
 
-struct HessHdr {
-    uint32_t start;
-    int nA, nF;
-    uint64_t pkA;
-};
-
-__device__ __forceinline__ HessHdr hess_hdr(const uint32_t *meta, int64_t i)
-{
-    const uint32_t *m = meta + (size_t)i * META_W;
-    HessHdr h;
-    h.start = m[0];
-    h.nA = (int)(m[1] & 0xFFFFu);
-    h.nF = (int)(m[1] >> 16);
-    h.pkA = (uint64_t)m[2] | ((uint64_t)m[3] << 32);
-    return h;
-}
-
-__device__ __forceinline__ int hess_cnt(uint64_t pk, int t) { return (int)((pk >> (8 * t)) & 255u); }
-
-__device__ __forceinline__ void hess_pair(bool same, int t, int n1, int n2, int &j, int &k)
-{
-    if (!same) {
-        j = t / n2;
-        k = t - j * n2;
-    } else {   // t = j (2 n - j - 1) / 2 + (k - j - 1), 0 <= j < k < n
-        const float nn = (float)(2 * n1 - 1);
-        j = (int)((nn - sqrtf(fmaxf(nn * nn - 8.0f * (float)t, 0.f))) * 0.5f);
-        j = max(0, min(j, n1 - 2));
-        while (j > 0 && (j * (2 * n1 - j - 1)) / 2 > t) --j;
-        while (((j + 1) * (2 * n1 - j - 2)) / 2 <= t) ++j;
-        k = j + 1 + (t - (j * (2 * n1 - j - 1)) / 2);
-    }
-}
-
-__device__ __forceinline__ int hess_triu(int S, int a, int b) { return a * S - (a * (a - 1)) / 2 + (b - a); }
-
-// ITEMS (anihip_aev_backward_second_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi: central
-// atom row_atom[q], dgrad row q, the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), output slab
-// row_dir[q] - dir0 of out [n_dir][n_atoms][3]; blockIdx.y = 0.
-// STRAIN (anihip_aev_backward_second_strain_items, strain second derivatives; item rows, n_slabs = 9): row_dir[q] = 3 a + b
-// names the strain direction S_ab and the output slab, every entry moves with d' = d_a e_b (replacing t_j - t_i), and the
-// row also adds sum_e d_{e,x} g_{e,y} -- g = the tangent part of d E_i / d d_e, i.e. the derivative of the row's virial
-// along S_ab -- to ss[i / atoms_per_mol][3 x + y][3 a + b] (one wave sum per component, one fp64 atomic per component and
-// row).  The mode has no tangent array and no slab offset: `tangent` carries ss (double [C][9][9]) and `dir0` carries
-// atoms_per_mol, so that the kernel's signature, and with it the code of the other instantiations, stays as it was.
-template <bool ITEMS, bool STRAIN = false>
-__global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const float *__restrict__ tab, int64_t n_atoms,
+// M (hess_rows.h): Dense -- central atoms lo <= q < hi, direction blockIdx.y of tangent, dgrad and out.  Item
+// (anihip_aev_backward_second_items, sparse Hessians) and Strain (anihip_aev_backward_second_strain_items, strain second
+// derivatives): the wave's index q runs over item rows lo <= q < hi, dgrad row q, output slab row_dir[q] - dir0 of out
+// [n_slabs][n_atoms][3] (Strain: dir0 = 0, n_slabs = 9); blockIdx.y = 0.  A strain row also adds sum_e d_{e,x} g_{e,y} --
+// g = the tangent part of d E_i / d d_e, i.e. the derivative of the row's virial along S_ab -- to
+// sa.ss[i / sa.atoms_per_mol][3 x + y][3 a + b] (one wave sum per component, one fp64 atomic per component and row).
+template <Dir M>
+__global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(GenArgs a, const float *__restrict__ tab, int64_t n_atoms,
                                                              int64_t lo, int64_t hi, const int32_t *__restrict__ species,
                                                              const uint32_t *__restrict__ meta,
                                                              const float4 *__restrict__ ent,
@@ -131,9 +87,9 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
                                                              const float *__restrict__ dgrad, float *__restrict__ out,
                                                              const int32_t *__restrict__ row_atom,
                                                              const int32_t *__restrict__ row_dir, int64_t dir0,
-                                                             int64_t n_slabs)
+                                                             int64_t n_slabs, StrainAcc sa)
 {
-    static_assert(ITEMS || !STRAIN, "strain rows are item rows");
+    constexpr bool ITEMS = M != Dir::Dense, STRAIN = M == Dir::Strain;
     __shared__ float4 s_u[HESS_WPB][MAXR];     // unit vector, r
     __shared__ float4 s_ud[HESS_WPB][MAXR];    // its derivative along the direction: u', r'
     __shared__ float4 s_fcr[HESS_WPB][MAXR];   // radial envelope fc, fc', fc''
@@ -146,44 +102,29 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
     float *gx = s_g[wib][0], *gy = s_g[wib][1], *gz = s_g[wib][2];
     const int64_t dir = blockIdx.y;
     const float *tg = ITEMS ? nullptr : tangent + (size_t)dir * 3 * n_atoms;
-    double *ss = STRAIN ? reinterpret_cast<double *>(const_cast<float *>(tangent)) : nullptr;
-    const int64_t atoms_per_mol = STRAIN ? dir0 : 1;
     const float *dg = ITEMS ? dgrad : dgrad + (size_t)dir * n_atoms * a.L;
     float *o = out + (size_t)dir * 3 * n_atoms;
     const int64_t nw = (int64_t)gridDim.x * HESS_WPB;
     const int nAZ = a.nA * a.nZ;
     for (int64_t q = lo + blockIdx.x * (int64_t)HESS_WPB + wib; q < hi; q += nw) {
-        const int64_t i = ITEMS ? (int64_t)row_atom[q] : q;
+        const DirRow row = ITEMS ? dir_item(row_atom, row_dir, q, dir0) : DirRow{q, dir, -1, 0};
+        const int64_t i = row.i;
         if (species[i] < 0) continue;
-        const HessHdr h = hess_hdr(meta, i);
+        const GenHdr h = gen_hdr(meta, i);
         const int nR = h.nA + h.nF;
         if (nR == 0) continue;
-        int64_t da = -1;   // ITEMS: t = e_dc on atom da
-        int dc = 0;
         if (ITEMS) {
-            const int64_t slab = row_dir[q] - (STRAIN ? 0 : dir0);
-            if (slab < 0 || slab >= n_slabs) continue;   // (a row outside the caller's slabs)
-            da = row_dir[q] / 3;
-            dc = row_dir[q] - 3 * (int)da;
-            o = out + (size_t)slab * 3 * n_atoms;
+            if (row.slab < 0 || row.slab >= n_slabs) continue;   // (a row outside the caller's slabs)
+            o = out + (size_t)row.slab * 3 * n_atoms;
         }
-        auto tang = [&](size_t n, int k) {
-            if (ITEMS) return (int64_t)n == da && k == dc ? 1.0f : 0.0f;
-            return tg[3 * n + k];
-        };
-        const float tix = tang(i, 0), tiy = tang(i, 1), tiz = tang(i, 2);
+        const float3 ti = dir_tangent3<M>(tg, row, i);
         for (int e = lane; e < nR; e += WAVE) {
             const float4 d = ent[h.start + e];
             const float r = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z), ir = 1.0f / r;
             const float ux = d.x * ir, uy = d.y * ir, uz = d.z * ir;
             const int jn = (int)(__float_as_uint(d.w) & IDX_MASK);
-            float dx, dy, dz;
-            if (STRAIN) {   // d' = d_a e_b (a = da, b = dc)
-                const float sa = da == 0 ? d.x : (da == 1 ? d.y : d.z);
-                dx = dc == 0 ? sa : 0.f; dy = dc == 1 ? sa : 0.f; dz = dc == 2 ? sa : 0.f;
-            } else {
-                dx = tang(jn, 0) - tix; dy = tang(jn, 1) - tiy; dz = tang(jn, 2) - tiz;
-            }
+            const float3 dp = dir_dprime<M>(tg, row, ti, jn, make_float3(d.x, d.y, d.z));
+            const float dx = dp.x, dy = dp.y, dz = dp.z;
             const float rd = ux * dx + uy * dy + uz * dz;
             su[e] = make_float4(ux, uy, uz, r);
             sud[e] = make_float4((dx - ux * rd) * ir, (dy - uy * rd) * ir, (dz - uz * rd) * ir, rd);
@@ -218,19 +159,19 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
         // ---- angular (lane = pair) ----
         int o1 = 0;
         for (int s1 = 0; s1 < a.S; ++s1) {
-            const int n1 = hess_cnt(h.pkA, s1);
+            const int n1 = gen_cnt(h.pkA, s1);
             int o2 = o1;
             for (int s2 = s1; s2 < a.S; ++s2) {
-                const int n2 = hess_cnt(h.pkA, s2);
+                const int n2 = gen_cnt(h.pkA, s2);
                 const bool same = s1 == s2;
                 const int np = same ? (n1 * (n1 - 1)) / 2 : n1 * n2;
-                const int boff = a.radlen + hess_triu(a.S, s1, s2) * nAZ;
+                const int boff = a.radlen + gen_triu(a.S, s1, s2) * nAZ;
                 const float *ww = w + boff, *wwd = wd + boff;
                 for (int t0 = 0; t0 < np; t0 += WAVE) {
                     const int t = t0 + lane;
                     if (t < np) {
                         int j, k;
-                        hess_pair(same, t, n1, n2, j, k);
+                        gen_pair(same, t, n1, n2, j, k);
                         const int e1 = o1 + j, e2 = (same ? o1 : o2) + k;
                         const float4 A1 = su[e1], A2 = su[e2], B1 = sud[e1], B2 = sud[e2];
                         const float4 G1 = sfa[e1], G2 = sfa[e2];
@@ -306,7 +247,7 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
                 const float t = wave_sum(vs[c]);
                 if (lane == c) mine = t;
             }
-            if (lane < 9) atomicAdd(ss + (size_t)(i / atoms_per_mol) * 81 + 9 * lane + row_dir[q], (double)mine);
+            if (lane < 9) atomicAdd(sa.ss + (size_t)(i / sa.atoms_per_mol) * 81 + 9 * lane + row.slab, (double)mine);
         }
         const float tx = wave_sum(ox), ty = wave_sum(oy), tz = wave_sum(oz);
         if (lane == 0) {
@@ -316,6 +257,24 @@ __global__ __launch_bounds__(HESS_WPB * WAVE) void k_aev_bwd2(HessArgs a, const 
         }
         wave_sync();
     }
+}
+
+// every entry point: central atoms (Dense; grid.y = the n_dir directions) or item rows lo <= q < hi
+template <Dir M>
+static int bwd2_launch(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo, int64_t hi,
+                       int64_t n_dir, const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
+                       const float *tangent, const float *dgrad, float *out, const int32_t *row_atom,
+                       const int32_t *row_dir, int64_t dir0, int64_t n_slabs, StrainAcc sa)
+{
+    GenArgs a;
+    if (int rc = gen_args(p, &a)) return rc;
+    if (hi == lo || n_dir == 0) return 0;
+    const int64_t b = std::min<int64_t>((hi - lo + HESS_WPB - 1) / HESS_WPB, M == Dir::Dense ? 1024 : 4096);
+    hipLaunchKernelGGL(k_aev_bwd2<M>, dim3((unsigned)b, (unsigned)n_dir), dim3(HESS_WPB * WAVE), 0, (hipStream_t)stream, a,
+                       table, n_atoms, lo, hi, species, meta, (const float4 *)ent, grad_aev, tangent, dgrad, out, row_atom,
+                       row_dir, dir0, n_slabs, sa);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace anihip
@@ -330,30 +289,9 @@ extern "C" int anihip_aev_backward_second(void *stream, const anihip_aev_params 
     ANIHIP_REQUIRE(p && table && species && meta && ent && grad_aev && tangent && dgrad && out, "null pointer argument");
     ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
     ANIHIP_REQUIRE(0 <= n_dir && n_dir <= 65535, "n_dir must be 0..65535 (got %lld)", (long long)n_dir);
-    ANIHIP_REQUIRE(p->num_species >= 1 && p->num_species <= MAX_S - 1, "num_species must be 1..7");
-    ANIHIP_REQUIRE(p->n_shf_r >= 1 && p->n_shf_r <= 32 && p->n_shf_a >= 1 && p->n_shf_a <= 16 && p->n_shf_z >= 1 &&
-                       p->n_shf_z <= 16,
-                   "symmetry-function grid outside n_shf_r <= 32, n_shf_a <= 16, n_shf_z <= 16 (got %d, %d x %d)",
-                   p->n_shf_r, p->n_shf_a, p->n_shf_z);
-    ANIHIP_REQUIRE(p->cutoff_kind == ANIHIP_CUTOFF_COSINE || p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH,
-                   "cutoff_kind must be ANIHIP_CUTOFF_COSINE or ANIHIP_CUTOFF_SMOOTH");
     (void)status;
-    if (hi == lo || n_dir == 0) return 0;
-    HessArgs a;
-    a.S = p->num_species;
-    a.nR = p->n_shf_r; a.nA = p->n_shf_a; a.nZ = p->n_shf_z;
-    a.radlen = a.S * a.nR;
-    a.L = a.radlen + (a.S * (a.S + 1) / 2) * a.nA * a.nZ;
-    a.Rcr = p->Rcr; a.Rca = p->Rca; a.EtaR = p->EtaR; a.EtaA = p->EtaA; a.Zeta = p->Zeta;
-    a.smooth = p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH;
-    int64_t b = (hi - lo + HESS_WPB - 1) / HESS_WPB;
-    if (b > 1024) b = 1024;
-    const dim3 grid((unsigned)b, (unsigned)n_dir), block(HESS_WPB * WAVE);
-    hipLaunchKernelGGL(k_aev_bwd2<false>, grid, block, 0, (hipStream_t)stream, a, table, n_atoms, lo, hi, species, meta,
-                       (const float4 *)ent, grad_aev, tangent, dgrad, out, (const int32_t *)nullptr, (const int32_t *)nullptr,
-                       (int64_t)0, (int64_t)0);
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
+    return bwd2_launch<Dir::Dense>(stream, p, table, n_atoms, lo, hi, n_dir, species, meta, ent, grad_aev, tangent, dgrad,
+                                   out, nullptr, nullptr, 0, 0, StrainAcc{});
 }
 
 extern "C" int anihip_aev_backward_second_items(void *stream, const anihip_aev_params *p, const float *table,
@@ -365,28 +303,8 @@ extern "C" int anihip_aev_backward_second_items(void *stream, const anihip_aev_p
     ANIHIP_REQUIRE(p && table && species && meta && ent && grad_aev && row_atom && row_dir && dgrad && out,
                    "null pointer argument");
     ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0 && n_dir >= 0, "negative size");
-    ANIHIP_REQUIRE(p->num_species >= 1 && p->num_species <= MAX_S - 1, "num_species must be 1..7");
-    ANIHIP_REQUIRE(p->n_shf_r >= 1 && p->n_shf_r <= 32 && p->n_shf_a >= 1 && p->n_shf_a <= 16 && p->n_shf_z >= 1 &&
-                       p->n_shf_z <= 16,
-                   "symmetry-function grid outside n_shf_r <= 32, n_shf_a <= 16, n_shf_z <= 16 (got %d, %d x %d)",
-                   p->n_shf_r, p->n_shf_a, p->n_shf_z);
-    ANIHIP_REQUIRE(p->cutoff_kind == ANIHIP_CUTOFF_COSINE || p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH,
-                   "cutoff_kind must be ANIHIP_CUTOFF_COSINE or ANIHIP_CUTOFF_SMOOTH");
-    if (n_rows == 0) return 0;
-    HessArgs a;
-    a.S = p->num_species;
-    a.nR = p->n_shf_r; a.nA = p->n_shf_a; a.nZ = p->n_shf_z;
-    a.radlen = a.S * a.nR;
-    a.L = a.radlen + (a.S * (a.S + 1) / 2) * a.nA * a.nZ;
-    a.Rcr = p->Rcr; a.Rca = p->Rca; a.EtaR = p->EtaR; a.EtaA = p->EtaA; a.Zeta = p->Zeta;
-    a.smooth = p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH;
-    int64_t b = (n_rows + HESS_WPB - 1) / HESS_WPB;
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL(k_aev_bwd2<true>, dim3((unsigned)b), dim3(HESS_WPB * WAVE), 0, (hipStream_t)stream, a, table, n_atoms,
-                       (int64_t)0, n_rows, species, meta, (const float4 *)ent, grad_aev, (const float *)nullptr, dgrad, out,
-                       row_atom, row_dir, dir0, n_dir);
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
+    return bwd2_launch<Dir::Item>(stream, p, table, n_atoms, 0, n_rows, 1, species, meta, ent, grad_aev, nullptr, dgrad, out,
+                                  row_atom, row_dir, dir0, n_dir, StrainAcc{});
 }
 
 extern "C" int anihip_aev_backward_second_strain_items(void *stream, const anihip_aev_params *p, const float *table,
@@ -401,26 +319,6 @@ extern "C" int anihip_aev_backward_second_strain_items(void *stream, const anihi
     ANIHIP_REQUIRE(atoms_per_mol >= 1 && n_atoms % atoms_per_mol == 0,
                    "atoms_per_mol must be >= 1 and divide n_atoms (got %lld, %lld)", (long long)atoms_per_mol,
                    (long long)n_atoms);
-    ANIHIP_REQUIRE(p->num_species >= 1 && p->num_species <= MAX_S - 1, "num_species must be 1..7");
-    ANIHIP_REQUIRE(p->n_shf_r >= 1 && p->n_shf_r <= 32 && p->n_shf_a >= 1 && p->n_shf_a <= 16 && p->n_shf_z >= 1 &&
-                       p->n_shf_z <= 16,
-                   "symmetry-function grid outside n_shf_r <= 32, n_shf_a <= 16, n_shf_z <= 16 (got %d, %d x %d)",
-                   p->n_shf_r, p->n_shf_a, p->n_shf_z);
-    ANIHIP_REQUIRE(p->cutoff_kind == ANIHIP_CUTOFF_COSINE || p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH,
-                   "cutoff_kind must be ANIHIP_CUTOFF_COSINE or ANIHIP_CUTOFF_SMOOTH");
-    if (n_rows == 0) return 0;
-    HessArgs a;
-    a.S = p->num_species;
-    a.nR = p->n_shf_r; a.nA = p->n_shf_a; a.nZ = p->n_shf_z;
-    a.radlen = a.S * a.nR;
-    a.L = a.radlen + (a.S * (a.S + 1) / 2) * a.nA * a.nZ;
-    a.Rcr = p->Rcr; a.Rca = p->Rca; a.EtaR = p->EtaR; a.EtaA = p->EtaA; a.Zeta = p->Zeta;
-    a.smooth = p->cutoff_kind == ANIHIP_CUTOFF_SMOOTH;
-    int64_t b = (n_rows + HESS_WPB - 1) / HESS_WPB;
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL((k_aev_bwd2<true, true>), dim3((unsigned)b), dim3(HESS_WPB * WAVE), 0, (hipStream_t)stream, a, table,
-                       n_atoms, (int64_t)0, n_rows, species, meta, (const float4 *)ent, grad_aev,
-                       reinterpret_cast<const float *>(ss), dgrad, out, row_atom, row_dir, atoms_per_mol, (int64_t)9);
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
+    return bwd2_launch<Dir::Strain>(stream, p, table, n_atoms, 0, n_rows, 1, species, meta, ent, grad_aev, nullptr, dgrad,
+                                    out, row_atom, row_dir, 0, 9, StrainAcc{ss, nullptr, atoms_per_mol});
 }

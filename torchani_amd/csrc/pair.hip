@@ -7,7 +7,9 @@
 // concerns itself from its own row: atomic energy sum_j e_ij / 2 (core.py:195-198) and gradient
 // sum_j e'(d_ij) d r_ij / d r_i -- no atomics, deterministic.  (Rows from a LAMMPS full list are not symmetric: there the
 // pair term is pushed to the neighbor with float atomics, flag ANIHIP_PAIR_PUSH.)
-#include "anihip_common.h"
+#include "hess_rows.h"
+
+#include <type_traits>
 
 namespace anihip {
 
@@ -211,35 +213,30 @@ __device__ __forceinline__ void envelope2(float r, float inv_rc, float rev_rc, f
 // then for every direction gathers t[k][j], applies B and the wave sums give (H t[k])_i.  No atomics: deterministic.
 constexpr int HVP_ROUNDS = (MAXR + WAVE - 1) / WAVE;
 
-// ITEMS (anihip_pair_analytic_hvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi: central atom
-// row_atom[q], ONE direction, the implicit unit tangent e_c on atom a (row_dir[q] = 3 a + c), output slab row_dir[q] - dir0
-// of out [n_dir][n_atoms][3] (an item row names each (direction, atom) once: still no atomics).
-// STRAIN (anihip_pair_analytic_hvp_strain, strain second derivatives): central atoms lo <= i < hi, the n_dir = 9 strain
-// directions S_ab (k = 3 a + b), each pair moving with d' = d_a e_b:  out[k][i] += -sum_j B_ij d'_ij (no atomics).  Each lane
-// also keeps, over its pairs, M_xp = sum d_x d_p a / 2 (the pair virial) and the fully symmetric
-// T_xypq = sum c r^2 u_x u_y u_p u_q / 2 (6 + 15 numbers); the strain-strain term
+// M (hess_rows.h): Dense -- central atoms lo <= i < hi, the n_dir directions of tangent [n_dir][n_atoms][3].  Item
+// (anihip_pair_analytic_hvp_items, sparse Hessians): the wave's index q runs over item rows lo <= q < hi, ONE direction
+// each, output slab row_dir[q] - dir0 of out [n_dir][n_atoms][3] (an item row names each (direction, atom) once: still no
+// atomics).  Strain (anihip_pair_analytic_hvp_strain, strain second derivatives): central atoms lo <= i < hi, the n_dir = 9
+// strain directions S_ab (k = 3 a + b) each:  out[k][i] += -sum_j B_ij d'_ij (no atomics).  Each lane also keeps, over its
+// pairs, M_xp = sum d_x d_p a / 2 (the pair virial) and the fully symmetric T_xypq = sum c r^2 u_x u_y u_p u_q / 2
+// (6 + 15 numbers); the strain-strain term
 //   ss[mol][3 x + y][3 p + q] += sum_pairs d_x (B d'_pq)_y / 2 = delta_yq M_xp + T_xypq
-// and virial[mol][3 x + y] += M_xy are added per molecule (mol = i / atoms_per_mol) with one wave reduction and fp64 atomics
-// whenever the wave's molecule changes.  The mode has no tangent array and no item rows: `tangent` carries ss (double
-// [C][9][9]), `row_atom` carries virial (double [C][9] or null) and `dir0` carries atoms_per_mol, so that the kernel's
-// signature, and with it the code of the other instantiations, stays as it was.
-template <int KIND, bool ITEMS = false, bool STRAIN = false>
+// and virial[mol][3 x + y] += M_xy are added per molecule (mol = i / sa.atoms_per_mol) to sa.ss and sa.virial with one wave
+// reduction and fp64 atomics whenever the wave's molecule changes.
+template <int KIND, Dir M>
 __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, int64_t hi,
                                                   const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
                                                   const float4 *__restrict__ ent, const float *__restrict__ tab,
                                                   PairExtra extra, float cutoff, int smooth, int clamp_r, int64_t n_dir,
                                                   const float *__restrict__ tangent, float *__restrict__ out,
-                                                  const int32_t *__restrict__ row_atom = nullptr,
-                                                  const int32_t *__restrict__ row_dir = nullptr, int64_t dir0 = 0)
+                                                  const int32_t *__restrict__ row_atom,
+                                                  const int32_t *__restrict__ row_dir, int64_t dir0, StrainAcc sa)
 {
-    static_assert(!(ITEMS && STRAIN), "strain directions run over the central atoms");
+    constexpr bool ITEMS = M == Dir::Item, STRAIN = M == Dir::Strain;
     const int lane = lane_id();
     const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
     const size_t stride = (size_t)n_atoms * 3;
     const float inv_rc = 1.0f / cutoff, rev_rc = 0.5f / cutoff, pi_rc = 3.14159265358979f / cutoff;
-    double *ss = STRAIN ? reinterpret_cast<double *>(const_cast<float *>(tangent)) : nullptr;
-    double *virial = STRAIN ? reinterpret_cast<double *>(const_cast<int32_t *>(row_atom)) : nullptr;
-    const int64_t atoms_per_mol = STRAIN ? dir0 : 1;
     constexpr int NS = STRAIN ? 21 : 1;
     float sm[NS];   // STRAIN: M (6, pairs x <= p) then T (15, by the powers of x and y)
     if (STRAIN) {
@@ -262,35 +259,29 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
             for (int c = 0; c < 6; ++c) mv = c == im ? sm[c] : mv;
 #pragma unroll
             for (int c = 0; c < 15; ++c) tv = c == it ? sm[(STRAIN ? 6 + c : 0)] : tv;
-            atomicAdd(ss + (size_t)mol * 81 + l, (double)((y == qq ? mv : 0.f) + tv));
-            if (virial && pq == 0) {   // (l = 0, 9, .., 72: component xy of the virial = M_xy)
+            atomicAdd(sa.ss + (size_t)mol * 81 + l, (double)((y == qq ? mv : 0.f) + tv));
+            if (sa.virial && pq == 0) {   // (l = 0, 9, .., 72: component xy of the virial = M_xy)
                 const int lm = min(x, y), hm = max(x, y);
                 const int iv = lm * 3 - (lm * (lm - 1)) / 2 + (hm - lm);
                 float vv = 0.f;
 #pragma unroll
                 for (int c = 0; c < 6; ++c) vv = c == iv ? sm[c] : vv;
-                atomicAdd(virial + (size_t)mol * 9 + xy, (double)vv);
+                atomicAdd(sa.virial + (size_t)mol * 9 + xy, (double)vv);
             }
         }
 #pragma unroll
         for (int c = 0; c < NS; ++c) sm[c] = 0.f;
     };
     for (int64_t qi = lo + blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); qi < hi; qi += nw) {
-        const int64_t i = ITEMS ? (int64_t)row_atom[qi] : qi;
-        if (STRAIN && i / atoms_per_mol != mol) {
+        const DirRow row = ITEMS ? dir_item(row_atom, row_dir, qi, dir0) : DirRow{qi, 0, -1, 0};
+        const int64_t i = row.i;
+        if (STRAIN && i / sa.atoms_per_mol != mol) {
             if (mol >= 0) flush();
-            mol = i / atoms_per_mol;
+            mol = i / sa.atoms_per_mol;
         }
         const int si = species[i];
         if (si < 0) continue;
-        int64_t da = -1, slab = 0;   // ITEMS: t = e_dc on atom da, written to slab
-        int dc = 0;
-        if (ITEMS) {
-            slab = row_dir[qi] - dir0;
-            if (slab < 0 || slab >= n_dir) continue;   // (a row outside the caller's slabs)
-            da = row_dir[qi] / 3;
-            dc = row_dir[qi] - 3 * (int)da;
-        }
+        if (ITEMS && (row.slab < 0 || row.slab >= n_dir)) continue;   // (a row outside the caller's slabs)
         const uint32_t start = meta[(size_t)i * META_W], c = meta[(size_t)i * META_W + 1];
         const int nR = (int)(c & 0xFFFFu) + (int)(c >> 16);
         for (int b0 = 0; b0 < nR; b0 += HVP_ROUNDS * WAVE) {   // (one pass for every row of at most ANIHIP_MAX_RAD entries)
@@ -344,24 +335,18 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
             }
             for (int64_t kd = 0; kd < (ITEMS ? 1 : n_dir); ++kd) {
                 const float *tk = ITEMS ? nullptr : tangent + (size_t)kd * stride;
-                auto tang = [&](int64_t n, int k) {
-                    if (ITEMS) return n == da && k == dc ? 1.0f : 0.0f;
-                    if (STRAIN) return 0.0f;   // (no tangent array)
-                    return tk[3 * n + k];
-                };
-                const float vx = tang(i, 0), vy = tang(i, 1), vz = tang(i, 2);
+                const DirRow dk = STRAIN ? dir_row(i, kd, (int)kd) : row;
+                const float3 ti = dir_tangent3<M>(tk, dk, i);
                 float hx = 0.f, hy = 0.f, hz = 0.f;
 #pragma unroll
                 for (int q = 0; q < HVP_ROUNDS; ++q) {
                     if (b0 + q * WAVE >= nR) break;   // (wave-uniform)
-                    float dx, dy, dz;
-                    if (STRAIN) {   // t_i - t_j = -d' = -d_a e_b, direction kd = 3 a + b
-                        const int sa = (int)kd / 3, sb = (int)kd - 3 * sa;
-                        const float m = -(sa == 0 ? ux[q] : (sa == 1 ? uy[q] : uz[q])) * rr[(STRAIN ? q : 0)];
-                        dx = sb == 0 ? m : 0.f; dy = sb == 1 ? m : 0.f; dz = sb == 2 ? m : 0.f;
-                    } else {
-                        dx = vx - tang(jj[q], 0); dy = vy - tang(jj[q], 1); dz = vz - tang(jj[q], 2);
-                    }
+                    // B_ij acts on t_i - t_j: the d' of the entry seen from j (neighbor i, displacement -d = -r u)
+                    const float rq = STRAIN ? rr[(STRAIN ? q : 0)] : 0.f;
+                    const float3 tj = dir_tangent3<M>(tk, dk, jj[q]);
+                    const float3 dp = STRAIN ? dir_dprime<M>(tk, dk, tj, i, make_float3(-ux[q] * rq, -uy[q] * rq, -uz[q] * rq))
+                                             : make_float3(ti.x - tj.x, ti.y - tj.y, ti.z - tj.z);
+                    const float dx = dp.x, dy = dp.y, dz = dp.z;
                     const float cu = bc[q] * (ux[q] * dx + uy[q] * dy + uz[q] * dz);
                     hx += ba[q] * dx + cu * ux[q];
                     hy += ba[q] * dy + cu * uy[q];
@@ -369,7 +354,7 @@ __global__ __launch_bounds__(256) void k_pair_hvp(int64_t n_atoms, int64_t lo, i
                 }
                 hx = wave_sum(hx); hy = wave_sum(hy); hz = wave_sum(hz);
                 if (lane == 0) {
-                    float *o = out + (size_t)(ITEMS ? slab : kd) * stride + 3 * i;
+                    float *o = out + (size_t)(ITEMS ? row.slab : kd) * stride + 3 * i;
                     o[0] += hx; o[1] += hy; o[2] += hz;
                 }
             }
@@ -599,6 +584,60 @@ __global__ __launch_bounds__(256) void k_d3_cngrad(int64_t lo, int64_t hi, const
     }
 }
 
+// the checks and launch constants shared by the anihip_pair_analytic* entry points (hvp: the Hessian-vector products)
+struct PairSetup {
+    PairExtra x;
+    int smooth, clamp_r;
+};
+
+static int pair_setup(int32_t kind, int64_t n_atoms, const float *extra, float cutoff, int32_t cutoff_kind, int32_t flags,
+                      bool hvp, PairSetup *s)
+{
+    ANIHIP_REQUIRE(!hvp || n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
+    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
+    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
+    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
+    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
+    ANIHIP_REQUIRE(!hvp || !(flags & ANIHIP_PAIR_PUSH),
+                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    *s = PairSetup{};
+    if (extra)
+        for (int k = 0; k < 8; ++k) s->x.v[k] = extra[k];
+    s->smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
+    s->clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
+    return 0;
+}
+
+// four waves per 256-thread block, one per central atom (row), at most 2048 blocks
+static unsigned pair_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, 256 * 8)); }
+
+// f(std::integral_constant<int, KIND>{}) for the runtime kind (checked by pair_setup)
+template <class F>
+static void with_kind(int32_t kind, F &&f)
+{
+    switch (kind) {
+        case ANIHIP_PAIR_XTB: f(std::integral_constant<int, ANIHIP_PAIR_XTB>{}); break;
+        case ANIHIP_PAIR_ZBL: f(std::integral_constant<int, ANIHIP_PAIR_ZBL>{}); break;
+        case ANIHIP_PAIR_LJ: f(std::integral_constant<int, ANIHIP_PAIR_LJ>{}); break;
+        default: f(std::integral_constant<int, ANIHIP_PAIR_COULOMB>{}); break;
+    }
+}
+
+template <Dir M>
+static int pair_hvp_launch(void *stream, int32_t kind, const PairSetup &s, int64_t n_atoms, int64_t lo, int64_t hi,
+                           const int32_t *species, const uint32_t *meta, const float *ent, const float *pair_table,
+                           float cutoff, int64_t n_dir, const float *tangent, float *out, const int32_t *row_atom,
+                           const int32_t *row_dir, int64_t dir0, StrainAcc sa)
+{
+    with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((k_pair_hvp<decltype(K)::value, M>), dim3(pair_blocks(hi - lo)), dim3(256), 0,
+                           (hipStream_t)stream, n_atoms, lo, hi, species, meta, (const float4 *)ent, pair_table, s.x, cutoff,
+                           s.smooth, s.clamp_r, n_dir, tangent, out, row_atom, row_dir, dir0, sa);
+    });
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace anihip
 
 using namespace anihip;
@@ -610,28 +649,15 @@ extern "C" int anihip_pair_analytic(void *stream, int32_t kind, int64_t n_atoms,
 {
     ANIHIP_REQUIRE(species && meta && ent && pair_table, "null pointer argument");
     ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
-    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
-    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
-    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
-    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
+    PairSetup s;
+    if (int rc = pair_setup(kind, n_atoms, extra, cutoff, cutoff_kind, flags, false, &s)) return rc;
     if (hi == lo) return 0;
-    int64_t blocks = (hi - lo + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    PairExtra x{};
-    if (extra)
-        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
-    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0, push = (flags & ANIHIP_PAIR_PUSH) ? 1 : 0;
-    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
-#define ANIHIP_LAUNCH_PAIR(K)                                                                                          \
-    hipLaunchKernelGGL((k_pair<K>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, lo, hi, species, meta,   \
-                       (const float4 *)ent, pair_table, x, cutoff, smooth, push, clamp_r, atomic_e, grad_coords, virial)
-    switch (kind) {
-        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR(ANIHIP_PAIR_XTB); break;
-        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR(ANIHIP_PAIR_ZBL); break;
-        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR(ANIHIP_PAIR_LJ); break;
-        default: ANIHIP_LAUNCH_PAIR(ANIHIP_PAIR_COULOMB); break;
-    }
-#undef ANIHIP_LAUNCH_PAIR
+    const int push = (flags & ANIHIP_PAIR_PUSH) ? 1 : 0;
+    with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((k_pair<decltype(K)::value>), dim3(pair_blocks(hi - lo)), dim3(256), 0, (hipStream_t)stream, lo,
+                           hi, species, meta, (const float4 *)ent, pair_table, s.x, cutoff, s.smooth, push, s.clamp_r,
+                           atomic_e, grad_coords, virial);
+    });
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -643,35 +669,13 @@ extern "C" int anihip_pair_analytic_hvp(void *stream, int32_t kind, int64_t n_at
 {
     ANIHIP_REQUIRE(species && meta && ent && pair_table, "null pointer argument");
     ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
-    ANIHIP_REQUIRE(n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
-    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
-    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
-    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
-    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
-    ANIHIP_REQUIRE(!(flags & ANIHIP_PAIR_PUSH),
-                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    PairSetup s;
+    if (int rc = pair_setup(kind, n_atoms, extra, cutoff, cutoff_kind, flags, true, &s)) return rc;
     ANIHIP_REQUIRE(n_dir >= 0, "n_dir must not be negative");
     if (hi == lo || n_dir == 0) return 0;
     ANIHIP_REQUIRE(tangent && out, "null pointer argument");
-    int64_t blocks = (hi - lo + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    PairExtra x{};
-    if (extra)
-        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
-    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
-    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
-#define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
-    hipLaunchKernelGGL((k_pair_hvp<K>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_atoms, lo, hi,     \
-                       species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r, n_dir, tangent, out)
-    switch (kind) {
-        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
-        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;
-        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_LJ); break;
-        default: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_COULOMB); break;
-    }
-#undef ANIHIP_LAUNCH_PAIR_HVP
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
+    return pair_hvp_launch<Dir::Dense>(stream, kind, s, n_atoms, lo, hi, species, meta, ent, pair_table, cutoff, n_dir,
+                                       tangent, out, nullptr, nullptr, 0, StrainAcc{});
 }
 
 extern "C" int anihip_pair_analytic_hvp_items(void *stream, int32_t kind, int64_t n_atoms, const int32_t *species,
@@ -682,34 +686,11 @@ extern "C" int anihip_pair_analytic_hvp_items(void *stream, int32_t kind, int64_
 {
     ANIHIP_REQUIRE(species && meta && ent && pair_table && row_atom && row_dir && out, "null pointer argument");
     ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0 && n_dir >= 0, "negative size");
-    ANIHIP_REQUIRE(n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
-    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
-    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
-    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
-    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
-    ANIHIP_REQUIRE(!(flags & ANIHIP_PAIR_PUSH),
-                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    PairSetup s;
+    if (int rc = pair_setup(kind, n_atoms, extra, cutoff, cutoff_kind, flags, true, &s)) return rc;
     if (n_rows == 0 || n_dir == 0) return 0;
-    int64_t blocks = (n_rows + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    PairExtra x{};
-    if (extra)
-        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
-    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
-    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
-#define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
-    hipLaunchKernelGGL((k_pair_hvp<K, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_atoms,       \
-                       (int64_t)0, n_rows, species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r,   \
-                       n_dir, (const float *)nullptr, out, row_atom, row_dir, dir0)
-    switch (kind) {
-        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
-        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;
-        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_LJ); break;
-        default: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_COULOMB); break;
-    }
-#undef ANIHIP_LAUNCH_PAIR_HVP
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
+    return pair_hvp_launch<Dir::Item>(stream, kind, s, n_atoms, 0, n_rows, species, meta, ent, pair_table, cutoff, n_dir,
+                                      nullptr, out, row_atom, row_dir, dir0, StrainAcc{});
 }
 
 extern "C" int anihip_pair_analytic_hvp_strain(void *stream, int32_t kind, int64_t n_atoms, int64_t atoms_per_mol, int64_t lo,
@@ -722,35 +703,11 @@ extern "C" int anihip_pair_analytic_hvp_strain(void *stream, int32_t kind, int64
     ANIHIP_REQUIRE(atoms_per_mol >= 1 && n_atoms % atoms_per_mol == 0,
                    "atoms_per_mol must be >= 1 and divide n_atoms (got %lld, %lld)", (long long)atoms_per_mol,
                    (long long)n_atoms);
-    ANIHIP_REQUIRE(n_atoms <= (int64_t)IDX_MASK, "more atoms than a neighbor row can index");
-    ANIHIP_REQUIRE(cutoff > 0.f, "cutoff must be positive (the rows hold pairs up to their own radial cutoff)");
-    ANIHIP_REQUIRE(cutoff_kind == ANIHIP_CUTOFF_COSINE || cutoff_kind == ANIHIP_CUTOFF_SMOOTH, "unknown cutoff_kind");
-    ANIHIP_REQUIRE(kind >= ANIHIP_PAIR_XTB && kind <= ANIHIP_PAIR_COULOMB, "unknown pair potential kind");
-    ANIHIP_REQUIRE(kind != ANIHIP_PAIR_ZBL || extra, "ZBL needs its 4 + 4 screening constants");
-    ANIHIP_REQUIRE(!(flags & ANIHIP_PAIR_PUSH),
-                   "pair Hessian-vector products need symmetric rows (ANIHIP_PAIR_PUSH rows are not supported)");
+    PairSetup s;
+    if (int rc = pair_setup(kind, n_atoms, extra, cutoff, cutoff_kind, flags, true, &s)) return rc;
     if (hi == lo) return 0;
-    int64_t blocks = (hi - lo + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    PairExtra x{};
-    if (extra)
-        for (int k = 0; k < 8; ++k) x.v[k] = extra[k];
-    const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
-    const int clamp_r = (flags & ANIHIP_PAIR_NO_CLAMP) ? 0 : 1;
-#define ANIHIP_LAUNCH_PAIR_HVP(K)                                                                                      \
-    hipLaunchKernelGGL((k_pair_hvp<K, false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,        \
-                       n_atoms, lo, hi, species, meta, (const float4 *)ent, pair_table, x, cutoff, smooth, clamp_r,      \
-                       (int64_t)9, reinterpret_cast<const float *>(ss), out, reinterpret_cast<const int32_t *>(virial),   \
-                       (const int32_t *)nullptr, atoms_per_mol)
-    switch (kind) {
-        case ANIHIP_PAIR_XTB: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_XTB); break;
-        case ANIHIP_PAIR_ZBL: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_ZBL); break;
-        case ANIHIP_PAIR_LJ: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_LJ); break;
-        default: ANIHIP_LAUNCH_PAIR_HVP(ANIHIP_PAIR_COULOMB); break;
-    }
-#undef ANIHIP_LAUNCH_PAIR_HVP
-    ANIHIP_CHECK_HIP(hipGetLastError());
-    return 0;
+    return pair_hvp_launch<Dir::Strain>(stream, kind, s, n_atoms, lo, hi, species, meta, ent, pair_table, cutoff, 9, nullptr,
+                                        out, nullptr, nullptr, 0, StrainAcc{ss, virial, atoms_per_mol});
 }
 
 extern "C" int anihip_pair_xtb_repulsion(void *stream, int64_t n_atoms, int64_t lo, int64_t hi, const int32_t *species,
@@ -775,16 +732,15 @@ extern "C" int anihip_pair_d3(void *stream, int64_t n_atoms, int64_t lo, int64_t
     D3P p;
     p.s6 = params->s6; p.s8 = params->s8; p.a1 = params->a1; p.a2 = params->a2;
     for (int k = 0; k < 8; ++k) { p.cov[k] = params->cov_radius_bohr[k]; p.sq[k] = params->sqrt_q[k]; }
-    auto blocks_for = [](int64_t n) { int64_t b = (n + 3) / 4; return (unsigned)(b > 256 * 8 ? 256 * 8 : (b < 1 ? 1 : b)); };
     const int smooth = cutoff_kind == ANIHIP_CUTOFF_SMOOTH ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_d3_cn, dim3(blocks_for(n_atoms)), dim3(256), 0, st, n_atoms, species, meta,
+    hipLaunchKernelGGL(k_d3_cn, dim3(pair_blocks(n_atoms)), dim3(256), 0, st, n_atoms, species, meta,
                        (const float4 *)ent, p, cutoff, cn);
-    hipLaunchKernelGGL(k_d3_pair, dim3(blocks_for(n_atoms)), dim3(256), 0, st, n_atoms, lo, hi, species, meta,
+    hipLaunchKernelGGL(k_d3_pair, dim3(pair_blocks(n_atoms)), dim3(256), 0, st, n_atoms, lo, hi, species, meta,
                        (const float4 *)ent, (const float4 *)c6_table, p, cutoff, smooth, cn, gcn, atomic_e,
                        grad_coords, virial);
     if (grad_coords && hi > lo)
-        hipLaunchKernelGGL(k_d3_cngrad, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, species, meta,
+        hipLaunchKernelGGL(k_d3_cngrad, dim3(pair_blocks(hi - lo)), dim3(256), 0, st, lo, hi, species, meta,
                            (const float4 *)ent, p, cutoff, gcn, grad_coords, virial);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;

@@ -231,15 +231,20 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
                    cutoff: tp.Optional[float] = None) -> None:
         """atomic_e [N] += pair halves, grad_coords [N, 3] += gradient, virial [3, 3] += for the central atoms of nbrs."""
         _require_cuda(species32, atomic_e, grad_coords, virial)
-        cut = self.cutoff if cutoff is None else cutoff
-        if math.isinf(cut):
-            cut = 1e30   # the rows decide (with the envelope == 1 up to rounding at finite distances)
-        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
-        ex = self._extra()
         _lib.check(_lib.lib().anihip_pair_analytic(
             _stream(), self.kind, species32.numel(), nbrs.lo, nbrs.hi, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent),
-            _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
-            _lib.CUTOFF_KINDS[self.cutoff_fn], flags, _ptr(atomic_e), _ptr(grad_coords), _ptr(virial)))
+            *self._kernel_args(species32, nbrs, cutoff), _ptr(atomic_e), _ptr(grad_coords), _ptr(virial)))
+
+    def _kernel_args(self, species32: Tensor, nbrs: NeighborRows, cutoff: tp.Optional[float] = None) -> tuple:
+        """(table, extra constants, cutoff, cutoff kind, flags) of the anihip_pair_analytic* calls.  An infinite cutoff is
+        passed as 1e30: the rows decide (with the envelope == 1 up to rounding at finite distances)."""
+        cut = self.cutoff if cutoff is None else cutoff
+        if math.isinf(cut):
+            cut = 1e30
+        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
+        ex = self._extra()   # (a buffer the potential keeps: its address stays valid)
+        return (_ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
+                _lib.CUTOFF_KINDS[self.cutoff_fn], flags)
 
     def hvp(self, species32: Tensor, nbrs: NeighborRows, tangent: Tensor, out: Tensor,
             cutoff: tp.Optional[float] = None) -> None:
@@ -253,15 +258,9 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
             raise ValueError("tangent and out must be contiguous float32 tensors")
         if tangent.numel() != 3 * n * K or out.numel() != 3 * n * K:
             raise ValueError(f"tangent and out must be [K, {n}, 3]")
-        cut = self.cutoff if cutoff is None else cutoff
-        if math.isinf(cut):
-            cut = 1e30
-        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
-        ex = self._extra()
         _lib.check(_lib.lib().anihip_pair_analytic_hvp(
             _stream(), self.kind, n, nbrs.lo, nbrs.hi, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent),
-            _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
-            _lib.CUTOFF_KINDS[self.cutoff_fn], flags, K, _ptr(tangent), _ptr(out)))
+            *self._kernel_args(species32, nbrs, cutoff), K, _ptr(tangent), _ptr(out)))
 
     def hvp_items(self, species32: Tensor, nbrs: NeighborRows, row_atom: Tensor, row_dir: Tensor, dir0: int,
                   out: Tensor) -> None:
@@ -274,11 +273,8 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
             raise ValueError(f"out must be a contiguous float32 [K, {n}, 3] tensor")
         if math.isinf(self.cutoff):
             raise ValueError("an infinite cutoff has no sparse Hessian")
-        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
-        ex = self._extra()
         _lib.check(_lib.lib().anihip_pair_analytic_hvp_items(
-            _stream(), self.kind, n, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent), _ptr(self.table(species32.device)),
-            None if ex is None else ex.ctypes.data, float(self.cutoff), _lib.CUTOFF_KINDS[self.cutoff_fn], flags,
+            _stream(), self.kind, n, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent), *self._kernel_args(species32, nbrs),
             row_atom.numel(), _ptr(row_atom), _ptr(row_dir), dir0, out.shape[0], _ptr(out)))
 
     def hvp_strain(self, species32: Tensor, nbrs: NeighborRows, out: Tensor, ss: Tensor, virial: Tensor,
@@ -294,15 +290,9 @@ class _AnalyticPair(_Standalone, torch.nn.Module):
         if ss.dtype != torch.float64 or virial.dtype != torch.float64 or ss.shape != (nc, 9, 9) or \
                 virial.shape != (nc, 9) or nc == 0 or n % nc:
             raise ValueError("ss [C, 9, 9] and virial [C, 9] must be float64, C dividing the atoms")
-        cut = self.cutoff if cutoff is None else cutoff
-        if math.isinf(cut):
-            cut = 1e30
-        flags = (0 if nbrs.symmetric else _lib.PAIR_PUSH) | (0 if self.clamp_distances else _lib.PAIR_NO_CLAMP)
-        ex = self._extra()
         _lib.check(_lib.lib().anihip_pair_analytic_hvp_strain(
             _stream(), self.kind, n, n // nc, nbrs.lo, nbrs.hi, _ptr(species32), _ptr(nbrs.meta), _ptr(nbrs.ent),
-            _ptr(self.table(species32.device)), None if ex is None else ex.ctypes.data, float(cut),
-            _lib.CUTOFF_KINDS[self.cutoff_fn], flags, _ptr(out), _ptr(ss), _ptr(virial)))
+            *self._kernel_args(species32, nbrs, cutoff), _ptr(out), _ptr(ss), _ptr(virial)))
 
     def compute_from_rows(self, species32: Tensor, coords: Tensor, nbrs: NeighborRows) -> Tensor:
         """Molecular energies [C] (float64), differentiable with respect to coords."""
