@@ -1,6 +1,6 @@
 """Headline benchmark: ANI-2x energy+forces throughput (atom*steps/s) on a periodic water box.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1: one process per GPU over RCCL.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is
 one of the ranks; started plainly with --gpus N it launches the N ranks itself (torch.distributed.run on 127.0.0.1) and
@@ -12,12 +12,17 @@ the SAME box over the ranks (strong scaling): spatial slabs of the cell-sorted o
 ONE all-to-all per step over RCCL (halo force rows to the slab neighbours, the fp64 partial energies to everybody).
 Weights are seeded random parameters of the ANI-2x architecture (the published ones are a download), data is synthetic.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: it sets up, warms up, times the
+K steps, writes --dump-outputs if asked, and prints the contract fields with the workload's configuration.  With --full
+the line also carries what takes work of its own after the timed steps:
+  parity_sample : sampled atoms of the headline box against the fp64 oracle (the run fails outside the gates)
   roofline      : the fused radial+angular AEV forward kernel against the HBM roofline
   roofline_mfma : the ensemble stack (fwd + input-gradient bwd): the fp16 MFMA flops issued by the split-fp16
                   path for the EXECUTED work (layer 0 skips all-zero AEV slabs) against the dense fp16 MFMA peak
-  cpu_baseline  : the CPU oracle (float build, all host cores) timed on a bounded sub-box, N=1 only
   stages_ms     : per-stage device time of one step on this rank (HIP events on the engine's stream)
+  collective    : N > 1: what every rank saw and sent, the cost of cutting the partition
+  secondary     : N = 1: BASELINE configs 2 / 3 / 5 and the opt-in two-product backward on the headline box
+  cpu_baseline  : the CPU oracle (float build, all host cores) timed on a bounded sub-box, N=1 only
 """
 from __future__ import annotations
 
@@ -219,14 +224,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--waters-side", type=int, default=92, help="waters per box edge (92 -> 2,336,064 atoms)")
-    ap.add_argument("--cpu-side", type=int, default=36, help="waters per edge of the CPU-baseline sub-box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-2 / config-3 secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the result against the oracle and measure the stages, rooflines, "
+                         "secondary configurations and CPU baseline (the options below marked --full tune these)")
+    ap.add_argument("--cpu-side", type=int, default=36, help="--full: waters per edge of the CPU-baseline sub-box")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the config-2 / config-3 secondary measurements")
     ap.add_argument("--parity-sample", type=int, default=512,
-                    help="atoms of the headline box checked against the fp64 oracle after the timed loop (N = 1; 0 = skip)")
+                    help="--full: atoms of the headline box checked against the fp64 oracle after the timed loop (0 = skip)")
     ap.add_argument("--no-dense-stage", action="store_true",
-                    help="skip the extra (untimed-region) dense-MLP stage timing, e.g. under rocprofv3 so the "
-                         "kernel statistics hold the product configuration only")
+                    help="--full: skip the extra (untimed-region) dense-MLP stage timing")
     ap.add_argument("--dist-backend", default=None,
                     help="development aid: torch.distributed backend override (gloo lets several ranks share one "
                          "GPU to exercise the N>1 code path without RCCL); implies --share-gpu")
@@ -277,7 +284,7 @@ def main():
 
     from torchani_amd import _lib
     from torchani_amd.models import ANI2x
-    from torchani_amd.parallel import exchange_transport, init_from_env, shard_range
+    from torchani_amd.parallel import init_from_env, shard_range
 
     rank, world, local, group = init_from_env(args.dist_backend)
     if args.dist_backend == "gloo":
@@ -407,6 +414,52 @@ def main():
         dump_outputs(args.dump_outputs, out)
     model.aev_computer.last_neighbors().raise_on_overflow()
     assert torch.isfinite(out.energies).all() and torch.isfinite(out.forces).all()
+    # (for a box of 65 536 atoms or more the steps took this decision and it is cached: no work here)
+    sorted_copy = group is None and model._wants_locality_sort(species.to(torch.int32), coords, cell, pbc, species)
+
+    res = {
+        "metric": "atom*steps/sec (energy+forces) ANI-2x",
+        "value": n_atoms * args.steps / elapsed,
+        "unit": "atom*steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {
+            "arithmetic": "fp32 throughout; ensemble GEMMs as split-fp16 x3 MFMA with fp32 accumulation "
+                          "(fp32-class accuracy: per-atom energies within 1e-7 Ha of the fp64 reference)",
+            "workload": f"ANI-2x 8-member ensemble, {n_atoms}-atom periodic water box (0.1 atoms/A^3), "
+                        "energy+forces, seeded random weights",
+            "n_atoms": n_atoms, "box_A": float(cell_np[0, 0]),
+            "sharding": "spatial slabs of the coordinate-sorted order (any input order), each rank works on its slab + a "
+                        "5.1 A halo; ONE all-to-all per step: halo force rows to the slab neighbours only, partial "
+                        "energies to every rank; forces stay with the rank that owns the atoms (not gathered); the "
+                        "partition's validity is checked every step on the device and read one step late (no host sync)",
+            "shuffled_input": bool(args.shuffle), "evaluated_on_cell_sorted_copy": bool(sorted_copy),
+            # (False: the default arithmetic.  True: NOT the default -- see --two-product-backward)
+            "two_product_backward": bool(args.two_product_backward),
+        },
+        "ms_per_step_median": median_ms,
+        "energy_Ha": float(out.energies.reshape(-1)[0]),   # (total energy of the box: the same number at every N)
+    }
+    if args.full:
+        full_measurements(args, res, model, step, out, species, coords, cell, pbc, sorted_copy, group, rank, world, local,
+                          dev, elapsed_rank)
+    if rank == 0:
+        print(json.dumps(res))
+    if group is not None:
+        torch.distributed.barrier(group)
+        torch.distributed.destroy_process_group()
+
+
+def full_measurements(args, res, model, step, out, species, coords, cell, pbc, sorted_copy, group, rank, world, local, dev,
+                      elapsed_rank):
+    """--full: the oracle check of the last timed step's result and the measurements beyond the headline, all after the
+    timed steps; adds its objects to the line `res`."""
+    from torchani_amd import _lib
+    from torchani_amd.parallel import exchange_transport
+
+    n_atoms = species.shape[1]
     # ---- is the headline result RIGHT?  Sampled atoms of the full box against the fp64 oracle (outside the timed region):
     # the cluster within 2 Rcr of an atom reproduces its energy and force in the periodic box exactly (oracle/sampled_parity.py)
     # N > 1: rank 0 checks atoms it OWNS (forces stay with their owners; the clusters are cut from the whole box, which every
@@ -438,7 +491,6 @@ def main():
     lo, hi = 0, n_atoms
     n_local = n_atoms
     coords_l = coords
-    sorted_copy = group is None and model._wants_locality_sort(sp_given, coords, cell, pbc, species)
     if group is not None or sorted_copy:   # this rank's local system [left halo | owned | right halo] of the spatial
         # shards (one GPU, incoherent atom order: the cell-sorted copy the step works on, models.ANI.locality_sort)
         part = model._spatial_partition(sp_given, coords, cell, pbc, rank, world)
@@ -531,29 +583,7 @@ def main():
     mlp_tflops_dense = (flops_dense * n_shard / (st["mlp_fwd_bwd_dense"] * 1e-3) / 1e12
                         if "mlp_fwd_bwd_dense" in st else None)
 
-    res = {
-        "metric": "atom*steps/sec (energy+forces) ANI-2x",
-        "value": n_atoms * args.steps / elapsed,
-        "unit": "atom*steps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {
-            "arithmetic": "fp32 throughout; ensemble GEMMs as split-fp16 x3 MFMA with fp32 accumulation "
-                          "(fp32-class accuracy: per-atom energies within 1e-7 Ha of the fp64 reference)",
-            "workload": f"ANI-2x 8-member ensemble, {n_atoms}-atom periodic water box (0.1 atoms/A^3), "
-                        "energy+forces, seeded random weights",
-            "n_atoms": n_atoms, "box_A": float(cell_np[0, 0]),
-            "sharding": "spatial slabs of the coordinate-sorted order (any input order), each rank works on its slab + a "
-                        "5.1 A halo; ONE all-to-all per step: halo force rows to the slab neighbours only, partial "
-                        "energies to every rank; forces stay with the rank that owns the atoms (not gathered); the "
-                        "partition's validity is checked every step on the device and read one step late (no host sync)",
-            "shuffled_input": bool(args.shuffle), "evaluated_on_cell_sorted_copy": bool(sorted_copy),
-            # (False: the default arithmetic.  True: NOT the default -- see --two-product-backward)
-            "two_product_backward": bool(args.two_product_backward),
-        },
-        "ms_per_step_median": median_ms,
+    res.update({
         "roofline": {
             # `achieved` / `frac`: the kernel that MOVES the algorithmic bytes of SURVEY 8(d) -- every row written in full into a
             # caller's buffer (AEVComputer.forward; bytes moved = bytes counted) -- timed live in this run.  The step itself runs
@@ -625,8 +655,7 @@ def main():
         },
         "stages_ms": st,
         "parity_sample": parity,
-        "energy_Ha": float(out.energies.reshape(-1)[0]),   # (total energy of the box: the same number at every N)
-    }
+    })
     if group is not None:
         per_rank = [None] * world
         torch.distributed.all_gather_object(per_rank, st, group=group)
@@ -711,10 +740,6 @@ def main():
                     # itself would do here if the ratio carries over
                     res["cpu_baseline"]["port_over_reference"] = ratio
                     res["cpu_baseline"]["reference_equivalent"] = res["cpu_baseline"]["value"] / ratio
-        print(json.dumps(res))
-    if group is not None:
-        torch.distributed.barrier(group)
-        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -259,7 +259,8 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--waters-side", "16", "--dist-backend", "gloo", "--no-dense-stage", "--no-secondary", "--no-cpu-baseline", "--parity-sample", "128"]
+           "--warmup", "1", "--waters-side", "16", "--dist-backend", "gloo", "--full", "--no-dense-stage", "--no-secondary", "--no-cpu-baseline",
+           "--parity-sample", "128"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -296,7 +297,7 @@ def test_bench_four_ranks_gloo_equals_one_rank():
     assert p1.returncode == 0, p1.stdout[-2000:] + p1.stderr[-4000:]
     one = json.loads([ln for ln in p1.stdout.splitlines() if ln.startswith("{")][0])
     pw = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
-                         "--parity-sample", "128"] + common, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                         "--full", "--parity-sample", "128"] + common, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert pw.returncode == 0, pw.stdout[-2000:] + pw.stderr[-4000:]
     lines = [ln for ln in pw.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, pw.stdout[-2000:]
@@ -326,7 +327,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--waters-side", "16",
-           "--dist-backend", "gloo", "--no-dense-stage", "--no-secondary", "--no-cpu-baseline", "--parity-sample", "128"]
+           "--dist-backend", "gloo", "--full", "--no-dense-stage", "--no-secondary", "--no-cpu-baseline", "--parity-sample", "128"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -2321,7 +2321,7 @@ def test_network_arithmetic_under_weight_distribution_stress(dev, oracle64, name
 def test_headline_scale_sampled_parity(dev):
     """>= 1 M atoms (several network chunks, 32-bit row offsets, bin-local coordinates in a 220 A box): 256 sampled atoms of
     a 1 073 733-atom periodic water box against the fp64 oracle on the 10.2 A clusters around them (oracle/sampled_parity.py;
-    bench.py runs the same check at 2.34 M atoms after its timed loop)."""
+    bench.py --full runs the same check at 2.34 M atoms after its timed loop)."""
     from bench import water_box
     from oracle.sampled_parity import sampled_parity
 
