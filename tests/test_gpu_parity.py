@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import GOLDEN_NAMES, load_golden, oracle_networks, oracle_params, seeded_state
+from _util import GOLDEN_NAMES, _stress_state, load_golden, oracle_networks, oracle_params, seeded_state
 from torchani_amd import _lib
 from torchani_amd.engine import PackedNetworks
 
@@ -2258,34 +2258,6 @@ def test_aev_with_unequally_spaced_shifts(dev, oracle64):
         report(f"aev   custom shifts (flags={want_flags})   max|aev err| = {err:.2e}   vjp err = {verr:.2e} (|vjp|max {vmag:.1f})")
         assert err < AEV_TOL
         assert verr <= VJP_REG_REL * max(1.0, vmag)
-
-
-def _stress_state(case, seed=11):
-    """ANI-2x x 8 parameter sets that stress the split-fp16 network arithmetic (its power-of-two scales come from
-    weight-norm BOUNDS, include/anihip.h: anihip_mlp_desc.fused_bounds) away from the uniform +-1/sqrt(fan_in) init."""
-    from torchani_amd.weights import NN_PREFIX, random_state_dict
-
-    sd = {k: v.copy() for k, v in random_state_dict("ani2x", 8, seed).items()}
-    rs = np.random.RandomState(seed + 1)
-    layer_of = lambda k: 3 if ".final_layer." in k else int(k.split(".layers.")[1].split(".")[0])   # noqa: E731
-    if case.startswith("scale"):
-        sc = {"scale_small": (0.125, 0.125, 0.125, 0.125), "scale_large": (8.0, 8.0, 8.0, 8.0),
-              "scale_mixed": (8.0, 0.125, 8.0, 0.125)}[case]
-        for k in sd:
-            if k.startswith(NN_PREFIX):
-                sd[k] = (sd[k] * np.float32(sc[layer_of(k)])).astype(np.float32)
-    elif case == "student_t":
-        for k in sd:
-            if k.startswith(NN_PREFIX) and k.endswith("weight"):
-                bound = 1.0 / np.sqrt(sd[k].shape[1])
-                sd[k] = (rs.standard_t(3, size=sd[k].shape) * bound / np.sqrt(3.0)).astype(np.float32)
-    elif case == "outlier_row":
-        for sym, layer, r in (("H", 1, 7), ("O", 0, 100), ("C", 2, 3)):
-            k = f"{NN_PREFIX}members.3.atomics.{sym}.layers.{layer}.weight"
-            sd[k][r] *= np.float32(100.0)
-    else:
-        raise ValueError(case)
-    return sd
 
 
 @pytest.mark.parametrize("case", ["scale_small", "scale_large", "scale_mixed", "student_t", "outlier_row"])

@@ -2611,8 +2611,15 @@ extern "C" int anihip_mlp_weight_grads(void *stream_, const anihip_mlp_desc *d, 
         if (!forward_done)
             if (int rc = train_forward_fused(stream, d, n_atoms, lo, hi, species, aev, w, dlt, atomic_e)) return rc;
         const int cr_chunks = (int)((n + CR_ROWS - 1) / CR_ROWS) + S;
-        // (max |d Loss / d atomic_e| over the atoms of this call: the fp16 scale of the weight-gradient kernels' D operand)
-        if (ANIHIP_WGRAD_F16) launch_absmax(stream, grad_atomic_e + lo, n, w.amax, AMAX_STAGE_GATOM);
+        // (max |d Loss / d atomic_e| over the real atoms of this call: the fp16 scale of the weight-gradient kernels' D operand.
+        // k_absmax only raises the slots: they are zeroed here, not just by the species bucketing of the forward -- a second
+        // call on the same forward (forward_done) would otherwise keep the larger maximum of the first, and a D operand
+        // scaled for it loses bits of a much smaller upstream to fp16's subnormal range.  Padding atoms are skipped for the
+        // same reason: their upstream reaches no gradient)
+        if (ANIHIP_WGRAD_F16) {
+            zero_words_async(stream, w.amax + AMAX_STAGE_GATOM * MAX_S * AMAX_SLOTS, sizeof(unsigned) * AMAX_SLOTS);
+            launch_absmax(stream, grad_atomic_e + lo, species + lo, n, w.amax, AMAX_STAGE_GATOM);
+        }
         for (int l = nl - 1; l >= 0; --l) {
             const bool output_layer = l == nl - 1;
             ColReduceArgs c{};

@@ -17,7 +17,8 @@ constexpr int AMAX_STAGES = 8, AMAX_SLOTS = 32;
 constexpr int AMAX_WORDS = AMAX_STAGES * MAX_S * AMAX_SLOTS;
 // stages 0..5: the layer-by-layer kernels and the fused kernel's d0 scale; of the training step's weight gradients:
 constexpr int AMAX_STAGE_ACT0 = 6;    // [species] max |act0| over the tiles and members of the fused training kernel
-constexpr int AMAX_STAGE_GATOM = 7;   // [0] max |d Loss / d atomic_e| over the atoms of the call
+constexpr int AMAX_STAGE_GATOM = 7;   // [0] max |d Loss / d atomic_e| over the real atoms of the call (its slots are zeroed by the
+                                      // species bucketing AND by anihip_mlp_weight_grads before k_absmax: calls on one forward)
 
 // dW = D^T X over the rows (atoms) of one species on v_mfma_f32_32x32x16_bf16 with three-way bf16 splits (train.hip)
 struct WgradB3Problem {
@@ -58,7 +59,7 @@ struct WgradB3Args {
 };
 // rows_total: atoms of all species together (bounds the number of row chunks)
 void launch_wgrad_b3(hipStream_t stream, const WgradB3Args &a, int64_t rows_total);
-void launch_absmax(hipStream_t stream, const float *x, int64_t n, unsigned *amax, int stage);
+void launch_absmax(hipStream_t stream, const float *x, const int32_t *species, int64_t n, unsigned *amax, int stage);
 
 // anihip_mlp_repack of an ANIHIP_MLP_F16X3 descriptor (train.hip)
 int repack_f16(hipStream_t stream, const anihip_mlp_desc *d, const void *const *src, const int32_t *out_in, int32_t *status,

@@ -64,12 +64,13 @@ __device__ __forceinline__ float pow2_scale_of(float mx)   // mx * scale in [2^1
     const int e = (int)(__float_as_uint(mx) >> 23) - 127;
     return __uint_as_float((unsigned)(127 + 13 - e) << 23);
 }
-// max |x| over n floats into the running-max table (slot of the stage, species 0)
-__global__ __launch_bounds__(256) void k_absmax(const float *x, int64_t n, unsigned *amax, int stage)
+// max |x| over n floats into the running-max table (slot of the stage, species 0); species non-NULL: over the atoms with a
+// network only (the upstream of a padding atom reaches no gradient and must not set the scale of the real atoms' rows)
+__global__ __launch_bounds__(256) void k_absmax(const float *x, const int32_t *species, int64_t n, unsigned *amax, int stage)
 {
     float m = 0.f;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        m = fmaxf(m, fabsf(x[i]));
+        if (!species || species[i] >= 0) m = fmaxf(m, fabsf(x[i]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0 && m > 0.f)
@@ -388,12 +389,12 @@ void launch_wgrad_b3(hipStream_t stream, const WgradB3Args &a, int64_t rows_tota
     }
 }
 
-void launch_absmax(hipStream_t stream, const float *x, int64_t n, unsigned *amax, int stage)
+void launch_absmax(hipStream_t stream, const float *x, const int32_t *species, int64_t n, unsigned *amax, int stage)
 {
     if (n <= 0) return;
     int64_t blocks = (n + 1023) / 1024;
     if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(k_absmax, dim3((unsigned)blocks), dim3(256), 0, stream, x, n, amax, stage);
+    hipLaunchKernelGGL(k_absmax, dim3((unsigned)blocks), dim3(256), 0, stream, x, species, n, amax, stage);
 }
 
 // ---- Adam ---------------------------------------------------------------------------------------------------------------
