@@ -361,6 +361,31 @@ int anihip_block_hessian_prepare(void *stream, int64_t n_atoms, int64_t nnz, con
 int anihip_block_hessian_spmm(void *stream, int64_t n_atoms, int32_t m, const int64_t *coff, const int32_t *rows,
                               const float *ablocks, const float *x, float *y);
 
+/* L-BFGS geometry optimization of a batch of molecules (torchani_amd.geomopt, csrc/lbfgs.hip): one step of ASE's LBFGS
+ * without line search for every molecule c of [n_mol][atoms_per_mol] that has not converged.  active uint8 [C][A] (0: padding
+ * or fixed atom: its force is taken as zero, it never moves), coords fp32 [C][A][3] (x_k, moved IN PLACE to x_k+1), forces
+ * fp32 [C][A][3] (f_k at coords).  Per molecule:  converged[c] |= max_i |f_i| < fmax, and a converged molecule is left
+ * untouched (last_step zero, n_steps unchanged); else the pair (x_k - x_k-1, f_k-1 - f_k) is stored if its curvature s.y
+ * (fp64) is positive, the oldest pair dropped beyond `memory`, p = -H f-gradient with H0 = inv_alpha I, scaled to the
+ * longest atom step maxstep, and x_k+1 = x_k + damping p; last_step fp32 [C][A][3] = the displacement applied,
+ * n_steps[c] += 1.  workspace: anihip_lbfgs_workspace_bytes(n_mol, atoms_per_mol, memory) bytes, ZERO-FILLED before the
+ * first step and kept between steps (it holds the history); converged uint8 [C] and n_steps int32 [C] are caller state
+ * too.  Four launches, whatever memory, n_mol and atoms_per_mol; no atomics: bit-identical run to run. */
+#define ANIHIP_LBFGS_MAX_MEMORY 256
+typedef struct {
+    int32_t n_mol, atoms_per_mol;
+    int32_t memory;   /* stored pairs, 1 .. ANIHIP_LBFGS_MAX_MEMORY */
+    int32_t flags;    /* 0 */
+    double inv_alpha; /* H0 = inv_alpha I (Angstrom^2 / Hartree) */
+    double maxstep;   /* Angstrom */
+    double damping;
+    double fmax;      /* Hartree / Angstrom */
+} anihip_lbfgs_params;
+size_t anihip_lbfgs_workspace_bytes(int64_t n_mol, int64_t atoms_per_mol, int32_t memory);   /* 0 + anihip_last_error() */
+int anihip_lbfgs_step(void *stream, const anihip_lbfgs_params *params, const uint8_t *active, float *coords,
+                      const float *forces, void *workspace, size_t workspace_bytes, float *last_step, uint8_t *converged,
+                      int32_t *n_steps);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -1,0 +1,338 @@
+"""Batched L-BFGS geometry optimization (torchani_amd.geomopt, anihip_lbfgs_step) on the MI355X: lock-step parity of every
+step against the fp64 two-loop reference (tests/_geomopt_ref.py) on padded ANI-2x batches, a periodic box and the 46 357-atom
+solvated box; the Lennard-Jones minima of LJ13 and LJ7; the optimized LJ13 through the Hessian and vibrational analysis;
+fixed atoms, convergence checked by an independent evaluation, bit-identical runs and no host synchronization in step()."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from _geomopt_ref import LbfgsReference
+from _util import load_golden, seeded_state
+
+pytestmark = pytest.mark.gpu
+
+REPORT = os.environ.get("TORCHANI_AMD_GEOMOPT_REPORT")
+PARITY = 1e-4   # max |last_step - dr_ref| <= PARITY * max |dr_ref|, per molecule and step
+LJ13_MIN, LJ7_MIN = -44.326801, -16.505384   # Wales and Doye (1997), in eps
+# The fp32 coordinates resolve a position near 1 sigma to 1.2e-7 sigma; at LJ force constants of ~60 eps / sigma^2 that is a
+# force grid of several 1e-6 eps / sigma, below which no fp32 optimizer can go: the minima are asked for at 1e-5.
+LJ_FMAX = 1e-5
+
+
+def report(line):
+    print(line)
+    if not REPORT:
+        return
+    try:
+        os.makedirs(os.path.dirname(REPORT) or ".", exist_ok=True)
+        with open(REPORT, "a") as f:
+            f.write(line + "\n")
+    except OSError:
+        pass
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from torchani_amd import _lib
+
+    _lib.lib()
+    return torch.device("cuda:0")
+
+
+def _ani_case(base, dev, **kw):
+    from torchani_amd.models import ANI1x, ANI2x
+
+    g = load_golden(base)
+    sp = torch.from_numpy(g["species"].astype(np.int64)).to(dev)
+    x = torch.from_numpy(g["coords"]).to(dev)
+    cell = None if g["cell"] is None else torch.from_numpy(g["cell"]).to(dev)
+    pbc = None if g["pbc"] is None else torch.from_numpy(np.asarray(g["pbc"])).to(dev)
+    ctor = ANI2x if g["kind"] == "ani2x" else ANI1x
+    model = ctor(state_dict=seeded_state(g["kind"], 8, g["seed"]), device=dev, periodic_table_index=False,
+                 cutoff_fn=g["cutoff_fn"], row_capacity=256, **kw)
+    return model, sp, x, cell, pbc
+
+
+def _lockstep(model, sp, x, cell, pbc, memory, n_steps, fixed=None, **kw):
+    """Steps the optimizer one at a time; the reference builds its own history from the x_k, f_k read back before each
+    step.  Returns the worst max |last_step - dr_ref| / max |dr_ref| over molecules and steps, and the reference."""
+    from torchani_amd.geomopt import GeometryOptimizer
+
+    opt = GeometryOptimizer(model, sp, x, cell, pbc, memory=memory, fixed=fixed, **kw)
+    active = (sp >= 0) if fixed is None else (sp >= 0) & ~fixed
+    active = active.cpu().numpy()
+    p = opt._params
+    ref = LbfgsReference(sp.shape[0], memory, p.maxstep, 1.0 / p.inv_alpha, p.damping, opt.fmax)
+    worst = 0.0
+    for k in range(n_steps):
+        xk, fk = opt.coordinates.cpu().numpy(), opt.forces.cpu().numpy()
+        opt.step()
+        dr = ref.step(xk, fk, active)
+        got = opt.last_step.cpu().numpy()
+        assert np.array_equal(opt.converged.cpu().numpy(), ref.converged), k
+        assert np.array_equal(opt.n_steps.cpu().numpy(), ref.n_steps), k
+        for c in range(sp.shape[0]):
+            scale = np.abs(dr[c]).max()
+            err = np.abs(got[c] - dr[c]).max()
+            if scale == 0.0:
+                assert err == 0.0, (k, c)
+                continue
+            worst = max(worst, err / scale)
+            assert err <= PARITY * scale, (k, c, err / scale)
+    return worst, ref
+
+
+@pytest.mark.parametrize("memory", [5, 100])
+def test_lockstep_padded_batch(dev, memory):
+    model, sp, x, cell, pbc = _ani_case("rand_batch_ani2x", dev)
+    assert bool((sp < 0).any())   # padding atoms
+    worst, _ = _lockstep(model, sp, x, cell, pbc, memory, 40)
+    report(f"geomopt lock-step rand_batch_ani2x, memory {memory}, 40 steps: worst |d last_step| / max |dr_ref| = {worst:.1e}")
+
+
+def test_lockstep_periodic(dev):
+    model, sp, x, cell, pbc = _ani_case("water_pbc_ani2x", dev)
+    worst, _ = _lockstep(model, sp, x, cell, pbc, 5, 30)
+    report(f"geomopt lock-step water_pbc_ani2x, memory 5, 30 steps: worst |d last_step| / max |dr_ref| = {worst:.1e}")
+
+
+def test_lockstep_solvated_box_46k(dev):
+    model, sp, x, cell, pbc = _ani_case("cfg3_1hz5_water_ani2x", dev)
+    worst, _ = _lockstep(model, sp, x, cell, pbc, 100, 15)
+    report(f"geomopt lock-step cfg3_1hz5_water_ani2x ({sp.numel()} atoms, {-(-3 * sp.numel() // 1024)} chunks), 15 steps: "
+           f"worst |d last_step| / max |dr_ref| = {worst:.1e}")
+
+
+def test_lockstep_batch_of_large_molecules(dev):
+    """Several molecules that each span several chunks of k_lb_dots (C > 1 and G > 1): two perturbed copies of 1hz5, the
+    second with padding atoms."""
+    model, sp, x, cell, pbc = _ani_case("1hz5_ani2x", dev)
+    assert sp.shape[0] == 1 and 3 * sp.shape[1] > 2 * 1024
+    gen = torch.Generator().manual_seed(5)
+    x2 = torch.cat([x, x + 0.02 * torch.randn(x.shape, generator=gen, dtype=torch.float64).to(dev, x.dtype)])
+    sp2 = sp.repeat(2, 1)
+    sp2[1, -17:] = -1
+    worst, _ = _lockstep(model, sp2, x2, cell, pbc, 5, 15)
+    report(f"geomopt lock-step 2 x 1hz5_ani2x ({sp.shape[1]} atoms, {-(-3 * sp.shape[1] // 1024)} chunks each), memory 5, "
+           f"15 steps: worst |d last_step| / max |dr_ref| = {worst:.1e}")
+
+
+def test_negative_curvature_pairs_are_rejected(dev):
+    """Lennard-Jones dimers started beyond the inflection point (r > 1.2445 sigma, where d2E / dr2 < 0): their first pairs
+    have s.y <= 0 and are not stored (ASE would store them); the kernel must skip exactly the pairs the reference skips."""
+    from torchani_amd.potentials import LennardJones
+
+    lj = LennardJones(("H",), eps=(1.0,), sigma=(1.0,)).to(dev)
+    x = torch.zeros((3, 2, 3), dtype=torch.float64)
+    x[:, 1, 0] = torch.tensor([1.5, 1.8, 2.2], dtype=torch.float64)
+    sp = torch.ones((3, 2), dtype=torch.int64, device=dev)
+    worst, ref = _lockstep(lj, sp, x.to(dev), None, None, 5, 12, alpha=70.0)
+    report(f"geomopt LJ dimers beyond the inflection point, 12 steps: pairs rejected {ref.rejected.tolist()}, stored "
+           f"{[len(p) for p in ref.pairs]}; worst |d last_step| / max |dr_ref| = {worst:.1e}")
+    assert np.all(ref.rejected >= 1)
+
+
+def _icosahedron(r):
+    phi = (1 + 5 ** 0.5) / 2
+    v = []
+    for a in (-1.0, 1.0):
+        for b in (-phi, phi):
+            v += [(0.0, a, b), (a, b, 0.0), (b, 0.0, a)]
+    v = np.array(v) / np.linalg.norm(v[0]) * r
+    return np.vstack([np.zeros((1, 3)), v])
+
+
+def _bipyramid():
+    t = 2 * np.pi * np.arange(5) / 5
+    ring = np.stack([0.95 * np.cos(t), 0.95 * np.sin(t), np.zeros(5)], axis=1)
+    return np.vstack([ring, [[0.0, 0.0, 0.59], [0.0, 0.0, -0.59]]])
+
+
+def _lj_batch(dev, n13=3, seed=0):
+    """n13 perturbed LJ13 icosahedra and one LJ7 pentagonal bipyramid padded to 13 atoms (eps = 1 Ha, sigma = 1 A)."""
+    from torchani_amd.potentials import LennardJones
+
+    rs = np.random.RandomState(seed)
+    xs, sps = [], []
+    for i in range(n13):
+        xs.append(_icosahedron(1.09) + rs.uniform(-0.04, 0.04, (13, 3)) * (i + 1) / n13)
+        sps.append(np.ones(13, dtype=np.int64))
+    x7 = np.zeros((13, 3))
+    x7[:7] = _bipyramid() + rs.uniform(-0.03, 0.03, (7, 3))
+    xs.append(x7)
+    sps.append(np.array([1] * 7 + [-1] * 6, dtype=np.int64))
+    lj = LennardJones(("H",), eps=(1.0,), sigma=(1.0,)).to(dev)
+    return lj, torch.from_numpy(np.stack(sps)).to(dev), torch.from_numpy(np.stack(xs)).to(dev)
+
+
+_LJ_CACHE = {}
+
+
+def _lj_minimized(dev):
+    """The LJ batch stepped to fmax = LJ_FMAX; the coordinates of every molecule when its convergence was seen."""
+    if "out" in _LJ_CACHE:
+        return _LJ_CACHE["out"]
+    from torchani_amd.geomopt import GeometryOptimizer
+
+    lj, sp, x = _lj_batch(dev)
+    opt = GeometryOptimizer(lj, sp, x, memory=100, alpha=70.0)
+    opt.fmax = LJ_FMAX
+    seen = {}
+    for k in range(3000):
+        opt.step()
+        if k % 10 == 9:
+            conv = opt.converged.cpu().numpy()
+            for c in np.nonzero(conv)[0]:
+                seen.setdefault(int(c), (k, opt.coordinates[c].clone()))
+            if conv.all():
+                break
+    _LJ_CACHE["out"] = (lj, sp, x, opt, seen)
+    return _LJ_CACHE["out"]
+
+
+def test_lennard_jones_minima(dev):
+    lj, sp, x, opt, seen = _lj_minimized(dev)
+    n_steps = opt.n_steps.cpu().numpy()
+    e = opt.energies.cpu().numpy()
+    report(f"geomopt LJ13 x 3 + LJ7 (padded), fmax {LJ_FMAX:.0e}: n_steps {n_steps.tolist()}, E {e.tolist()}")
+    assert bool(opt.converged.all())
+    ref = np.array([LJ13_MIN] * (sp.shape[0] - 1) + [LJ7_MIN])
+    assert np.all(np.abs(e - ref) <= 1e-5 * np.abs(ref)), e - ref
+    for c, (k, xc) in seen.items():   # frozen from its convergence on: bit-identical
+        assert torch.equal(opt.coordinates[c], xc), c
+    assert len(set(n_steps.tolist())) > 1
+    assert torch.equal(opt.coordinates[-1, 7:], x[-1, 7:].float())   # padding atoms never move
+
+
+def test_optimized_lj13_vibrational_analysis(dev):
+    from torchani_amd import grad
+
+    lj, sp, _, opt, _ = _lj_minimized(dev)
+    x13 = opt.coordinates[:1].double()
+    H = grad.energies_forces_and_hessians(lj, sp[:1], x13).hessians
+    masses = torch.full((1, 13), 39.948, dtype=torch.float64, device=dev)
+    va = grad.vibrational_analysis(masses, H.double())
+    f = va.freqs.cpu().numpy()
+    order = np.argsort(np.abs(f))
+    top = np.abs(f).max()
+    report(f"geomopt LJ13 minimum: six smallest |freq| / max {np.abs(f[order[:6]]).max() / top:.1e}, "
+           f"lowest vibration {f[order[6]]:.1f} cm^-1, highest {top:.1f} cm^-1")
+    assert np.abs(f[order[:6]]).max() <= 0.02 * top
+    assert np.all(f[order[6:]] > 0.05 * top) and len(order[6:]) == 33
+
+
+def test_returned_structures_meet_fmax(dev):
+    from torchani_amd import grad
+    from torchani_amd.geomopt import optimize_geometry
+
+    lj, sp, x = _lj_batch(dev, seed=1)
+    fmax = 1e-4
+    res = optimize_geometry(lj, sp, x, fmax=fmax, steps=2000, alpha=70.0)
+    assert res.coordinates.dtype == x.dtype and bool(res.converged.all())
+    ef = grad.energies_and_forces(lj, sp, res.coordinates.clone())
+    fn = ef.forces.norm(dim=-1).masked_fill(sp < 0, 0.0).amax(dim=1)
+    assert bool((fn < fmax).all()), fn.tolist()
+    assert torch.allclose(ef.energies, res.energies, rtol=0, atol=1e-9)
+
+    model, sp2, x2, cell, pbc = _ani_case("rand_batch_ani2x", dev)
+    res = optimize_geometry(model, sp2, x2, cell, pbc, steps=300)
+    out = model.energies_and_forces(sp2, res.coordinates)
+    fn = out.forces.norm(dim=-1).masked_fill(sp2 < 0, 0.0).amax(dim=1)
+    conv = res.converged
+    report(f"geomopt rand_batch_ani2x, default fmax, 300 steps: {int(conv.sum())} of {conv.numel()} converged, "
+           f"n_steps {res.n_steps.tolist()}")
+    assert bool((fn[conv] < 0.05 / 27.211386024367243 * (1 + 1e-4)).all())
+
+
+def test_fixed_atoms(dev):
+    from torchani_amd.geomopt import GeometryOptimizer, optimize_geometry
+
+    model, sp, x, cell, pbc = _ani_case("rand_batch_ani2x", dev)
+    fixed = torch.zeros_like(sp, dtype=torch.bool)
+    fixed[:, :3] = True
+    opt = GeometryOptimizer(model, sp, x, cell, pbc, fixed=fixed)
+    x0 = opt.coordinates.clone()
+    for _ in range(20):
+        opt.step()
+        assert torch.all(opt.last_step[fixed] == 0)
+    assert torch.equal(opt.coordinates[fixed], x0[fixed])
+    assert not torch.equal(opt.coordinates[~fixed & (sp >= 0)], x0[~fixed & (sp >= 0)])
+    _lockstep(model, sp, x, cell, pbc, 5, 15, fixed=fixed)
+
+    # an LJ13 whose centre and one outer atom are held 1.3 times too far apart (one held atom alone would not do: the free
+    # ones would move the cluster around it): it converges although the held atoms' forces stay large
+    lj, sp13, x13 = _lj_batch(dev, n13=1)
+    sp13, x13 = sp13[:1], x13[:1].clone()
+    x13[0, 1] = x13[0, 0] + 1.3 * (x13[0, 1] - x13[0, 0])
+    fixed13 = torch.zeros_like(sp13, dtype=torch.bool)
+    fixed13[0, :2] = True
+    fmax = 1e-4
+    res = optimize_geometry(lj, sp13, x13, fmax=fmax, steps=2000, alpha=70.0, fixed=fixed13)
+    fn = res.forces[0].norm(dim=-1)
+    report(f"geomopt LJ13 with two held atoms: converged {bool(res.converged[0])} in {int(res.n_steps[0])} steps, "
+           f"max |F| of the free atoms {fn[2:].max().item():.1e}, of the held ones {fn[:2].tolist()}")
+    assert bool(res.converged[0]) and torch.equal(res.coordinates[0, :2], x13[0, :2].float().double())
+    assert fn[2:].max().item() < fmax < fn[:2].min().item()
+
+
+def test_deterministic_forces_give_bit_identical_runs(dev):
+    from torchani_amd.geomopt import GeometryOptimizer
+
+    model, sp, x, cell, pbc = _ani_case("water_pbc_ani2x", dev)
+    model.deterministic_forces = True
+    runs = []
+    for _ in range(2):
+        opt = GeometryOptimizer(model, sp, x, cell, pbc, memory=10)
+        for _ in range(25):
+            opt.step()
+        runs.append((opt.coordinates.clone(), opt.last_step.clone(), opt.n_steps.clone()))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+def test_step_does_not_synchronize(dev):
+    from torchani_amd.geomopt import GeometryOptimizer
+
+    model, sp, x, cell, pbc = _ani_case("rand_batch_ani2x", dev)
+    opt = GeometryOptimizer(model, sp, x, cell, pbc)
+    for _ in range(3):   # (the third evaluation captures the automatic HIP graph)
+        opt.step()
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        for _ in range(5):
+            opt.step()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    assert int(opt.n_steps.max()) > 0
+
+
+def test_device_errors(dev):
+    from torchani_amd.geomopt import GeometryOptimizer, optimize_geometry
+
+    model, sp, x, cell, pbc = _ani_case("rand_batch_ani2x", dev)
+    with pytest.raises(ValueError, match="ROCm"):
+        GeometryOptimizer(model, sp.cpu(), x.cpu())
+    with pytest.raises(ValueError, match="memory"):
+        GeometryOptimizer(model, sp, x, memory=0)
+    with pytest.raises(ValueError, match="maxstep"):
+        GeometryOptimizer(model, sp, x, maxstep=0.0)
+    with pytest.raises(ValueError, match="fmax"):
+        optimize_geometry(model, sp, x, fmax=-1.0)
+    with pytest.raises(ValueError, match="fixed"):
+        GeometryOptimizer(model, sp, x, fixed=torch.zeros(sp.shape[1], dtype=torch.bool, device=dev))
+
+
+def test_result_is_a_copy(dev):
+    from torchani_amd.geomopt import GeometryOptimizer
+
+    model, sp, x, cell, pbc = _ani_case("rand_batch_ani2x", dev)
+    opt = GeometryOptimizer(model, sp, x.float(), cell, pbc)
+    res = opt.run(steps=3)
+    kept = [t.clone() for t in res]
+    opt.step()
+    assert all(torch.equal(a, b) for a, b in zip(res, kept))

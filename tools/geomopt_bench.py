@@ -1,0 +1,115 @@
+"""Per-iteration GPU time of the L-BFGS step (anihip_lbfgs_step: four kernels) next to the energies-and-forces evaluation it
+drives, at full history: memory = 100, fmax = 0 (nothing converges) and --iters > 100 iterations, so that the ring is full
+and wraps.  HIP events around each part of every iteration; medians over the iterations after the first 101.
+    python tools/geomopt_bench.py [--iters 130] [--json out.json] [--only config2,conformers2560,config3]
+    python tools/geomopt_bench.py --trace-summary run_kernel_trace.csv   (of `rocprofv3 --kernel-trace` over a run above:
+                                  the median time per kernel over the calls after the first 101, i.e. at full history)
+  config2        256 molecules of A = 28 (tests/golden/cfg2_xyz13_28_ani2x.npz), batch mode (graph replay from the third call)
+  conformers2560 those 256 molecules ten times over: 2560 conformers, 71 680 atom slots
+  config3        the 46 357-atom solvated 1hz5 box, periodic, cell mode
+Bytes moved per L-BFGS step are estimated from the shapes (lbfgs_step_bytes), so that the achieved rate can be compared
+with HBM: S and Y read twice in fp32 and the fp64 m x m matrices of k_lb_solve, which outweigh S and Y for small molecules."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def lbfgs_step_bytes(C, A, memory):
+    """Device bytes one step moves at full history, per molecule: k_lb_dots and k_lb_direction each read S and Y
+    [memory][3A] fp32; k_lb_solve reads the upper triangles of R^-1 (from its transpose, for a) and of R^-1 (for t) and all of
+    Y^T Y, fp64 m x m: 2 m^2 x 8 bytes.  (The partial sums, coordinates and forces are a few per cent on top.)"""
+    return C * (2 * 2 * memory * 3 * A * 4 + 2 * memory * memory * 8)
+
+
+def measure(name, model, sp, x, cell, pbc, iters, memory=100):
+    from torchani_amd.geomopt import GeometryOptimizer, lbfgs_workspace_bytes
+
+    opt = GeometryOptimizer(model, sp, x, cell, pbc, memory=memory)
+    opt.fmax = 0.0
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(iters)]
+    for k in range(iters):
+        e0, e1, e2 = ev[k]
+        e0.record()
+        opt._lbfgs_step()
+        e1.record()
+        opt._evaluate()
+        e2.record()
+    torch.cuda.synchronize()
+    opt.raise_on_overflow()
+    full = range(memory + 1, iters)
+    lb = np.array([ev[k][0].elapsed_time(ev[k][1]) for k in full]) * 1e3
+    ef = np.array([ev[k][1].elapsed_time(ev[k][2]) for k in full]) * 1e3
+    C, A = sp.shape
+    out = {"workload": name, "molecules": C, "atoms_per_molecule": A, "memory": memory, "iterations": iters,
+           "iterations_timed": len(lb), "lbfgs_us_median": float(np.median(lb)), "lbfgs_us_min": float(lb.min()),
+           "energies_forces_us_median": float(np.median(ef)), "ratio_median": float(np.median(lb) / np.median(ef)),
+           "step_MB": lbfgs_step_bytes(C, A, memory) / 1e6,
+           "step_TB_per_s": lbfgs_step_bytes(C, A, memory) / (np.median(lb) * 1e-6) / 1e12,
+           "workspace_MB": lbfgs_workspace_bytes(C, A, memory) / 1e6,
+           "n_steps_min": int(opt.n_steps.min())}
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def trace_summary(path, skip=101):
+    """Median duration (us) of each k_lb_* kernel over its calls after the first `skip`, and their sum."""
+    import collections
+    import csv
+
+    per = collections.defaultdict(list)
+    for r in csv.DictReader(open(path)):
+        if "k_lb_" in r["Kernel_Name"]:
+            name = r["Kernel_Name"].split("(")[0].replace("anihip::", "").replace("void ", "")
+            per[name].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    med = {k: float(np.median(v[skip:])) for k, v in per.items()}
+    return {"median_us_after_call": skip, **med, "sum_us": sum(med.values())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=130)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--only", default="config2,conformers2560,config3")
+    ap.add_argument("--trace-summary", default=None, metavar="CSV")
+    args = ap.parse_args()
+    if args.trace_summary:
+        print(json.dumps(trace_summary(args.trace_summary)))
+        return
+    assert args.iters > 101, "the history is full from iteration 101 on"
+    from torchani_amd.models import ANI2x
+
+    dev = torch.device("cuda:0")
+    want = args.only.split(",")
+    res = {}
+    with np.load(os.path.join(GOLD, "cfg2_xyz13_28_ani2x.npz")) as z:
+        sp2, x2 = z["species"].astype(np.int64), z["coords"]
+    if "config2" in want:
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="batch")
+        res["config2"] = measure("config 2: 256 molecules, A = 28", model, torch.from_numpy(sp2).to(dev),
+                                 torch.from_numpy(x2).to(dev), None, None, args.iters)
+    if "conformers2560" in want:
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="batch")
+        res["conformers2560"] = measure("2560 conformers, A = 28", model, torch.from_numpy(np.tile(sp2, (10, 1))).to(dev),
+                                        torch.from_numpy(np.tile(x2, (10, 1, 1))).to(dev), None, None, args.iters)
+    if "config3" in want:
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="cell")
+        with np.load(os.path.join(GOLD, "cfg3_1hz5_water_ani2x.npz")) as z:
+            sp3, x3, cell = z["species"].astype(np.int64), z["coords"], z["cell"]
+        res["config3"] = measure("config 3: 1hz5 solvated, 46 357 atoms, periodic", model, torch.from_numpy(sp3).to(dev),
+                                 torch.from_numpy(x3).to(dev), torch.from_numpy(cell).to(dev), (True, True, True), args.iters)
+    if args.json:
+        os.makedirs(os.path.dirname(args.json) or ".", exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -7,7 +7,7 @@ from . import constants, weights  # noqa: F401  (import-light; no torch needed)
 
 __all__ = ["AEVComputer", "ANINetworks", "ANIModel", "Ensemble", "SpeciesConverter", "SpeciesEnergies",
            "SpeciesAEV", "AtomicNetwork", "models", "grad", "parallel", "utils", "potentials", "ase", "md", "extras",
-           "single_point", "SelfEnergy"]
+           "single_point", "SelfEnergy", "geomopt"]
 
 
 def __getattr__(name):
@@ -16,7 +16,7 @@ def __getattr__(name):
     import importlib
 
     if name in ("models", "grad", "parallel", "engine", "aev", "nn", "tuples", "_lib", "utils", "potentials", "ase", "md",
-                "ops", "extras"):
+                "ops", "extras", "geomopt"):
         return importlib.import_module(f".{name}", __name__)
     if name in ("arch", "io", "electro"):   # host-side conveniences outside the hot path
         return importlib.import_module(f".extras.{name}", __name__)

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -41,6 +41,7 @@ ABI_VERSION = 12
 REPACK_FUSED_ONLY = 1
 BLOCK_HESSIAN_MAX_VECTORS = 64   # ANIHIP_BLOCK_HESSIAN_MAX_VECTORS
 BLOCK_HESSIAN_BAD_INDEX, BLOCK_HESSIAN_NO_PARTNER, BLOCK_HESSIAN_NO_DIAGONAL = 1, 2, 4
+LBFGS_MAX_MEMORY = 256   # ANIHIP_LBFGS_MAX_MEMORY
 
 
 class AevParams(C.Structure):
@@ -105,6 +106,12 @@ class MlpDesc(C.Structure):
         ("activation", C.c_int32),
         ("net", SpeciesNet * MAX_SPECIES),
     ]
+
+
+class LbfgsParams(C.Structure):
+    """anihip_lbfgs_params (include/anihip.h)."""
+    _fields_ = [("n_mol", C.c_int32), ("atoms_per_mol", C.c_int32), ("memory", C.c_int32), ("flags", C.c_int32),
+                ("inv_alpha", C.c_double), ("maxstep", C.c_double), ("damping", C.c_double), ("fmax", C.c_double)]
 
 
 class MlpShape(C.Structure):
@@ -245,6 +252,10 @@ def lib() -> C.CDLL:
     L.anihip_block_hessian_prepare.restype = C.c_int
     L.anihip_block_hessian_spmm.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
     L.anihip_block_hessian_spmm.restype = C.c_int
+    L.anihip_lbfgs_workspace_bytes.restype = sz
+    L.anihip_lbfgs_workspace_bytes.argtypes = [i64, i64, i32]
+    L.anihip_lbfgs_step.argtypes = [vp, C.POINTER(LbfgsParams), vp, vp, vp, vp, sz, vp, vp, vp]
+    L.anihip_lbfgs_step.restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
     for name in ("anihip_aev_table_pack", "anihip_nbr_build_batch", "anihip_nbr_build_cell", "anihip_nbr_from_half",
@@ -274,6 +285,7 @@ EXPORTED_SYMBOLS = [
     "anihip_mlp_rows_hvp_prepare", "anihip_mlp_rows_hvp", "anihip_pair_analytic_hvp_items",
     "anihip_block_hessian_prepare", "anihip_block_hessian_spmm",
     "anihip_aev_jvp_strain_items", "anihip_aev_backward_second_strain_items", "anihip_pair_analytic_hvp_strain",
+    "anihip_lbfgs_workspace_bytes", "anihip_lbfgs_step",
 ]
 
 

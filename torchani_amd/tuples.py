@@ -113,6 +113,19 @@ class VibAnalysis(tp.NamedTuple):
     rmasses: Tensor
 
 
+class OptimizedGeometries(tp.NamedTuple):
+    """What geomopt.GeometryOptimizer.run / geomopt.optimize_geometry return: coordinates [C, A, 3] in the input dtype,
+    energies [C] (float64) and forces [C, A, 3] of a final evaluation at those coordinates, converged (bool [C]) and
+    n_steps (int32 [C], the steps each molecule moved)."""
+
+    species: Tensor
+    coordinates: Tensor
+    energies: Tensor
+    forces: Tensor
+    converged: Tensor
+    n_steps: Tensor
+
+
 class SparseVibAnalysis(tp.NamedTuple):
     """What grad.sparse_vibrational_analysis returns for C molecules and k modes: freqs [C, k], modes [C, k, A, 3],
     fconstants [C, k] and rmasses [C, k] as in VibAnalysis (zero on padding atoms), eigenvalues [C, k] of the mass-weighted
