@@ -1694,97 +1694,101 @@ struct MlpWorkspace {
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// the next piece of `bytes` at offset `off` of the workspace, 256-byte aligned (NULL while only its size is worked out)
+static char *take(char *base, size_t &off, size_t bytes)
+{
+    char *p = base ? base + off : nullptr;
+    off += align256(bytes);
+    return p;
+}
+
+// widest species at layer boundary l (dims[l])
+static int max_width(const anihip_mlp_desc *d, int l)
+{
+    int mx = 0;
+    for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l] ? mx : d->net[s].dims[l];
+    return mx;
+}
+
+// layer-0 reduction length: the slab order of the fp16 planes (radial part padded to 32, then one 32-wide slab per species
+// pair) or the plain AEV order padded to 32
+static int layer0_width(const anihip_mlp_desc *d, bool slab_order)
+{
+    const int L = d->aev_len, kp_rad = slab_order ? d->aev_radial_len : 0;
+    return kp_rad > 0 ? 32 * ((kp_rad + 31) / 32 + (L - kp_rad) / 32) : ((L + 31) / 32) * 32;
+}
+
 // n_act: hidden-layer buffers carved (-1: all of them, what the layer-by-layer kernels and the training passes use; the fused
 // kernel needs act[0] for its d E / d act0 hand-over, and none at all with the layer-0 backward inside)
 static size_t mlp_carve(const anihip_mlp_desc *d, int64_t n, char *base, MlpWorkspace *w, int n_act = -1)
 {
     size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    int *ctl = (int *)take(sizeof(int) * (CTL_WORDS + AMAX_WORDS));
-    int *perm = (int *)take(sizeof(int) * (size_t)(n + 1));
-    float *mpart = (float *)take(sizeof(float) * (size_t)(n + 1) * (size_t)d->n_members);
+    int *ctl = (int *)take(base, off, sizeof(int) * (CTL_WORDS + AMAX_WORDS));
+    int *perm = (int *)take(base, off, sizeof(int) * (size_t)(n + 1));
+    float *mpart = (float *)take(base, off, sizeof(float) * (size_t)(n + 1) * (size_t)d->n_members);
     const size_t tiles = (size_t)((n + 31) / 32) + ANIHIP_MAX_SPECIES;   // (finest tiling of the fused kernel)
-    int4 *ttab = (int4 *)take(sizeof(int4) * tiles);
+    int4 *ttab = (int4 *)take(base, off, sizeof(int4) * tiles);
     // (row lists: 32 per tile at the finest tiling, 64 per tile at the coarsest, which has up to one partly filled tile
     // per species more rows than atoms)
-    int *trows = (int *)take(sizeof(int) * (32 * tiles + 64 * (size_t)ANIHIP_MAX_SPECIES));
+    int *trows = (int *)take(base, off, sizeof(int) * (32 * tiles + 64 * (size_t)ANIHIP_MAX_SPECIES));
     const size_t tiles64 = (size_t)((n + 63) / 64) + ANIHIP_MAX_SPECIES;
     const size_t qtiles = tiles64 <= (size_t)FUSED_TILE_QUEUE_MAX ? tiles64 : 0;
-    int4 *ttab2 = (int4 *)take(sizeof(int4) * qtiles);
-    int *trows2 = (int *)take(sizeof(int) * 64 * qtiles);
+    int4 *ttab2 = (int4 *)take(base, off, sizeof(int4) * qtiles);
+    int *trows2 = (int *)take(base, off, sizeof(int) * 64 * qtiles);
     if (w) {
         w->ctl = ctl; w->amax = (unsigned *)(ctl + CTL_WORDS); w->perm = perm; w->member_part = mpart;
         w->tile_tab = ttab; w->tile_rows = trows; w->tile_tab2 = qtiles ? ttab2 : nullptr; w->tile_rows2 = qtiles ? trows2 : nullptr;
     }
     const int nh = d->net[0].n_layers - 1;  // hidden layers
     for (int l = 0; l < nh; ++l) {
-        int mx = 0;
-        for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
-        int64_t ld = (int64_t)mx * d->n_members;
+        const int64_t ld = (int64_t)max_width(d, l + 1) * d->n_members;
         if (n_act >= 0 && l >= n_act) {
             if (w) { w->act[l] = nullptr; w->ld[l] = ld; }
             continue;
         }
         // (layer 0 doubles as the tile-major d E / d act0 buffer: one partly filled 64-row block per species)
-        float *a = (float *)take(sizeof(float) * (size_t)ld * (size_t)(n + 1 + (l == 0 ? 64 * ANIHIP_MAX_SPECIES : 0)));
+        float *a = (float *)take(base, off, sizeof(float) * (size_t)ld * (size_t)(n + 1 + (l == 0 ? 64 * ANIHIP_MAX_SPECIES : 0)));
         if (w) { w->act[l] = a; w->ld[l] = ld; }
     }
     return off;
 }
 
-// pre-activation buffers of the hidden layers behind offset `off` (GELU training passes only; CELU: none)
-static size_t carve_zp(const anihip_mlp_desc *d, int64_t n, char *base, size_t off, MlpWorkspace *w)
+// k buffers of the widest species' width x M x (rows + 1) floats per hidden layer behind offset `off`: buf[j][l]
+static size_t carve_layers(const anihip_mlp_desc *d, int64_t rows, char *base, size_t off, int k,
+                           float *(*buf)[ANIHIP_MAX_LAYERS])
 {
     const int nh = d->net[0].n_layers - 1;
+    for (int j = 0; j < k; ++j)
+        for (int l = 0; l < nh; ++l) {
+            float *b = (float *)take(base, off, sizeof(float) * (size_t)max_width(d, l + 1) * d->n_members * (size_t)(rows + 1));
+            if (buf) buf[j][l] = b;
+        }
+    return off;
+}
+
+// what the training, tangent and HVP passes start from: the inference workspace with every activation kept + the
+// pre-activations of the hidden layers (GELU networks only; CELU: none)
+static size_t kept_carve(const anihip_mlp_desc *d, int64_t n, char *base, MlpWorkspace *w)
+{
+    size_t off = mlp_carve(d, n, base, w);
     for (int l = 0; l < ANIHIP_MAX_LAYERS; ++l)
         if (w) w->zp[l] = nullptr;
-    if (d->activation != ANIHIP_ACT_GELU) return off;
-    for (int l = 0; l < nh; ++l) {
-        int mx = 0;
-        for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
-        if (w) w->zp[l] = base ? (float *)(base + off) : nullptr;
-        off += align256(sizeof(float) * (size_t)mx * d->n_members * (size_t)(n + 1));
-    }
+    if (d->activation == ANIHIP_ACT_GELU) off = carve_layers(d, n, base, off, 1, w ? &w->zp : nullptr);
     return off;
 }
 
-// training pass: the inference workspace + one gradient buffer per hidden layer (the activations are kept)
+// training pass: + one gradient buffer per hidden layer
 static size_t mlp_train_carve(const anihip_mlp_desc *d, int64_t n, char *base, MlpWorkspace *w,
-                              float **dlt /* [ANIHIP_MAX_LAYERS] */)
+                              float *(*dlt)[ANIHIP_MAX_LAYERS])
 {
-    size_t off = align256(mlp_carve(d, n, base, w));
-    off = carve_zp(d, n, base, off, w);
-    const int nh = d->net[0].n_layers - 1;
-    for (int l = 0; l < nh; ++l) {
-        int mx = 0;
-        for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
-        const size_t bytes = sizeof(float) * (size_t)mx * d->n_members * (size_t)(n + 1);
-        if (dlt) dlt[l] = base ? (float *)(base + off) : nullptr;
-        off += align256(bytes);
-    }
-    return off;
+    return carve_layers(d, n, base, kept_carve(d, n, base, w), 1, dlt);
 }
 
-// tangent pass: the inference workspace + four more buffers per hidden layer (zdot, adot, p, q)
+// tangent pass: + four buffers per hidden layer (zdot, adot, p, q)
 static size_t mlp_tangent_carve(const anihip_mlp_desc *d, int64_t n, char *base, MlpWorkspace *w,
                                 float *(*buf)[ANIHIP_MAX_LAYERS] /* [4] */)
 {
-    size_t off = align256(mlp_carve(d, n, base, w));
-    off = carve_zp(d, n, base, off, w);
-    const int nh = d->net[0].n_layers - 1;
-    for (int k = 0; k < 4; ++k)
-        for (int l = 0; l < nh; ++l) {
-            int mx = 0;
-            for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
-            const size_t bytes = sizeof(float) * (size_t)mx * d->n_members * (size_t)(n + 1);
-            if (buf) buf[k][l] = base ? (float *)(base + off) : nullptr;
-            off += align256(bytes);
-        }
-    return off;
+    return carve_layers(d, n, base, kept_carve(d, n, base, w), 4, buf);
 }
 
 }  // namespace anihip
@@ -1852,8 +1856,7 @@ static FbPlan fb_plan(const anihip_mlp_desc *d, int64_t n, bool want_grad)
     FbPlan p{};
     const int S = d->num_species, nh = d->net[0].n_layers - 1, L = d->aev_len;
     const bool h3 = d->precision == ANIHIP_MLP_F16X3;
-    const int kp_rad = h3 ? d->aev_radial_len : 0;
-    const int K0p = kp_rad > 0 ? 32 * ((kp_rad + 31) / 32 + (L - kp_rad) / 32) : ((L + 31) / 32) * 32;
+    const int K0p = layer0_width(d, h3);
     p.fused = h3 && nh == 3 && K0p <= 32 * 32 && L % 4 == 0;
     for (int s = 0; s < S && p.fused; ++s) {
         const anihip_species_net &nn = d->net[s];
@@ -1995,11 +1998,148 @@ static void launch_gemm(hipStream_t stream, GemmArgs &g, bool f16x3)
         hipLaunchKernelGGL((k_gemm<EPI>), dim3((unsigned)total), dim3(GEMM_THREADS), 0, stream, g);
 }
 
+// (the tangent-pass epilogues exist in k_gemm only)
 template <int EPI>
 static void launch_gemm_fp32(hipStream_t stream, GemmArgs &g)
 {
     const int64_t total = (int64_t)g.nrow_tiles_ub * g.ncol_max * g.batch;
     hipLaunchKernelGGL((k_gemm<EPI>), dim3((unsigned)total), dim3(GEMM_THREADS), 0, stream, g);
+}
+
+// what every layer-by-layer GEMM of a pass over `rows` sorted rows (control block ctl) shares; y_gather: the tangent pass over
+// (direction, atom) rows
+static GemmArgs gemm_args(const anihip_mlp_desc *d, const int *ctl, int64_t rows, const int *y_gather = nullptr)
+{
+    GemmArgs g{};
+    g.ctl = ctl; g.S = d->num_species; g.alpha = d->celu_alpha; g.inv_alpha = 1.0f / d->celu_alpha;
+    g.nrow_tiles_ub = (int)((rows + BM - 1) / BM) + d->num_species;
+    g.amax_in = g.amax_out = -1;
+    g.act = d->activation;
+    g.y_gather = y_gather;
+    return g;
+}
+
+// forward GEMM of layer l for every species: B = w[l] (+ the bias); layer 0 is ONE [n_s, K0] x [K0, M*H1] GEMM, a hidden layer M
+// batched ones.  h3: B as the split-fp16 planes wh[l], shaped like wt[l] ([N][K], K contiguous), layer 0 reduced over k0p
+static void fwd_problems(GemmArgs &g, const anihip_mlp_desc *d, int l, bool bias, bool h3 = false, int k0p = 0)
+{
+    const int M = d->n_members;
+    g.batch = l == 0 ? 1 : M;
+    g.ncol_max = ((l == 0 ? max_width(d, 1) * M : max_width(d, l + 1)) + BN - 1) / BN;
+    for (int s = 0; s < d->num_species; ++s) {
+        const anihip_species_net &nn = d->net[s];
+        GemmProblem &p = g.prob[s];
+        p.B = nn.w[l];
+        if (bias) p.bias = nn.bias[l];
+        if (l == 0) {
+            p.K = nn.dims[0]; p.N = nn.dims[1] * M; p.ldb = p.N;
+        } else {
+            p.K = nn.dims[l]; p.N = nn.dims[l + 1]; p.ldb = p.N;
+            p.a_boff = nn.dims[l]; p.c_boff = nn.dims[l + 1];
+            p.b_stride = (int64_t)p.K * p.N;
+            if (bias) p.bias_stride = p.N;
+        }
+        if (h3) {
+            p.Bh = (const _Float16 *)nn.wh[l];
+            p.k_valid = p.K;
+            p.w_inv_scale = 1.0f / nn.wh_scale[l];
+            if (l == 0) {
+                p.K = k0p; p.ldbh = k0p; p.bh_stride = 0; p.bh_plane = (int64_t)p.N * k0p;
+            } else {
+                p.ldbh = p.K; p.bh_stride = (int64_t)p.N * p.K; p.bh_plane = (int64_t)M * p.N * p.K;
+            }
+        }
+    }
+}
+
+// backward GEMM of layer l (d / d input from d / d output) for every species: B = wt[l]; layer 0 is ONE [n_s, M*H1] x [M*H1, n0]
+// GEMM onto the n0 padded AEV columns, a hidden layer M batched ones.  h3: B as the planes wth[l], shaped like w[l]
+static void bwd_problems(GemmArgs &g, const anihip_mlp_desc *d, int l, int n0, bool h3 = false)
+{
+    const int M = d->n_members;
+    g.batch = l == 0 ? 1 : M;
+    g.ncol_max = ((l == 0 ? n0 : max_width(d, l)) + BN - 1) / BN;
+    for (int s = 0; s < d->num_species; ++s) {
+        const anihip_species_net &nn = d->net[s];
+        GemmProblem &p = g.prob[s];
+        p.B = nn.wt[l];
+        if (l == 0) {
+            p.K = nn.dims[1] * M; p.N = n0; p.ldb = p.N;
+        } else {
+            p.K = nn.dims[l + 1]; p.N = nn.dims[l]; p.ldb = p.N;
+            p.a_boff = nn.dims[l + 1]; p.c_boff = nn.dims[l];
+            p.b_stride = (int64_t)p.K * p.N;
+        }
+        if (h3) {
+            p.Bh = (const _Float16 *)nn.wth[l];
+            p.k_valid = p.K;
+            p.w_inv_scale = 1.0f / nn.wh_scale[l];
+            p.ldbh = p.K;
+            p.bh_stride = l == 0 ? 0 : (int64_t)p.N * p.K;
+            p.bh_plane = (l == 0 ? 1 : (int64_t)M) * p.N * p.K;
+        }
+    }
+}
+
+// output layer: energies (+ the seed of the backward pass); h carries the caller's own fields
+static void launch_head(hipStream_t stream, const anihip_mlp_desc *d, const MlpWorkspace &w, int64_t n_atoms, int64_t n,
+                        HeadArgs h)
+{
+    const int S = d->num_species, nl = d->net[0].n_layers, nh = nl - 1;
+    for (int s = 0; s < S; ++s) {
+        h.w[s] = d->net[s].w[nl - 1];
+        h.bias[s] = d->net[s].bias[nl - 1];
+        h.Hp[s] = d->net[s].dims[nl - 1];
+    }
+    h.ctl = w.ctl; h.perm = w.perm; h.act = w.act[nh - 1]; h.ld = w.ld[nh - 1];
+    h.n_atoms = n_atoms; h.S = S; h.M = d->n_members; h.inv_alpha = 1.0f / d->celu_alpha;
+    int64_t blocks = (n + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(k_head, dim3((unsigned)blocks), dim3(256), 0, stream, h);
+}
+
+// compute units of the device (256 if it reports none), queried once per process
+static int cu_count(int *n_cus)
+{
+    static int cached = 0;
+    if (cached == 0) {
+        int dev = 0, v = 0;
+        ANIHIP_CHECK_HIP(hipGetDevice(&dev));
+        ANIHIP_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
+        cached = v > 0 ? v : 256;
+    }
+    *n_cus = cached;
+    return 0;
+}
+
+// the fused network kernel's arguments common to inference and training (the species' networks, the workspace, the AEV
+// rows); returns the dynamic LDS bytes of tiles of `rows` atoms
+static size_t fused_args(const anihip_mlp_desc *d, const MlpWorkspace &w, const float *aev, int rows, FusedArgs &f)
+{
+    size_t lds = 0;
+    for (int s = 0; s < d->num_species; ++s) {
+        const anihip_species_net &nn = d->net[s];
+        FusedSpecies &fs = f.sp[s];
+        fs.H1 = nn.dims[1]; fs.H2 = nn.dims[2]; fs.H3 = nn.dims[3];
+        fs.w0 = (const _Float16 *)nn.whf[0];
+        fs.w1 = (const _Float16 *)nn.whf[1]; fs.w2 = (const _Float16 *)nn.whf[2];
+        fs.w2t = (const _Float16 *)nn.wthf[2]; fs.w1t = (const _Float16 *)nn.wthf[1];
+        fs.w0t = (const _Float16 *)nn.wthf[0];
+        fs.is0 = 1.0f / nn.wh_scale[0]; fs.is1 = 1.0f / nn.wh_scale[1]; fs.is2 = 1.0f / nn.wh_scale[2];
+        fs.b0 = nn.bias[0]; fs.b1 = nn.bias[1]; fs.b2 = nn.bias[2]; fs.w3 = nn.w[3]; fs.b3 = nn.bias[3];
+        fs.bounds = nn.fused_bounds;
+        const size_t xu = fs.H1 > fs.H3 ? fs.H1 : fs.H3;
+        size_t halves = 2 * (size_t)rows * (fs.H2 + FR_XPAD) + 2 * (size_t)rows * (xu + FR_XPAD);
+        const size_t slab = 2 * (size_t)rows * FR_SLAB_LD;
+        if (halves < 3 * FR_GROUP * slab) halves = 3 * FR_GROUP * slab;   // staging slots 1..3
+        halves += FusedCfg<2, 1>::FIXED_HALVES;
+        lds = lds > halves * 2 ? lds : halves * 2;
+    }
+    f.ctl = w.ctl; f.amax = w.amax; f.aev = aev; f.L = d->aev_len; f.perm = w.perm;
+    f.kp_rad = d->aev_radial_len; f.n_slabs = layer0_width(d, true) / 32;
+    f.tile_tab = w.tile_tab; f.tile_rows = w.tile_rows; f.member_part = w.member_part;
+    f.S = d->num_species; f.M = d->n_members; f.alpha = d->celu_alpha; f.inv_alpha = 1.0f / d->celu_alpha;
+    return lds;
 }
 
 extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms,
@@ -2018,23 +2158,11 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
                    "workspace too small (anihip_mlp_forward_backward_workspace_bytes)");
     MlpWorkspace w;
     mlp_carve(d, n, (char *)workspace, &w, plan.n_act);
-    const int S = d->num_species, M = d->n_members, nl = d->net[0].n_layers, nh = nl - 1;
+    const int S = d->num_species, M = d->n_members, nh = d->net[0].n_layers - 1;
     const int L = d->aev_len;
     const bool h3 = d->precision == ANIHIP_MLP_F16X3;
-    // layer-0 reduction length: plain AEV order padded to 32, or the slab order of the fp16 planes
     const int kp_rad = h3 ? d->aev_radial_len : 0;
-    const int K0p = kp_rad > 0 ? 32 * ((kp_rad + 31) / 32 + (L - kp_rad) / 32) : ((L + 31) / 32) * 32;
-    const float alpha = d->celu_alpha, inv_alpha = 1.0f / d->celu_alpha;
-
-    const int nrow_ub = (int)((n + BM - 1) / BM) + S;
-    auto ncol_of = [&](int l_out, bool cat) {
-        int mx = 0;
-        for (int s = 0; s < S; ++s) {
-            int N = d->net[s].dims[l_out] * (cat ? M : 1);
-            mx = mx > N ? mx : N;
-        }
-        return (mx + BN - 1) / BN;
-    };
+    const int K0p = layer0_width(d, h3);
 
     // fused network kernel (f16x3, three hidden layers of width <= 256, at most 32 AEV slabs): one kernel
     // from the AEV rows to d E / d act0, then the layer-0 backward GEMM
@@ -2072,39 +2200,13 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
 
     // 2. forward through the hidden layers
     for (int l = 0; l < (fused ? 0 : nh); ++l) {
-        GemmArgs g{};
-        g.ctl = w.ctl; g.S = S; g.alpha = alpha; g.inv_alpha = inv_alpha;
-        g.nrow_tiles_ub = nrow_ub;
-        g.C = w.act[l]; g.ldc = w.ld[l]; g.c_scatter = nullptr; g.n_store = 0;
+        GemmArgs g = gemm_args(d, w.ctl, n);
+        fwd_problems(g, d, l, true, h3, K0p);
+        g.C = w.act[l]; g.ldc = w.ld[l];
         if (l == 0) {
-            g.A = aev; g.lda = L; g.a_gather = w.perm; g.batch = 1;
-            g.ncol_max = ncol_of(1, true);
+            g.A = aev; g.lda = L; g.a_gather = w.perm;
         } else {
-            g.A = w.act[l - 1]; g.lda = w.ld[l - 1]; g.a_gather = nullptr; g.batch = M;
-            g.ncol_max = ncol_of(l + 1, false);
-        }
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.w[l]; p.bias = nn.bias[l];
-            if (l == 0) {
-                p.K = nn.dims[0]; p.N = nn.dims[1] * M; p.ldb = p.N;
-                p.a_boff = 0; p.c_boff = 0; p.b_stride = 0; p.bias_stride = 0;
-            } else {
-                p.K = nn.dims[l]; p.N = nn.dims[l + 1]; p.ldb = p.N;
-                p.a_boff = nn.dims[l]; p.c_boff = nn.dims[l + 1];
-                p.b_stride = (int64_t)p.K * p.N; p.bias_stride = p.N;
-            }
-            if (h3) {  // B planes shaped like wt[l]: [N][K], K contiguous
-                p.Bh = (const _Float16 *)nn.wh[l];
-                p.k_valid = p.K;
-                p.w_inv_scale = 1.0f / nn.wh_scale[l];
-                if (l == 0) {
-                    p.K = K0p; p.ldbh = K0p; p.bh_stride = 0; p.bh_plane = (int64_t)p.N * K0p;
-                } else {
-                    p.ldbh = p.K; p.bh_stride = (int64_t)p.N * p.K; p.bh_plane = (int64_t)M * p.N * p.K;
-                }
-            }
+            g.A = w.act[l - 1]; g.lda = w.ld[l - 1];
         }
         g.amax = w.amax; g.amax_out = h3 ? l : -1; g.amax_in = (h3 && l > 0) ? l - 1 : -1;
         g.a_static_scale = 4.0f;  // layer-0 input: |aev| < 16376 by construction (see include/anihip.h)
@@ -2127,36 +2229,15 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
                          !(d->flags & ANIHIP_MLP_FLAG_NO_SLAB_MASK);
     if (fused) {
         FusedArgs f{};
-        size_t lds = 0;
         // tiling: 64 atoms x 8 waves, one workgroup per CU
         const int rows = fused_rows;
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            FusedSpecies &fs = f.sp[s];
-            fs.H1 = nn.dims[1]; fs.H2 = nn.dims[2]; fs.H3 = nn.dims[3];
-            fs.w0 = (const _Float16 *)nn.whf[0];
-            fs.w1 = (const _Float16 *)nn.whf[1]; fs.w2 = (const _Float16 *)nn.whf[2];
-            fs.w2t = (const _Float16 *)nn.wthf[2]; fs.w1t = (const _Float16 *)nn.wthf[1];
-            fs.w0t = (const _Float16 *)nn.wthf[0];
-            fs.is0 = 1.0f / nn.wh_scale[0]; fs.is1 = 1.0f / nn.wh_scale[1]; fs.is2 = 1.0f / nn.wh_scale[2];
-            fs.b0 = nn.bias[0]; fs.b1 = nn.bias[1]; fs.b2 = nn.bias[2]; fs.w3 = nn.w[3]; fs.b3 = nn.bias[3];
-            fs.bounds = nn.fused_bounds;
-            const size_t xu = fs.H1 > fs.H3 ? fs.H1 : fs.H3;
-            size_t halves = 2 * (size_t)rows * (fs.H2 + FR_XPAD) + 2 * (size_t)rows * (xu + FR_XPAD);
-            const size_t slab = 2 * (size_t)rows * FR_SLAB_LD;
-            if (halves < 3 * FR_GROUP * slab) halves = 3 * FR_GROUP * slab;   // staging slots 1..3
-            halves += FusedCfg<2, 1>::FIXED_HALVES;
-            lds = lds > halves * 2 ? lds : halves * 2;
-        }
-        f.ctl = w.ctl; f.amax = w.amax; f.aev = aev; f.L = L; f.kp_rad = kp_rad; f.n_slabs = n_slabs;
+        const size_t lds = fused_args(d, w, aev, rows, f);
         f.slab_mask = tab_mask;
-        f.d0 = w.act[0]; f.ld0 = w.ld[0]; f.perm = w.perm;
+        f.d0 = w.act[0]; f.ld0 = w.ld[0];
         // tile-major hand-over to the 256 x 256 layer-0 backward GEMM (the 128 x 128 kernel of small inputs reads rows)
         f.d0_tm = (big_tiles && grad_aev) ? 1 : 0;
         if (d->flags & ANIHIP_MLP_FLAG_D0_ROWS) f.d0_tm = 0;
         d0_tm = f.d0_tm;
-        f.tile_tab = w.tile_tab; f.tile_rows = w.tile_rows;
-        f.member_part = w.member_part; f.S = S; f.M = M; f.alpha = alpha; f.inv_alpha = inv_alpha;
         f.want_grad = grad_aev ? 1 : 0;
         f.owner = 0;   // (member-major sweep; the layer-0 backward inside the kernel switches to owner order below)
         f.l0b = fused_l0b ? 1 : 0;
@@ -2172,13 +2253,8 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
         const int64_t tiles = fused_tiles;
         f.tiles_total = (int)tiles;
         // persistent workgroups over the (member, tile) items, as many as are resident at once
-        static int n_cus = 0;
-        if (n_cus == 0) {
-            int dev = 0, v = 0;
-            ANIHIP_CHECK_HIP(hipGetDevice(&dev));
-            ANIHIP_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-            n_cus = v > 0 ? v : 256;
-        }
+        int n_cus;
+        if (int rc = cu_count(&n_cus)) return rc;
         const int64_t items = tiles * M;
         const int64_t resident = (int64_t)n_cus * (2 * lds <= 160 * 1024 ? 2 : 1);
         const int64_t units = f.owner ? tiles : items;
@@ -2213,6 +2289,19 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
             // species' workgroups start on the CUs as they come free and take fewer tiles the later they start.  (Without the
             // queue the overlap buys nothing: a late workgroup then carries its static share to the end.)  Not inside a stream
             // capture (the step then stays a chain of kernel nodes).
+            // (the shaped variants' LDS limits are set before the fork: nothing between the fork and the join may return, or
+            // the work queued on the process-wide second stream would never be joined back to the caller's stream)
+            int shaped[MAX_S];
+            for (int s = 0; s < S; ++s) {
+                const FusedSpecies &fs = f.sp[s];
+                int v = FUSED_CELU_L0B;
+                if (fs.H1 == 256 && fs.H2 == 192 && fs.H3 == 160) v = FUSED_CELU_L0B_256;
+                else if (fs.H1 == 192 && fs.H2 == 160 && fs.H3 == 128) v = FUSED_CELU_L0B_192;
+                else if (fs.H1 == 224 && fs.H2 == 192 && fs.H3 == 160) v = FUSED_CELU_L0B_224;
+                else if (fs.H1 == 160 && fs.H2 == 128 && fs.H3 == 96) v = FUSED_CELU_L0B_160;
+                if (v != FUSED_CELU_L0B) ANIHIP_CHECK_HIP(hipFuncSetAttribute(fused_kernel(v), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                shaped[s] = v;
+            }
             OverlapSet *ov = nullptr;
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
             // (from four rounds of tiles on: below, the fork / join and the draws cost more than they balance -- water boxes of
@@ -2232,16 +2321,9 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
                 ANIHIP_CHECK_HIP(hipStreamWaitEvent(aux, ov->fork, 0));
             }
             for (int s = 0; s < S; ++s) {
-                const FusedSpecies &fs = f.sp[s];
-                int v = FUSED_CELU_L0B;
-                if (fs.H1 == 256 && fs.H2 == 192 && fs.H3 == 160) v = FUSED_CELU_L0B_256;
-                else if (fs.H1 == 192 && fs.H2 == 160 && fs.H3 == 128) v = FUSED_CELU_L0B_192;
-                else if (fs.H1 == 224 && fs.H2 == 192 && fs.H3 == 160) v = FUSED_CELU_L0B_224;
-                else if (fs.H1 == 160 && fs.H2 == 128 && fs.H3 == 96) v = FUSED_CELU_L0B_160;
-                if (v != FUSED_CELU_L0B) ANIHIP_CHECK_HIP(hipFuncSetAttribute(fused_kernel(v), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 f.only_species = s;
                 f.queue = aux ? w.ctl + CTL_QUEUE + s : nullptr;   // (zeroed with the control block by the bucketing)
-                launch_fused(v, (unsigned)grid, lds, (aux && (s & 1)) ? aux : stream, f);
+                launch_fused(shaped[s], (unsigned)grid, lds, (aux && (s & 1)) ? aux : stream, f);
             }
             if (ov) {
                 ANIHIP_CHECK_HIP(hipEventRecord(ov->join, aux));
@@ -2270,54 +2352,22 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
     // 3. output layer (+ seed of the backward pass, written in place over the last activations)
     if (!fused) {
         HeadArgs h{};
-        for (int s = 0; s < S; ++s) {
-            h.w[s] = d->net[s].w[nl - 1];
-            h.bias[s] = d->net[s].bias[nl - 1];
-            h.Hp[s] = d->net[s].dims[nl - 1];
-        }
-        h.ctl = w.ctl; h.perm = w.perm; h.act = w.act[nh - 1]; h.ld = w.ld[nh - 1];
-        h.atomic_e = atomic_e; h.member_e = member_e; h.n_atoms = n_atoms; h.S = S; h.M = M;
-        h.inv_alpha = inv_alpha; h.want_grad = grad_aev ? 1 : 0;
+        h.atomic_e = atomic_e; h.member_e = member_e; h.want_grad = grad_aev ? 1 : 0;
         h.amax = h3 ? w.amax : nullptr; h.amax_out = 3;
-        int64_t blocks = (n + 3) / 4;
-        if (blocks > 256 * 8) blocks = 256 * 8;
-        hipLaunchKernelGGL(k_head, dim3((unsigned)blocks), dim3(256), 0, stream, h);
+        launch_head(stream, d, w, n_atoms, n, h);
     }
 
     // 4. backward to the AEV rows
     if (grad_aev && !fused_l0b) {
         for (int l = fused ? 0 : nh - 1; l >= 0; --l) {
-            GemmArgs g{};
-            g.ctl = w.ctl; g.S = S; g.alpha = alpha; g.inv_alpha = inv_alpha;
-            g.nrow_tiles_ub = nrow_ub;
-            g.A = w.act[l]; g.lda = w.ld[l]; g.a_gather = nullptr;
+            GemmArgs g = gemm_args(d, w.ctl, n);
+            g.act = ANIHIP_ACT_CELU;   // (a GELU network gets here for the layer-0 backward only: no activation)
+            bwd_problems(g, d, l, K0p, h3);
+            g.A = w.act[l]; g.lda = w.ld[l];
             if (l == 0) {
-                g.batch = 1; g.C = grad_aev; g.ldc = L; g.c_scatter = w.perm; g.n_store = L;
-                g.ncol_max = (K0p + BN - 1) / BN;
+                g.C = grad_aev; g.ldc = L; g.c_scatter = w.perm; g.n_store = L;
             } else {
-                g.batch = M; g.C = w.act[l - 1]; g.ldc = w.ld[l - 1]; g.c_scatter = nullptr;
-                g.ncol_max = ncol_of(l, false);
-            }
-            for (int s = 0; s < S; ++s) {
-                const anihip_species_net &nn = d->net[s];
-                GemmProblem &p = g.prob[s];
-                p.B = nn.wt[l]; p.bias = nullptr; p.bias_stride = 0;
-                if (l == 0) {
-                    p.K = nn.dims[1] * M; p.N = K0p; p.ldb = p.N;
-                    p.a_boff = 0; p.c_boff = 0; p.b_stride = 0;
-                } else {
-                    p.K = nn.dims[l + 1]; p.N = nn.dims[l]; p.ldb = p.N;
-                    p.a_boff = nn.dims[l + 1]; p.c_boff = nn.dims[l];
-                    p.b_stride = (int64_t)p.K * p.N;
-                }
-                if (h3) {  // B planes shaped like w[l]: [N = layer input index][K = layer output index]
-                    p.Bh = (const _Float16 *)nn.wth[l];
-                    p.k_valid = p.K;
-                    p.w_inv_scale = 1.0f / nn.wh_scale[l];
-                    p.ldbh = p.K;
-                    p.bh_stride = l == 0 ? 0 : (int64_t)p.N * p.K;
-                    p.bh_plane = (l == 0 ? 1 : (int64_t)M) * p.N * p.K;
-                }
+                g.C = w.act[l - 1]; g.ldc = w.ld[l - 1];
             }
             g.amax = w.amax;
             g.amax_in = h3 ? 3 + (nh - 1 - l) : -1;
@@ -2368,38 +2418,18 @@ static int train_forward(hipStream_t stream, const anihip_mlp_desc *d, int64_t n
                          const int32_t *species, const float *aev, MlpWorkspace &w, float *atomic_e,
                          float *grad_aev)
 {
-    const int S = d->num_species, M = d->n_members, nl = d->net[0].n_layers, nh = nl - 1, L = d->aev_len;
-    const int64_t n = hi - lo;
+    const int S = d->num_species, M = d->n_members, nh = d->net[0].n_layers - 1, L = d->aev_len;
     // (scratch of the counting sort: the per-member energies buffer is written only later)
     launch_bucketing(stream, lo, hi, species, S, w.ctl, CTL_WORDS + AMAX_WORDS, reinterpret_cast<int *>(w.member_part), w.perm,
                      atomic_e, grad_aev, L, (float *)nullptr, M, n_atoms);
     for (int l = 0; l < nh; ++l) {
-        GemmArgs g{};
-        g.ctl = w.ctl; g.S = S; g.alpha = d->celu_alpha; g.inv_alpha = 1.0f / d->celu_alpha;
-        g.nrow_tiles_ub = (int)((n + BM - 1) / BM) + S;
-        g.amax_in = g.amax_out = -1;
-        g.C = w.act[l]; g.ldc = w.ld[l];
-        g.act = d->activation; g.Xout = w.zp[l];
-        int wmax = 0;
-        for (int s = 0; s < S; ++s) wmax = wmax > d->net[s].dims[l + 1] ? wmax : d->net[s].dims[l + 1];
+        GemmArgs g = gemm_args(d, w.ctl, hi - lo);
+        fwd_problems(g, d, l, true);
+        g.C = w.act[l]; g.ldc = w.ld[l]; g.Xout = w.zp[l];
         if (l == 0) {
-            g.A = aev; g.lda = L; g.a_gather = w.perm; g.batch = 1;
-            g.ncol_max = (wmax * M + BN - 1) / BN;
+            g.A = aev; g.lda = L; g.a_gather = w.perm;
         } else {
-            g.A = w.act[l - 1]; g.lda = w.ld[l - 1]; g.batch = M;
-            g.ncol_max = (wmax + BN - 1) / BN;
-        }
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.w[l]; p.bias = nn.bias[l];
-            if (l == 0) {
-                p.K = nn.dims[0]; p.N = nn.dims[1] * M; p.ldb = p.N;
-            } else {
-                p.K = nn.dims[l]; p.N = nn.dims[l + 1]; p.ldb = p.N;
-                p.a_boff = nn.dims[l]; p.c_boff = nn.dims[l + 1];
-                p.b_stride = (int64_t)p.K * p.N; p.bias_stride = p.N;
-            }
+            g.A = w.act[l - 1]; g.lda = w.ld[l - 1];
         }
         launch_gemm<EPI_BIAS_CELU>(stream, g, false);
     }
@@ -2427,8 +2457,7 @@ static int train_forward_fused(hipStream_t stream, const anihip_mlp_desc *d, int
     const int S = d->num_species, M = d->n_members, L = d->aev_len;
     const int64_t n = hi - lo;
     const int kp_rad = d->aev_radial_len;
-    const int K0p = kp_rad > 0 ? 32 * ((kp_rad + 31) / 32 + (L - kp_rad) / 32) : ((L + 31) / 32) * 32;
-    const int n_slabs = K0p / 32;
+    const int n_slabs = layer0_width(d, true) / 32;
     const uint32_t all_slabs = n_slabs >= 32 ? 0xFFFFFFFFu : ((1u << n_slabs) - 1u);
     constexpr int rows = 64;
     launch_bucketing(stream, lo, hi, species, S, w.ctl, CTL_WORDS + AMAX_WORDS, reinterpret_cast<int *>(w.member_part), w.perm,
@@ -2438,39 +2467,16 @@ static int train_forward_fused(hipStream_t stream, const anihip_mlp_desc *d, int
     const int ani_species = (lo == 0 && hi == n_atoms && kp_rad == 16 * S && kp_rad > 0) ? S : 0;
     launch_tile_table(stream, w.ctl, S, w.perm, nullptr, all_slabs, (int)tiles, rows, w.tile_tab, w.tile_rows, ani_species);
     FusedArgs f{};
-    size_t lds = 0;
-    for (int s = 0; s < S; ++s) {
-        const anihip_species_net &nn = d->net[s];
-        FusedSpecies &fs = f.sp[s];
-        fs.H1 = nn.dims[1]; fs.H2 = nn.dims[2]; fs.H3 = nn.dims[3];
-        fs.w0 = (const _Float16 *)nn.whf[0];
-        fs.w1 = (const _Float16 *)nn.whf[1]; fs.w2 = (const _Float16 *)nn.whf[2];
-        fs.w2t = (const _Float16 *)nn.wthf[2]; fs.w1t = (const _Float16 *)nn.wthf[1];
-        fs.w0t = (const _Float16 *)nn.wthf[0];
-        fs.is0 = 1.0f / nn.wh_scale[0]; fs.is1 = 1.0f / nn.wh_scale[1]; fs.is2 = 1.0f / nn.wh_scale[2];
-        fs.b0 = nn.bias[0]; fs.b1 = nn.bias[1]; fs.b2 = nn.bias[2]; fs.w3 = nn.w[3]; fs.b3 = nn.bias[3];
-        fs.bounds = nn.fused_bounds;
-        const size_t xu = fs.H1 > fs.H3 ? fs.H1 : fs.H3;
-        size_t halves = 2 * (size_t)rows * (fs.H2 + FR_XPAD) + 2 * (size_t)rows * (xu + FR_XPAD);
-        const size_t slab = 2 * (size_t)rows * FR_SLAB_LD;
-        if (halves < 3 * FR_GROUP * slab) halves = 3 * FR_GROUP * slab;
-        halves += FusedCfg<2, 1>::FIXED_HALVES;
-        lds = lds > halves * 2 ? lds : halves * 2;
-    }
-    f.ctl = w.ctl; f.amax = w.amax; f.aev = aev; f.L = L; f.kp_rad = kp_rad; f.n_slabs = n_slabs;
+    const size_t lds = fused_args(d, w, aev, rows, f);
     f.slab_mask = nullptr;
-    f.d0 = dlt[0]; f.ld0 = w.ld[0]; f.d0_tm = 0; f.perm = w.perm;
-    f.tile_tab = w.tile_tab; f.tile_rows = w.tile_rows;
-    f.member_part = w.member_part; f.S = S; f.M = M; f.alpha = d->celu_alpha; f.inv_alpha = 1.0f / d->celu_alpha;
+    f.d0 = dlt[0]; f.ld0 = w.ld[0]; f.d0_tm = 0;
     f.want_grad = 1; f.owner = 0; f.l0b = 0; f.grad_aev = nullptr;
     f.tiles_total = (int)tiles;
     for (int l = 0; l < 3; ++l) { f.tr_act[l] = w.act[l]; f.tr_ld[l] = w.ld[l]; f.tr_dlt[l] = dlt[l]; }
     const void *kfn = fused_kernel(FUSED_TRAIN);
     ANIHIP_CHECK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int dev = 0, n_cus = 0;
-    ANIHIP_CHECK_HIP(hipGetDevice(&dev));
-    ANIHIP_CHECK_HIP(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (n_cus <= 0) n_cus = 256;
+    int n_cus;
+    if (int rc = cu_count(&n_cus)) return rc;
     const int64_t items = tiles * M;
     const int64_t grid = items < n_cus ? items : n_cus;
     launch_fused(FUSED_TRAIN, (unsigned)grid, lds, stream, f);
@@ -2484,21 +2490,72 @@ static int train_forward_fused(hipStream_t stream, const anihip_mlp_desc *d, int
 static void train_head(hipStream_t stream, const anihip_mlp_desc *d, int64_t n_atoms, int64_t n, MlpWorkspace &w,
                        float *seed, const float *g_atom, float *atomic_e)
 {
-    const int S = d->num_species, nl = d->net[0].n_layers, nh = nl - 1;
+    const int nh = d->net[0].n_layers - 1;
     HeadArgs h{};
-    for (int s = 0; s < S; ++s) {
-        h.w[s] = d->net[s].w[nl - 1];
-        h.bias[s] = d->net[s].bias[nl - 1];
-        h.Hp[s] = d->net[s].dims[nl - 1];
-    }
-    h.ctl = w.ctl; h.perm = w.perm; h.act = w.act[nh - 1]; h.ld = w.ld[nh - 1];
-    h.seed = seed; h.g_atom = g_atom;
-    h.atomic_e = atomic_e; h.member_e = nullptr; h.n_atoms = n_atoms; h.S = S; h.M = d->n_members;
-    h.inv_alpha = 1.0f / d->celu_alpha; h.want_grad = seed ? 1 : 0; h.amax = nullptr; h.amax_out = 0;
+    h.seed = seed; h.g_atom = g_atom; h.atomic_e = atomic_e; h.want_grad = seed ? 1 : 0;
     h.act_kind = d->activation; h.zpre = w.zp[nh - 1];
-    int64_t blocks = (n + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(k_head, dim3((unsigned)blocks), dim3(256), 0, stream, h);
+    launch_head(stream, d, w, n_atoms, n, h);
+}
+
+// k_col_reduce over the sorted rows of the call: the output layer (l = nl - 1) sums X = its input rows into gw[l] with the 1 / M
+// of the ensemble mean (and the row scales into gbias[l] when bias_too), a hidden layer sums d / d z rows into gbias[l].
+// g_atom: per-atom row scale (NULL: 1).  mstride: the fast path's per-member destinations (n_per, out_mstride); NULL: packed
+static void launch_col_reduce(hipStream_t stream, const anihip_mlp_desc *d, const MlpWorkspace &w, int64_t n,
+                              const anihip_species_grads *grads, int l, const float *X, int64_t ldx, const float *g_atom,
+                              bool bias_too, const int64_t *mstride = nullptr)
+{
+    const int S = d->num_species, M = d->n_members;
+    const bool output_layer = l == d->net[0].n_layers - 1;
+    ColReduceArgs c{};
+    int mx = 0;
+    for (int s = 0; s < S; ++s) {
+        const int width = d->net[s].dims[output_layer ? l : l + 1];
+        c.X[s] = X;
+        c.ncols[s] = M * width;
+        if (mstride) c.n_per[s] = width;
+        c.out[s] = output_layer ? grads[s].gw[l] : grads[s].gbias[l];
+        c.extra[s] = output_layer && bias_too ? grads[s].gbias[l] : nullptr;
+        mx = mx > c.ncols[s] ? mx : c.ncols[s];
+    }
+    c.ldx = ldx; c.ctl = w.ctl; c.perm = w.perm; c.S = S; c.M = M;
+    c.g_atom = g_atom;
+    c.inv_m = output_layer ? 1.0f / (float)M : 1.0f;   // (d e / d z of the hidden layers carries the 1 / M already)
+    c.ct_max = (mx + 255) / 256;
+    if (mstride) c.out_mstride = *mstride;
+    const int cr_chunks = (int)((n + CR_ROWS - 1) / CR_ROWS) + S;
+    hipLaunchKernelGGL(k_col_reduce, dim3((unsigned)(cr_chunks * c.ct_max)), dim3(256), 0, stream, c);
+}
+
+// exact-fp32 weight gradients of layer l, d W^T += D^T X over the sorted rows: D = d / d z rows of the layer, X = its input
+// (layer 0: [n_atoms][L] rows in atom order, gathered; a hidden layer: the rows of the layer below)
+static void launch_wgrad(hipStream_t stream, const anihip_mlp_desc *d, const MlpWorkspace &w, int64_t n,
+                         const anihip_species_grads *grads, int l, const float *D, const float *X)
+{
+    const int S = d->num_species, M = d->n_members, L = d->aev_len;
+    WgradArgs a{};
+    a.ctl = w.ctl; a.S = S;
+    a.x_gather = l == 0 ? w.perm : nullptr;
+    a.batch = l == 0 ? 1 : M;
+    int kmax = 0, nmax = 0;
+    for (int s = 0; s < S; ++s) {
+        const anihip_species_net &nn = d->net[s];
+        WgradProblem &p = a.prob[s];
+        p.X = X; p.D = D; p.ldd = w.ld[l]; p.dW = grads[s].gw[l];
+        if (l == 0) {
+            p.ldx = L; p.x_boff = 0; p.K = L; p.k_valid = L;
+            p.d_boff = 0; p.N = nn.dims[1] * M; p.ldw = L; p.w_bstride = 0;
+        } else {
+            p.ldx = w.ld[l - 1]; p.x_boff = nn.dims[l]; p.K = nn.dims[l]; p.k_valid = p.K;
+            p.d_boff = nn.dims[l + 1]; p.N = nn.dims[l + 1]; p.ldw = p.K; p.w_bstride = (int64_t)p.K * p.N;
+        }
+        kmax = kmax > p.K ? kmax : p.K;
+        nmax = nmax > p.N ? nmax : p.N;
+    }
+    a.ki_max = (kmax + 63) / 64;
+    a.nj_max = (nmax + 255) / 256;
+    const int wg_chunks = (int)((n + WG_ROWS - 1) / WG_ROWS) + S;
+    const int64_t total = (int64_t)wg_chunks * a.batch * a.ki_max * a.nj_max;
+    hipLaunchKernelGGL(k_wgrad, dim3((unsigned)total), dim3(256), 0, stream, a);
 }
 
 extern "C" int anihip_mlp_train_forward(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms, int64_t lo,
@@ -2514,7 +2571,7 @@ extern "C" int anihip_mlp_train_forward(void *stream_, const anihip_mlp_desc *d,
     ANIHIP_REQUIRE(workspace_bytes >= mlp_train_carve(d, n, nullptr, nullptr, nullptr), "workspace too small");
     MlpWorkspace w;
     float *dlt[ANIHIP_MAX_LAYERS];
-    mlp_train_carve(d, n, (char *)workspace, &w, dlt);
+    mlp_train_carve(d, n, (char *)workspace, &w, &dlt);
     if (train_fused(d)) {
         if (int rc = train_forward_fused(stream, d, n_atoms, lo, hi, species, aev, w, dlt, atomic_e)) return rc;
         ANIHIP_CHECK_HIP(hipGetLastError());
@@ -2538,7 +2595,7 @@ extern "C" int anihip_mlp_repack(void *stream_, const anihip_mlp_desc *d, const 
     RepackArgs a{};
     a.src = (const float *const *)src;
     a.S = d->num_species; a.M = d->n_members; a.nl = d->net[0].n_layers;
-    a.k0p = ((d->aev_len + 31) / 32) * 32;
+    a.k0p = layer0_width(d, false);
     int64_t biggest = 0;
     for (int s = 0; s < a.S; ++s) {
         const anihip_species_net &nn = d->net[s];
@@ -2601,8 +2658,7 @@ extern "C" int anihip_mlp_weight_grads(void *stream_, const anihip_mlp_desc *d, 
     ANIHIP_REQUIRE(workspace_bytes >= mlp_train_carve(d, n, nullptr, nullptr, nullptr), "workspace too small");
     MlpWorkspace w;
     float *dlt[ANIHIP_MAX_LAYERS];
-    mlp_train_carve(d, n, (char *)workspace, &w, dlt);
-    const float alpha = d->celu_alpha, inv_alpha = 1.0f / d->celu_alpha;
+    mlp_train_carve(d, n, (char *)workspace, &w, &dlt);
 
     if (fast) {
         // Fast path: forward + unit-gradient backward by the fused kernel (anihip_mlp_train_forward, or here), then per layer
@@ -2610,7 +2666,6 @@ extern "C" int anihip_mlp_weight_grads(void *stream_, const anihip_mlp_desc *d, 
         // d e / d z by the upstream d Loss / d atomic_e of their atoms.  No GEMM runs in this call.
         if (!forward_done)
             if (int rc = train_forward_fused(stream, d, n_atoms, lo, hi, species, aev, w, dlt, atomic_e)) return rc;
-        const int cr_chunks = (int)((n + CR_ROWS - 1) / CR_ROWS) + S;
         // (max |d Loss / d atomic_e| over the real atoms of this call: the fp16 scale of the weight-gradient kernels' D operand.
         // k_absmax only raises the slots: they are zeroed here, not just by the species bucketing of the forward -- a second
         // call on the same forward (forward_done) would otherwise keep the larger maximum of the first, and a D operand
@@ -2621,27 +2676,9 @@ extern "C" int anihip_mlp_weight_grads(void *stream_, const anihip_mlp_desc *d, 
             launch_absmax(stream, grad_atomic_e + lo, species + lo, n, w.amax, AMAX_STAGE_GATOM);
         }
         for (int l = nl - 1; l >= 0; --l) {
-            const bool output_layer = l == nl - 1;
-            ColReduceArgs c{};
-            int mx = 0;
-            for (int s = 0; s < S; ++s) {
-                const int width = d->net[s].dims[output_layer ? nl - 1 : l + 1];
-                c.X[s] = output_layer ? w.act[nh - 1] : dlt[l];
-                c.ncols[s] = M * width;
-                c.n_per[s] = width;
-                c.out[s] = output_layer ? grads[s].gw[nl - 1] : grads[s].gbias[l];
-                c.extra[s] = output_layer ? grads[s].gbias[nl - 1] : nullptr;
-                mx = mx > c.ncols[s] ? mx : c.ncols[s];
-            }
-            c.ldx = output_layer ? w.ld[nh - 1] : w.ld[l];
-            c.ctl = w.ctl; c.perm = w.perm; c.S = S; c.M = M;
-            c.g_atom = grad_atomic_e;
-            c.inv_m = output_layer ? 1.0f / (float)M : 1.0f;   // (d e / d z of the hidden layers carries the 1 / M already)
-            c.ct_max = (mx + 255) / 256;
-            c.out_mstride = mstride;
             // (the bias gradients of the hidden layers are column sums of the rows the weight-gradient kernel stages anyway)
-            if (output_layer) {
-                hipLaunchKernelGGL(k_col_reduce, dim3((unsigned)(cr_chunks * c.ct_max)), dim3(256), 0, stream, c);
+            if (l == nl - 1) {
+                launch_col_reduce(stream, d, w, n, grads, l, w.act[nh - 1], w.ld[nh - 1], grad_atomic_e, true, &mstride);
                 continue;
             }
             WgradB3Args a{};
@@ -2711,91 +2748,25 @@ extern "C" int anihip_mlp_weight_grads(void *stream_, const anihip_mlp_desc *d, 
     } else if (grad_aev) {
         launch_zero_padding(stream, lo, hi, species, atomic_e, grad_aev, L, nullptr, M, n_atoms);
     }
-    const int nrow_ub = (int)((n + BM - 1) / BM) + S;
-    auto width_max = [&](int l) {
-        int mx = 0;
-        for (int s = 0; s < S; ++s) mx = mx > d->net[s].dims[l] ? mx : d->net[s].dims[l];
-        return mx;
-    };
-    auto gemm_base = [&]() {
-        GemmArgs g{};
-        g.ctl = w.ctl; g.S = S; g.alpha = alpha; g.inv_alpha = inv_alpha; g.nrow_tiles_ub = nrow_ub;
-        g.amax_in = g.amax_out = -1;
-        g.act = d->activation;
-        return g;
-    };
 
     // 3. output layer: energies, seed of the backward pass (scaled by the upstream gradient), d w_out, d b_out
     train_head(stream, d, n_atoms, n, w, dlt[nh - 1], grad_atomic_e, atomic_e);
-    const int cr_chunks = (int)((n + CR_ROWS - 1) / CR_ROWS) + S;
-    auto col_reduce = [&](int l, const float *X, int64_t ldx, bool output_layer) {
-        ColReduceArgs c{};
-        int mx = 0;
-        for (int s = 0; s < S; ++s) {
-            c.X[s] = X;
-            c.ncols[s] = M * d->net[s].dims[output_layer ? nl - 1 : l + 1];
-            c.out[s] = output_layer ? grads[s].gw[nl - 1] : grads[s].gbias[l];
-            c.extra[s] = output_layer ? grads[s].gbias[nl - 1] : nullptr;
-            mx = mx > c.ncols[s] ? mx : c.ncols[s];
-        }
-        c.ldx = ldx; c.ctl = w.ctl; c.perm = w.perm; c.S = S; c.M = M;
-        c.g_atom = output_layer ? grad_atomic_e : nullptr;
-        c.inv_m = output_layer ? 1.0f / (float)M : 1.0f;
-        c.ct_max = (mx + 255) / 256;
-        hipLaunchKernelGGL(k_col_reduce, dim3((unsigned)(cr_chunks * c.ct_max)), dim3(256), 0, stream, c);
-    };
-    col_reduce(nl - 1, w.act[nh - 1], w.ld[nh - 1], true);
+    launch_col_reduce(stream, d, w, n, grads, nl - 1, w.act[nh - 1], w.ld[nh - 1], grad_atomic_e, true);
 
     // 4. backward through the hidden layers (gradients in their own buffers), weight and bias gradients
-    const int wg_chunks = (int)((n + WG_ROWS - 1) / WG_ROWS) + S;
     for (int l = nh - 1; l >= 0; --l) {
-        col_reduce(l, dlt[l], w.ld[l], false);
-        WgradArgs a{};
-        a.ctl = w.ctl; a.S = S;
-        a.x_gather = l == 0 ? w.perm : nullptr;
-        a.batch = l == 0 ? 1 : M;
-        int kmax = 0, nmax = 0;
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            WgradProblem &p = a.prob[s];
-            p.D = dlt[l]; p.ldd = w.ld[l]; p.dW = grads[s].gw[l];
-            if (l == 0) {
-                p.X = aev; p.ldx = L; p.x_boff = 0; p.K = L; p.k_valid = L;
-                p.d_boff = 0; p.N = nn.dims[1] * M; p.ldw = L; p.w_bstride = 0;
-            } else {
-                p.X = w.act[l - 1]; p.ldx = w.ld[l - 1]; p.x_boff = nn.dims[l]; p.K = nn.dims[l]; p.k_valid = p.K;
-                p.d_boff = nn.dims[l + 1]; p.N = nn.dims[l + 1]; p.ldw = p.K; p.w_bstride = (int64_t)p.K * p.N;
-            }
-            kmax = kmax > p.K ? kmax : p.K;
-            nmax = nmax > p.N ? nmax : p.N;
-        }
-        a.ki_max = (kmax + 63) / 64;
-        a.nj_max = (nmax + 255) / 256;
-        const int64_t total = (int64_t)wg_chunks * a.batch * a.ki_max * a.nj_max;
-        hipLaunchKernelGGL(k_wgrad, dim3((unsigned)total), dim3(256), 0, stream, a);
+        launch_col_reduce(stream, d, w, n, grads, l, dlt[l], w.ld[l], nullptr, false);
+        launch_wgrad(stream, d, w, n, grads, l, dlt[l], l == 0 ? aev : w.act[l - 1]);
 
         if (l == 0 && !grad_aev) break;
-        GemmArgs g = gemm_base();
+        GemmArgs g = gemm_args(d, w.ctl, n);
+        bwd_problems(g, d, l, layer0_width(d, false));
         g.A = dlt[l]; g.lda = w.ld[l];
         if (l == 0) {
-            g.batch = 1; g.C = grad_aev; g.ldc = L; g.c_scatter = w.perm; g.n_store = L;
-            g.ncol_max = (((L + 31) / 32) * 32 + BN - 1) / BN;
+            g.C = grad_aev; g.ldc = L; g.c_scatter = w.perm; g.n_store = L;
         } else {
-            g.batch = M; g.C = dlt[l - 1]; g.ldc = w.ld[l - 1]; g.Y = w.act[l - 1]; g.ldy = w.ld[l - 1];
+            g.C = dlt[l - 1]; g.ldc = w.ld[l - 1]; g.Y = w.act[l - 1]; g.ldy = w.ld[l - 1];
             g.X = w.zp[l - 1];
-            g.ncol_max = (width_max(l) + BN - 1) / BN;
-        }
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.wt[l];
-            if (l == 0) {
-                p.K = nn.dims[1] * M; p.N = ((L + 31) / 32) * 32; p.ldb = p.N;
-            } else {
-                p.K = nn.dims[l + 1]; p.N = nn.dims[l]; p.ldb = p.N;
-                p.a_boff = nn.dims[l + 1]; p.c_boff = nn.dims[l];
-                p.b_stride = (int64_t)p.K * p.N;
-            }
         }
         if (l == 0)
             launch_gemm<EPI_SCATTER>(stream, g, false);
@@ -2817,51 +2788,19 @@ struct TangentPass {
     float **zd, **ad, **P, **Q;
 };
 
-static int tp_width_max(const anihip_mlp_desc *d, int l)
-{
-    int mx = 0;
-    for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l] ? mx : d->net[s].dims[l];
-    return mx;
-}
-
-static GemmArgs tp_gemm_base(const TangentPass &t)
-{
-    GemmArgs g{};
-    g.ctl = t.ctl; g.S = t.d->num_species; g.alpha = t.d->celu_alpha; g.inv_alpha = 1.0f / t.d->celu_alpha;
-    g.nrow_tiles_ub = (int)((t.n + BM - 1) / BM) + t.d->num_species;
-    g.amax_in = g.amax_out = -1;
-    g.act = t.d->activation;
-    g.y_gather = t.y_gather;
-    return g;
-}
-
 // zdot_l = W_l adot_{l-1}, adot_l = c'(z_l) zdot_l   (adot_0 = tangent rows)
 static void tangent_forward(hipStream_t stream, const TangentPass &t, const float *tangent)
 {
     const anihip_mlp_desc *d = t.d;
-    const int S = d->num_species, M = d->n_members, nh = d->net[0].n_layers - 1, L = d->aev_len;
     const MlpWorkspace &w = *t.w;
-    for (int l = 0; l < nh; ++l) {
-        GemmArgs g = tp_gemm_base(t);
+    for (int l = 0; l < d->net[0].n_layers - 1; ++l) {
+        GemmArgs g = gemm_args(d, t.ctl, t.n, t.y_gather);
+        fwd_problems(g, d, l, false);
         g.C = t.zd[l]; g.C2 = t.ad[l]; g.ldc = w.ld[l]; g.Y = w.act[l]; g.ldy = w.ld[l]; g.X = w.zp[l];
         if (l == 0) {
-            g.A = tangent; g.lda = L; g.a_gather = t.a_gather; g.batch = 1;
-            g.ncol_max = (tp_width_max(d, 1) * M + BN - 1) / BN;
+            g.A = tangent; g.lda = d->aev_len; g.a_gather = t.a_gather;
         } else {
-            g.A = t.ad[l - 1]; g.lda = w.ld[l - 1]; g.batch = M;
-            g.ncol_max = (tp_width_max(d, l + 1) + BN - 1) / BN;
-        }
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.w[l];
-            if (l == 0) {
-                p.K = nn.dims[0]; p.N = nn.dims[1] * M; p.ldb = p.N;
-            } else {
-                p.K = nn.dims[l]; p.N = nn.dims[l + 1]; p.ldb = p.N;
-                p.a_boff = nn.dims[l]; p.c_boff = nn.dims[l + 1];
-                p.b_stride = (int64_t)p.K * p.N;
-            }
+            g.A = t.ad[l - 1]; g.lda = w.ld[l - 1];
         }
         launch_gemm_fp32<EPI_TANGENT>(stream, g);
     }
@@ -2887,28 +2826,32 @@ static void tangent_head(hipStream_t stream, const TangentPass &t, float *datomi
 // adjoints of layer l - 1 from those of layer l:  mu = W^T p -> (p, mu c'' zdot);  nu = W^T q -> q += nu c'
 static void tangent_adjoint(hipStream_t stream, const TangentPass &t, int l)
 {
-    const anihip_mlp_desc *d = t.d;
-    const int S = d->num_species, M = d->n_members;
     const MlpWorkspace &w = *t.w;
     for (int pass = 0; pass < 2; ++pass) {
-        GemmArgs g = tp_gemm_base(t);
-        g.A = pass == 0 ? t.P[l] : t.Q[l]; g.lda = w.ld[l]; g.batch = M;
+        GemmArgs g = gemm_args(t.d, t.ctl, t.n, t.y_gather);
+        bwd_problems(g, t.d, l, 0);
+        g.A = pass == 0 ? t.P[l] : t.Q[l]; g.lda = w.ld[l];
         g.C = pass == 0 ? t.P[l - 1] : t.Q[l - 1]; g.C2 = t.Q[l - 1]; g.ldc = w.ld[l - 1];
         g.Y = w.act[l - 1]; g.Z = t.zd[l - 1]; g.ldy = w.ld[l - 1]; g.X = w.zp[l - 1];
-        g.ncol_max = (tp_width_max(d, l) + BN - 1) / BN;
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.wt[l];
-            p.K = nn.dims[l + 1]; p.N = nn.dims[l]; p.ldb = p.N;
-            p.a_boff = nn.dims[l + 1]; p.c_boff = nn.dims[l];
-            p.b_stride = (int64_t)p.K * p.N;
-        }
         if (pass == 0)
             launch_gemm_fp32<EPI_ADJ_P>(stream, g);
         else
             launch_gemm_fp32<EPI_ADJ_Q>(stream, g);
     }
+}
+
+// the tangent pass of an input HVP over its rows (without the weight gradients), then the layer-0 input adjoint
+// out = W_0^T q_0 scattered through the rows' map (q_0 = d S / d z_0 carries the 1 / M of the ensemble mean)
+static void hvp_tail(hipStream_t stream, const TangentPass &t, const float *tangent, float *out)
+{
+    tangent_forward(stream, t, tangent);
+    tangent_head(stream, t, nullptr);
+    for (int l = t.d->net[0].n_layers - 2; l >= 1; --l) tangent_adjoint(stream, t, l);
+    GemmArgs g = gemm_args(t.d, t.ctl, t.n);
+    bwd_problems(g, t.d, 0, layer0_width(t.d, false));
+    g.A = t.Q[0]; g.lda = t.w->ld[0];
+    g.C = out; g.ldc = t.d->aev_len; g.c_scatter = t.a_gather; g.n_store = t.d->aev_len;
+    launch_gemm_fp32<EPI_SCATTER>(stream, g);
 }
 
 extern "C" size_t anihip_mlp_tangent_workspace_bytes(const anihip_mlp_desc *d, int64_t n_central)
@@ -2946,62 +2889,23 @@ extern "C" int anihip_mlp_tangent_weight_grads(void *stream_, const anihip_mlp_d
     MlpWorkspace w;
     float *buf[4][ANIHIP_MAX_LAYERS];
     mlp_tangent_carve(d, n, (char *)workspace, &w, buf);
-    float **zd = buf[0], **ad = buf[1], **P = buf[2], **Q = buf[3];
+    float **ad = buf[1], **P = buf[2], **Q = buf[3];
 
     // 1. bucket by species, activations a_l (datomic_e doubles as the array whose padding entries get zeroed)
     if (int rc = train_forward(stream, d, n_atoms, lo, hi, species, aev, w, datomic_e, nullptr)) return rc;
-    TangentPass tp{d, &w, w.ctl, w.perm, nullptr, n, zd, ad, P, Q};
+    TangentPass tp{d, &w, w.ctl, w.perm, nullptr, n, buf[0], ad, P, Q};
     // 2. tangents: zdot_l = W_l adot_{l-1}, adot_l = c'(z_l) zdot_l   (adot_0 = tangent rows)
     tangent_forward(stream, tp, tangent);
     // 3. output layer: adjoint seeds p, q of the last hidden layer, d atomic_e, d w_out (d b_out = 0)
     tangent_head(stream, tp, datomic_e);
-    const int cr_chunks = (int)((n + CR_ROWS - 1) / CR_ROWS) + S;
-    auto col_reduce = [&](const float *X, int64_t ldx, int l_out, bool weights, float scale) {
-        ColReduceArgs c{};
-        int mx = 0;
-        for (int s = 0; s < S; ++s) {
-            c.X[s] = X;
-            c.ncols[s] = M * d->net[s].dims[l_out];
-            c.out[s] = weights ? grads[s].gw[nl - 1] : grads[s].gbias[l_out - 1];
-            c.extra[s] = nullptr;
-            mx = mx > c.ncols[s] ? mx : c.ncols[s];
-        }
-        c.ldx = ldx; c.ctl = w.ctl; c.perm = w.perm; c.S = S; c.M = M; c.g_atom = nullptr; c.inv_m = scale;
-        c.ct_max = (mx + 255) / 256;
-        hipLaunchKernelGGL(k_col_reduce, dim3((unsigned)(cr_chunks * c.ct_max)), dim3(256), 0, stream, c);
-    };
-    col_reduce(ad[nh - 1], w.ld[nh - 1], nl - 1, true, 1.0f / (float)M);   // d S / d w_out = sum adot_last / M
+    // d S / d w_out = sum adot_last / M
+    launch_col_reduce(stream, d, w, n, grads, nl - 1, ad[nh - 1], w.ld[nh - 1], nullptr, false);
 
     // 4. adjoints down the layers; d S / d W_l = p_l adot_{l-1}^T + q_l a_{l-1}^T, d S / d b_l = sum q_l
-    const int wg_chunks = (int)((n + WG_ROWS - 1) / WG_ROWS) + S;
     for (int l = nh - 1; l >= 0; --l) {
-        col_reduce(Q[l], w.ld[l], l + 1, false, 1.0f);
-        for (int term = 0; term < 2; ++term) {
-            WgradArgs a{};
-            a.ctl = w.ctl; a.S = S;
-            a.x_gather = l == 0 ? w.perm : nullptr;
-            a.batch = l == 0 ? 1 : M;
-            int kmax = 0, nmax = 0;
-            for (int s = 0; s < S; ++s) {
-                const anihip_species_net &nn = d->net[s];
-                WgradProblem &p = a.prob[s];
-                p.D = term == 0 ? P[l] : Q[l]; p.ldd = w.ld[l]; p.dW = grads[s].gw[l];
-                if (l == 0) {
-                    p.X = term == 0 ? tangent : aev; p.ldx = L; p.x_boff = 0; p.K = L; p.k_valid = L;
-                    p.d_boff = 0; p.N = nn.dims[1] * M; p.ldw = L; p.w_bstride = 0;
-                } else {
-                    p.X = term == 0 ? ad[l - 1] : w.act[l - 1]; p.ldx = w.ld[l - 1]; p.x_boff = nn.dims[l];
-                    p.K = nn.dims[l]; p.k_valid = p.K;
-                    p.d_boff = nn.dims[l + 1]; p.N = nn.dims[l + 1]; p.ldw = p.K; p.w_bstride = (int64_t)p.K * p.N;
-                }
-                kmax = kmax > p.K ? kmax : p.K;
-                nmax = nmax > p.N ? nmax : p.N;
-            }
-            a.ki_max = (kmax + 63) / 64;
-            a.nj_max = (nmax + 255) / 256;
-            const int64_t total = (int64_t)wg_chunks * a.batch * a.ki_max * a.nj_max;
-            hipLaunchKernelGGL(k_wgrad, dim3((unsigned)total), dim3(256), 0, stream, a);
-        }
+        launch_col_reduce(stream, d, w, n, grads, l, Q[l], w.ld[l], nullptr, false);
+        launch_wgrad(stream, d, w, n, grads, l, P[l], l == 0 ? tangent : ad[l - 1]);
+        launch_wgrad(stream, d, w, n, grads, l, Q[l], l == 0 ? aev : w.act[l - 1]);
         if (l == 0) break;
         tangent_adjoint(stream, tp, l);   // mu = W^T p -> (p, mu c'' zdot);  nu = W^T q -> q += nu c'
     }
@@ -3035,39 +2939,32 @@ __global__ __launch_bounds__(256) void k_hvp_rows(const int *ctl, const int *per
     }
 }
 
-// workspace: the atoms' inference workspace (activations kept, once per atom) + the rows' control block, permutation and
-// activation gather + zdot, adot, p, q per hidden layer and row
-static size_t mlp_hvp_carve(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_dir, char *base, MlpWorkspace *w,
-                            float *(*buf)[ANIHIP_MAX_LAYERS], float **atomic_e, int **rctl, int **rperm, int **ygather)
+// workspace of the input HVPs: the atoms' part first (the kept workspace, per-atom energies and, for explicit rows, the atoms'
+// sorted positions) -- it does not depend on n_rows, so anihip_mlp_rows_hvp_prepare fills it once per call -- then the rows'
+// control block, permutation and activation gather, and zdot, adot, p, q per hidden layer and row
+struct HvpWorkspace {
+    MlpWorkspace w;
+    float *atomic_e;
+    int *pos;   // explicit rows only (else NULL): sorted position of each atom
+    int *rctl, *rperm, *ygather;
+    float *buf[4][ANIHIP_MAX_LAYERS];
+};
+static size_t hvp_carve(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_rows, bool with_pos, char *base, HvpWorkspace *h)
 {
-    size_t off = align256(mlp_carve(d, n_atoms, base, w));
-    off = carve_zp(d, n_atoms, base, off, w);
-    const int64_t rows = n_atoms * n_dir;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    float *ae = (float *)take(sizeof(float) * (size_t)(n_atoms + 1));
-    int *rc = (int *)take(sizeof(int) * CTL_WORDS);
-    int *rp = (int *)take(sizeof(int) * (size_t)(rows + 1));
-    int *yg = (int *)take(sizeof(int) * (size_t)(rows + 1));
-    if (atomic_e) { *atomic_e = ae; *rctl = rc; *rperm = rp; *ygather = yg; }
-    const int nh = d->net[0].n_layers - 1;
-    for (int k = 0; k < 4; ++k)
-        for (int l = 0; l < nh; ++l) {
-            int mx = 0;
-            for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
-            float *b = (float *)take(sizeof(float) * (size_t)mx * d->n_members * (size_t)(rows + 1));
-            if (buf) buf[k][l] = b;
-        }
-    return off;
+    size_t off = kept_carve(d, n_atoms, base, h ? &h->w : nullptr);
+    float *ae = (float *)take(base, off, sizeof(float) * (size_t)(n_atoms + 1));
+    int *ps = with_pos ? (int *)take(base, off, sizeof(int) * (size_t)(n_atoms + 1)) : nullptr;
+    int *rc = (int *)take(base, off, sizeof(int) * CTL_WORDS);
+    int *rp = (int *)take(base, off, sizeof(int) * (size_t)(n_rows + 1));
+    int *yg = (int *)take(base, off, sizeof(int) * (size_t)(n_rows + 1));
+    if (h) { h->atomic_e = ae; h->pos = ps; h->rctl = rc; h->rperm = rp; h->ygather = yg; }
+    return carve_layers(d, n_rows, base, off, 4, h ? h->buf : nullptr);
 }
 
 extern "C" size_t anihip_mlp_input_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_dir)
 {
     if (!d || n_atoms < 0 || n_dir < 0) return 0;
-    return mlp_hvp_carve(d, n_atoms, n_dir, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return hvp_carve(d, n_atoms, n_atoms * n_dir, false, nullptr, nullptr);
 }
 
 extern "C" int anihip_mlp_input_hvp(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species,
@@ -3080,49 +2977,25 @@ extern "C" int anihip_mlp_input_hvp(void *stream_, const anihip_mlp_desc *d, int
     ANIHIP_REQUIRE(n_atoms >= 0 && n_dir >= 0, "negative size");
     ANIHIP_REQUIRE(n_atoms * n_dir < ((int64_t)1 << 31) - 1, "n_atoms * n_dir must stay below 2^31 (got %lld)",
                    (long long)(n_atoms * n_dir));
-    const int S = d->num_species, M = d->n_members, nl = d->net[0].n_layers, nh = nl - 1, L = d->aev_len;
     const int64_t rows = n_atoms * n_dir;
     if (rows == 0) return 0;
-    ANIHIP_REQUIRE(workspace_bytes >= mlp_hvp_carve(d, n_atoms, n_dir, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                    nullptr),
+    ANIHIP_REQUIRE(workspace_bytes >= hvp_carve(d, n_atoms, rows, false, nullptr, nullptr),
                    "workspace too small (anihip_mlp_input_hvp_workspace_bytes)");
-    MlpWorkspace w;
-    float *buf[4][ANIHIP_MAX_LAYERS];
-    float *atomic_e;
-    int *rctl, *rperm, *ygather;
-    mlp_hvp_carve(d, n_atoms, n_dir, (char *)workspace, &w, buf, &atomic_e, &rctl, &rperm, &ygather);
+    HvpWorkspace h;
+    hvp_carve(d, n_atoms, rows, false, (char *)workspace, &h);
     // (rows of padding atoms are never bucketed: they stay zero)
-    zero_words_async(stream, out, sizeof(float) * (size_t)rows * L);
+    zero_words_async(stream, out, sizeof(float) * (size_t)rows * d->aev_len);
     // 1. the atoms: species buckets, exact-fp32 forward with the activations kept -- once per atom, not per direction
-    if (int rc = train_forward(stream, d, n_atoms, 0, n_atoms, species, aev, w, atomic_e, nullptr)) return rc;
+    if (int rc = train_forward(stream, d, n_atoms, 0, n_atoms, species, aev, h.w, h.atomic_e, nullptr)) return rc;
     // 2. the (direction, atom) rows
-    zero_words_async(stream, rctl, sizeof(int) * CTL_WORDS);
+    zero_words_async(stream, h.rctl, sizeof(int) * CTL_WORDS);
     int64_t blocks = (rows + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_hvp_rows, dim3((unsigned)blocks), dim3(256), 0, stream, w.ctl, w.perm, S, (int)n_dir, n_atoms, rctl,
-                       rperm, ygather);
-    // 3. the tangent pass over the rows (activations gathered per row), without the weight gradients
-    TangentPass tp{d, &w, rctl, rperm, ygather, rows, buf[0], buf[1], buf[2], buf[3]};
-    tangent_forward(stream, tp, tangent);
-    tangent_head(stream, tp, nullptr);
-    for (int l = nh - 1; l >= 1; --l) tangent_adjoint(stream, tp, l);
-    // 4. the layer-0 input adjoint: out = W_0^T q_0 (q_0 = d S / d z_0 carries the 1 / M of the ensemble mean)
-    {
-        const int K0p = ((L + 31) / 32) * 32;
-        GemmArgs g = tp_gemm_base(tp);
-        g.y_gather = nullptr;
-        g.A = buf[3][0]; g.lda = w.ld[0]; g.a_gather = nullptr; g.batch = 1;
-        g.C = out; g.ldc = L; g.c_scatter = rperm; g.n_store = L;
-        g.ncol_max = (K0p + BN - 1) / BN;
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.wt[0];
-            p.K = nn.dims[1] * M; p.N = K0p; p.ldb = p.N;
-            p.a_boff = 0; p.c_boff = 0; p.b_stride = 0;
-        }
-        launch_gemm_fp32<EPI_SCATTER>(stream, g);
-    }
+    hipLaunchKernelGGL(k_hvp_rows, dim3((unsigned)blocks), dim3(256), 0, stream, h.w.ctl, h.w.perm, d->num_species, (int)n_dir,
+                       n_atoms, h.rctl, h.rperm, h.ygather);
+    // 3. the tangent pass over the rows (activations gathered per row), the layer-0 input adjoint
+    TangentPass tp{d, &h.w, h.rctl, h.rperm, h.ygather, rows, h.buf[0], h.buf[1], h.buf[2], h.buf[3]};
+    hvp_tail(stream, tp, tangent, out);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -3168,40 +3041,10 @@ __global__ __launch_bounds__(256) void k_rows_ctl(int S, int64_t n_rows, const i
     }
 }
 
-// workspace: the atoms' part (inference workspace with the activations kept, per-atom energies, sorted positions) first --
-// it does not depend on n_rows, so anihip_mlp_rows_hvp_prepare fills it once per call -- then the rows' part
-static size_t mlp_rows_carve(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_rows, char *base, MlpWorkspace *w,
-                             float *(*buf)[ANIHIP_MAX_LAYERS], float **atomic_e, int **pos, int **rctl, int **rid,
-                             int **ygather)
-{
-    size_t off = align256(mlp_carve(d, n_atoms, base, w));
-    off = carve_zp(d, n_atoms, base, off, w);
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    float *ae = (float *)take(sizeof(float) * (size_t)(n_atoms + 1));
-    int *ps = (int *)take(sizeof(int) * (size_t)(n_atoms + 1));
-    int *rc = (int *)take(sizeof(int) * CTL_WORDS);
-    int *ri = (int *)take(sizeof(int) * (size_t)(n_rows + 1));
-    int *yg = (int *)take(sizeof(int) * (size_t)(n_rows + 1));
-    if (atomic_e) { *atomic_e = ae; *pos = ps; *rctl = rc; *rid = ri; *ygather = yg; }
-    const int nh = d->net[0].n_layers - 1;
-    for (int k = 0; k < 4; ++k)
-        for (int l = 0; l < nh; ++l) {
-            int mx = 0;
-            for (int s = 0; s < d->num_species; ++s) mx = mx > d->net[s].dims[l + 1] ? mx : d->net[s].dims[l + 1];
-            float *b = (float *)take(sizeof(float) * (size_t)mx * d->n_members * (size_t)(n_rows + 1));
-            if (buf) buf[k][l] = b;
-        }
-    return off;
-}
-
 extern "C" size_t anihip_mlp_rows_hvp_workspace_bytes(const anihip_mlp_desc *d, int64_t n_atoms, int64_t n_rows)
 {
     if (!d || n_atoms < 0 || n_rows < 0) return 0;
-    return mlp_rows_carve(d, n_atoms, n_rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return hvp_carve(d, n_atoms, n_rows, true, nullptr, nullptr);
 }
 
 extern "C" int anihip_mlp_rows_hvp_prepare(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms, const int32_t *species,
@@ -3211,20 +3054,16 @@ extern "C" int anihip_mlp_rows_hvp_prepare(void *stream_, const anihip_mlp_desc 
     if (int rc = check_desc(d)) return rc;
     ANIHIP_REQUIRE(species && aev && workspace, "null pointer argument");
     ANIHIP_REQUIRE(n_atoms >= 0 && n_atoms < ((int64_t)1 << 31) - 1, "n_atoms must be 0 .. 2^31 - 2");
-    ANIHIP_REQUIRE(workspace_bytes >= mlp_rows_carve(d, n_atoms, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                     nullptr, nullptr),
+    ANIHIP_REQUIRE(workspace_bytes >= hvp_carve(d, n_atoms, 0, true, nullptr, nullptr),
                    "workspace too small (anihip_mlp_rows_hvp_workspace_bytes)");
     if (n_atoms == 0) return 0;
-    MlpWorkspace w;
-    float *buf[4][ANIHIP_MAX_LAYERS];
-    float *atomic_e;
-    int *pos, *rctl, *rid, *ygather;
-    mlp_rows_carve(d, n_atoms, 0, (char *)workspace, &w, buf, &atomic_e, &pos, &rctl, &rid, &ygather);
+    HvpWorkspace h;
+    hvp_carve(d, n_atoms, 0, true, (char *)workspace, &h);
     // species buckets, exact-fp32 forward with the activations kept, once per call
-    if (int rc = train_forward(stream, d, n_atoms, 0, n_atoms, species, aev, w, atomic_e, nullptr)) return rc;
+    if (int rc = train_forward(stream, d, n_atoms, 0, n_atoms, species, aev, h.w, h.atomic_e, nullptr)) return rc;
     int64_t blocks = (n_atoms + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_rows_pos, dim3((unsigned)blocks), dim3(256), 0, stream, w.ctl, w.perm, d->num_species, pos);
+    hipLaunchKernelGGL(k_rows_pos, dim3((unsigned)blocks), dim3(256), 0, stream, h.w.ctl, h.w.perm, d->num_species, h.pos);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -3238,44 +3077,20 @@ extern "C" int anihip_mlp_rows_hvp(void *stream_, const anihip_mlp_desc *d, int6
     ANIHIP_REQUIRE(species && row_atom && tangent && workspace && out, "null pointer argument");
     ANIHIP_REQUIRE(n_atoms >= 0 && n_rows >= 0, "negative size");
     ANIHIP_REQUIRE(n_rows < ((int64_t)1 << 31) - 1, "n_rows must stay below 2^31 (got %lld)", (long long)n_rows);
-    const int S = d->num_species, M = d->n_members, nl = d->net[0].n_layers, nh = nl - 1, L = d->aev_len;
     if (n_rows == 0) return 0;
-    ANIHIP_REQUIRE(workspace_bytes >= mlp_rows_carve(d, n_atoms, n_rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                     nullptr, nullptr),
+    ANIHIP_REQUIRE(workspace_bytes >= hvp_carve(d, n_atoms, n_rows, true, nullptr, nullptr),
                    "workspace too small (anihip_mlp_rows_hvp_workspace_bytes)");
-    MlpWorkspace w;
-    float *buf[4][ANIHIP_MAX_LAYERS];
-    float *atomic_e;
-    int *pos, *rctl, *rid, *ygather;
-    mlp_rows_carve(d, n_atoms, n_rows, (char *)workspace, &w, buf, &atomic_e, &pos, &rctl, &rid, &ygather);
-    zero_words_async(stream, out, sizeof(float) * (size_t)n_rows * L);
-    zero_words_async(stream, rctl, sizeof(int) * CTL_WORDS);
+    HvpWorkspace h;
+    hvp_carve(d, n_atoms, n_rows, true, (char *)workspace, &h);
+    zero_words_async(stream, out, sizeof(float) * (size_t)n_rows * d->aev_len);
+    zero_words_async(stream, h.rctl, sizeof(int) * CTL_WORDS);
     int64_t blocks = (n_rows + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_rows_ctl, dim3((unsigned)blocks), dim3(256), 0, stream, S, n_rows, species, row_atom, pos, rctl,
-                       rid, ygather);
-    // the tangent pass over the rows (activations gathered per row), without the weight gradients
-    TangentPass tp{d, &w, rctl, rid, ygather, n_rows, buf[0], buf[1], buf[2], buf[3]};
-    tangent_forward(stream, tp, tangent);
-    tangent_head(stream, tp, nullptr);
-    for (int l = nh - 1; l >= 1; --l) tangent_adjoint(stream, tp, l);
-    // the layer-0 input adjoint: out = W_0^T q_0
-    {
-        const int K0p = ((L + 31) / 32) * 32;
-        GemmArgs g = tp_gemm_base(tp);
-        g.y_gather = nullptr;
-        g.A = buf[3][0]; g.lda = w.ld[0]; g.a_gather = nullptr; g.batch = 1;
-        g.C = out; g.ldc = L; g.c_scatter = rid; g.n_store = L;
-        g.ncol_max = (K0p + BN - 1) / BN;
-        for (int s = 0; s < S; ++s) {
-            const anihip_species_net &nn = d->net[s];
-            GemmProblem &p = g.prob[s];
-            p.B = nn.wt[0];
-            p.K = nn.dims[1] * M; p.N = K0p; p.ldb = p.N;
-            p.a_boff = 0; p.c_boff = 0; p.b_stride = 0;
-        }
-        launch_gemm_fp32<EPI_SCATTER>(stream, g);
-    }
+    hipLaunchKernelGGL(k_rows_ctl, dim3((unsigned)blocks), dim3(256), 0, stream, d->num_species, n_rows, species, row_atom,
+                       h.pos, h.rctl, h.rperm, h.ygather);
+    // the tangent pass over the rows (activations gathered per row), the layer-0 input adjoint
+    TangentPass tp{d, &h.w, h.rctl, h.rperm, h.ygather, n_rows, h.buf[0], h.buf[1], h.buf[2], h.buf[3]};
+    hvp_tail(stream, tp, tangent, out);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }
