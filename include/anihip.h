@@ -39,7 +39,9 @@ extern "C" {
 #define ANIHIP_ST_ENTRY_OVERFLOW 1u   /* neighbor entries exceeded ent_capacity */
 #define ANIHIP_ST_ROW_OVERFLOW 2u     /* one atom has > ANIHIP_MAX_ANG / ANIHIP_MAX_RAD neighbors or > 255 of one species */
 #define ANIHIP_ST_GRID_OVERFLOW 4u    /* internal: grid coarsened to fit max_cells (not an error) */
-#define ANIHIP_STATUS_WORDS 8         /* status[1] = total neighbor entries, status[2] = #cells */
+#define ANIHIP_STATUS_WORDS 8         /* status[1] = total neighbor entries, status[2] = #cells, status[3] = #cells that
+                                         anihip_nbr_build_cell left to its per-atom kernel (stencil of more than 64 bins
+                                         or more candidates than the per-bin kernel stages) */
 
 #define ANIHIP_MAX_SPECIES 8
 #define ANIHIP_MAX_ANG 128 /* angular neighbors per atom (cuAEV's analogous bound: csrc/aev.cu:11) */

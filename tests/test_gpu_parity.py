@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from _nbr_rows import compare_rows, wrap_coords
 from _util import GOLDEN_NAMES, _stress_state, load_golden, oracle_networks, oracle_params, seeded_state
 from torchani_amd import _lib
 from torchani_amd.engine import PackedNetworks
@@ -97,35 +98,20 @@ def test_neighbor_rows_match_oracle(dev, oracle64, name):
     C, A = g["species"].shape
     start, j, d, r = oracle64.neighbors(g["species"], g["coords"].astype(np.float64), consts.Rcr, g["cell"],
                                         g["pbc"])
+    periodic = g["cell"] is not None and g["pbc"] is not None and bool(np.any(g["pbc"]))
+    cell64 = g["cell"].astype(np.float64) if periodic else None
+    xw = wrap_coords(g["coords"], cell64, g["pbc"])
     for mode in modes_for(g):
         nbrs = eng.neighbors(sp.to(torch.int32).contiguous(), x.contiguous(), cell, pbc, mode=mode, row_cap=256)
         torch.cuda.synchronize()
         nbrs.raise_on_overflow()
         meta, ent = unpack_rows(nbrs, C * A)
-        worst = 0.0
-        for i in range(C * A):
-            nA, nF = int(meta[i, 1] & 0xFFFF), int(meta[i, 1] >> 16)
-            lo, hi = start[i], start[i + 1]
-            assert nA + nF == hi - lo, f"{name}/{mode}: atom {i} has {nA + nF} neighbors, oracle {hi - lo}"
-            if hi == lo:
-                continue
-            row = ent[meta[i, 0]: meta[i, 0] + nA + nF]
-            w = row[:, 3].copy().view(np.uint32)
-            jj, spj = (w & 0x0FFFFFFF).astype(np.int64), (w >> 28).astype(np.int64)
-            assert np.array_equal(spj, g["species"].reshape(-1)[jj])
-            rr = np.linalg.norm(row[:, :3].astype(np.float64), axis=1)
-            # angular-range group first, each group sorted by species
-            assert np.all(rr[:nA] <= consts.Rca + 1e-5) and np.all(rr[nA:] >= consts.Rca - 1e-5)
-            assert np.all(np.diff(spj[:nA]) >= 0) and np.all(np.diff(spj[nA:]) >= 0)
-            cntA = np.concatenate([(meta[i, 2] >> (8 * np.arange(4))) & 255, (meta[i, 3] >> (8 * np.arange(4))) & 255])
-            cntF = np.concatenate([(meta[i, 4] >> (8 * np.arange(4))) & 255, (meta[i, 5] >> (8 * np.arange(4))) & 255])
-            assert np.array_equal(cntA, np.bincount(spj[:nA], minlength=8))
-            assert np.array_equal(cntF, np.bincount(spj[nA:], minlength=8))
-            # same (j, displacement) multiset as the oracle
-            ko = np.lexsort((d[lo:hi, 2], d[lo:hi, 1], d[lo:hi, 0], j[lo:hi]))
-            km = np.lexsort((row[:, 2], row[:, 1], row[:, 0], jj))
-            assert np.array_equal(j[lo:hi][ko], jj[km]), f"{name}/{mode}: atom {i} neighbor indices differ"
-            worst = max(worst, np.abs(d[lo:hi][ko] - row[km, :3]).max())
+        # (tests/_nbr_rows.py: per row the oracle's (j, image) set exactly, species bits, angular group first and split at
+        # Rca within 1e-5, groups sorted by species, packed per-species counts)
+        res = compare_rows(f"{name}/{mode}", meta, ent, 0, C * A, g["species"], (start, j, d, r), xw, cell64,
+                           consts.Rcr, consts.Rca, band_rcr=0.0, band_rca=1e-5)
+        assert res.pairs == j.shape[0]
+        worst = res.worst
         report(f"nbr   {name:22s} {mode:5s} max|d - d_ref| = {worst:.2e} A")
         assert worst < 5e-6
 

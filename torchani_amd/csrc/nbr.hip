@@ -518,7 +518,8 @@ __global__ __launch_bounds__(NBR_WPB * WAVE) void k_nbr_cell(
     float4 *ent, uint32_t *status, const int *handled, const int *n_unhandled)
 {
     // second pass behind k_nbr_cell2: only the atoms of the cells that kernel left (more candidates than it stages, or a
-    // stencil of more than 64 bins); nothing left -> nothing to do
+    // stencil of more than 64 bins); nothing left -> nothing to do.  status[3] reports how many bins that is.
+    if (n_unhandled && blockIdx.x == 0 && threadIdx.x == 0) status[3] = (uint32_t)*n_unhandled;
     if (n_unhandled && *n_unhandled == 0) return;
     __shared__ float4 s_hits[NBR_WPB][MAXR];
     __shared__ int s_pend[NBR_WPB][WAVE];      // inclusive prefix of the bin populations
@@ -606,6 +607,20 @@ __global__ __launch_bounds__(NBR_WPB * WAVE) void k_nbr_cell(
     }
 }
 
+// sum of the eight byte counters of a group.  A sum that can reach 256 (the four-chunk rows: MAXR hits) must not be taken in
+// a byte: a far group of exactly 256 entries in mixed species came back as an empty row without a flag.  WIDE adds the
+// bytes in 16-bit lanes; rows of at most 128 hits keep the single multiply.
+template <bool WIDE>
+__device__ __forceinline__ int byte_sum(uint64_t p)
+{
+    if constexpr (WIDE) {
+        const uint64_t h = (p & 0x00FF00FF00FF00FFull) + ((p >> 8) & 0x00FF00FF00FF00FFull);
+        return (int)((h * 0x0001000100010001ull) >> 48);
+    } else {
+        return (int)((p * 0x0101010101010101ull) >> 56);
+    }
+}
+
 // rows of the (up to) two central atoms of a sweep from their hits in the staged candidate list (see k_nbr_cell2); the two
 // atoms go through every step together, so that the dependent chain hit index -> candidate -> class -> ballot -> rank of
 // one atom fills the gaps of the other's
@@ -678,7 +693,7 @@ __device__ __forceinline__ void emit_from_stage(const float4 *cand, const uint16
         uint32_t *meta_i = meta + (size_t)ia[t] * META_W;
         const size_t row0 = (size_t)(ia[t] - lo) * row_cap;
         float4 *row = ent + row0;
-        const int nA = (int)((pk[t][0] * 0x0101010101010101ull) >> 56), nF = (int)((pk[t][1] * 0x0101010101010101ull) >> 56);
+        const int nA = byte_sum<(CAP > 255)>(pk[t][0]), nF = byte_sum<(CAP > 255)>(pk[t][1]);
         const bool bad = over[t] || big[t] || nA + nF > row_cap || nA > MAXA;
         if (bad && lane == 0) atomicOr(&status[0], ANIHIP_ST_ROW_OVERFLOW);
         if (!bad) {
