@@ -2181,7 +2181,7 @@ def test_energies_are_run_to_run_deterministic(dev):
     assert (druns[0].forces - runs[0].forces).abs().max().item() < 1e-6
     # (a different decomposition is a different -- equally valid -- rounding: a pair that straddles two shards is
     # pushed as two separately rounded terms instead of one gathered sum; reproducibility is per decomposition)
-    parts = [det._energies_and_forces_core(spt.to(torch.int32), xt, ct, (True, True, True), None, True, False, (r, 3))
+    parts = [det._energies_and_forces_core(spt.to(torch.int32), xt, ct, (True, True, True), shard=(r, 3))
              for r in range(3)]
     assert (sum(p.forces for p in parts) - druns[0].forces).abs().max().item() < 1e-7
 

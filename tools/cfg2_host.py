@@ -1,4 +1,4 @@
-"""Host-side cost of one graph-replayed config-2 step (development): where the wall time of ANI.graphed(...)(coords) goes."""
+"""Host-side cost of one config-2 step (development): the eager call, and where the wall time of ANI.graphed(...)(coords) goes."""
 import os
 import sys
 import time
@@ -35,6 +35,7 @@ def loop(fn, reps=200, sync_each=False):
     return (t1 - t0) / reps * 1e6, (t2 - t0) / reps * 1e6
 
 
+print("eager call       host %.1f us / step, wall %.1f us / step" % loop(lambda: model.energies_and_forces(spd, xd)))
 print("full call        host %.1f us / step, wall %.1f us / step" % loop(lambda: g(xd)))
 print("full call, sync each step: %.1f us" % loop(lambda: g(xd), sync_each=True)[1])
 print("graph.replay()   host %.1f us, wall %.1f us" % loop(lambda: g.graph.replay()))

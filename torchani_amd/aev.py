@@ -18,6 +18,7 @@ from .constants import AEVConstants, aev_constants_1x, aev_constants_2x, cutoff_
 from ._lib import MAX_RAD as _MAX_RAD
 from .engine import AevEngine, NeighborRows, VerletRows
 from .tuples import Neighbors, SpeciesAEV
+from .utils import pbc_tuple
 
 
 def _envelope(name: str, distances: Tensor, cutoff: float) -> Tensor:
@@ -402,7 +403,7 @@ class AEVComputer(torch.nn.Module):
             raise ValueError("expected elem_idxs [C, A] and coords [C, A, 3]")
         if (cell is None) != (pbc is None):
             raise ValueError("cell and pbc must be given together")
-        pbc_t = None if pbc is None else tuple(bool(b) for b in pbc.tolist())
+        pbc_t = pbc_tuple(pbc)
         species32 = elem_idxs.to(torch.int32).contiguous()
         out = _AEVFunction.apply(coords, species32, cell, pbc_t, self)
         if self.check_overflow and not torch.cuda.is_current_stream_capturing() and self._last_neighbors.overflowed():
@@ -443,7 +444,7 @@ def cell_list(cutoff: float, species: Tensor, coords: Tensor, cell: tp.Optional[
     eng = _cell_list_engines.get(float(cutoff))
     if eng is None:
         eng = _cell_list_engines[float(cutoff)] = AevEngine(aev_constants_2x(7)._replace(Rcr=float(cutoff), Rca=1e-3))
-    pbc_t = None if (pbc is None or cell is None) else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
+    pbc_t = None if cell is None else pbc_tuple(pbc)
     sp32 = species.clamp(min=-1, max=0).to(torch.int32).contiguous()   # (only "dummy or not" matters for the pair search)
     rows = eng.neighbors(sp32, coords.detach().to(torch.float32).contiguous(), cell, pbc_t, mode="cell",
                          row_cap=_MAX_RAD)

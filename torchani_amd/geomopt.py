@@ -31,6 +31,7 @@ from . import _lib
 from .engine import _stream
 from .tuples import OptimizedGeometries
 from .units import HARTREE_TO_EV
+from .utils import pbc_tuple
 
 DEFAULT_ALPHA = 70.0 / HARTREE_TO_EV   # ASE LBFGS(alpha=70 eV / A^2), in Hartree / A^2
 DEFAULT_FMAX = 0.05 / HARTREE_TO_EV    # ASE Optimizer.run(fmax=0.05 eV / A), in Hartree / A
@@ -94,7 +95,7 @@ class GeometryOptimizer:
         Cn, A = species.shape
         self.model, self.species, self.cell = model, species, cell
         # (a host tuple once: a pbc tensor would cost a synchronization at every evaluation)
-        self.pbc = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
+        self.pbc = pbc_tuple(pbc)
         self._dtype = coordinates.dtype
         self.coordinates = coordinates.detach().to(torch.float32).clone().contiguous()
         active = species >= 0

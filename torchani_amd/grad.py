@@ -34,6 +34,7 @@ from torch import Tensor
 from .tuples import (BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians,
                      EnergiesForcesStrainHessians, ForcesHessians, SparseVibAnalysis, VibAnalysis)
 from . import units as _units
+from .utils import pbc_tuple
 
 
 def forces(energies: Tensor, coordinates: Tensor, retain_graph: tp.Optional[bool] = None,
@@ -198,7 +199,7 @@ def _second_order_inputs(model, species: Tensor, coordinates: Tensor, cell, pbc,
         nnp = model.potentials["nnp"]._enabled
         if nnp or sparse:
             aevc = model.aev_computer
-            nbrs = aevc.neighbor_rows(species32, c32, cell, None if pbc is None else tuple(bool(b) for b in pbc.tolist()))
+            nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_tuple(pbc))
             nbrs.raise_on_overflow()
             eng = aevc.engine()
         if nnp:

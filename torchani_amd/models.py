@@ -30,6 +30,7 @@ from .engine import FIXED_SCALE, _n_cus as _n_cus_of, energy_forces_finish, ener
 from .extras.electro import BaseChargeNormalizer, ChargeNormalizer  # noqa: F401
 from .nn import ANINetworks, AtomicNetwork, Ensemble, SelfEnergy, SpeciesConverter
 from .parallel import join_exact, shard_range, split_exact
+from .utils import pbc_tuple, tensor_key
 from .tuples import EnergiesScalars, AtomicStdev, ForceMagnitudes, ForceStdev, SpeciesEnergiesQBC, SpeciesForces, FusedEnergiesForces, SpeciesEnergies
 from .weights import arch_gsaes, arch_networks, arch_spec, random_state_dict
 
@@ -42,6 +43,14 @@ class NNPotential(torch.nn.Module):
         self.aev_computer = aev_computer
         self.neural_networks = neural_networks
         self._enabled = True
+
+
+class _LocalStage(tp.NamedTuple):
+    """What ANI._local_stage hands to the two paths of the fused step, besides the forces in their accumulator."""
+    net_e: Tensor                 # per-atom energies of the networks [n] fp32
+    atomic_e: Tensor              # ... plus those of the pair potentials
+    energies: Tensor              # partial energies [C] fp64 of the central range, self energies included
+    virial: tp.Optional[Tensor]   # [3, 3] fp64 of the central range, if asked for
 
 
 class ANI(torch.nn.Module):
@@ -166,7 +175,7 @@ class ANI(torch.nn.Module):
         rc = min(pot.cutoff, 1.0e3)
         if pot._own_engine is None or abs(pot._own_engine.consts.Rcr - rc) > 1e-9:
             pot._own_engine = AevEngine(self.aev_computer.engine().consts._replace(Rcr=rc, Rca=1e-3))
-        pbc_t = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
+        pbc_t = pbc_tuple(pbc)
         c32 = coords.detach().to(torch.float32).contiguous()
         rows = pot._own_engine.neighbors(species32, c32, cell, pbc_t, lo=lo, hi=hi, mode=self.aev_computer.neighbor_mode,
                                          row_cap=_lib_MAX_RAD)
@@ -180,7 +189,7 @@ class ANI(torch.nn.Module):
         ``check_overflow=True`` then costs no host synchronisation: BASELINE config 2 through the default API)."""
         if species.dim() != 2:
             return False
-        if cell is not None and pbc is not None and any(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc)):
+        if cell is not None and pbc is not None and any(pbc_tuple(pbc)):
             return False
         aevc = self.aev_computer
         if aevc.neighbor_mode not in ("batch", "auto"):
@@ -219,9 +228,10 @@ class ANI(torch.nn.Module):
         """
         if not coords.is_cuda:
             raise ValueError("torchani_amd's engine needs tensors on a ROCm device (no CPU fallback)")
-        if check_overflow and self._overflow_impossible(species, cell, pbc):
+        pbc_t = pbc_tuple(pbc)   # (once: everything below takes the tuple)
+        if check_overflow and self._overflow_impossible(species, cell, pbc_t):
             check_overflow = False   # (nothing to read: no host synchronisation for batches of small molecules)
-        out = self._auto_graph_call(species, coords, cell, pbc, group, shard, stress, check_overflow)
+        out = self._auto_graph_call(species, coords, cell, pbc_t, group, shard, stress, check_overflow)
         if out is not None:
             return out
         elem_idxs = self._elem_idxs(species)
@@ -231,8 +241,11 @@ class ANI(torch.nn.Module):
         hint = 0 if torch.cuda.is_current_stream_capturing() else self._tile_hint(species, species32, n_central)
         if self.two_product_backward:
             hint |= _lib.MLP_FLAG_BWD_TWO_PRODUCTS
-        out = self._energies_and_forces_core(species32, c32, cell, pbc, group, reduce_forces, False, shard, stress, hint,
-                                             species)
+        def step():
+            return self._energies_and_forces_core(species32, c32, cell, pbc_t, group=group, reduce_forces=reduce_forces,
+                                                  shard=shard, stress=stress, tile_hint=hint, species_key=species)
+
+        out = step()
         if check_overflow and not torch.cuda.is_current_stream_capturing():
             # one host sync after everything is queued: a row over capacity was zeroed by the builder, the result
             # would be silently wrong (the reference asserts on the device, csrc/aev.cu:229).  Retry once at the
@@ -242,13 +255,12 @@ class ANI(torch.nn.Module):
                 if aevc.row_capacity < MAX_RAD:
                     warnings.warn(f"neighbor rows overflowed row_capacity={aevc.row_capacity}: retrying with {MAX_RAD}")
                     aevc.row_capacity = MAX_RAD
-                    out = self._energies_and_forces_core(species32, c32, cell, pbc, group, reduce_forces, False, shard,
-                                                         stress, hint, species)
+                    out = step()
                 aevc.last_neighbors().raise_on_overflow()
             self._raise_on_pair_overflow()
         return out
 
-    def _auto_graph_call(self, species, coords, cell, pbc, group, shard, stress, check_overflow):
+    def _auto_graph_call(self, species, coords, cell, pbc_t, group, shard, stress, check_overflow):
         """Small systems are launch-bound (a dozen kernels of a few microseconds): from the third call with the SAME species
         tensor (identity and version -- an MD loop, a batch re-evaluated with new coordinates) and shapes, the step is
         replayed as one HIP graph (GraphedEnergiesForces); results are copied out of the graph's static buffers.
@@ -258,22 +270,18 @@ class ANI(torch.nn.Module):
                 or self.deterministic_forces or self.aev_computer.verlet is not None   # (its displacement check syncs)
                 or torch.cuda.is_current_stream_capturing()):
             return None
-        pbc_key = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
-        key = (species.data_ptr(), species._version, tuple(species.shape), coords.device, cell is None, pbc_key,
-               self._config_stamp())
+        key = (tensor_key(species), coords.device, cell is None, pbc_t, self._config_stamp())
         ent = self._graphs.get(key)
         if ent is None:
             if len(self._graphs) >= 4:
                 self._graphs.pop(next(iter(self._graphs)))
-            # (the entry keeps the species tensor alive: while it exists no other tensor can show up under its address, so
-            # an equal key always means the same tensor with the same contents)
-            self._graphs[key] = ent = [0, None, species]
+            self._graphs[key] = ent = [0, None, species]   # (holds the tensor: utils.tensor_key)
         ent[0] += 1
         if ent[0] < 3:
             return None
         if ent[1] is None:
             try:
-                ent[1] = GraphedEnergiesForces(self, species, coords, cell, pbc)
+                ent[1] = GraphedEnergiesForces(self, species, coords, cell, pbc_t)
             except RuntimeError as err:   # something on the path cannot be captured: stay eager for good
                 warnings.warn(f"HIP graph capture of energies_and_forces failed ({err}); continuing without graphs")
                 self.auto_graph_atoms = 0
@@ -305,7 +313,7 @@ class ANI(torch.nn.Module):
         reference to the tensor so that its address cannot be handed to another one meanwhile."""
         if n_central < 16384:
             return 0
-        key = (species.data_ptr(), species._version, tuple(species.shape))
+        key = tensor_key(species)
         hit = self.__dict__.get("_n_elem_cache")
         if hit is None or hit[0] != key:
             present = torch.bincount(elem_idxs.reshape(-1).clamp(min=-1) + 1, minlength=len(self.symbols) + 1)[1:]
@@ -409,7 +417,7 @@ class ANI(torch.nn.Module):
             # (a capture must own the tensors it records -- GraphedEnergiesForces asks before it captures and passes its
             # own copy down; anything else that captures gets the numbering as given)
             return species32, None
-        key = (key_tensor.data_ptr(), key_tensor._version, tuple(key_tensor.shape))
+        key = tensor_key(key_tensor)
         hit = self.__dict__.get("_species_order_cache")
         if hit is None or hit[0] != key:
             S = self.aev_computer.num_species
@@ -434,116 +442,117 @@ class ANI(torch.nn.Module):
             self.__dict__["_species_order_cache"] = hit
         return (species32 if hit[2] is None else hit[3]), hit[2]
 
-    def _energies_and_forces_core(self, species32: Tensor, c32: Tensor, cell, pbc, group, reduce_forces,
-                                  check_overflow, shard, stress: bool = False, tile_hint: int = 0,
-                                  species_key: tp.Optional[Tensor] = None,
+    def _energies_and_forces_core(self, species32: Tensor, c32: Tensor, cell, pbc_t, *, group=None,
+                                  reduce_forces: bool = True, shard: tp.Optional[tp.Tuple[int, int]] = None,
+                                  stress: bool = False, tile_hint: int = 0, species_key: tp.Optional[Tensor] = None,
                                   engine_species: tp.Optional[tp.Tuple[Tensor, tp.Optional[tp.Tuple[int, ...]]]] = None
                                   ) -> FusedEnergiesForces:
-        """The stream-ordered part of energies_and_forces (element indices int32, coords fp32 contiguous):
-        no host synchronisation unless check_overflow, so it can be captured into a HIP graph."""
+        """The stream-ordered part of energies_and_forces (element indices int32, coords fp32 contiguous, pbc as a host
+        tuple): no host synchronisation, so it can be captured into a HIP graph."""
         C, A = species32.shape
         n = C * A
         if (group is None and shard is None and C == 1 and n >= 65536 and self.locality_sort != "never"
                 and not torch.cuda.is_current_stream_capturing() and self._spatial_ok(C, n)
-                and self._wants_locality_sort(species32, c32, cell, pbc, species_key)):
+                and self._wants_locality_sort(species32, c32, cell, pbc_t, species_key)):
             shard = (0, 1)   # one "rank" owning everything: the spatial path works on the cell-sorted copy
         if (group is not None or shard is not None) and self._spatial_ok(C, n):
-            return self._energies_and_forces_spatial(species32, c32, cell, pbc, group, reduce_forces, check_overflow, shard,
-                                                     stress, tile_hint, species_key)
+            return self._energies_and_forces_spatial(species32, c32, cell, pbc_t, group, reduce_forces, shard, stress,
+                                                     tile_hint, species_key)
         lo, hi = shard_range(n, group) if shard is None else shard_range(n, rank=shard[0], world=shard[1])
-        aevc = self.aev_computer
-        eng = aevc.engine()
-        pbc_t = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
-        given = species32
-        # (the kernels' numbering of the species; `given` indexes the self energies)
-        species32, order = engine_species if engine_species is not None else self._engine_species(given, species_key)
-        nbrs = aevc.neighbor_rows(species32, c32, cell, pbc_t, lo=lo, hi=hi)
-        packed = self.neural_networks._pack(c32.device, order)
-        # per-atom flags of the AEV slabs that are not identically zero (absent neighbor species): the
-        # layer-0 GEMMs skip the others
-        slab_mask = None
-        # AEV rows and their gradients exist for this rank's central atoms only ([hi - lo, L] buffers)
-        plain = self._plain_slabs(eng, packed)
-        if packed.radial_len == 16 * eng.params.num_species and eng.tuned and eng.n_slabs <= 32:
-            if self.keep_aev_rows and not torch.cuda.is_current_stream_capturing() and eng.rows_wanted(n, lo, hi, c32.device):
-                # rows and flags in the engine's kept buffers, updated in place (AevEngine.forward_update): from the second
-                # consecutive call with these sizes on
-                aev, slab_mask = eng.forward_update(species32, nbrs)
-            else:
-                # (the AEV kernel writes the flags of every central atom; the others are read by nobody, zero for tidiness)
-                slab_mask = (torch.empty if (lo == 0 and hi == n) else torch.zeros)(n, dtype=torch.int32, device=c32.device)
-                aev = eng.forward(species32, nbrs, slab_mask=slab_mask, shard_rows=True)
-        else:
-            if plain:   # a general grid: flags of the plain 32-column slabs from the general AEV kernel
-                slab_mask = torch.zeros(n, dtype=torch.int32, device=c32.device)
-            aev = eng.forward(species32, nbrs, slab_mask=slab_mask, shard_rows=True)
-        atomic_e, grad_aev, _ = packed.forward_backward(species32, aev, lo=lo, hi=hi, want_grad=True,
-                                                        chunk=self.mlp_chunk, slab_mask=slab_mask,
-                                                        shard_rows=True, tile_hint=tile_hint, plain_slabs=plain)
-        if plain:
-            slab_mask = None   # (the general AEV backward reads the blocks of present species only: no flags needed)
-        virial = torch.empty((3, 3), dtype=torch.float64, device=c32.device) if stress else None
-        pair_e, pair_g, pair_w = self._pair_terms(species32, c32, cell, pbc_t, nbrs, lo, hi, stress)
+        # (the kernels' numbering of the species; the given one indexes the self energies)
+        sp_e, order = engine_species if engine_species is not None else self._engine_species(species32, species_key)
         from .parallel import FORCE_COLLECTIVES
 
         world = 1 if group is None else torch.distributed.get_world_size(group)
         several = world > 1 or (group is not None and FORCE_COLLECTIVES)
-        sae = self._sae64(c32.device) if self.energy_shifter._enabled else None
-        if self.deterministic_forces:
-            # order-independent sums: int64 fixed-point accumulators (2^-32) for the forces (ANIHIP_BWD_FIXED_POINT), and
-            # for a sharded run ONE int64 all-reduce that also carries energies and virial at the same resolution
-            n_tail = (C + (9 if stress else 0)) if several else 0
-            red = torch.zeros(3 * n + n_tail, dtype=torch.int64, device=c32.device)
-            eng.backward(species32, nbrs, grad_aev, grad_coords=red[:3 * n].view(n, 3), shard_rows=True,
-                         virial=virial, slab_mask=slab_mask, fixed_point=True)
-            if pair_g is not None:   # (computed without atomics: deterministic as well)
-                red[:3 * n] += torch.round(pair_g.reshape(-1).to(torch.float64) / FIXED_SCALE).to(torch.int64)
-                if stress:
-                    virial += pair_w
-            energies = energy_reduce(given, atomic_e if pair_e is None else atomic_e + pair_e, sae, lo, hi)
-            if several:
-                red[3 * n:3 * n + C] = torch.round(energies / FIXED_SCALE).to(torch.int64)
-                if stress:
-                    red[3 * n + C:] = torch.round(virial.reshape(-1) / FIXED_SCALE).to(torch.int64)
-                torch.distributed.all_reduce(red if reduce_forces else red[3 * n:], group=group)
-                energies = red[3 * n:3 * n + C].to(torch.float64) * FIXED_SCALE
-                if stress:
-                    virial = (red[3 * n + C:].to(torch.float64) * FIXED_SCALE).view(3, 3)
-                self.last_collective = {"collectives_per_step": 1, "world_size": world,
-                                        "bytes": 8 * (red.numel() if reduce_forces else n_tail)}
-            forces = fixed_to_float(red[:3 * n]).neg_().view(C, A, 3)
+        # forces are accumulated straight into the buffer that a sharded run all-reduces, ONE collective per step:
+        # [3 n forces | C partial energies | 9 virial entries].  fp32: every fp64 value of the tail rides as four
+        # exactly-summable fp32 parts (parallel.split_exact); deterministic_forces: everything as int64 fixed point (2^-32).
+        # Either way the sum over ranks is exact and independent of the reduction order
+        fixed = self.deterministic_forces
+        parts = 1 if fixed else 4
+        n_tail = parts * (C + (9 if stress else 0)) if several else 0
+        red = torch.empty(3 * n + n_tail, dtype=torch.int64 if fixed else torch.float32, device=c32.device)
+        st = self._local_stage(sp_e, species32, c32, cell, pbc_t, lo, hi, order, tile_hint, stress, red[:3 * n].view(n, 3))
+        energies, virial = st.energies, st.virial
+        if several:
+            def pack(v):
+                return torch.round(v / FIXED_SCALE).to(torch.int64) if fixed else split_exact(v).reshape(-1)
+
+            def unpack(r):
+                return r.to(torch.float64) * FIXED_SCALE if fixed else join_exact(r.view(-1, 4))
+
+            e_end = 3 * n + parts * C
+            red[3 * n:e_end] = pack(energies)
+            if stress:
+                red[e_end:] = pack(virial.reshape(-1))
+            torch.distributed.all_reduce(red if reduce_forces else red[3 * n:], group=group)
+            energies = unpack(red[3 * n:e_end])
+            if stress:
+                virial = unpack(red[e_end:]).view(3, 3)
+            self.last_collective = {"collectives_per_step": 1, "world_size": world,
+                                    "bytes": red.element_size() * (red.numel() if reduce_forces else n_tail)}
+        forces = fixed_to_float(red[:3 * n]).neg_() if fixed else red[:3 * n]
+        return FusedEnergiesForces(energies, forces.view(C, A, 3), st.net_e.view(C, A), virial)
+
+    def _local_stage(self, species: Tensor, given: Tensor, c32: Tensor, cell, pbc_t, lo: int, hi: int,
+                     order: tp.Optional[tp.Tuple[int, ...]], tile_hint: int, stress: bool, acc: Tensor) -> _LocalStage:
+        """What every fused step does with the system in front of it, for the central atoms lo .. hi: neighbor rows -> AEV rows
+        and slab flags -> networks forward + backward -> pair terms -> AEV backward -> fp64 energy sums.
+
+        species / given [C, A] int32: the kernels' numbering (_engine_species, with its ``order``) and the caller's, which
+        indexes the self energies.  acc [n, 3], owned by the caller and zeroed here, right before the AEV backward adds
+        to it (a large system's rows are then still in cache), takes what this range's terms push onto all atoms: fp32 FORCES, or for order-independent sums the GRADIENT in int64 fixed point (2^-32 Ha/A,
+        ANIHIP_BWD_FIXED_POINT)."""
+        aevc = self.aev_computer
+        eng = aevc.engine()
+        dev = c32.device
+        n = species.numel()
+        nbrs = aevc.neighbor_rows(species, c32, cell, pbc_t, lo=lo, hi=hi)
+        packed = self.neural_networks._pack(dev, order)
+        # per-atom flags of the AEV slabs that are not identically zero (absent neighbor species): the layer-0 GEMMs skip
+        # the others.  AEV rows and their gradients exist for the central atoms only ([hi - lo, L] buffers)
+        slab_mask = None
+        plain = self._plain_slabs(eng, packed)
+        if packed.radial_len == 16 * eng.params.num_species and eng.tuned and eng.n_slabs <= 32:
+            if self.keep_aev_rows and not torch.cuda.is_current_stream_capturing() and eng.rows_wanted(n, lo, hi, dev):
+                # rows and flags in the engine's kept buffers, updated in place (AevEngine.forward_update): from the second
+                # consecutive call with these sizes on
+                aev, slab_mask = eng.forward_update(species, nbrs)
+            else:
+                # (the AEV kernel writes the flags of every central atom; the others are read by nobody, zero for tidiness)
+                slab_mask = (torch.empty if (lo == 0 and hi == n) else torch.zeros)(n, dtype=torch.int32, device=dev)
+                aev = eng.forward(species, nbrs, slab_mask=slab_mask, shard_rows=True)
         else:
-            # forces are accumulated straight into the buffer that a sharded run all-reduces: [3 n forces | 4 C energy
-            # parts | 36 virial parts]
-            n_tail = (4 * C + (36 if stress else 0)) if several else 0
-            red = torch.zeros(3 * n + n_tail, dtype=torch.float32, device=c32.device)
-            grad_coords = eng.backward(species32, nbrs, grad_aev, grad_coords=red[:3 * n].view(n, 3), shard_rows=True,
-                                       virial=virial, slab_mask=slab_mask)
-            if pair_g is not None:
-                grad_coords += pair_g
-                if stress:
-                    virial += pair_w
+            if plain:   # a general grid: flags of the plain 32-column slabs from the general AEV kernel
+                slab_mask = torch.zeros(n, dtype=torch.int32, device=dev)
+            aev = eng.forward(species, nbrs, slab_mask=slab_mask, shard_rows=True)
+        net_e, grad_aev, _ = packed.forward_backward(species, aev, lo=lo, hi=hi, want_grad=True, chunk=self.mlp_chunk,
+                                                     slab_mask=slab_mask, shard_rows=True, tile_hint=tile_hint,
+                                                     plain_slabs=plain)
+        if plain:
+            slab_mask = None   # (the general AEV backward reads the blocks of present species only: no flags needed)
+        virial = torch.empty((3, 3), dtype=torch.float64, device=dev) if stress else None
+        pair_e, pair_g, pair_w = self._pair_terms(species, c32, cell, pbc_t, nbrs, lo, hi, stress)
+        atomic_e = net_e if pair_e is None else net_e + pair_e
+        sae = self._sae64(dev) if self.energy_shifter._enabled else None
+        fixed = acc.dtype == torch.int64
+        acc.zero_()
+        eng.backward(species, nbrs, grad_aev, grad_coords=acc, shard_rows=True, virial=virial, slab_mask=slab_mask,
+                     fixed_point=fixed)
+        if pair_g is not None:   # (computed without atomics: deterministic as well)
+            acc += torch.round(pair_g.to(torch.float64) / FIXED_SCALE).to(torch.int64) if fixed else pair_g
+            if stress:
+                virial += pair_w
+        if fixed:
+            # (acc stays the GRADIENT: either path flips the sign where it always did -- as integers before the exchange or as
+            # floats behind the all-reduce, the same numbers but for the sign bit of an exact zero, which stays as it was)
+            energies = energy_reduce(given, atomic_e, sae, lo, hi)
+        else:
             # (energies and the sign flip of the gradient share the last launch of the step)
-            energies = energy_forces_finish(given, atomic_e if pair_e is None else atomic_e + pair_e, sae,
-                                            grad_coords, lo, hi)
-            forces = grad_coords.view(C, A, 3)
-            if several:
-                # ONE collective per step: the fp64 partial energies (and virial) ride in the fp32 force buffer as four
-                # exactly-summable fp32 parts each (parallel.split_exact), so the sum over ranks is exact and
-                # independent of the reduction order
-                red[3 * n:3 * n + 4 * C] = split_exact(energies).reshape(-1)
-                if stress:
-                    red[3 * n + 4 * C:] = split_exact(virial.reshape(-1)).reshape(-1)
-                torch.distributed.all_reduce(red if reduce_forces else red[3 * n:], group=group)
-                energies = join_exact(red[3 * n:3 * n + 4 * C].view(C, 4))
-                if stress:
-                    virial = join_exact(red[3 * n + 4 * C:].view(9, 4)).view(3, 3)
-                self.last_collective = {"collectives_per_step": 1, "world_size": world,
-                                        "bytes": 4 * (red.numel() if reduce_forces else n_tail)}
-        if check_overflow:
-            nbrs.raise_on_overflow()
+            energies = energy_forces_finish(given, atomic_e, sae, acc, lo, hi)
         aevc._last_neighbors = nbrs
-        return FusedEnergiesForces(energies, forces, atomic_e.view(C, A), virial)
+        return _LocalStage(net_e, atomic_e, energies, virial)
 
     # ---- one big system on several ranks: spatial shards + halo (parallel.SpatialShards) ---------------------------
     partition = "spatial"   # "index": contiguous index ranges + one all-reduce of the whole force array (round-2 scheme)
@@ -556,14 +565,13 @@ class ANI(torch.nn.Module):
     # kept until an atom has moved half a cell).  "always" / "never" force the choice.
     locality_sort = "auto"
 
-    def _wants_locality_sort(self, species32: Tensor, c32: Tensor, cell, pbc, key_tensor: tp.Optional[Tensor]) -> bool:
+    def _wants_locality_sort(self, species32: Tensor, c32: Tensor, cell, pbc_t, key_tensor: tp.Optional[Tensor]) -> bool:
         if self.locality_sort == "always":
             return True
         key_tensor = species32 if key_tensor is None else key_tensor
-        key = (key_tensor.data_ptr(), key_tensor._version, tuple(key_tensor.shape))
+        key = tensor_key(key_tensor)
         hit = self.__dict__.get("_locality_cache")
         if hit is None or hit[0] != key:
-            pbc_t = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
             part = self._spatial_partition(species32.view(-1), c32, cell, pbc_t, 0, 1, key_tensor)
             # neighbors in the cell-sorted order that are also near each other in the given order
             # (a random order puts 2 / 256 of them within n / 256 places; a lattice or an MD engine's order most of them)
@@ -633,11 +641,10 @@ class ANI(torch.nn.Module):
         spk = species32 if species_key is None else species_key
         # (the species decide which atoms are padding: those are sorted last and kept out of every halo, so a partition cut
         # for one species tensor must not serve another)
-        key = (c32.data_ptr(), c32._version, tuple(c32.shape), None if cell is None else (cell.data_ptr(), cell._version),
-               pbc_t, rank, world, spk.data_ptr(), spk._version, tuple(spk.shape))
+        key = (tensor_key(c32), None if cell is None else (cell.data_ptr(), cell._version), pbc_t, rank, world, tensor_key(spk))
         hit = self.__dict__.get("_spatial_cache")
-        if hit is not None and hit[0] != key and (self.partition_skin > 0.0 or world == 1) and hit[0][2] == key[2] and \
-                hit[0][4:] == key[4:] and (cell is None) == (hit[3] is None):
+        if hit is not None and hit[0] != key and (self.partition_skin > 0.0 or world == 1) and hit[0][0][2] == key[0][2] and \
+                hit[0][2:] == key[2:] and (cell is None) == (hit[3] is None):   # (other coordinates of the same shape, same setup)
             part = hit[1]
             if world > 1 and (self.partition_check == "strict" or not part.check_pending):
                 # same-step guard: nothing is known yet about coordinates that moved since the cut (the first moved step
@@ -668,8 +675,8 @@ class ANI(torch.nn.Module):
             self.__dict__["_spatial_cache"] = hit
         return hit[1]
 
-    def _energies_and_forces_spatial(self, species32: Tensor, c32: Tensor, cell, pbc, group, reduce_forces, check_overflow,
-                                     shard, stress: bool, tile_hint: int, species_key: tp.Optional[Tensor] = None
+    def _energies_and_forces_spatial(self, species32: Tensor, c32: Tensor, cell, pbc_t, group, reduce_forces, shard,
+                                     stress: bool, tile_hint: int, species_key: tp.Optional[Tensor] = None
                                      ) -> FusedEnergiesForces:
         """energies_and_forces of ONE system sharded spatially: this rank evaluates the central atoms of its slab on the
         local system [left halo | owned | right halo], one all-gather of the halo force rows (+ partial energy / virial)
@@ -680,7 +687,6 @@ class ANI(torch.nn.Module):
             rank, world = torch.distributed.get_rank(group), torch.distributed.get_world_size(group)
         else:
             rank, world = shard
-        pbc_t = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
         part = self._spatial_partition(species32, c32, cell, pbc_t, rank, world, species_key)
         sp_e, order = self._engine_species(species32, species_key)   # (sp_given indexes the self energies)
         sp_given = part.local(species32).view(1, -1).contiguous()
@@ -688,23 +694,7 @@ class ANI(torch.nn.Module):
         x_l = part.local(c32, 3).view(1, -1, 3).contiguous()
         nl = part.n_local
         lo, hi = part.n_left, part.n_left + part.n_owned
-        aevc = self.aev_computer
-        eng = aevc.engine()
         dev = c32.device
-        nbrs = aevc.neighbor_rows(sp_l, x_l, cell, pbc_t, lo=lo, hi=hi)
-        packed = self.neural_networks._pack(dev, order)
-        slab_mask = None
-        plain = self._plain_slabs(eng, packed)
-        if packed.radial_len == 16 * eng.params.num_species and eng.tuned and eng.n_slabs <= 32:
-            if self.keep_aev_rows and not torch.cuda.is_current_stream_capturing() and eng.rows_wanted(nl, lo, hi, dev):
-                aev, slab_mask = eng.forward_update(sp_l, nbrs)   # (kept buffers, updated in place)
-            else:
-                slab_mask = torch.zeros(nl, dtype=torch.int32, device=dev)
-                aev = eng.forward(sp_l, nbrs, slab_mask=slab_mask, shard_rows=True)
-        else:
-            if plain:
-                slab_mask = torch.zeros(nl, dtype=torch.int32, device=dev)
-            aev = eng.forward(sp_l, nbrs, slab_mask=slab_mask, shard_rows=True)
         if world > 1 and not torch.cuda.is_current_stream_capturing() and part.n_owned >= 24000:
             # a rank's own launch scheme of the network stage (_tile_hint prices whole systems): from the composition of the atoms
             # it owns, worked out once per partition (one host read: the partition is cut once per skin of motion)
@@ -714,32 +704,12 @@ class ANI(torch.nn.Module):
                 hint_l = _lib.MLP_FLAG_SHAPED if self._per_species_launches_pay(counts, _n_cus_of(dev)) else 0
                 part._tile_hint_owned = hint_l
             tile_hint |= hint_l
-        atomic_e, grad_aev, _ = packed.forward_backward(sp_l, aev, lo=lo, hi=hi, want_grad=True, chunk=self.mlp_chunk,
-                                                        slab_mask=slab_mask, shard_rows=True, tile_hint=tile_hint,
-                                                        plain_slabs=plain)
-        if plain:
-            slab_mask = None
-        virial = torch.empty((3, 3), dtype=torch.float64, device=dev) if stress else None
-        pair_e, pair_g, pair_w = self._pair_terms(sp_l, x_l, cell, pbc_t, nbrs, lo, hi, stress)
-        sae = self._sae64(dev) if self.energy_shifter._enabled else None
-        e_atom = atomic_e if pair_e is None else atomic_e + pair_e
         fixed = self.deterministic_forces
+        rows = torch.empty((nl, 3), dtype=torch.int64 if fixed else torch.float32, device=dev)
+        st = self._local_stage(sp_l, sp_given, x_l, cell, pbc_t, lo, hi, order, tile_hint, stress, rows)
+        energies, virial, e_atom = st.energies, st.virial, st.atomic_e
         if fixed:
-            rows = torch.zeros((nl, 3), dtype=torch.int64, device=dev)
-            eng.backward(sp_l, nbrs, grad_aev, grad_coords=rows, shard_rows=True, virial=virial, slab_mask=slab_mask,
-                         fixed_point=True)
-            if pair_g is not None:
-                rows += torch.round(pair_g.to(torch.float64) / FIXED_SCALE).to(torch.int64)
-            energies = energy_reduce(sp_given, e_atom, sae, lo, hi)
             rows.neg_()
-        else:
-            rows = torch.zeros((nl, 3), dtype=torch.float32, device=dev)
-            eng.backward(sp_l, nbrs, grad_aev, grad_coords=rows, shard_rows=True, virial=virial, slab_mask=slab_mask)
-            if pair_g is not None:
-                rows += pair_g
-            energies = energy_forces_finish(sp_given, e_atom, sae, rows, lo, hi)   # (negates rows: forces)
-        if stress and pair_w is not None:
-            virial += pair_w
         tail = energies if not stress else torch.cat([energies, virial.reshape(-1)])
         from .parallel import FORCE_COLLECTIVES
 
@@ -769,9 +739,6 @@ class ANI(torch.nn.Module):
                                 "op": "all_to_all(halo force rows -> slab neighbours, partial energy -> all)", "n_local": nl,
                                 "peers": list(part.peers),
                                 "n_owned": part.n_owned, "n_halo": part.n_left + part.n_right}
-        if check_overflow:
-            nbrs.raise_on_overflow()
-        aevc._last_neighbors = nbrs
         return FusedEnergiesForces(energies, forces.view(1, n, 3), ae.view(1, n), virial)
 
     def _sae64(self, device) -> Tensor:
@@ -1034,7 +1001,7 @@ class GraphedEnergiesForces:
         self.species32 = model._elem_idxs(species).to(torch.int32).contiguous()   # (validity check syncs once)
         self.coords = coords.detach().to(torch.float32).contiguous().clone()
         self.cell = None if cell is None else cell.detach().clone()
-        self.pbc = pbc
+        self.pbc = pbc_tuple(pbc)
         self.warmup = warmup
         self.tile_hint = model._tile_hint(self.species32, self.species32, self.species32.numel())
         # the kernels' species numbering (ANI.compact_species): worked out here, outside the capture, and OWNED by this
@@ -1074,8 +1041,7 @@ class GraphedEnergiesForces:
         self._release()
 
     def _run(self) -> FusedEnergiesForces:
-        return self.model._energies_and_forces_core(self.species32, self.coords, self.cell, self.pbc, None, True,
-                                                    False, None, tile_hint=self.tile_hint,
+        return self.model._energies_and_forces_core(self.species32, self.coords, self.cell, self.pbc, tile_hint=self.tile_hint,
                                                     engine_species=(self.engine_species32, self.species_order))
 
     def __call__(self, coords: Tensor, cell: tp.Optional[Tensor] = None) -> FusedEnergiesForces:

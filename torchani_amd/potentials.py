@@ -28,6 +28,7 @@ from torch import Tensor
 from . import _lib
 from .constants import ATOMIC_NUMBER
 from .engine import AevEngine, NeighborRows, _ptr, _require_cuda, _stream
+from .utils import pbc_tuple
 
 # resources/atomic_constants.json "xtb_repulsion_alpha" / "xtb_repulsion_yeff" (Grimme et al., GFN2-xTB,
 # https://pubs.acs.org/doi/10.1021/acs.jctc.8b01176), elements up to Kr
@@ -132,7 +133,7 @@ class _Standalone:
         rc = min(self.cutoff, 1.0e3)
         if self._own_engine is None or abs(self._own_engine.consts.Rcr - rc) > 1e-9:
             self._own_engine = AevEngine(aev_constants_2x(len(self.symbols))._replace(Rcr=rc, Rca=1e-3))
-        pbc_t = None if pbc is None else tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
+        pbc_t = pbc_tuple(pbc)
         mode = "cell" if (species32.shape[0] == 1 and species32.shape[1] > 512) else "batch"
         rows = self._own_engine.neighbors(species32, coords.detach().to(torch.float32).contiguous(), cell, pbc_t, mode=mode,
                                           row_cap=_lib.MAX_RAD)

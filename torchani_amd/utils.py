@@ -17,6 +17,21 @@ PADDING: tp.Dict[str, float] = {"species": PADDING_SPECIES, "numbers": PADDING_S
 ATOMIC_KEYS = ("species", "numbers", "atomic_numbers", "coordinates", "forces")
 
 
+def pbc_tuple(pbc: tp.Union[Tensor, tp.Sequence[bool], None]) -> tp.Optional[tp.Tuple[bool, ...]]:
+    """Periodic flags (a Tensor, a sequence or None) as the host tuple the engine takes, None as None.  Reading a device
+    tensor is a host synchronisation: public entry points convert once and pass the tuple down."""
+    if pbc is None:
+        return None
+    return tuple(bool(b) for b in (pbc.tolist() if isinstance(pbc, Tensor) else pbc))
+
+
+def tensor_key(t: Tensor) -> tp.Tuple[int, int, tp.Tuple[int, ...]]:
+    """Identity, version and shape of a tensor: the key of the caches of values derived from its contents.  An entry under
+    this key must hold a reference to ``t`` -- while it lives no other tensor can show up under its address, so an equal
+    key means the same tensor with the same contents."""
+    return (t.data_ptr(), t._version, tuple(t.shape))
+
+
 def cumsum_from_zero(input_: Tensor) -> Tensor:
     """Exclusive cumulative sum along dim 0 (utils.py:132-136)."""
     out = torch.zeros_like(input_)
