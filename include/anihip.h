@@ -388,6 +388,51 @@ int anihip_lbfgs_step(void *stream, const anihip_lbfgs_params *params, const uin
                       const float *forces, void *workspace, size_t workspace_bytes, float *last_step, uint8_t *converged,
                       int32_t *n_steps);
 
+/* Molecular dynamics of a batch of molecules (torchani_amd.md.BatchedDynamics, csrc/md.hip): velocity Verlet (NVE) and
+ * Langevin dynamics in the BAOAB splitting, layout [n_mol][atoms_per_mol] = [C][A].  Units: Angstrom, fs, amu, Hartree;
+ * ANIHIP_MD_ACC_UNIT = (Hartree / Angstrom) / amu in Angstrom / fs^2.  A step of the caller is anihip_md_drift, the forces at
+ * the new coordinates, anihip_md_kick.  active uint8 [C][A]: 0 = a padding or fixed atom, which never moves and whose velocity
+ * is set to zero.  One thread per atom, no atomics, every sum in a fixed order: bit-identical run to run.
+ *
+ * anihip_md_drift, per active atom:  v += dt/2 f inv_mass;  NVE: x += dt v;  Langevin (flags & ANIHIP_MD_LANGEVIN):
+ * x += dt/2 v,  v = c1 v + sqrt(kT_c (1 - c1^2) inv_mass) xi,  x += dt/2 v,  c1 = exp(-friction_c dt).  inv_mass fp32 [C][A] =
+ * ANIHIP_MD_ACC_UNIT / m (m in amu), kT fp32 [C] = k_B T_c in HARTREE (so kT inv_mass is a velocity squared), friction fp32 [C]
+ * in 1 / fs; both may be NULL for NVE.  The position of an atom is the pair coords + coords_lo (fp32 [C][A][3] each; the
+ * caller zero-fills coords_lo once): every `x +=` is a two-sum, after which coords -- what the engine reads -- is the fp32
+ * nearest to the pair.  velocities fp32 [C][A][3] (Angstrom / fs), forces fp32 [C][A][3] (Hartree / Angstrom).
+ *
+ * Noise: xi = anihip_md_noise(seed, step, ...), a pure function of (seed, step, replica id, atom index within the molecule).
+ * Philox4x32-10 with key (seed low, seed high) and counter (atom index, replica_ids[c] -- int64 [C], values below 2^32 -- or
+ * c when NULL, step low, step high) gives u0..u3; with p(u) = ((u >> 9) + 0.5) 2^-23:
+ *   xi_x = sqrt(-2 ln p(u0)) cos(2 pi p(u1)),  xi_y = sqrt(-2 ln p(u0)) sin(2 pi p(u1)),  xi_z = sqrt(-2 ln p(u2)) cos(2 pi p(u3)).
+ * The caller advances `step` by one per drift.  anihip_md_noise writes out fp32 [C][A][3] for every atom, active or not.
+ *
+ * anihip_md_kick: v += dt/2 f ANIHIP_MD_ACC_UNIT / mass (mass fp32 [C][A], amu), then kinetic[c] (fp64, Hartree) =
+ * 1/2 sum m v^2 / ANIHIP_MD_ACC_UNIT over the active atoms.  anihip_md_remove_drift: v -= sum m v / sum m over the active atoms
+ * of each molecule.  Both sum per 256-atom chunk and, for molecules of more than one chunk, per molecule in a second launch;
+ * workspace: anihip_md_workspace_bytes(n_mol, atoms_per_mol) bytes of scratch, no state.  Launches: drift 1, kick 1 or 2,
+ * remove_drift 2 or 3, noise 1. */
+#define ANIHIP_MD_ACC_UNIT 0.26254996403871417
+#define ANIHIP_MD_LANGEVIN 1
+typedef struct {
+    int32_t n_mol, atoms_per_mol;
+    int32_t flags;      /* ANIHIP_MD_LANGEVIN or 0 (NVE) */
+    int32_t reserved;   /* 0 */
+    double dt;          /* fs, > 0 */
+    uint64_t seed;      /* Philox key */
+    uint64_t step;      /* Philox counter words 2 and 3 */
+} anihip_md_params;
+size_t anihip_md_workspace_bytes(int64_t n_mol, int64_t atoms_per_mol);   /* 0 + anihip_last_error() */
+int anihip_md_drift(void *stream, const anihip_md_params *params, const uint8_t *active, const float *inv_mass,
+                    const float *kT, const float *friction, const int64_t *replica_ids, float *coords, float *coords_lo,
+                    float *velocities, const float *forces);
+int anihip_md_kick(void *stream, const anihip_md_params *params, const uint8_t *active, const float *mass, float *velocities,
+                   const float *forces, double *kinetic, void *workspace, size_t workspace_bytes);
+int anihip_md_remove_drift(void *stream, const anihip_md_params *params, const uint8_t *active, const float *mass,
+                           float *velocities, void *workspace, size_t workspace_bytes);
+int anihip_md_noise(void *stream, uint64_t seed, uint64_t step, int64_t n_mol, int64_t atoms_per_mol,
+                    const int64_t *replica_ids, float *out);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -1,5 +1,13 @@
-"""MD step rate with and without Verlet-skin neighbor reuse (cf. the reference's tools/md-benchmark.py, which drives
-the same path through ASE):   python tools/md_bench.py [--side 64] [--steps 20]"""
+"""MD step rate (cf. the reference's tools/md-benchmark.py, which drives the same path through ASE):
+
+    python tools/md_bench.py [--side 64] [--steps 20]                      the host driver with and without Verlet-skin reuse
+    python tools/md_bench.py --integrator both --langevin --repeats 7 ...  host driver (md.MolecularDynamics) against the
+                                                                           on-device integrator (md.BatchedDynamics)
+
+--system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
+molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
+median, the fastest and the slowest repeat are printed: the spread to hold a difference against.  Whenever the device integrator
+is timed both models are built with row_capacity=256, since BatchedDynamics raises on a neighbor-row overflow instead of retrying."""
 import argparse
 import os
 import sys
@@ -8,42 +16,91 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from bench import water_box  # noqa: E402
+
+ELEMENT_MASSES = [1.008, 12.011, 14.007, 15.999, 32.06, 18.998, 35.45]   # ANI-2x element order
+
+
+def load_system(args, dev):
+    """species (element indices), coordinates, cell, pbc, the neighbor lists to time."""
+    if args.system == "molecules":
+        with np.load(os.path.join(ROOT, "tests", "golden", "cfg2_xyz13_28_ani2x.npz")) as z:
+            sp, x = z["species"].astype(np.int64), z["coords"]
+        return torch.from_numpy(sp).to(dev), torch.from_numpy(x).to(dev), None, None, ("batch",)
+    sp, x, cell = water_box(args.side)
+    return (torch.from_numpy(sp.astype(np.int64)).to(dev), torch.from_numpy(x).to(dev), torch.from_numpy(cell).to(dev),
+            (True, True, True), ("cell_list", "verlet_cell_list"))
+
+
+def make_driver(kind, args, model, sp, x, cell, pbc, masses):
+    from torchani_amd.md import BatchedDynamics, MolecularDynamics
+
+    temperature = 300.0 if args.langevin else None
+    if kind == "host":
+        md = MolecularDynamics(model, sp, x, cell, pbc, dt=0.5, masses=masses, temperature=temperature, seed=1)
+    else:
+        md = BatchedDynamics(model, sp, x, cell, pbc, dt=0.5, masses=masses, temperature=temperature, seed=1)
+    md.set_temperature(300.0)
+    return md
+
+
+def timed(md, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    md.run(steps)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=64)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--system", choices=("water", "molecules"), default="water")
+    ap.add_argument("--integrator", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--neighborlist", choices=("cell_list", "verlet_cell_list"), default=None,
+                    help="--system water: time this neighbor list alone (default: both)")
+    ap.add_argument("--langevin", action="store_true", help="Langevin dynamics at 300 K, friction 0.002 / fs (default: NVE)")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
                     help="refresh the skin list at every size (VerletRows.rebuild_above = inf): how the crossover was measured")
     args = ap.parse_args()
-    from torchani_amd.md import MolecularDynamics
     from torchani_amd.models import ANI2x
 
     dev = torch.device("cuda:0")
-    sp, x, cell = water_box(args.side)
-    spd = torch.from_numpy(sp.astype(np.int64)).to(dev)
-    xd, cd = torch.from_numpy(x).to(dev), torch.from_numpy(cell).to(dev)
-    masses = torch.tensor([1.008, 12.011, 14.007, 15.999, 32.06, 18.998, 35.45], device=dev)[spd]
-    for nl in ("cell_list", "verlet_cell_list"):
-        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl)
-        if args.force_verlet and model.aev_computer.verlet is not None:
-            model.aev_computer.verlet.rebuild_above = float("inf")
-        md = MolecularDynamics(model, spd, xd, cd, (True, True, True), dt=0.5, masses=masses, seed=1)
-        md.set_temperature(300.0)
-        md.run(3)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        md.run(args.steps)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / args.steps
-        ver = model.aev_computer.verlet
-        extra = (f", pair searches {ver.n_builds}, reuses {ver.n_reuses}, steps rebuilt outright {ver.n_direct}"
-                 if ver is not None else "")
-        print(f"{nl:17s} {sp.size} atoms: {dt * 1e3:.2f} ms/step = {sp.size / dt / 1e6:.2f} M atom*steps/s, "
-              f"T = {md.temperatures().item():.0f} K{extra}")
+    sp, x, cell, pbc, lists = load_system(args, dev)
+    if args.neighborlist is not None and args.system == "water":
+        lists = (args.neighborlist,)
+    n_atoms = int((sp >= 0).sum())
+    masses = torch.tensor(ELEMENT_MASSES, device=dev)[sp.clamp(min=0)]
+    kinds = ("host", "device") if args.integrator == "both" else (args.integrator,)
+    for nl in lists:
+        drivers = {}
+        for kind in kinds:   # (a model each: the automatic HIP graph of a small system belongs to one species tensor)
+            # (BatchedDynamics never reads the overflow status inside a step, so it cannot retry with longer neighbor rows as
+            # the host driver's evaluation does: when it is timed, both models get the longest rows from the start)
+            rows = {"row_capacity": 256} if "device" in kinds else {}
+            model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl, **rows)
+            if args.force_verlet and model.aev_computer.verlet is not None:
+                model.aev_computer.verlet.rebuild_above = float("inf")
+            drivers[kind] = make_driver(kind, args, model, sp, x, cell, pbc, masses)
+            drivers[kind].run(args.warmup)
+        times = {kind: [] for kind in kinds}
+        for _ in range(args.repeats):
+            for kind in kinds:
+                times[kind].append(timed(drivers[kind], args.steps))
+        for kind in kinds:
+            md, t = drivers[kind], np.array(times[kind]) * 1e3
+            ver = md.model.aev_computer.verlet
+            extra = (f", pair searches {ver.n_builds}, reuses {ver.n_reuses}, steps rebuilt outright {ver.n_direct}"
+                     if ver is not None else "")
+            spread = f" (fastest {t.min():.3f}, slowest {t.max():.3f} of {len(t)} repeats)" if len(t) > 1 else ""
+            print(f"{nl:17s} {kind:6s} {'langevin' if args.langevin else 'nve':8s} {n_atoms} atoms: {np.median(t):.3f} ms/step"
+                  f"{spread} = {n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M atom*steps/s, "
+                  f"T = {md.temperatures().mean().item():.0f} K{extra}")
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -42,6 +42,7 @@ REPACK_FUSED_ONLY = 1
 BLOCK_HESSIAN_MAX_VECTORS = 64   # ANIHIP_BLOCK_HESSIAN_MAX_VECTORS
 BLOCK_HESSIAN_BAD_INDEX, BLOCK_HESSIAN_NO_PARTNER, BLOCK_HESSIAN_NO_DIAGONAL = 1, 2, 4
 LBFGS_MAX_MEMORY = 256   # ANIHIP_LBFGS_MAX_MEMORY
+MD_LANGEVIN = 1   # ANIHIP_MD_LANGEVIN
 
 
 class AevParams(C.Structure):
@@ -112,6 +113,12 @@ class LbfgsParams(C.Structure):
     """anihip_lbfgs_params (include/anihip.h)."""
     _fields_ = [("n_mol", C.c_int32), ("atoms_per_mol", C.c_int32), ("memory", C.c_int32), ("flags", C.c_int32),
                 ("inv_alpha", C.c_double), ("maxstep", C.c_double), ("damping", C.c_double), ("fmax", C.c_double)]
+
+
+class MdParams(C.Structure):
+    """anihip_md_params (include/anihip.h)."""
+    _fields_ = [("n_mol", C.c_int32), ("atoms_per_mol", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("dt", C.c_double), ("seed", C.c_uint64), ("step", C.c_uint64)]
 
 
 class MlpShape(C.Structure):
@@ -256,6 +263,14 @@ def lib() -> C.CDLL:
     L.anihip_lbfgs_workspace_bytes.argtypes = [i64, i64, i32]
     L.anihip_lbfgs_step.argtypes = [vp, C.POINTER(LbfgsParams), vp, vp, vp, vp, sz, vp, vp, vp]
     L.anihip_lbfgs_step.restype = C.c_int
+    L.anihip_md_workspace_bytes.restype = sz
+    L.anihip_md_workspace_bytes.argtypes = [i64, i64]
+    L.anihip_md_drift.argtypes = [vp, C.POINTER(MdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_md_kick.argtypes = [vp, C.POINTER(MdParams), vp, vp, vp, vp, vp, vp, sz]
+    L.anihip_md_remove_drift.argtypes = [vp, C.POINTER(MdParams), vp, vp, vp, vp, sz]
+    L.anihip_md_noise.argtypes = [vp, C.c_uint64, C.c_uint64, i64, i64, vp, vp]
+    for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise"):
+        getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
     for name in ("anihip_aev_table_pack", "anihip_nbr_build_batch", "anihip_nbr_build_cell", "anihip_nbr_from_half",
@@ -286,6 +301,7 @@ EXPORTED_SYMBOLS = [
     "anihip_block_hessian_prepare", "anihip_block_hessian_spmm",
     "anihip_aev_jvp_strain_items", "anihip_aev_backward_second_strain_items", "anihip_pair_analytic_hvp_strain",
     "anihip_lbfgs_workspace_bytes", "anihip_lbfgs_step",
+    "anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
 ]
 
 

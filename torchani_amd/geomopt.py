@@ -65,6 +65,48 @@ def _check_run_args(fmax: float, steps: int, check_every: int) -> None:
         raise ValueError("steps must be >= 0 and check_every >= 1")
 
 
+class ModelEvaluator:
+    """Energies [C] (fp64) and forces [C, A, 3] (fp32) of a model at fp32 coordinates that the caller updates in place, queued
+    on the stream without a host synchronization (GeometryOptimizer, md.BatchedDynamics).  The model is an ``ANI`` model
+    (``energies_and_forces`` with ``check_overflow=False`` and the same species tensor at every call, so small systems replay
+    the automatic HIP graph) or a standalone pair potential, evaluated through its ``accumulate`` on its own neighbor rows."""
+
+    def __init__(self, model, species: Tensor, cell: tp.Optional[Tensor], pbc) -> None:
+        from .potentials import _Standalone
+
+        self.model, self.species, self.cell = model, species, cell
+        # (a host tuple once: a pbc tensor would cost a synchronization at every evaluation)
+        self.pbc = pbc_tuple(pbc)
+        self.standalone = isinstance(model, _Standalone)
+        if self.standalone:
+            self._species32 = model._to_elem_idxs(species, True).to(torch.int32).contiguous()
+            self._rows = None
+
+    def __call__(self, coordinates: Tensor) -> tp.Tuple[Tensor, Tensor]:
+        if self.standalone:
+            Cn, A = self.species.shape
+            rows = self.model._standalone_rows(self._species32, coordinates, self.cell, self.pbc)
+            atomic = torch.zeros(Cn * A, dtype=torch.float32, device=coordinates.device)
+            grad = torch.zeros((Cn * A, 3), dtype=torch.float32, device=coordinates.device)
+            self.model.accumulate(self._species32, rows, atomic, grad)
+            self._rows = rows
+            return atomic.view(Cn, A).to(torch.float64).sum(dim=1), grad.neg_().view(Cn, A, 3)
+        out = self.model.energies_and_forces(self.species, coordinates, self.cell, self.pbc, check_overflow=False)
+        return out.energies, out.forces.to(torch.float32).contiguous()
+
+    def raise_on_overflow(self) -> None:
+        """Raise if a neighbor row of the last evaluation overflowed (one host synchronization)."""
+        if self.standalone:
+            if self._rows is not None and self._rows.overflowed():
+                raise RuntimeError(f"{type(self.model).__name__}: an atom has more than {_lib.MAX_RAD} neighbors inside the "
+                                   f"cutoff ({self.model.cutoff} A): the forces would be wrong")
+            return
+        m = self.model
+        if not m._overflow_impossible(self.species, self.cell, self.pbc):
+            m.aev_computer.last_neighbors().raise_on_overflow()
+        m._raise_on_pair_overflow()
+
+
 class GeometryOptimizer:
     """L-BFGS minimization of the energy of every molecule of species [C, A], coordinates [C, A, 3] (Angstrom).
 
@@ -77,8 +119,6 @@ class GeometryOptimizer:
     def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
                  memory: int = 100, maxstep: float = 0.2, alpha: float = DEFAULT_ALPHA, damping: float = 1.0,
                  fixed: tp.Optional[Tensor] = None) -> None:
-        from .potentials import _Standalone
-
         if species.dim() != 2 or tuple(coordinates.shape) != (species.shape[0], species.shape[1], 3):
             raise ValueError("expected species [C, A] and coordinates [C, A, 3]")
         if isinstance(memory, bool) or int(memory) != memory or not 1 <= memory <= MAX_MEMORY:
@@ -93,19 +133,14 @@ class GeometryOptimizer:
             raise ValueError("GeometryOptimizer needs tensors on a ROCm device (no CPU fallback)")
         dev = coordinates.device
         Cn, A = species.shape
-        self.model, self.species, self.cell = model, species, cell
-        # (a host tuple once: a pbc tensor would cost a synchronization at every evaluation)
-        self.pbc = pbc_tuple(pbc)
+        self._model_eval = ModelEvaluator(model, species, cell, pbc)
+        self.model, self.species, self.cell, self.pbc = model, species, cell, self._model_eval.pbc
         self._dtype = coordinates.dtype
         self.coordinates = coordinates.detach().to(torch.float32).clone().contiguous()
         active = species >= 0
         if fixed is not None:
             active = active & ~fixed.to(device=dev, dtype=torch.bool)
         self._active = active.to(torch.uint8).contiguous()
-        self._standalone = isinstance(model, _Standalone)
-        if self._standalone:
-            self._species32 = model._to_elem_idxs(species, True).to(torch.int32).contiguous()
-            self._rows = None
         self._params = _lib.LbfgsParams(Cn, A, int(memory), 0, 1.0 / float(alpha), float(maxstep), float(damping),
                                         DEFAULT_FMAX)
         self.fmax = DEFAULT_FMAX
@@ -117,19 +152,7 @@ class GeometryOptimizer:
 
     def _evaluate(self) -> None:
         """energies and forces at the current coordinates, queued on the stream."""
-        if self._standalone:
-            Cn, A = self.species.shape
-            rows = self.model._standalone_rows(self._species32, self.coordinates, self.cell, self.pbc)
-            atomic = torch.zeros(Cn * A, dtype=torch.float32, device=self.coordinates.device)
-            grad = torch.zeros((Cn * A, 3), dtype=torch.float32, device=self.coordinates.device)
-            self.model.accumulate(self._species32, rows, atomic, grad)
-            self._rows = rows
-            self.energies = atomic.view(Cn, A).to(torch.float64).sum(dim=1)
-            self.forces = grad.neg_().view(Cn, A, 3)
-        else:
-            out = self.model.energies_and_forces(self.species, self.coordinates, self.cell, self.pbc, check_overflow=False)
-            self.energies = out.energies
-            self.forces = out.forces.to(torch.float32).contiguous()
+        self.energies, self.forces = self._model_eval(self.coordinates)
 
     def _lbfgs_step(self) -> None:
         """The optimizer step alone (anihip_lbfgs_step): coordinates, last_step, converged and n_steps updated."""
@@ -147,15 +170,7 @@ class GeometryOptimizer:
 
     def raise_on_overflow(self) -> None:
         """Raise if a neighbor row of the last evaluation overflowed (one host synchronization)."""
-        if self._standalone:
-            if self._rows is not None and self._rows.overflowed():
-                raise RuntimeError(f"{type(self.model).__name__}: an atom has more than {_lib.MAX_RAD} neighbors inside the "
-                                   f"cutoff ({self.model.cutoff} A): the forces would be wrong")
-            return
-        m = self.model
-        if not m._overflow_impossible(self.species, self.cell, self.pbc):
-            m.aev_computer.last_neighbors().raise_on_overflow()
-        m._raise_on_pair_overflow()
+        self._model_eval.raise_on_overflow()
 
     def run(self, fmax: float = DEFAULT_FMAX, steps: int = 1000, check_every: int = 10) -> OptimizedGeometries:
         """At most ``steps`` steps until every molecule has max |f_i| < fmax (Hartree / Angstrom).  The host reads the
