@@ -550,6 +550,82 @@ def test_aev_jvp_matches_reference(dev, oracle64, base):
         assert torch.all(jt.view(C, A, -1)[sp32 < 0] == 0)
 
 
+@pytest.mark.parametrize("base", ["small_ani2x", "ch4_ani1x", "rand_batch_ani2x", "water_pbc_smooth_ani2x"])
+def test_aev_jvp_entry_points_agree(dev, base):
+    """anihip_aev_jvp and anihip_aev_jvp_batched with one direction launch the same kernel on the same grid (no atomics):
+    the rows lo..hi are equal bit for bit -- over all central atoms and over a proper sub-range.  The 8 x 4 and the 4 x 8
+    instantiation, padding atoms, the smooth cutoff."""
+    from torchani_amd.aev import AEVComputer
+    from torchani_amd.weights import arch_spec
+
+    g = load_golden(base)
+    consts = arch_spec(g["kind"])[1]._replace(cutoff_fn=g["cutoff_fn"])
+    C, A = g["species"].shape
+    N = C * A
+    sp32 = torch.from_numpy(g["species"].astype(np.int32)).to(dev)
+    x = torch.from_numpy(g["coords"]).to(dev).contiguous()
+    cell = None if g["cell"] is None else torch.from_numpy(g["cell"]).to(dev)
+    pbc = None if g["pbc"] is None else tuple(bool(b) for b in g["pbc"])
+    td = torch.from_numpy(fgrad_direction(g["species"]).astype(np.float32)).to(dev)
+    aevc = AEVComputer(consts, neighborlist="batch", row_capacity=256).to(dev)
+    eng = aevc.engine()
+    for lo, hi in ((0, N), (max(1, N // 3), N - max(1, N // 4))):
+        assert (lo, hi) == (0, N) or 0 < lo < hi < N
+        rows = aevc.neighbor_rows(sp32, x, cell, pbc, lo=lo, hi=hi)
+        one = eng.jvp(sp32, rows, td)
+        many = eng.jvp_batched(sp32, rows, td[None])
+        torch.cuda.synchronize()
+        rows.raise_on_overflow()
+        assert many.shape == (1, N, eng.L)
+        assert one[lo:hi].abs().max().item() > 0
+        assert torch.equal(one[lo:hi], many[0, lo:hi])
+
+
+def long_row_lattice():
+    """9 x 9 x 9 atoms on a cubic lattice of spacing 1.5 A, each coordinate jittered by +-0.1 A, the seven ANI-2x species
+    at random: an inner atom has about 170 neighbors inside the radial and 56 inside the angular cutoff."""
+    rs = np.random.RandomState(7)
+    k = np.arange(9) * 1.5
+    x = np.stack(np.meshgrid(k, k, k, indexing="ij"), axis=-1).reshape(-1, 3) + rs.uniform(-0.1, 0.1, (729, 3))
+    return rs.randint(0, 7, (1, 729)).astype(np.int64), x.astype(np.float32)[None]
+
+
+def test_aev_jvp_row_longer_than_two_waves(dev, oracle64):
+    """The tangent kernel reads the third and fourth 64-entry chunk of a neighbor row on a path of their own (the first two
+    are prefetched an atom ahead): rows of 129..256 radial entries against the oracle on every row, at the bound of
+    test_aev_jvp_matches_reference, with the adjoint identity against the backward kernel."""
+    from torchani_amd.aev import AEVComputer
+    from torchani_amd.weights import arch_spec
+
+    sp, x = long_row_lattice()
+    consts = arch_spec("ani2x")[1]
+    d = np.linalg.norm(x[0, :, None, :].astype(np.float64) - x[0, None, :, :].astype(np.float64), axis=-1)
+    np.fill_diagonal(d, np.inf)
+    n_rad, n_ang = (d <= consts.Rcr).sum(axis=1).max(), (d <= consts.Rca).sum(axis=1).max()
+    report(f"jvp   long rows: longest radial row {n_rad}, longest angular row {n_ang}")
+    assert 128 < n_rad <= 256 and n_ang <= 128
+    t = fgrad_direction(sp)
+    _, jt_ref = oracle64.aev_jvp(oracle_params("ani2x"), sp, x.astype(np.float64), t)
+    sp32 = torch.from_numpy(sp.astype(np.int32)).to(dev)
+    xd = torch.from_numpy(x).to(dev).contiguous()
+    td = torch.from_numpy(t.astype(np.float32)).to(dev)
+    aevc = AEVComputer(consts, neighborlist="batch", row_capacity=256).to(dev)
+    eng = aevc.engine()
+    rows = aevc.neighbor_rows(sp32, xd)
+    jt = eng.jvp(sp32, rows, td)
+    torch.cuda.synchronize()
+    rows.raise_on_overflow()
+    scale = np.abs(jt_ref).max()
+    err = np.abs(jt.cpu().numpy().astype(np.float64) - jt_ref.reshape(729, -1)).max()
+    report(f"jvp   long rows: max|J t err| = {err:.2e} (max |J t| {scale:.2f})")
+    assert err < 2e-5 * max(1.0, scale)
+    w = torch.from_numpy(np.random.RandomState(5).uniform(-1, 1, (729, eng.L)).astype(np.float32)).to(dev)
+    gc = eng.backward(sp32, rows, w)
+    lhs = (w.double() * jt.double()).sum().item()
+    rhs = (gc.double() * td.view(-1, 3).double()).sum().item()
+    assert abs(lhs - rhs) < 1e-4 * max(1.0, abs(lhs))
+
+
 @pytest.mark.parametrize("base", FGRAD_NAMES)
 def test_tangent_weight_grads_match_oracle(dev, oracle64, base):
     """anihip_mlp_tangent_weight_grads: d/d params of S = sum_i v_i . d e_i / d aev_i against the oracle (pinned to the

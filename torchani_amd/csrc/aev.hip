@@ -1,4 +1,4 @@
-// Radial + angular AEV forward and analytic backward for gfx950 (wave64).
+// Radial + angular AEV forward, analytic backward and forward-mode derivative for gfx950 (wave64).
 //
 // One wave owns one central atom at a time (persistent waves stride over the shard).  The atom's species-sorted neighbor
 // row (written by nbr.hip) is loaded with one coalesced 16-B load per lane -- header and entries of the NEXT atom are
@@ -11,7 +11,8 @@
 //               64-B block of every neighbor's dE/dAEV row), angular part over all neighbor pairs in one tournament
 //               with lane-owned j and plain LDS read-add-write for k, dE/dAEV staged block-wise; the few remaining
 //               global accumulations are float atomics or (ANIHIP_BWD_FIXED_POINT) 64-bit integer atomics.
-//   k_aev_fwd<.., JVP = true>  forward-mode derivative J t (the reference's double backward), four lanes per pair.
+//   k_aev_jvp   forward-mode derivative J t (the reference's double backward): four lanes per (j, k) pair, species-pair
+//               blocks one after the other, reductions on DPP / permlane swaps.  No atomics.
 //
 // Maths restated from the reference (paths relative to /root/reference/torchani/):
 //   aev/_terms.py:99-104,171-186 (radial), :34-55,324-325,339-343 (angular), cutoffs.py:80-81,
@@ -60,7 +61,7 @@ struct AtomQueue {
     __device__ __forceinline__ int64_t granted() const { return atom((uint32_t)__builtin_amdgcn_readfirstlane((int)v)); }
 };
 
-constexpr int FWD_WPB = 4;      // k_aev_fwd (tangent pass)
+constexpr int JVP_WPB = 4;      // k_aev_jvp
 constexpr int FWD3_WPB = QW;    // k_aev_fwd3
 constexpr int BWD_WPB = QW;     // k_aev_bwd
 constexpr int STAGE_FLOATS = 1024;  // >= L (S<=7: 1008)
@@ -116,27 +117,6 @@ __device__ __forceinline__ int byte_at(uint64_t pk, int sh)
     return (int)((w >> (sh & 31)) & 255u);
 }
 
-// (j,k) of the t-th pair of a block: rectangle for two different species, circular tournament for
-// pairs inside one species (every unordered pair exactly once, no sqrt / triangular-index decode)
-__device__ __forceinline__ void decode_pair(bool same, int t, int nj, int nk, float inv_div, int div,
-                                            int &jr, int &kr)
-{
-    if (!same) {
-        jr = (int)(((float)t + 0.5f) * inv_div);  // t / nk
-        kr = t - jr * nk;
-    } else {
-        const int rect = nj * div;  // div = (n-1)/2 partners per row
-        if (t < rect) {
-            jr = (int)(((float)t + 0.5f) * inv_div);
-            kr = jr + 1 + (t - jr * div);
-            kr = kr >= nj ? kr - nj : kr;
-        } else {  // n even: the n/2 diameters
-            jr = t - rect;
-            kr = jr + (nj >> 1);
-        }
-    }
-}
-
 // ---- cross-lane helpers (gfx950) -------------------------------------------------------------------
 // v + (v shifted right by N lanes inside each 16-lane DPP row, zero fill)
 template <int N>
@@ -157,39 +137,18 @@ __device__ __forceinline__ float sum32(float x, float y)
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// sums inside a quad / an aligned group of 8 lanes on the VALU (DPP), no LDS round trip
+// v moved between lanes by the DPP control CTRL on the VALU, no LDS round trip (lanes without a source read 0)
 template <int CTRL>
 __device__ __forceinline__ float dpp_perm(float v)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
-__device__ __forceinline__ float quad_sum(float v)
-{
-    v += dpp_perm<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_perm<0x4E>(v);   // quad_perm [2,3,0,1]
-    return v;
-}
-__device__ __forceinline__ float oct_sum(float v)
-{
-    v = quad_sum(v);
-    v += dpp_perm<0x141>(v);  // row_half_mirror: lane l <-> 7 - l of each 8-lane half row
-    return v;
-}
 
-// branch-free (j,k) decode of pair t of a block (see decode_pair); `rect` = INT_MAX for rectangles
-__device__ __forceinline__ void decode_pair2(bool same, int t, int nj, int div, float inv_div, int rect,
-                                             int half, int &jr, int &kr)
-{
-    const int q = (int)(((float)t + 0.5f) * inv_div);
-    const int rem = t - q * div;
-    int k2 = same ? q + 1 + rem : rem;
-    k2 = (same && k2 >= nj) ? k2 - nj : k2;
-    const bool diam = t >= rect;
-    jr = diam ? t - rect : q;
-    kr = diam ? t - rect + half : k2;
-}
-
-// The same decode advanced incrementally: pair t = qd * div + rem of slot p moves on by 16 per step, so the quotient /
+// (j, k) of the t-th pair of a species-pair block of nj x nk angular neighbors.  Two different species: the rectangle,
+// j = t / nk, k = t % nk (div = nk).  Inside one species: the circular tournament, every unordered pair exactly once with no
+// sqrt / triangular-index decode -- row j has the div = (nj - 1) / 2 partners k = j + 1 + rem (mod nj), t = j div + rem, and
+// for even nj the nj / 2 diameters (j, j + nj / 2) follow at t >= rect = nj div.
+// The decode is advanced incrementally: pair t = qd * div + rem of slot p moves on by 16 per step, so the quotient /
 // remainder follow from two adds and a carry instead of a float division and an integer multiply per step.
 // 16 / div for the wave-uniform group size div (0 for div == 0), on the scalar unit
 __device__ __forceinline__ int quot16(int div)
@@ -269,17 +228,18 @@ __device__ __forceinline__ AtomHdr hdr_decode(uint32_t w)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// JVP = true turns the kernel into the forward-mode derivative  out = (d aev / d r) . tang  (J t) for a coordinate-space
-// direction tang [n_atoms][3]: the reference's cuaev double backward (csrc/aev.cu:1986-2015 and the is_double_backward
-// kernel variants) -- the derivative of grad_coords = J^T grad_aev with respect to grad_aev, contracted with the
-// gradient arriving at the forces.  Same lane layout and reductions; every neighbor additionally carries
-// r' = u . d', u' = (d' - u r') / r, fc' r' (d' = t_j - t_i), every term is replaced by its directional derivative.
-template <int NA, int NZ, bool JVP>
-__global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
+// The forward-mode derivative  out = (d aev / d r) . tang  (J t) for a coordinate-space direction tang [n_atoms][3]: the
+// reference's cuaev double backward (csrc/aev.cu:1986-2015 and the is_double_backward kernel variants) -- the derivative
+// of grad_coords = J^T grad_aev with respect to grad_aev, contracted with the gradient arriving at the forces.  Lanes:
+// 8 neighbor slots x 8 shift pairs (radial), 16 pair slots x 4 quarters of the shifts (angular).  Every neighbor carries
+// r' = u . d', u' = (d' - u r') / r, fc' r' (d' = t_j - t_i) next to its geometry, every term is its directional
+// derivative.
+template <int NA, int NZ>
+__global__ __launch_bounds__(JVP_WPB * WAVE, 4) void k_aev_jvp(
     AevArgs a, const float *__restrict__ tab, int64_t lo, int64_t hi,
     const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
-    const float4 *__restrict__ ent, float *__restrict__ aev, uint32_t *__restrict__ slab_mask,
-    const float *__restrict__ tang, int64_t dir_t, int64_t dir_o)
+    const float4 *__restrict__ ent, float *__restrict__ aev, const float *__restrict__ tang, int64_t dir_t,
+    int64_t dir_o)
 {
     static_assert(NA % 4 == 0 && NZ % 4 == 0 && NA * NZ == 32, "angular tiling");
     // several directions in one launch (anihip_aev_jvp_batched): direction blockIdx.y reads tangent + y dir_t, writes
@@ -287,20 +247,20 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
     tang += (size_t)blockIdx.y * dir_t;
     aev += (size_t)blockIdx.y * dir_o;
     constexpr int AQ = NA / 4, ZQ = NZ / 4;
-    __shared__ float4 s_ang[FWD_WPB][MAXA];   // ux uy uz r
-    __shared__ float s_afc[FWD_WPB][MAXA];    // fc(r, Rca)
-    __shared__ float2 s_rad[FWD_WPB][MAXR];   // r, 0.25 fc(r, Rcr)            (JVP: r, 0.25 fc r')
-    __shared__ float4 s_angd[JVP ? FWD_WPB : 1][JVP ? MAXA : 1];   // JVP: u'x u'y u'z r'
-    __shared__ float s_afcd[JVP ? FWD_WPB : 1][JVP ? MAXA : 1];    // JVP: fc'(r, Rca) r'
-    __shared__ float s_radb[JVP ? FWD_WPB : 1][JVP ? MAXR : 1];    // JVP: 0.25 fc'(r, Rcr) r'
+    __shared__ float4 s_ang[JVP_WPB][MAXA];   // ux uy uz r
+    __shared__ float s_afc[JVP_WPB][MAXA];    // fc(r, Rca)
+    __shared__ float2 s_rad[JVP_WPB][MAXR];   // r, 0.25 fc(r, Rcr) r'
+    __shared__ float4 s_angd[JVP_WPB][MAXA];  // u'x u'y u'z r'
+    __shared__ float s_afcd[JVP_WPB][MAXA];   // fc'(r, Rca) r'
+    __shared__ float s_radb[JVP_WPB][MAXR];   // 0.25 fc'(r, Rcr) r'
 
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();   // scalar LDS bases
     float4 *ang = s_ang[wib];
     float *afc = s_afc[wib];
     float2 *rad = s_rad[wib];
-    float4 *angd = s_angd[JVP ? wib : 0];
-    float *afcd = s_afcd[JVP ? wib : 0];
-    float *radb = s_radb[JVP ? wib : 0];
+    float4 *angd = s_angd[wib];
+    float *afcd = s_afcd[wib];
+    float *radb = s_radb[wib];
 
     // per-lane constants
     const int rp = lane >> 3, rsq = lane & 7;  // radial: neighbor slot, shift pair
@@ -324,8 +284,8 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
     const bool rad_writer = (lane & 8) && row < 2;
     const int rad_o = row * 8 + rsq;
 
-    const int64_t nw = (int64_t)gridDim.x * FWD_WPB;
-    int64_t i = lo + xcd_block() * (int64_t)FWD_WPB + wib;
+    const int64_t nw = (int64_t)gridDim.x * JVP_WPB;
+    int64_t i = lo + xcd_block() * (int64_t)JVP_WPB + wib;
     // software pipeline over atoms: header of atom i+nw and the first 128 entries of atom i+nw are in
     // flight while atom i is being computed
     uint32_t hw = hdr_load(meta, species, i, i < hi);
@@ -350,18 +310,7 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
                 const int e = c0 + lane;
                 float4 d = c0 == 0 ? e0 : (c0 == WAVE ? e1 : make_float4(1.f, 0.f, 0.f, 0.f));
                 if (c0 >= 2 * WAVE && e < nR) d = ent[start + e];
-                if (!JVP && e < nR) {
-                    const float r = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-                    rad[e] = make_float2(r, a.smooth ? 0.25f * smooth_cutoff(r, 1.0f / a.Rcr).x
-                                                     : 0.125f * __builtin_amdgcn_cosf(r * rev_rcr) + 0.125f);
-                    if (e < nA) {
-                        const float inv = 1.0f / r;
-                        ang[e] = make_float4(d.x * inv, d.y * inv, d.z * inv, r);
-                        afc[e] = a.smooth ? smooth_cutoff(r, 1.0f / a.Rca).x
-                                          : 0.5f * __builtin_amdgcn_cosf(r * rev_rca) + 0.5f;
-                    }
-                }
-                if (JVP && e < nR) {
+                if (e < nR) {
                     const float r = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z), inv = 1.0f / r;
                     const float ux = d.x * inv, uy = d.y * inv, uz = d.z * inv;
                     const float *tj = tang + 3 * (size_t)(__float_as_uint(d.w) & IDX_MASK), *ti = tang + 3 * (size_t)i;
@@ -400,12 +349,9 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
         if (padding) {
             float4 *out4 = reinterpret_cast<float4 *>(out);
             for (int f = lane; f < (a.L >> 2); f += WAVE) out4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (slab_mask && lane == 0) slab_mask[i] = 0u;
             continue;
         }
         wave_sync();
-        uint32_t smask = 0u;   // 32-wide slabs of this row that are not identically zero (include/anihip.h)
-        const int rslabs = (a.S + 1) >> 1;
 
         // ---- radial ----
         {
@@ -417,7 +363,6 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
                     if (rad_writer) out[t * 16 + rad_o] = 0.f;
                     continue;
                 }
-                smask |= 1u << (t >> 1);
                 for (int b = 0; b < n; b += 8) {
                     const int idx = b + rp;
                     const bool v = idx < n;
@@ -426,14 +371,10 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
                     const float2 rf = rad[e];
                     const float f = v ? rf.y : 0.f;
                     const float d0 = rf.x - shfR0, d1 = rf.x - shfR1;
-                    if (!JVP) {
-                        acc0 += __builtin_amdgcn_exp2f(a.kR * d0 * d0) * f;
-                        acc1 += __builtin_amdgcn_exp2f(a.kR * d1 * d1) * f;
-                    } else {   // d/dt [0.25 exp(-eta d^2) fc] = exp(..) (0.25 fc' r' - 2 eta d 0.25 fc r')
-                        const float fb = v ? radb[e] : 0.f;
-                        acc0 += __builtin_amdgcn_exp2f(a.kR * d0 * d0) * (fb - 2.0f * a.EtaR * d0 * f);
-                        acc1 += __builtin_amdgcn_exp2f(a.kR * d1 * d1) * (fb - 2.0f * a.EtaR * d1 * f);
-                    }
+                    // d/dt [0.25 exp(-eta d^2) fc] = exp(..) (0.25 fc' r' - 2 eta d 0.25 fc r')
+                    const float fb = v ? radb[e] : 0.f;
+                    acc0 += __builtin_amdgcn_exp2f(a.kR * d0 * d0) * (fb - 2.0f * a.EtaR * d0 * f);
+                    acc1 += __builtin_amdgcn_exp2f(a.kR * d1 * d1) * (fb - 2.0f * a.EtaR * d1 * f);
                 }
                 // 8 slots -> 1: inside the DPP row, then across rows.  Row 0 ends with the totals of
                 // acc0, row 1 with those of acc1 (lanes 8..15 = shift pair rsq).
@@ -463,7 +404,6 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
                         ok += nk;
                         continue;
                     }
-                    smask |= 1u << ((rslabs + P) & 31);
                     const int div = same ? ((nj - 1) >> 1) : nk;
                     const float inv_div = div > 0 ? 1.0f / (float)div : 0.f;
                     const int rect = same ? nj * div : 0x7FFFFFFF;
@@ -473,91 +413,49 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
                     for (int u = 0; u < AQ; ++u)
 #pragma unroll
                         for (int z = 0; z < NZ; ++z) acc[u][z] = 0.f;
-                    // software-pipelined over the steps: LDS reads of step s+1 are issued before the
-                    // arithmetic of step s
                     int jr, kr;
                     const int q16 = quot16(div), r16 = 16 - q16 * div;
                     const int jmax = nj - 1, kmax = (same ? nj : nk) - 1;
                     PairIter it = pair_begin(p, div, inv_div);
                     pair_get(it, same, nj, rect, half, jmax, kmax, jr, kr);
-                    if (!JVP) {
-                        float4 J = ang[oj + jr], K = ang[ok + kr];
-                        float fj = afc[oj + jr], fk = afc[ok + kr];
-                        for (int t0 = 0; t0 < np; t0 += 16) {
-                            const bool v = it.t < np;
-                            const float4 Jc = J, Kc = K;
-                            const float fcc = v ? 2.0f * fj * fk : 0.f;
-                            if (t0 + 16 < np) {
-                                pair_next(it, div, q16, r16);
-                                pair_get(it, same, nj, rect, half, jmax, kmax, jr, kr);
-                                J = ang[oj + jr];
-                                K = ang[ok + kr];
-                                fj = afc[oj + jr];
-                                fk = afc[ok + kr];
-                            }
-                            const float c = Jc.x * Kc.x + Jc.y * Kc.y + Jc.z * Kc.z;
-                            const float ct = 0.95f * c;
-                            const float st = __builtin_amdgcn_sqrtf(fmaxf(1.0f - ct * ct, 0.f));
-                            const float rm = 0.5f * (Jc.w + Kc.w);
-                            float f1t[ZQ], f2[AQ];
-    #pragma unroll
-                            for (int vz = 0; vz < ZQ; ++vz) {
-                                const float cz = ct * cosZ[vz] + st * sinZ[vz];
-                                const float hh = fmaxf(0.5f + 0.5f * cz, 0.f);
-                                f1t[vz] = __builtin_amdgcn_exp2f(a.Zeta * __builtin_amdgcn_logf(hh)) * fcc;
-                            }
-    #pragma unroll
-                            for (int u = 0; u < AQ; ++u) {
-                                const float d = rm - shfA[u];
-                                f2[u] = __builtin_amdgcn_exp2f(a.kA * d * d);
-                            }
-    #pragma unroll
-                            for (int z = 0; z < NZ; ++z) {
-                                const float f1 = quad_bcast_rt(f1t[z >> 2], z & 3);
-    #pragma unroll
-                                for (int u = 0; u < AQ; ++u) acc[u][z] += f2[u] * f1;
-                            }
+                    for (int t0 = 0; t0 < np; t0 += 16) {
+                        const bool v = it.t < np;
+                        const float4 Jc = ang[oj + jr], Kc = ang[ok + kr], Jd = angd[oj + jr], Kd = angd[ok + kr];
+                        const float fj = afc[oj + jr], fk = afc[ok + kr], fjd = afcd[oj + jr], fkd = afcd[ok + kr];
+                        pair_next(it, div, q16, r16);
+                        pair_get(it, same, nj, rect, half, jmax, kmax, jr, kr);
+                        const float fcc = v ? 2.0f * fj * fk : 0.f;                    // (the 2 of f1 = 2 h^zeta)
+                        const float fccd = v ? 2.0f * (fjd * fk + fj * fkd) : 0.f;
+                        const float c = Jc.x * Kc.x + Jc.y * Kc.y + Jc.z * Kc.z;
+                        const float cd = Jd.x * Kc.x + Jd.y * Kc.y + Jd.z * Kc.z + Jc.x * Kd.x + Jc.y * Kd.y + Jc.z * Kd.z;
+                        const float ct = 0.95f * c;
+                        const float st2 = fmaxf(1.0f - ct * ct, 1e-12f);
+                        const float rst = __builtin_amdgcn_rsqf(st2);
+                        const float st = st2 * rst;
+                        const float thd = -0.95f * cd * rst;                           // d theta / dt
+                        const float rm = 0.5f * (Jc.w + Kc.w), rmd = 0.5f * (Jd.w + Kd.w);
+                        float At[ZQ], Bt[ZQ], f2[AQ], df2[AQ];
+#pragma unroll
+                        for (int vz = 0; vz < ZQ; ++vz) {
+                            const float cz = ct * cosZ[vz] + st * sinZ[vz];   // cos(theta - ShfZ)
+                            const float sz = st * cosZ[vz] - ct * sinZ[vz];   // sin(theta - ShfZ)
+                            const float hh = fmaxf(0.5f + 0.5f * cz, 0.f);
+                            const float p1 = __builtin_amdgcn_exp2f((a.Zeta - 1.0f) * __builtin_amdgcn_logf(hh));
+                            const float f1 = hh * p1, df1 = -0.5f * a.Zeta * p1 * sz;  // h^zeta and its theta derivative
+                            At[vz] = df1 * thd * fcc + f1 * fccd;
+                            Bt[vz] = f1 * rmd * fcc;
                         }
-                    } else {
-                        for (int t0 = 0; t0 < np; t0 += 16) {
-                            const bool v = it.t < np;
-                            const float4 Jc = ang[oj + jr], Kc = ang[ok + kr], Jd = angd[oj + jr], Kd = angd[ok + kr];
-                            const float fj = afc[oj + jr], fk = afc[ok + kr], fjd = afcd[oj + jr], fkd = afcd[ok + kr];
-                            pair_next(it, div, q16, r16);
-                            pair_get(it, same, nj, rect, half, jmax, kmax, jr, kr);
-                            const float fcc = v ? 2.0f * fj * fk : 0.f;                    // (the 2 of f1 = 2 h^zeta)
-                            const float fccd = v ? 2.0f * (fjd * fk + fj * fkd) : 0.f;
-                            const float c = Jc.x * Kc.x + Jc.y * Kc.y + Jc.z * Kc.z;
-                            const float cd = Jd.x * Kc.x + Jd.y * Kc.y + Jd.z * Kc.z + Jc.x * Kd.x + Jc.y * Kd.y + Jc.z * Kd.z;
-                            const float ct = 0.95f * c;
-                            const float st2 = fmaxf(1.0f - ct * ct, 1e-12f);
-                            const float rst = __builtin_amdgcn_rsqf(st2);
-                            const float st = st2 * rst;
-                            const float thd = -0.95f * cd * rst;                           // d theta / dt
-                            const float rm = 0.5f * (Jc.w + Kc.w), rmd = 0.5f * (Jd.w + Kd.w);
-                            float At[ZQ], Bt[ZQ], f2[AQ], df2[AQ];
 #pragma unroll
-                            for (int vz = 0; vz < ZQ; ++vz) {
-                                const float cz = ct * cosZ[vz] + st * sinZ[vz];   // cos(theta - ShfZ)
-                                const float sz = st * cosZ[vz] - ct * sinZ[vz];   // sin(theta - ShfZ)
-                                const float hh = fmaxf(0.5f + 0.5f * cz, 0.f);
-                                const float p1 = __builtin_amdgcn_exp2f((a.Zeta - 1.0f) * __builtin_amdgcn_logf(hh));
-                                const float f1 = hh * p1, df1 = -0.5f * a.Zeta * p1 * sz;  // h^zeta and its theta derivative
-                                At[vz] = df1 * thd * fcc + f1 * fccd;
-                                Bt[vz] = f1 * rmd * fcc;
-                            }
+                        for (int u = 0; u < AQ; ++u) {
+                            const float d = rm - shfA[u];
+                            f2[u] = __builtin_amdgcn_exp2f(a.kA * d * d);
+                            df2[u] = -2.0f * a.EtaA * d * f2[u];
+                        }
 #pragma unroll
-                            for (int u = 0; u < AQ; ++u) {
-                                const float d = rm - shfA[u];
-                                f2[u] = __builtin_amdgcn_exp2f(a.kA * d * d);
-                                df2[u] = -2.0f * a.EtaA * d * f2[u];
-                            }
+                        for (int z = 0; z < NZ; ++z) {
+                            const float Az = quad_bcast_rt(At[z >> 2], z & 3), Bz = quad_bcast_rt(Bt[z >> 2], z & 3);
 #pragma unroll
-                            for (int z = 0; z < NZ; ++z) {
-                                const float Az = quad_bcast_rt(At[z >> 2], z & 3), Bz = quad_bcast_rt(Bt[z >> 2], z & 3);
-#pragma unroll
-                                for (int u = 0; u < AQ; ++u) acc[u][z] += f2[u] * Az + df2[u] * Bz;
-                            }
+                            for (int u = 0; u < AQ; ++u) acc[u][z] += f2[u] * Az + df2[u] * Bz;
                         }
                     }
                     // 16 slots -> 1.  Inside each DPP row (4 slots): two shifted adds leave the row
@@ -579,7 +477,6 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
                 oj += nj;
             }
         }
-        if (slab_mask && lane == 0) slab_mask[i] = smask;
         wave_sync();
     }
 }
@@ -587,16 +484,12 @@ __global__ __launch_bounds__(FWD_WPB * WAVE, JVP ? 4 : 7) void k_aev_fwd(
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------
-// k_aev_fwd3 (round 3): ONE lane per (j, k) pair and a FLAT slot assignment over all species-pair blocks of the atom.
-//   * k_aev_fwd2 walks the species-pair blocks one after the other, 32 two-lane pair slots at a time: on the water box
-//     an atom has 53 + 58 + 12 pairs (HH, HO, OO) in 2 + 2 + 1 = 5 iterations of 91 instructions -- 77 % of the slots
-//     hold a pair -- and every block pays its own 32-slot transpose-reduce.  Both lanes of a slot repeat the pair's
-//     geometry (index decode, two LDS reads, dot product, sqrt).
-//   * here a lane owns a pair slot for the whole atom: block b of the atom gets ns_b = pad4(ceil(np_b / I)) of the 64
+// k_aev_fwd3: ONE lane per (j, k) pair and a FLAT slot assignment over all species-pair blocks of the atom.
+//   * a lane owns a pair slot for the whole atom: block b of the atom gets ns_b = pad4(ceil(np_b / I)) of the 64
 //     slots (I = iterations, the smallest for which the blocks fit; a slot walks I consecutive pairs of ITS block), the
-//     lane evaluates all NA Gaussians and all NZ angle factors of its pair -- every constant is wave-uniform now and
-//     lives in scalar registers -- and keeps the whole NA x NZ block of sums (32 registers).  The same atom takes
-//     ceil(123 / 64) = 2 iterations, 96 % of the slots busy, the geometry once per pair.
+//     lane evaluates all NA Gaussians and all NZ angle factors of its pair -- every constant is wave-uniform and lives
+//     in scalar registers -- and keeps the whole NA x NZ block of sums (32 registers).  A water-box atom with its
+//     53 + 58 + 12 pairs (HH, HO, OO) takes ceil(123 / 64) = 2 iterations, 96 % of the slots busy, the geometry once per pair.
 //   * the 64 x 32 sums leave through LDS as a SEGMENTED reduction, 16 values per round: every lane writes its row
 //     (stride 20 floats: conflict-free 16-B accesses), lane group g = lane / 4 adds the four rows 4 g .. 4 g + 3 (blocks
 //     are padded to multiples of four slots, so a group never straddles two blocks), a two-step segmented scan over the
@@ -604,7 +497,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 //     carry the partial sums to the LAST group of every block, whose four lanes store 64 B of the AEV row.  No atomics,
 //     fixed order, any number of blocks for the price of one reduction.
 //   * atoms whose blocks do not fit 64 slots (many species with a few pairs each) are done in batches of blocks.
-// (k_aev_fwd2, the round-2 kernel described in the first bullet, is gone: 4.28 ms against 4.06 ms on the 2.34 M-atom box.)
+// (History: 4.06 ms on the 2.34 M-atom box against 4.28 ms of its predecessor, which walked the blocks one after the other.)
 #ifndef ANIHIP_FWD3_WAVES
 #define ANIHIP_FWD3_WAVES 4
 #endif
@@ -1776,54 +1669,45 @@ extern "C" int anihip_aev_forward_update(void *stream, const anihip_aev_params *
     return aev_forward(stream, p, table, n_atoms, lo, hi, species, meta, ent, aev, slab_mask, status, true, prev_mask);
 }
 
+// J t for n_dir directions, direction y of the launch grid reading tangent + y dir_t and writing daev + y dir_o.  `strided`:
+// the layout of anihip_aev_jvp_batched (dir_t = 3 n_atoms, dir_o = n_atoms L); anihip_aev_jvp is one direction at strides 0.
+static int aev_jvp(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo, int64_t hi,
+                   const int32_t *species, const uint32_t *meta, const float *ent, int64_t n_dir, bool strided,
+                   const float *tangent, float *daev)
+{
+    ANIHIP_REQUIRE(p && table && species && meta && ent && tangent && daev, "null pointer argument");
+    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
+    const int64_t dir_t = strided ? 3 * n_atoms : 0;
+    if (!tuned_grid(p))   // any other grid: the JVP instantiation of the general kernel
+        return strided ? aev_jvp_generic_dirs((hipStream_t)stream, p, table, lo, hi, species, meta, ent, daev, tangent,
+                                              (int)n_dir, dir_t, n_atoms)
+                       : aev_forward_generic((hipStream_t)stream, p, table, lo, hi, species, meta, ent, daev, tangent, nullptr);
+    AevArgs a;
+    if (int rc = make_args(p, &a)) return rc;
+    if (hi == lo || n_dir == 0) return 0;
+    const int64_t dir_o = strided ? n_atoms * (int64_t)a.L : 0;
+    dim3 grid(persistent_blocks(hi - lo, JVP_WPB, 4), (unsigned)n_dir), block(JVP_WPB * WAVE);
+    hipLaunchKernelGGL((p->n_shf_a == 8 ? k_aev_jvp<8, 4> : k_aev_jvp<4, 8>), grid, block, 0, (hipStream_t)stream, a, table,
+                       lo, hi, species, meta, (const float4 *)ent, daev, tangent, dir_t, dir_o);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int anihip_aev_jvp(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
                               int64_t lo, int64_t hi, const int32_t *species, const uint32_t *meta,
                               const float *ent, const float *tangent, float *daev, uint32_t *status)
 {
-    ANIHIP_REQUIRE(p && table && species && meta && ent && tangent && daev, "null pointer argument");
-    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
-    if (!tuned_grid(p))   // any other grid: the JVP instantiation of the general kernel
-        return aev_forward_generic((hipStream_t)stream, p, table, lo, hi, species, meta, ent, daev, tangent, nullptr);
-    AevArgs a;
-    if (int rc = make_args(p, &a)) return rc;
-    if (hi == lo) return 0;
-    dim3 grid(persistent_blocks(hi - lo, FWD_WPB, 4)), block(FWD_WPB * WAVE);
-    if (p->n_shf_a == 8)
-        hipLaunchKernelGGL((k_aev_fwd<8, 4, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
-                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, (int64_t)0, (int64_t)0);
-    else
-        hipLaunchKernelGGL((k_aev_fwd<4, 8, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
-                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, (int64_t)0, (int64_t)0);
-    ANIHIP_CHECK_HIP(hipGetLastError());
     (void)status;
-    return 0;
+    return aev_jvp(stream, p, table, n_atoms, lo, hi, species, meta, ent, 1, false, tangent, daev);
 }
 
 extern "C" int anihip_aev_jvp_batched(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
                                       int64_t lo, int64_t hi, const int32_t *species, const uint32_t *meta,
                                       const float *ent, int64_t n_dir, const float *tangent, float *daev, uint32_t *status)
 {
-    ANIHIP_REQUIRE(p && table && species && meta && ent && tangent && daev, "null pointer argument");
-    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
-    ANIHIP_REQUIRE(0 <= n_dir && n_dir <= 65535, "n_dir must be 0..65535 (got %lld)", (long long)n_dir);
-    if (hi == lo || n_dir == 0) return 0;
-    const int64_t dir_t = 3 * n_atoms;
-    if (!tuned_grid(p))
-        return aev_jvp_generic_dirs((hipStream_t)stream, p, table, lo, hi, species, meta, ent, daev, tangent, (int)n_dir, dir_t,
-                                    n_atoms);
-    AevArgs a;
-    if (int rc = make_args(p, &a)) return rc;
-    const int64_t dir_o = n_atoms * (int64_t)a.L;
-    dim3 grid(persistent_blocks(hi - lo, FWD_WPB, 4), (unsigned)n_dir), block(FWD_WPB * WAVE);
-    if (p->n_shf_a == 8)
-        hipLaunchKernelGGL((k_aev_fwd<8, 4, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
-                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, dir_t, dir_o);
-    else
-        hipLaunchKernelGGL((k_aev_fwd<4, 8, true>), grid, block, 0, (hipStream_t)stream, a, table, lo, hi, species,
-                           meta, (const float4 *)ent, daev, (uint32_t *)nullptr, tangent, dir_t, dir_o);
-    ANIHIP_CHECK_HIP(hipGetLastError());
     (void)status;
-    return 0;
+    ANIHIP_REQUIRE(0 <= n_dir && n_dir <= 65535, "n_dir must be 0..65535 (got %lld)", (long long)n_dir);
+    return aev_jvp(stream, p, table, n_atoms, lo, hi, species, meta, ent, n_dir, true, tangent, daev);
 }
 
 // item rows of a sparse Hessian: every grid through the general kernel (the tuned grids' tables hold the plain shifts too)
