@@ -392,7 +392,9 @@ int anihip_lbfgs_step(void *stream, const anihip_lbfgs_params *params, const uin
  * Langevin dynamics in the BAOAB splitting, layout [n_mol][atoms_per_mol] = [C][A].  Units: Angstrom, fs, amu, Hartree;
  * ANIHIP_MD_ACC_UNIT = (Hartree / Angstrom) / amu in Angstrom / fs^2.  A step of the caller is anihip_md_drift, the forces at
  * the new coordinates, anihip_md_kick.  active uint8 [C][A]: 0 = a padding or fixed atom, which never moves and whose velocity
- * is set to zero.  One thread per atom, no atomics, every sum in a fixed order: bit-identical run to run.
+ * is set to zero; 1 = a free atom; 2 (ANIHIP_MD_ATOM_CLUSTER) = an atom owned by a cluster of bond-length constraints (below),
+ * which drift and the kick of anihip_md_kick leave alone and the sums count.  One thread per atom, no atomics, every sum in
+ * a fixed order: bit-identical run to run.
  *
  * anihip_md_drift, per active atom:  v += dt/2 f inv_mass;  NVE: x += dt v;  Langevin (flags & ANIHIP_MD_LANGEVIN):
  * x += dt/2 v,  v = c1 v + sqrt(kT_c (1 - c1^2) inv_mass) xi,  x += dt/2 v,  c1 = exp(-friction_c dt).  inv_mass fp32 [C][A] =
@@ -432,6 +434,65 @@ int anihip_md_remove_drift(void *stream, const anihip_md_params *params, const u
                            float *velocities, void *workspace, size_t workspace_bytes);
 int anihip_md_noise(void *stream, uint64_t seed, uint64_t step, int64_t n_mol, int64_t atoms_per_mol,
                     const int64_t *replica_ids, float *out);
+
+/* Bond-length constraints (SHAKE / RATTLE) of the integrator above.  A constraint k holds |x_i - x_j| = d_k for two atoms of
+ * one molecule; the difference is the plain one of the unwrapped coordinates, no minimum image is taken.  Constraints that
+ * share atoms form a cluster, a connected component of the constraint graph, of at most ANIHIP_MD_CLUSTER_ATOMS atoms and
+ * ANIHIP_MD_CLUSTER_BONDS constraints (X-H stars, rigid three-site waters, short chains).  There are no angle constraints and
+ * no SETTLE.  w_i = inv_mass_i for an active atom and 0 for a fixed atom, which may anchor a constraint; a constraint between
+ * two atoms of w = 0 or on a padding atom is the caller's error.  Two operations, per cluster in fp64 on x = coords + coords_lo
+ * read exactly:
+ *   project_v(x, v): the v' = v - W J^T mu with r_ij . (v'_i - v'_j) = 0 for every constraint (r_ij = x_i - x_j; RATTLE's
+ *     velocity stage), a projector at fixed x.  Gauss-Seidel over the constraints in their stored order, mu_k = r.dv /
+ *     ((w_i + w_j) r.r); a constraint is converged at |r.dv| <= tolerance d_k v_scale, v_scale = the largest |v| component
+ *     of the cluster's atoms when the projection starts.
+ *   move(x, v, h): x' = x + h v + W J(x)^T lambda with |x'_i - x'_j| = d_k, the correction directions r_ij taken at the START
+ *     of the move (SHAKE); then v' = (x' - x) / h.  Gauss-Seidel, lambda_k = (|s|^2 - d_k^2) / (2 (w_i + w_j) s.r) with
+ *     s = x'_i - x'_j; a constraint is converged at | |s|^2 - d_k^2 | <= 2 tolerance d_k^2.
+ * An iteration count is the number of sweeps that corrected a constraint, at most max_iterations; a cluster that reaches
+ * max_iterations has not converged.  The step is geodesic BAOAB with one RATTLE per sub-step (Leimkuhler and Matthews 2016,
+ * K_r = 1), the projections that a later one at the same x makes redundant left out (move(x, v, h) = move(x, project_v(x, v), h)):
+ *   anihip_md_constrain_drift:   B v += dt/2 f w;  NVE move(dt);  Langevin move(dt/2), O v = c1 v + sqrt(kT (1 - c1^2) w) xi,
+ *     move(dt/2), with c1 and xi those of anihip_md_drift at the atom's own index, all in fp64; writes coords = (float)x,
+ *     coords_lo = (float)(x - coords), the fp32 velocities and iterations[q][0] (the larger count of the two moves).
+ *   anihip_md_constrain_kick:    B, project_v; writes the velocities and iterations[q][1].  It runs BEFORE anihip_md_kick, which
+ *     adds the kinetic energy of the projected velocities.
+ *   anihip_md_project_velocities: project_v alone; writes the velocities and iterations[q][1].
+ * All three touch only the atoms of clusters with w != 0 (marked 2 in `active`); one thread per cluster, the cluster staged
+ * in LDS, no atomics, one launch each.  A cluster whose table entries are out of range moves nothing and reports
+ * max_iterations.  Tables (device memory, built once by the caller, Q = n_clusters):
+ *   atoms int32 [Q][8]      global atom index c A + i of each slot (one molecule per cluster), slots past count[q][0] unused
+ *   count int32 [Q][2]      atoms (2..8) and constraints (1..12) of the cluster
+ *   bonds uint8 [Q][12][2]  the slots (a, b) of each constraint
+ *   d2    fp64  [Q][12]     d_k^2, Angstrom^2
+ *   w     fp64  [Q][8]      w of each slot (ANIHIP_MD_ACC_UNIT / m, 0 for a fixed atom)
+ *   iterations int32 [Q][2] OUT: position and velocity iteration counts of the last call that wrote them
+ * Two kernel instances: tables whose largest cluster has at most 4 atoms and 4 constraints (max_atoms, max_bonds below) run one
+ * with 24 KB of LDS per 64 clusters, any other the 8 / 12 instance with 52 KB.  Measured on one MI355X at tolerance 1e-8
+ * (profiles/md_constraints_bench.txt): 778 688 rigid waters add 0.59 ms to a 31.7 ms Langevin step (19 position and 29
+ * velocity sweeps per cluster at dt 0.5 fs, 24 and 31 at 2 fs); 524 clusters of X-H bonds add 0.06 ms to a 0.24 ms step (2 sweeps). */
+#define ANIHIP_MD_ATOM_CLUSTER 2
+#define ANIHIP_MD_CLUSTER_ATOMS 8
+#define ANIHIP_MD_CLUSTER_BONDS 12
+typedef struct {
+    int64_t n_clusters;
+    const int32_t *atoms, *count;
+    const uint8_t *bonds;
+    const double *d2, *w;
+    int32_t *iterations;
+    double tolerance;         /* > 0 */
+    int32_t max_iterations;   /* >= 1 */
+    int32_t max_atoms, max_bonds;   /* the largest count[q][0] and count[q][1] of the tables, or 0, 0 if not known: tables of
+                                       clusters of at most 4 atoms and 4 constraints run a kernel instance with less LDS */
+    int32_t reserved;         /* 0 */
+} anihip_md_clusters;
+int anihip_md_constrain_drift(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                              const float *kT, const float *friction, const int64_t *replica_ids, float *coords,
+                              float *coords_lo, float *velocities, const float *forces);
+int anihip_md_constrain_kick(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                             const float *coords, const float *coords_lo, float *velocities, const float *forces);
+int anihip_md_project_velocities(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                                 const float *coords, const float *coords_lo, float *velocities);
 
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]

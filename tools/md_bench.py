@@ -3,6 +3,9 @@
     python tools/md_bench.py [--side 64] [--steps 20]                      the host driver with and without Verlet-skin reuse
     python tools/md_bench.py --integrator both --langevin --repeats 7 ...  host driver (md.MolecularDynamics) against the
                                                                            on-device integrator (md.BatchedDynamics)
+    python tools/md_bench.py --integrator device --constraints none rigid-water --dt 2 ...
+                                                                           the device integrator without and with bond-length
+                                                                           constraints (md.hydrogen_constraints), alternating
 
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
@@ -35,13 +38,18 @@ def load_system(args, dev):
 
 
 def make_driver(kind, args, model, sp, x, cell, pbc, masses):
-    from torchani_amd.md import BatchedDynamics, MolecularDynamics
+    """kind: "host", "device", or "device+hydrogens" / "device+rigid-water" for the device integrator with constraints."""
+    from torchani_amd.md import BatchedDynamics, MolecularDynamics, hydrogen_constraints
 
     temperature = 300.0 if args.langevin else None
     if kind == "host":
-        md = MolecularDynamics(model, sp, x, cell, pbc, dt=0.5, masses=masses, temperature=temperature, seed=1)
+        md = MolecularDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1)
     else:
-        md = BatchedDynamics(model, sp, x, cell, pbc, dt=0.5, masses=masses, temperature=temperature, seed=1)
+        constraints = None
+        if "+" in kind:   # (species are ANI-2x element indices: H = 0, O = 3)
+            constraints = hydrogen_constraints(sp, x, cell, pbc, rigid_water=kind.endswith("rigid-water"), hydrogen=0, oxygen=3)
+        md = BatchedDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1,
+                             constraints=constraints)
     md.set_temperature(300.0)
     return md
 
@@ -63,6 +71,10 @@ def main():
     ap.add_argument("--neighborlist", choices=("cell_list", "verlet_cell_list"), default=None,
                     help="--system water: time this neighbor list alone (default: both)")
     ap.add_argument("--langevin", action="store_true", help="Langevin dynamics at 300 K, friction 0.002 / fs (default: NVE)")
+    ap.add_argument("--dt", type=float, default=0.5, help="time step, fs")
+    ap.add_argument("--constraints", nargs="+", choices=("none", "hydrogens", "rigid-water"), default=["none"],
+                    help="device integrator: X-H bonds (hydrogens) or whole waters (rigid-water) held rigid; several values are "
+                         "timed against each other in one process")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
@@ -77,12 +89,17 @@ def main():
     n_atoms = int((sp >= 0).sum())
     masses = torch.tensor(ELEMENT_MASSES, device=dev)[sp.clamp(min=0)]
     kinds = ("host", "device") if args.integrator == "both" else (args.integrator,)
+    if args.constraints != ["none"]:
+        if "device" not in kinds:
+            ap.error("--constraints needs the device integrator")
+        kinds = tuple(k for k in kinds if k != "device") + tuple("device" if c == "none" else "device+" + c
+                                                                 for c in args.constraints)
     for nl in lists:
         drivers = {}
         for kind in kinds:   # (a model each: the automatic HIP graph of a small system belongs to one species tensor)
             # (BatchedDynamics never reads the overflow status inside a step, so it cannot retry with longer neighbor rows as
             # the host driver's evaluation does: when it is timed, both models get the longest rows from the start)
-            rows = {"row_capacity": 256} if "device" in kinds else {}
+            rows = {"row_capacity": 256} if any(k.startswith("device") for k in kinds) else {}
             model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl, **rows)
             if args.force_verlet and model.aev_computer.verlet is not None:
                 model.aev_computer.verlet.rebuild_above = float("inf")
@@ -98,9 +115,13 @@ def main():
             extra = (f", pair searches {ver.n_builds}, reuses {ver.n_reuses}, steps rebuilt outright {ver.n_direct}"
                      if ver is not None else "")
             spread = f" (fastest {t.min():.3f}, slowest {t.max():.3f} of {len(t)} repeats)" if len(t) > 1 else ""
-            print(f"{nl:17s} {kind:6s} {'langevin' if args.langevin else 'nve':8s} {n_atoms} atoms: {np.median(t):.3f} ms/step"
-                  f"{spread} = {n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M atom*steps/s, "
-                  f"T = {md.temperatures().mean().item():.0f} K{extra}")
+            if getattr(md, "_clusters", None) is not None:   # the counts of the last step
+                it = md.constraint_iterations.double().mean(dim=0).tolist()
+                extra += (f", {int(md.n_constraints.sum())} constraints in {md.constraint_iterations.shape[0]} clusters, mean "
+                          f"iterations of the last step: positions {it[0]:.2f}, velocities {it[1]:.2f}")
+            print(f"{nl:17s} {kind:6s} {'langevin' if args.langevin else 'nve':8s} dt {args.dt:g} fs {n_atoms} atoms: "
+                  f"{np.median(t):.3f} ms/step{spread} = {n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M atom*steps/s, "
+                  f"{args.dt / (np.median(t) * 1e-3):.0f} fs simulated per second, T = {md.temperatures().mean().item():.0f} K{extra}")
 
 
 if __name__ == "__main__":

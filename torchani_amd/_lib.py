@@ -43,6 +43,7 @@ BLOCK_HESSIAN_MAX_VECTORS = 64   # ANIHIP_BLOCK_HESSIAN_MAX_VECTORS
 BLOCK_HESSIAN_BAD_INDEX, BLOCK_HESSIAN_NO_PARTNER, BLOCK_HESSIAN_NO_DIAGONAL = 1, 2, 4
 LBFGS_MAX_MEMORY = 256   # ANIHIP_LBFGS_MAX_MEMORY
 MD_LANGEVIN = 1   # ANIHIP_MD_LANGEVIN
+MD_ATOM_CLUSTER, MD_CLUSTER_ATOMS, MD_CLUSTER_BONDS = 2, 8, 12   # ANIHIP_MD_ATOM_CLUSTER, ANIHIP_MD_CLUSTER_*
 
 
 class AevParams(C.Structure):
@@ -119,6 +120,13 @@ class MdParams(C.Structure):
     """anihip_md_params (include/anihip.h)."""
     _fields_ = [("n_mol", C.c_int32), ("atoms_per_mol", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
                 ("dt", C.c_double), ("seed", C.c_uint64), ("step", C.c_uint64)]
+
+
+class MdClusters(C.Structure):
+    """anihip_md_clusters (include/anihip.h)."""
+    _fields_ = [("n_clusters", C.c_int64), ("atoms", C.c_void_p), ("count", C.c_void_p), ("bonds", C.c_void_p),
+                ("d2", C.c_void_p), ("w", C.c_void_p), ("iterations", C.c_void_p), ("tolerance", C.c_double),
+                ("max_iterations", C.c_int32), ("max_atoms", C.c_int32), ("max_bonds", C.c_int32), ("reserved", C.c_int32)]
 
 
 class MlpShape(C.Structure):
@@ -269,7 +277,11 @@ def lib() -> C.CDLL:
     L.anihip_md_kick.argtypes = [vp, C.POINTER(MdParams), vp, vp, vp, vp, vp, vp, sz]
     L.anihip_md_remove_drift.argtypes = [vp, C.POINTER(MdParams), vp, vp, vp, vp, sz]
     L.anihip_md_noise.argtypes = [vp, C.c_uint64, C.c_uint64, i64, i64, vp, vp]
-    for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise"):
+    L.anihip_md_constrain_drift.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_md_constrain_kick.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp, vp]
+    L.anihip_md_project_velocities.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp]
+    for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
+                 "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities"):
         getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
@@ -302,6 +314,7 @@ EXPORTED_SYMBOLS = [
     "anihip_aev_jvp_strain_items", "anihip_aev_backward_second_strain_items", "anihip_pair_analytic_hvp_strain",
     "anihip_lbfgs_workspace_bytes", "anihip_lbfgs_step",
     "anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
+    "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
 ]
 
 

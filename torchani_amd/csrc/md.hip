@@ -6,6 +6,9 @@
 //   k_md_kick      one thread per atom: v += dt/2 f / m, and the fp64 kinetic energy of each 256-atom chunk
 //   k_md_sum       one workgroup per molecule: the chunk sums added in chunk order (only for molecules of more than one chunk)
 //   k_md_momentum, k_md_sum, k_md_sub_vcm   anihip_md_remove_drift: sum m v and sum m per chunk, per molecule, then v -= v_cm
+//   k_md_constrain<mode, atoms, constraints>   one thread per cluster of bond-length constraints (SHAKE / RATTLE in fp64, the cluster staged in LDS):
+//                  the drift, the kick or the velocity projection alone of the atoms that clusters own (active == 2), which
+//                  k_md_drift and the kick of k_md_kick skip
 //
 // Positions are pairs of floats, coords + coords_lo: every `x +=` is a two-sum, so a step far below one ulp of the coordinate
 // is not lost, and coords (what the engine reads) is the fp32 nearest to the pair.  The noise xi is a pure function of (seed,
@@ -95,6 +98,7 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_drift(MdArgs a)
         v[0] = v[1] = v[2] = 0.f;
         return;
     }
+    if (a.active[at] == ANIHIP_MD_ATOM_CLUSTER) return;   // moved by k_md_constrain
     const float im = a.inv_mass[at], kick = a.hdt * im;
     float *x = a.coords + 3 * at, *lo = a.coords_lo + 3 * at;
     const float *f = a.forces + 3 * at;
@@ -161,7 +165,10 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_kick(MdArgs a)
     if (i < a.A) {
         const int64_t at = c * a.A + i;
         float *v = a.vel + 3 * at;
-        if (a.active[at]) {
+        if (a.active[at] == ANIHIP_MD_ATOM_CLUSTER) {   // kicked and projected by k_md_constrain, which ran first
+            const float vx = v[0], vy = v[1], vz = v[2];
+            ke[0] = 0.5 * (double)a.mass[at] * ((double)vx * vx + (double)vy * vy + (double)vz * vz);
+        } else if (a.active[at]) {
             const float m = a.mass[at], kick = a.hdt * (float)(ANIHIP_MD_ACC_UNIT / (double)m);
             const float *f = a.forces + 3 * at;
             const float vx = v[0] + kick * f[0], vy = v[1] + kick * f[1], vz = v[2] + kick * f[2];
@@ -215,6 +222,198 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_sub_vcm(MdArgs a)
     float *v = a.vel + 3 * (c * a.A + i);
 #pragma unroll
     for (int k = 0; k < 3; ++k) v[k] = (float)((double)v[k] - p[k] / p[3]);
+}
+
+// ---- bond-length constraints (include/anihip.h has the definition) ---------------------------------------------------------
+// One thread per cluster, MDC_BLOCK clusters per workgroup.  The constraints address the atoms of their cluster by slots known
+// only at run time, and an array of a thread indexed that way would live in scratch memory: the cluster is staged in LDS
+// instead, [row][thread] with the thread fastest, so that the threads of a wave never share a bank whatever slots they read.
+
+constexpr int MDC_BLOCK = 64;
+constexpr int MDC_NA = ANIHIP_MD_CLUSTER_ATOMS, MDC_NB = ANIHIP_MD_CLUSTER_BONDS;
+constexpr int MDC_SMALL = 4;   // a second instance for tables of clusters of at most 4 atoms and 4 constraints (rigid waters, XH3)
+enum { MDC_DRIFT = 0, MDC_KICK = 1, MDC_PROJECT = 2 };
+
+struct MdCluster {   // the rows of one thread
+    double (*x)[MDC_BLOCK], (*ref)[MDC_BLOCK], (*v)[MDC_BLOCK], (*w)[MDC_BLOCK], (*d2)[MDC_BLOCK];
+    int (*bond)[MDC_BLOCK];   // a | b << 8
+    int t, n, nb;
+    double tol;
+    int max_it;
+};
+
+// SHAKE: x holds the unconstrained positions, ref the positions the move started from (the correction directions).  Gauss-
+// Seidel in the stored constraint order; returns the number of sweeps that corrected a constraint (max_it: not converged).
+__device__ __forceinline__ int mdc_shake(const MdCluster &q)
+{
+    const int t = q.t;
+    int it = 0;
+    for (; it < q.max_it; ++it) {
+        bool moved = false;
+        for (int k = 0; k < q.nb; ++k) {
+            const int ab = q.bond[k][t], a = 3 * (ab & 255), b = 3 * (ab >> 8);
+            const double sx = q.x[a][t] - q.x[b][t], sy = q.x[a + 1][t] - q.x[b + 1][t], sz = q.x[a + 2][t] - q.x[b + 2][t];
+            const double d2 = q.d2[k][t], diff = sx * sx + sy * sy + sz * sz - d2;
+            if (fabs(diff) <= 2.0 * q.tol * d2) continue;   // (a NaN fails this test and is corrected until max_it)
+            moved = true;
+            const double rx = q.ref[a][t] - q.ref[b][t], ry = q.ref[a + 1][t] - q.ref[b + 1][t],
+                         rz = q.ref[a + 2][t] - q.ref[b + 2][t];
+            const double wa = q.w[a / 3][t], wb = q.w[b / 3][t];
+            const double g = diff / (2.0 * (wa + wb) * (sx * rx + sy * ry + sz * rz));
+            q.x[a][t] -= wa * g * rx, q.x[a + 1][t] -= wa * g * ry, q.x[a + 2][t] -= wa * g * rz;
+            q.x[b][t] += wb * g * rx, q.x[b + 1][t] += wb * g * ry, q.x[b + 2][t] += wb * g * rz;
+        }
+        if (!moved) break;
+    }
+    return it;
+}
+
+// move(x, v, h): x' = x + h v + W J(x)^T lambda on the constraint manifold, v' = (x' - x) / h; ref = x' afterwards
+__device__ __forceinline__ int mdc_move(const MdCluster &q, double h)
+{
+    const int t = q.t;
+    for (int r = 0; r < 3 * q.n; ++r) q.x[r][t] += h * q.v[r][t];
+    const int it = mdc_shake(q);
+    const double ih = 1.0 / h;
+    for (int r = 0; r < 3 * q.n; ++r) {
+        const double x1 = q.x[r][t];
+        q.v[r][t] = (x1 - q.ref[r][t]) * ih;
+        q.ref[r][t] = x1;
+    }
+    return it;
+}
+
+// project_v(x, v): v' = v - W J^T mu with r . (v'_a - v'_b) = 0 (RATTLE's velocity stage), Gauss-Seidel; a constraint is
+// converged at |r . dv| <= tol d v_scale, v_scale the largest |v| component of the cluster when the projection starts
+__device__ __forceinline__ int mdc_project(const MdCluster &q)
+{
+    const int t = q.t;
+    double vs = 0.0;
+    for (int r = 0; r < 3 * q.n; ++r) vs = fmax(vs, fabs(q.v[r][t]));
+    int it = 0;
+    for (; it < q.max_it; ++it) {
+        bool moved = false;
+        for (int k = 0; k < q.nb; ++k) {
+            const int ab = q.bond[k][t], a = 3 * (ab & 255), b = 3 * (ab >> 8);
+            const double rx = q.x[a][t] - q.x[b][t], ry = q.x[a + 1][t] - q.x[b + 1][t], rz = q.x[a + 2][t] - q.x[b + 2][t];
+            const double rv = rx * (q.v[a][t] - q.v[b][t]) + ry * (q.v[a + 1][t] - q.v[b + 1][t])
+                            + rz * (q.v[a + 2][t] - q.v[b + 2][t]);
+            if (fabs(rv) <= q.tol * sqrt(q.d2[k][t]) * vs) continue;
+            moved = true;
+            const double wa = q.w[a / 3][t], wb = q.w[b / 3][t];
+            const double g = rv / ((wa + wb) * (rx * rx + ry * ry + rz * rz));
+            q.v[a][t] -= wa * g * rx, q.v[a + 1][t] -= wa * g * ry, q.v[a + 2][t] -= wa * g * rz;
+            q.v[b][t] += wb * g * rx, q.v[b + 1][t] += wb * g * ry, q.v[b + 2][t] += wb * g * rz;
+        }
+        if (!moved) break;
+    }
+    return it;
+}
+
+// NA, NB: the most atoms and constraints a cluster of this launch may have (the tables keep their strides of 8 and 12): the
+// LDS of a workgroup, and with it the workgroups a CU holds, follows the clusters that are there
+template <int MODE, int NA, int NB>
+__global__ __launch_bounds__(MDC_BLOCK) void k_md_constrain(MdArgs a, anihip_md_clusters cl, int64_t n_atoms)
+{
+    __shared__ double sx[3 * NA][MDC_BLOCK], sv[3 * NA][MDC_BLOCK], sw[NA][MDC_BLOCK], sd2[NB][MDC_BLOCK];
+    __shared__ double sref[MODE == MDC_DRIFT ? 3 * NA : 1][MDC_BLOCK];
+    __shared__ int sbond[NB][MDC_BLOCK], sat[NA][MDC_BLOCK];
+    const int t = threadIdx.x;
+    const int64_t c = (int64_t)blockIdx.x * MDC_BLOCK + t;
+    if (c >= cl.n_clusters) return;   // (no barrier below: a thread reads only the LDS column it wrote)
+    MdCluster q = {sx, sref, sv, sw, sd2, sbond, t, cl.count[2 * c], cl.count[2 * c + 1], cl.tolerance, cl.max_iterations};
+    int32_t *iters = cl.iterations + 2 * c + (MODE == MDC_DRIFT ? 0 : 1);
+    // The tables and then the atoms are read by loops of constant length into registers, the slots past the cluster's own
+    // reading slot 0 again: every load of a phase is in flight at once, where a loop over the cluster's own length would wait
+    // for them one by one (a single wave per workgroup has little else to hide the latency with).
+    // A table that does not hold what the header asks for moves nothing and reports max_iterations.
+    bool ok = q.n >= 2 && q.n <= NA && q.nb >= 1 && q.nb <= NB;
+    int64_t g[NA];
+    double w[NA];
+#pragma unroll
+    for (int s = 0; s < NA; ++s) {
+        g[s] = cl.atoms[MDC_NA * c + s];
+        w[s] = cl.w[MDC_NA * c + s];
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const int ia = cl.bonds[2 * (MDC_NB * c + k)], ib = cl.bonds[2 * (MDC_NB * c + k) + 1];
+        ok = ok && (k >= q.nb || (ia < q.n && ib < q.n && ia != ib));
+        sbond[k][t] = ia | ib << 8;
+        sd2[k][t] = cl.d2[MDC_NB * c + k];
+    }
+#pragma unroll
+    for (int s = 0; s < NA; ++s) {
+        ok = ok && (s >= q.n || (g[s] >= 0 && g[s] < n_atoms));
+        if (s >= q.n) g[s] = g[0];
+    }
+    if (!ok) {
+        *iters = cl.max_iterations;
+        return;
+    }
+    const double hdt = 0.5 * a.dtd;
+    float xh[NA][3], xl[NA][3], v0[NA][3], f0[NA][3];
+#pragma unroll
+    for (int s = 0; s < NA; ++s) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            xh[s][k] = a.coords[3 * g[s] + k], xl[s][k] = a.coords_lo[3 * g[s] + k], v0[s][k] = a.vel[3 * g[s] + k];
+            f0[s][k] = MODE != MDC_PROJECT ? a.forces[3 * g[s] + k] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NA; ++s) {
+        if (s >= q.n) break;
+        sw[s][t] = w[s];
+        sat[s][t] = (int)g[s];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double x = (double)xh[s][k] + (double)xl[s][k];   // exact
+            sx[3 * s + k][t] = x;
+            if (MODE == MDC_DRIFT) sref[3 * s + k][t] = x;
+            // B; a fixed anchor stays at rest
+            sv[3 * s + k][t] = w[s] != 0.0 ? (double)v0[s][k] + hdt * (double)f0[s][k] * w[s] : 0.0;
+        }
+    }
+    int it;
+    if (MODE == MDC_DRIFT) {
+        if (a.langevin) {
+            it = mdc_move(q, hdt);
+            const int64_t mol = g[0] / a.A;   // (a cluster lies in one molecule)
+            const double gdt = (double)a.friction[mol] * a.dtd, c1 = exp(-gdt);
+            const double s2 = (double)a.kT[mol] * -expm1(-2.0 * gdt);
+            const uint32_t replica = md_replica(a, mol);
+            for (int s = 0; s < q.n; ++s) {   // O, with the noise of the atom's own index
+                const double w = sw[s][t];
+                if (w == 0.0) continue;
+                float xi[3];
+                md_normals(a, (uint32_t)(sat[s][t] - mol * a.A), replica, xi);
+                const double sigma = sqrt(s2 * w);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) sv[3 * s + k][t] = c1 * sv[3 * s + k][t] + sigma * (double)xi[k];
+            }
+            it = max(it, mdc_move(q, hdt));
+        } else {
+            it = mdc_move(q, a.dtd);
+        }
+    } else {
+        it = mdc_project(q);
+    }
+    *iters = it;
+    for (int s = 0; s < q.n; ++s) {
+        if (sw[s][t] == 0.0) continue;   // a fixed anchor is never written
+        const int64_t at = sat[s][t];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            a.vel[3 * at + k] = (float)sv[3 * s + k][t];
+            if (MODE == MDC_DRIFT) {
+                const double x = sx[3 * s + k][t];
+                const float hi = (float)x;
+                a.coords[3 * at + k] = hi;
+                a.coords_lo[3 * at + k] = (float)(x - (double)hi);
+            }
+        }
+    }
 }
 
 static int md_args(const anihip_md_params *params, MdArgs &a)
@@ -328,4 +527,67 @@ extern "C" int anihip_md_remove_drift(void *stream, const anihip_md_params *para
     hipLaunchKernelGGL(k_md_sub_vcm, md_grid(params, a), dim3(MD_BLOCK), 0, s, a);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+static int md_clusters(const anihip_md_clusters *clusters)
+{
+    ANIHIP_REQUIRE(clusters, "null pointer argument");
+    const anihip_md_clusters &q = *clusters;
+    ANIHIP_REQUIRE(q.n_clusters >= 0 && q.n_clusters < ((int64_t)1 << 31) * MDC_BLOCK, "n_clusters out of range");
+    ANIHIP_REQUIRE(q.n_clusters == 0 || (q.atoms && q.count && q.bonds && q.w && q.d2 && q.iterations),
+                   "null pointer in the cluster tables");
+    ANIHIP_REQUIRE(q.tolerance > 0.0 && q.max_iterations >= 1, "tolerance must be > 0 and max_iterations >= 1");
+    ANIHIP_REQUIRE(q.max_atoms >= 0 && q.max_bonds >= 0, "max_atoms and max_bonds must be >= 0");
+    return 0;
+}
+
+template <int MODE>
+static int md_constrain(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters, MdArgs &a)
+{
+    if (int rc = md_clusters(clusters)) return rc;
+    if (clusters->n_clusters == 0) return 0;
+    const unsigned grid = (unsigned)((clusters->n_clusters + MDC_BLOCK - 1) / MDC_BLOCK);
+    const int64_t n_atoms = (int64_t)params->n_mol * a.A;
+    // (max_atoms = 0: not known; a cluster larger than the launch allows moves nothing and reports max_iterations)
+    if (clusters->max_atoms >= 2 && clusters->max_atoms <= MDC_SMALL && clusters->max_bonds >= 1 && clusters->max_bonds <= MDC_SMALL)
+        hipLaunchKernelGGL((k_md_constrain<MODE, MDC_SMALL, MDC_SMALL>), dim3(grid), dim3(MDC_BLOCK), 0, (hipStream_t)stream, a,
+                           *clusters, n_atoms);
+    else
+        hipLaunchKernelGGL((k_md_constrain<MODE, MDC_NA, MDC_NB>), dim3(grid), dim3(MDC_BLOCK), 0, (hipStream_t)stream, a,
+                           *clusters, n_atoms);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_md_constrain_drift(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                                         const float *kT, const float *friction, const int64_t *replica_ids, float *coords,
+                                         float *coords_lo, float *velocities, const float *forces)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(coords && coords_lo && velocities && forces, "null pointer argument");
+    ANIHIP_REQUIRE(!a.langevin || (kT && friction), "Langevin dynamics needs kT and friction");
+    a.kT = kT, a.friction = friction, a.replica_ids = replica_ids;
+    a.coords = coords, a.coords_lo = coords_lo, a.vel = velocities, a.forces = forces;
+    return md_constrain<MDC_DRIFT>(stream, params, clusters, a);
+}
+
+extern "C" int anihip_md_constrain_kick(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                                        const float *coords, const float *coords_lo, float *velocities, const float *forces)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(coords && coords_lo && velocities && forces, "null pointer argument");
+    a.coords = const_cast<float *>(coords), a.coords_lo = const_cast<float *>(coords_lo), a.vel = velocities, a.forces = forces;
+    return md_constrain<MDC_KICK>(stream, params, clusters, a);
+}
+
+extern "C" int anihip_md_project_velocities(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                                            const float *coords, const float *coords_lo, float *velocities)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(coords && coords_lo && velocities, "null pointer argument");
+    a.coords = const_cast<float *>(coords), a.coords_lo = const_cast<float *>(coords_lo), a.vel = velocities;
+    return md_constrain<MDC_PROJECT>(stream, params, clusters, a);
 }

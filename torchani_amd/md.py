@@ -10,6 +10,8 @@ steps (VerletCellList, neighbors.py:759-884).
 elementwise updates.  ``BatchedDynamics`` keeps the state on the device and integrates in libanihip (csrc/md.hip): two or
 three launches around the force evaluation, no host synchronization in a step, a temperature and a friction per molecule,
 fixed atoms, noise that is a pure function of (seed, step, replica id, atom) and coordinates kept as pairs of floats.
+Bond-length constraints (``BondConstraints``, ``hydrogen_constraints``: SHAKE / RATTLE per cluster of coupled constraints) add
+one launch to each half of the step.
 """
 from __future__ import annotations
 
@@ -122,6 +124,214 @@ def _per_molecule(value, name: str, n_mol: int) -> Tensor:
     return t
 
 
+# ---- bond-length constraints: the host side ---------------------------------------------------------------------------------
+
+class BondConstraints:
+    """Bond-length constraints of a batch: ``pairs`` int64 [C, K, 2], atom indices within each molecule, padded with (-1, -1);
+    ``lengths`` [C, K] in Angstrom, or None for the distances in the initial coordinates."""
+
+    def __init__(self, pairs: Tensor, lengths: tp.Optional[Tensor] = None) -> None:
+        if pairs.dim() != 3 or pairs.shape[2] != 2 or pairs.dtype != torch.int64:
+            raise ValueError("pairs must be an int64 tensor of shape [C, K, 2]")
+        if lengths is not None and tuple(lengths.shape) != tuple(pairs.shape[:2]):
+            raise ValueError(f"lengths must have shape {tuple(pairs.shape[:2])}, got {tuple(lengths.shape)}")
+        self.pairs = pairs
+        self.lengths = None if lengths is None else lengths.to(torch.float64)
+
+    def counts(self) -> Tensor:
+        """Constraints per molecule, int64 [C]."""
+        return (self.pairs[..., 0] >= 0).sum(dim=1)
+
+
+class ConstraintClusters(tp.NamedTuple):
+    """The cluster tables of include/anihip.h (host tensors) and what the integrator derives from them."""
+    atoms: Tensor          # int32 [Q, 8]: global atom index c A + i of each slot in ascending order, -1 past the cluster
+    count: Tensor          # int32 [Q, 2]: atoms and constraints of the cluster
+    bonds: Tensor          # uint8 [Q, 12, 2]: slots (a, b) of each constraint, in the order of ``pairs``
+    d2: Tensor             # float64 [Q, 12]: squared lengths
+    w: Tensor              # float64 [Q, 8]: inv_mass of each slot, 0 for a fixed atom
+    molecule: Tensor       # int64 [Q]
+    per_molecule: Tensor   # int64 [C]: constraints of each molecule
+    owned: Tensor          # bool [C, A]: the active atoms that clusters move
+
+
+def _ranks(group: Tensor, n_groups: int) -> tp.Tuple[Tensor, Tensor]:
+    """The position of every element within its group, in the order given, and the group sizes."""
+    size = torch.bincount(group, minlength=n_groups)
+    order = torch.argsort(group, stable=True)
+    rank = torch.empty_like(group)
+    rank[order] = torch.arange(group.numel()) - (torch.cumsum(size, 0) - size)[group[order]]
+    return rank, size
+
+
+def build_constraint_clusters(species: Tensor, pairs: Tensor, lengths: Tensor, fixed: tp.Optional[Tensor] = None,
+                              inv_mass: tp.Optional[Tensor] = None) -> ConstraintClusters:
+    """Group the constraints ``pairs`` [C, K, 2] (padded with -1) of lengths [C, K] into clusters, the connected components
+    of the constraint graph, and lay out the tables of include/anihip.h.  Pure host torch; the tensors may live anywhere.
+
+    Clusters are ordered by their smallest atom, slots by atom index, constraints as in ``pairs``.  w = inv_mass [C, A] (1 if
+    None) of an active atom and 0 of a fixed one.  Raises ValueError for a padding atom, a pair of two fixed atoms, a repeated
+    pair, a cluster of more than 8 atoms or 12 constraints, and one of n atoms with more than 3n - 6 constraints (1 for n = 2,
+    3 for n = 3), which no geometry satisfies independently."""
+    NA, NB = _lib.MD_CLUSTER_ATOMS, _lib.MD_CLUSTER_BONDS
+    species, pairs = species.cpu(), pairs.cpu().to(torch.int64)
+    if species.dim() != 2 or pairs.dim() != 3 or pairs.shape[0] != species.shape[0] or pairs.shape[2] != 2:
+        raise ValueError("expected species [C, A] and pairs [C, K, 2]")
+    Cn, A = species.shape
+    if tuple(lengths.shape) != tuple(pairs.shape[:2]):
+        raise ValueError(f"lengths must have shape {tuple(pairs.shape[:2])}, got {tuple(lengths.shape)}")
+    lengths = lengths.cpu().to(torch.float64)
+    real = species >= 0
+    fx = torch.zeros_like(real) if fixed is None else fixed.cpu().to(torch.bool)
+    active = real & ~fx
+    if bool(((pairs < 0).any(dim=-1) & ~(pairs == -1).all(dim=-1)).any()):
+        raise ValueError("pairs are padded with (-1, -1): a pair with one negative index")
+    mol, k = (pairs[..., 0] >= 0).nonzero(as_tuple=True)
+    i, j, d = pairs[mol, k, 0], pairs[mol, k, 1], lengths[mol, k]
+
+    def where(bad: Tensor) -> str:
+        b = int(bad.nonzero()[0])
+        return f"molecule {int(mol[b])}, pair {int(k[b])} = ({int(i[b])}, {int(j[b])})"
+
+    bad = (i >= A) | (j >= A) | (i == j)
+    if bool(bad.any()):
+        raise ValueError(f"a constraint needs two different atoms below {A}: {where(bad)}")
+    bad = ~(real[mol, i] & real[mol, j])
+    if bool(bad.any()):
+        raise ValueError(f"constraint on a padding atom: {where(bad)}")
+    bad = ~(active[mol, i] | active[mol, j])
+    if bool(bad.any()):
+        raise ValueError(f"constraint between two fixed atoms: {where(bad)}")
+    bad = ~(torch.isfinite(d) & (d > 0))
+    if bool(bad.any()):
+        raise ValueError(f"constraint lengths must be > 0: {where(bad)}")
+    N = Cn * A
+    gi, gj = mol * A + i, mol * A + j
+    key = torch.minimum(gi, gj) * N + torch.maximum(gi, gj)
+    if torch.unique(key).numel() != key.numel():
+        first = {}
+        for b, kk in enumerate(key.tolist()):
+            if kk in first:
+                bad = torch.zeros_like(key, dtype=torch.bool)
+                bad[b] = True
+                raise ValueError(f"constraint given twice: {where(bad)}")
+            first[kk] = b
+    # connected components by passing the smallest label along the constraints: a component of at most 8 atoms has a
+    # diameter of at most 7, so labels still moving in round 8 belong to a larger one
+    label = torch.arange(N)
+    for _ in range(NA):
+        low = torch.minimum(label[gi], label[gj])
+        new = label.scatter_reduce(0, gi, low, "amin").scatter_reduce(0, gj, low, "amin")
+        moved = new != label
+        label = new
+        if not bool(moved.any()):
+            break
+    else:
+        at = int(moved.nonzero()[0])
+        raise ValueError(f"a cluster of coupled constraints has more than {NA} atoms (molecule {at // A}, around atom {at % A})")
+    nodes = torch.unique(torch.cat([gi, gj]))
+    roots, q_node = torch.unique(label[nodes], return_inverse=True)
+    Q = roots.numel()
+    slot, n_atoms = _ranks(q_node, Q)
+    if Q and int(n_atoms.max()) > NA:
+        q = int(n_atoms.argmax())
+        raise ValueError(f"a cluster of coupled constraints has more than {NA} atoms "
+                         f"(molecule {int(roots[q]) // A}, around atom {int(roots[q]) % A}: {int(n_atoms[q])})")
+    q_of, slot_of = torch.full((N,), -1, dtype=torch.int64), torch.full((N,), -1, dtype=torch.int64)
+    q_of[nodes], slot_of[nodes] = q_node, slot
+    qb = q_of[gi]
+    bslot, n_bonds = _ranks(qb, Q)
+    limit = torch.where(n_atoms == 2, torch.ones_like(n_atoms), 3 * n_atoms - 6)
+    for bad, what in ((n_bonds > NB, f"more than {NB} constraints"), (n_bonds > limit, "more constraints than 3n - 6 (1 for n = 2)")):
+        if bool(bad.any()):
+            q = int(bad.nonzero()[0])
+            raise ValueError(f"the cluster of molecule {int(roots[q]) // A} with smallest atom {int(roots[q]) % A} has {what}: "
+                             f"{int(n_atoms[q])} atoms, {int(n_bonds[q])} constraints")
+    atoms = torch.full((Q, NA), -1, dtype=torch.int32)
+    atoms[q_node, slot] = nodes.to(torch.int32)
+    bonds = torch.zeros((Q, NB, 2), dtype=torch.uint8)
+    bonds[qb, bslot, 0], bonds[qb, bslot, 1] = slot_of[gi].to(torch.uint8), slot_of[gj].to(torch.uint8)
+    d2 = torch.zeros((Q, NB), dtype=torch.float64)
+    d2[qb, bslot] = d * d
+    w_atom = torch.ones((Cn, A), dtype=torch.float64) if inv_mass is None else inv_mass.cpu().to(torch.float64)
+    w_atom = torch.where(active, w_atom, torch.zeros_like(w_atom)).reshape(-1)
+    w = torch.zeros((Q, NA), dtype=torch.float64)
+    w[q_node, slot] = w_atom[nodes]
+    owned = torch.zeros(N, dtype=torch.bool)
+    owned[nodes] = True
+    return ConstraintClusters(atoms, torch.stack([n_atoms, n_bonds], dim=1).to(torch.int32), bonds, d2, w, roots // A,
+                              torch.bincount(mol, minlength=Cn), owned.view(Cn, A) & active)
+
+
+def hydrogen_constraints(species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None,
+                         max_bond: float = 1.25, rigid_water: bool = False, *, hydrogen: int = 1,
+                         oxygen: int = 8) -> BondConstraints:
+    """X-H constraints from the geometry: every hydrogen is paired with its nearest heavy atom within ``max_bond`` Angstrom;
+    with ``rigid_water`` the H-H pair of every oxygen that holds exactly two such hydrogens and has no heavy atom within
+    1.3 ``max_bond`` is added, which makes the water rigid.  Lengths are the distances in ``coordinates``.
+
+    ``hydrogen`` and ``oxygen`` are the values of ``species`` that mark the two elements: atomic numbers by default, 0 and 3
+    for ANI-2x element indices.  With a cell the pairs of each system come from the engine's cell list (``aev.cell_list``,
+    minimum image); without one, from the distance matrix of each molecule.  The integrator takes the plain difference of the
+    unwrapped coordinates, so a bonded pair whose plain difference is not its minimum-image difference raises: unwrap the
+    molecule first.  Pairs are ordered X-H by hydrogen index, then H-H by oxygen index."""
+    if species.dim() != 2 or tuple(coordinates.shape) != (species.shape[0], species.shape[1], 3):
+        raise ValueError("expected species [C, A] and coordinates [C, A, 3]")
+    Cn, A = species.shape
+    reach = 1.3 * max_bond if rigid_water else max_bond
+    per_mol: tp.List[tp.Tuple[Tensor, Tensor]] = []
+    for c in range(Cn):
+        sp, x = species[c], coordinates[c].detach().to(torch.float64)
+        # candidate pairs (i, j), each once: their minimum-image distance and whether the plain difference is another
+        if cell is None:
+            dist = (x.unsqueeze(1) - x.unsqueeze(0)).norm(dim=-1)
+            real = sp >= 0
+            i, j = torch.triu(real.unsqueeze(1) & real.unsqueeze(0) & (dist <= reach), diagonal=1).nonzero(as_tuple=True)
+            dist = dist[i, j]
+            wrapped = torch.zeros_like(i, dtype=torch.bool)
+        else:
+            from .aev import cell_list
+
+            nb = cell_list(reach, species[c:c + 1], coordinates[c:c + 1], cell, pbc)
+            i, j, dist = nb.indices[0], nb.indices[1], nb.distances.to(torch.float64)
+            wrapped = ((x[i] - x[j]) - nb.diff_vectors.to(torch.float64)).abs().amax(dim=-1) > 1e-3
+        a, b = torch.cat([i, j]), torch.cat([j, i])   # both orientations
+        dist, wrapped = torch.cat([dist, dist]), torch.cat([wrapped, wrapped])
+        a_h, b_h = sp[a] == hydrogen, sp[b] == hydrogen
+        xh = a_h & ~b_h & (dist <= max_bond)
+        h, heavy, dh, wr = a[xh], b[xh], dist[xh], wrapped[xh]
+        # the nearest heavy atom of each hydrogen (the smallest index among equals)
+        best = torch.full((A,), float("inf"), dtype=torch.float64, device=x.device).scatter_reduce(0, h, dh, "amin")
+        near = dh == best[h]
+        h, heavy, wr = h[near], heavy[near], wr[near]
+        order = torch.argsort(h * A + heavy)
+        h, heavy, wr = h[order], heavy[order], wr[order]
+        first = torch.ones_like(h, dtype=torch.bool)
+        first[1:] = h[1:] != h[:-1]
+        h, heavy, wr = h[first], heavy[first], wr[first]
+        if bool(wr.any()):
+            bad = int(wr.nonzero()[0])
+            raise ValueError(f"system {c}: the bond between atoms {int(heavy[bad])} and {int(h[bad])} crosses the cell boundary "
+                             "(its plain difference is not its minimum-image difference); unwrap the molecule so that "
+                             "its atoms lie next to each other")
+        prs = torch.stack([heavy, h], dim=1)
+        if rigid_water:
+            n_h = torch.bincount(heavy, minlength=A)
+            n_heavy = torch.bincount(a[~a_h & ~b_h], minlength=A)
+            water = (sp == oxygen) & (n_h == 2) & (n_heavy == 0)
+            sel = water[heavy]   # (sorted by hydrogen: a stable sort by oxygen keeps each water's hydrogens in order)
+            hw = h[sel][torch.argsort(heavy[sel], stable=True)]
+            prs = torch.cat([prs, hw.view(hw.numel() // 2, 2)])
+        lens = (x[prs[:, 0]] - x[prs[:, 1]]).norm(dim=-1)
+        per_mol.append((prs.cpu(), lens.cpu()))
+    K = max(1, max(p.shape[0] for p, _ in per_mol))
+    pairs = torch.full((Cn, K, 2), -1, dtype=torch.int64)
+    lengths = torch.zeros((Cn, K), dtype=torch.float64)
+    for c, (p, l) in enumerate(per_mol):
+        pairs[c, :p.shape[0]], lengths[c, :p.shape[0]] = p, l
+    return BondConstraints(pairs, lengths)
+
+
 class BatchedDynamics:
     """NVE (velocity Verlet) or Langevin (BAOAB) dynamics of every molecule of species [C, A], coordinates [C, A, 3]
     (Angstrom, kept unwrapped), integrated on the device (csrc/md.hip; include/anihip.h has the exact definition).
@@ -132,6 +342,14 @@ class BatchedDynamics:
     [C] in 0 .. 2^32 - 1, the noise stream of each molecule (default: its batch index) -- a replica draws the same noise wherever it sits in
     the batch.  remove_drift: ``set_temperature`` removes each molecule's centre-of-mass velocity.
 
+    constraints: a ``BondConstraints`` (``hydrogen_constraints`` makes one) of bond lengths to hold, by SHAKE / RATTLE in a
+    geodesic BAOAB step (include/anihip.h): coupled constraints form clusters of at most 8 atoms and 12 constraints, the
+    difference of two atoms is the plain one of the unwrapped coordinates (no minimum image), and there are no angle
+    constraints.  Given ``lengths`` are imposed on the initial coordinates, and a bond more than 10 % off raises (a wrapped
+    molecule or a wrong index).  ``constraint_tolerance`` is the relative residual to converge to, ``constraint_max_iterations``
+    the sweeps allowed; ``run()`` raises when a cluster used them all.  ``temperatures()`` takes one degree of freedom off per
+    constraint.  None, or pairs that are all padding, leaves the trajectory bit-identical to the unconstrained one.
+
     Attributes: ``coordinates`` (fp32, updated in place; ``coordinates_lo`` is the residual of the two-float position),
     ``velocities`` (Angstrom / fs), ``forces`` and ``potential_energies`` at the coordinates, ``steps_done``.  ``step()`` never
     synchronizes with the host; ``run()`` reads the neighbor overflow status every ``check_every`` steps.
@@ -140,7 +358,8 @@ class BatchedDynamics:
     def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
                  dt: float = 0.5, masses: tp.Optional[Tensor] = None, temperature=None, friction=0.002,
                  fixed: tp.Optional[Tensor] = None, replica_ids: tp.Optional[Tensor] = None, seed: int = 0,
-                 remove_drift: bool = True) -> None:
+                 remove_drift: bool = True, constraints: tp.Optional[BondConstraints] = None,
+                 constraint_tolerance: float = 1e-8, constraint_max_iterations: int = 64) -> None:
         from .geomopt import ModelEvaluator
 
         if species.dim() != 2 or tuple(coordinates.shape) != (species.shape[0], species.shape[1], 3):
@@ -161,6 +380,10 @@ class BatchedDynamics:
             raise ValueError("replica_ids must be integers in 0 .. 2^32 - 1 (one Philox counter word)")
         if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 1 << 64:
             raise ValueError(f"seed must be an integer in 0 .. 2^64 - 1, got {seed}")
+        if constraints is not None and tuple(constraints.pairs.shape[:1]) != (Cn,):
+            raise ValueError(f"constraints must hold pairs of shape ({Cn}, K, 2), got {tuple(constraints.pairs.shape)}")
+        if not constraint_tolerance > 0 or constraint_max_iterations < 1:
+            raise ValueError("constraint_tolerance must be > 0 and constraint_max_iterations >= 1")
         if not (species.is_cuda and coordinates.is_cuda):
             raise ValueError("BatchedDynamics needs tensors on a ROCm device (no CPU fallback)")
         dev = coordinates.device
@@ -199,7 +422,68 @@ class BatchedDynamics:
         self._kinetic_stale = False
         self._mb_draws = 0
         self.steps_done = 0
+        self._clusters = None
+        if constraints is not None and bool((constraints.pairs >= 0).any()):
+            self._set_constraints(constraints, fixed, float(constraint_tolerance), int(constraint_max_iterations))
         self._evaluate()
+
+    def _set_constraints(self, constraints: BondConstraints, fixed: tp.Optional[Tensor], tolerance: float,
+                         max_iterations: int) -> None:
+        """Build the cluster tables, mark the atoms that clusters own, and put the coordinates on given lengths."""
+        from .engine import _stream
+
+        dev, (Cn, A) = self.coordinates.device, self.species.shape
+        pairs = constraints.pairs.cpu()
+        x = self.coordinates.double().cpu()
+        at = torch.arange(Cn).view(-1, 1)
+        dist = (x[at, pairs[..., 0].clamp(min=0)] - x[at, pairs[..., 1].clamp(min=0)]).norm(dim=-1)
+        lengths = dist if constraints.lengths is None else constraints.lengths.cpu()
+        cl = build_constraint_clusters(self.species, pairs, lengths, fixed, self._inv_mass)
+        off = ((dist / lengths - 1.0).abs() > 0.1) & (pairs[..., 0] >= 0)
+        if bool(off.any()):
+            c, k = (int(t) for t in off.nonzero()[0])
+            raise ValueError(f"molecule {c}: atoms {int(pairs[c, k, 0])} and {int(pairs[c, k, 1])} are {float(dist[c, k]):.3f} A "
+                             f"apart, more than 10 % off their constrained length {float(lengths[c, k]):.3f} A (a molecule "
+                             "wrapped across the cell, or a wrong index: the plain difference is taken, no minimum image)")
+        self._active[cl.owned.to(dev)] = _lib.MD_ATOM_CLUSTER
+        self.n_constraints = cl.per_molecule.to(dev)
+        self._dof = (self._dof - self.n_constraints).clamp(min=1)
+        self._dof_at_rest = (self._dof_at_rest - self.n_constraints).clamp(min=1)
+        self._cluster_tables = tuple(t.to(dev).contiguous() for t in (cl.atoms, cl.count, cl.bonds, cl.d2, cl.w))
+        self._cluster_host = cl
+        self.constraint_iterations = torch.zeros((cl.atoms.shape[0], 2), dtype=torch.int32, device=dev)
+        self._clusters = _lib.MdClusters(cl.atoms.shape[0], *(t.data_ptr() for t in self._cluster_tables),
+                                         self.constraint_iterations.data_ptr(), tolerance, max_iterations,
+                                         int(cl.count[:, 0].max()), int(cl.count[:, 1].max()), 0)
+        if constraints.lengths is not None:
+            # move(x, 0, .): SHAKE from rest along the bonds as they are; the velocity it leaves is discarded
+            params = _lib.MdParams(Cn, A, 0, 0, 1.0, 0, 0)
+            _lib.check(_lib.lib().anihip_md_constrain_drift(
+                _stream(), C.byref(params), C.byref(self._clusters), None, None, None, self.coordinates.data_ptr(),
+                self.coordinates_lo.data_ptr(), self.velocities.data_ptr(), torch.zeros_like(self.velocities).data_ptr()))
+            self.velocities.zero_()
+            self.raise_on_unconverged_constraints()
+
+    def _project_velocities(self) -> None:
+        from .engine import _stream
+
+        if self._clusters is not None:
+            _lib.check(_lib.lib().anihip_md_project_velocities(
+                _stream(), C.byref(self._params), C.byref(self._clusters), self.coordinates.data_ptr(),
+                self.coordinates_lo.data_ptr(), self.velocities.data_ptr()))
+
+    def raise_on_unconverged_constraints(self) -> None:
+        """Raise if a cluster used every iteration allowed in its last move or projection (one host synchronization)."""
+        if self._clusters is None:
+            return
+        worst, q = self.constraint_iterations.max(dim=1).values.max(dim=0)
+        if int(worst) >= self._clusters.max_iterations:
+            cl, q = self._cluster_host, int(q)
+            atoms = (cl.atoms[q, :int(cl.count[q, 0])] % self.species.shape[1]).tolist()
+            it = self.constraint_iterations[q].tolist()
+            raise RuntimeError(f"constraint cluster {q} (molecule {int(cl.molecule[q])}, atoms {atoms}) did not converge to "
+                               f"{self._clusters.tolerance:g} in {self._clusters.max_iterations} iterations (positions {it[0]}, "
+                               f"velocities {it[1]}): a smaller dt, or more iterations")
 
     def _evaluate(self) -> None:
         self.potential_energies, self.forces = self._model_eval(self.coordinates)
@@ -217,12 +501,21 @@ class BatchedDynamics:
             _stream(), C.byref(self._params), self._active.data_ptr(), self._inv_mass.data_ptr(), self._kT.data_ptr(),
             self.friction.data_ptr(), rid, self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(),
             self.velocities.data_ptr(), self.forces.data_ptr()))
+        if self._clusters is not None:
+            _lib.check(_lib.lib().anihip_md_constrain_drift(
+                _stream(), C.byref(self._params), C.byref(self._clusters), self._kT.data_ptr(), self.friction.data_ptr(), rid,
+                self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(), self.velocities.data_ptr(),
+                self.forces.data_ptr()))
         self.steps_done += 1
 
     def _kick(self) -> None:
         """Second half kick on the forces held, and the kinetic energies."""
         from .engine import _stream
 
+        if self._clusters is not None:   # (first: anihip_md_kick sums the kinetic energy of the projected velocities)
+            _lib.check(_lib.lib().anihip_md_constrain_kick(
+                _stream(), C.byref(self._params), C.byref(self._clusters), self.coordinates.data_ptr(),
+                self.coordinates_lo.data_ptr(), self.velocities.data_ptr(), self.forces.data_ptr()))
         _lib.check(_lib.lib().anihip_md_kick(
             _stream(), C.byref(self._params), self._active.data_ptr(), self.masses.data_ptr(), self.velocities.data_ptr(),
             self.forces.data_ptr(), self._kinetic.data_ptr(), self._workspace.data_ptr(), self._workspace.numel()))
@@ -239,13 +532,15 @@ class BatchedDynamics:
         self._model_eval.raise_on_overflow()
 
     def run(self, n_steps: int, check_every: int = 10) -> None:
-        """``n_steps`` steps; the host reads the neighbor overflow status every ``check_every`` steps and after the last."""
+        """``n_steps`` steps; the host reads the neighbor overflow status and the constraints' iteration counts every
+        ``check_every`` steps and after the last."""
         if n_steps < 0 or check_every < 1:
             raise ValueError("n_steps must be >= 0 and check_every >= 1")
         for k in range(n_steps):
             self.step()
             if (k + 1) % check_every == 0 or k + 1 == n_steps:
                 self.raise_on_overflow()
+                self.raise_on_unconverged_constraints()
 
     # ---- velocities ------------------------------------------------------------------------------------------------
     def noise(self, step: int) -> Tensor:
@@ -265,6 +560,7 @@ class BatchedDynamics:
         _lib.check(_lib.lib().anihip_md_remove_drift(
             _stream(), C.byref(self._params), self._active.data_ptr(), self.masses.data_ptr(), self.velocities.data_ptr(),
             self._workspace.data_ptr(), self._workspace.numel()))
+        self._project_velocities()
         self._kinetic_stale = True
         self._drift_removed = True
 
@@ -272,7 +568,8 @@ class BatchedDynamics:
         """Copy ``velocities`` [C, A, 3] (Angstrom / fs) in; padding and fixed atoms keep zero.  They are taken to carry a
         centre-of-mass velocity (``temperatures()`` counts every degree of freedom) until
         ``remove_center_of_mass_velocity()`` is called."""
-        self.velocities.copy_(velocities.to(self.velocities) * self._active.unsqueeze(-1))
+        self.velocities.copy_(velocities.to(self.velocities) * (self._active != 0).unsqueeze(-1))
+        self._project_velocities()
         self._kinetic_stale = True
         self._drift_removed = False
 
@@ -281,7 +578,7 @@ class BatchedDynamics:
         dynamics at step words of their own (the top bit set, then a draw counter); then the drift is removed if
         ``remove_drift`` is on.  The thermostat's ``temperature`` is left alone."""
         kelvin = _per_molecule(kelvin, "temperature", self.species.shape[0]).to(self.coordinates.device)
-        sigma = torch.sqrt((KB_HARTREE * kelvin).view(-1, 1) * self._inv_mass) * self._active
+        sigma = torch.sqrt((KB_HARTREE * kelvin).view(-1, 1) * self._inv_mass) * (self._active != 0)
         self.set_velocities(sigma.unsqueeze(-1) * self.noise(_MB_STEP | self._mb_draws))
         self._mb_draws += 1
         if self.remove_drift:
@@ -292,14 +589,14 @@ class BatchedDynamics:
         """fp64 [C]: what the last kick computed, or a sum over the velocities if they were set since."""
         if self._kinetic_stale:
             v2 = self.velocities.double().pow(2).sum(dim=-1)
-            return 0.5 * (self.masses.double() * self._active * v2).sum(dim=1) / ACC_UNIT
+            return 0.5 * (self.masses.double() * (self._active != 0) * v2).sum(dim=1) / ACC_UNIT
         return self._kinetic.clone()
 
     def total_energies(self) -> Tensor:
         return self.potential_energies + self.kinetic_energies()
 
     def temperatures(self) -> Tensor:
-        """2 KE / (dof k_B), dof = 3 (active atoms), less 3 where the centre-of-mass velocity has been removed
+        """2 KE / (dof k_B), dof = 3 (active atoms) less the molecule's constraints, less 3 where the centre-of-mass velocity has been removed
         (``set_temperature`` with ``remove_drift``, or ``remove_center_of_mass_velocity()``, since the velocities were last
         set) and the momentum is conserved (NVE, no fixed atom in the molecule)."""
         return 2.0 * self.kinetic_energies() / ((self._dof_at_rest if self._drift_removed else self._dof) * KB_HARTREE)
