@@ -79,8 +79,10 @@ typedef struct {
  * table = ShfR[32] | ShfA[16] | cos(ShfZ)[16] | sin(ShfZ)[16]  (trig evaluated in double on the
  * fp32-rounded ShfZ) | q_R ShfR[16] | q_A ShfA[16] | cos/2 [16] | sin/2 [16] with
  * q = sqrt(Eta log2 e)  (exp(-Eta x^2) = exp2(-(q x)^2): the kernels keep distances pre-scaled).  The caller uploads
- * it to the device.  For the 16 / 8 x 4 / 4 x 8 grids the upper halves of the q_A ShfA and cos/2 blocks (slots 104-111,
- * 120-127) carry the constants of the backward kernel's Gaussian recurrences (ANIHIP_AEV_REC_BWD). */
+ * it to the device.  For the 16 / 8 x 4 / 4 x 8 grids, slots those grids leave free carry the constants of the backward
+ * kernel's Gaussian recurrences (ANIHIP_AEV_REC_BWD; csrc/anihip_common.h TAB_RECR / TAB_RECA / TAB_RECAK): the upper
+ * half of the ShfR block (slots 16-25), the ninth slot of the q_A ShfA block (104), and the upper half of the sin/2
+ * block (136-143). */
 #define ANIHIP_AEV_TABLE_FLOATS 144
 int anihip_aev_table_pack(anihip_aev_params *p /* flags are set */, const float *ShfR, const float *ShfA,
                           const float *ShfZ, float *table_out /* host, ANIHIP_AEV_TABLE_FLOATS */);

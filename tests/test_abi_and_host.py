@@ -163,6 +163,30 @@ def test_aev_table_pack_recurrence_constants(lib):
     assert not e.params.flags & 2 and e.params.flags & 1   # (the forward's flag only looks at ShfA)
 
 
+def test_aev_table_layout_of_the_header_comment(lib):
+    """The table layout stated in include/anihip.h: anihip_aev_table_pack called directly on the ANI-2x shifts sets
+    ANIHIP_AEV_REC_BWD and puts the backward kernel's recurrence constants at slots 16 (2 D_R, first of 16..25), 104 (2 D_A) and
+    136 (K_1, first of 136..143), each computed here in fp64 from the fp32 shifts; slots 120..127 stay what the cos / 2 block
+    leaves there (nothing: zero)."""
+    from torchani_amd import _lib
+    from torchani_amd.constants import aev_constants_2x
+
+    c = aev_constants_2x()
+    p = _lib.AevParams(num_species=7, n_shf_r=16, n_shf_a=8, n_shf_z=4, Rcr=c.Rcr, Rca=c.Rca, EtaR=c.EtaR, EtaA=c.EtaA,
+                       Zeta=c.Zeta)
+    shfr, shfa, shfz = (np.asarray(v, dtype=np.float32) for v in (c.ShfR, c.ShfA, c.ShfZ))
+    t = np.zeros(_lib.TABLE_FLOATS, dtype=np.float32)
+    assert lib.anihip_aev_table_pack(ctypes.byref(p), shfr.ctypes.data, shfa.ctypes.data, shfz.ctypes.data, t.ctypes.data) == 0
+    assert p.flags & 2, "ANIHIP_AEV_REC_BWD"
+    log2e = np.float64(np.float32(1.4426950408889634))
+    qr, qa = np.sqrt(np.float64(np.float32(c.EtaR)) * log2e), np.sqrt(np.float64(np.float32(c.EtaA)) * log2e)
+    DR = qr * (np.float64(shfr[15]) - np.float64(shfr[0])) / 15
+    DA = qa * (np.float64(shfa[7]) - np.float64(shfa[0])) / 7
+    for slot, want in ((16, 2 * DR), (104, 2 * DA), (136, 2.0 ** -(DA * DA))):
+        assert abs(np.float64(t[slot]) - want) <= 2e-7 * abs(want), (slot, t[slot], want)
+    assert np.all(t[105:112] == 0) and np.all(t[120:128] == 0)
+
+
 def test_per_species_launch_rule_follows_the_measurements():
     """models.ANI._per_species_launches_pay prices "one fused launch per species, compile-time widths" against "one launch, tiles
     handed out by falling cost" in tiles per workgroup; the choices measured on the MI355X (water boxes 24 k ... 2.3 M atoms, the

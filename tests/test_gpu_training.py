@@ -12,6 +12,7 @@ import torch
 
 from _util import (FGRAD_NAMES, WGRAD_NAMES, fgrad_direction, load_fgrads, load_golden, oracle_networks, oracle_params,
                    seeded_state, wgrad_upstream)
+from _aev_cases import long_row_lattice
 from test_gpu_parity import report
 
 pytestmark = pytest.mark.gpu
@@ -579,15 +580,6 @@ def test_aev_jvp_entry_points_agree(dev, base):
         assert many.shape == (1, N, eng.L)
         assert one[lo:hi].abs().max().item() > 0
         assert torch.equal(one[lo:hi], many[0, lo:hi])
-
-
-def long_row_lattice():
-    """9 x 9 x 9 atoms on a cubic lattice of spacing 1.5 A, each coordinate jittered by +-0.1 A, the seven ANI-2x species
-    at random: an inner atom has about 170 neighbors inside the radial and 56 inside the angular cutoff."""
-    rs = np.random.RandomState(7)
-    k = np.arange(9) * 1.5
-    x = np.stack(np.meshgrid(k, k, k, indexing="ij"), axis=-1).reshape(-1, 3) + rs.uniform(-0.1, 0.1, (729, 3))
-    return rs.randint(0, 7, (1, 729)).astype(np.int64), x.astype(np.float32)[None]
 
 
 def test_aev_jvp_row_longer_than_two_waves(dev, oracle64):
