@@ -496,6 +496,33 @@ int anihip_md_constrain_kick(void *stream, const anihip_md_params *params, const
 int anihip_md_project_velocities(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
                                  const float *coords, const float *coords_lo, float *velocities);
 
+/* Isotropic stochastic cell rescaling (Bernetti and Bussi 2020) of the integrator above: a first-order barostat that samples
+ * the NPT ensemble from the virial alone, without trial energies or an accept / reject step.  Per molecule c, with
+ * eps = ln V and V = |det(cell_c)|, one move is
+ *   P_int = (2 K_c - tr W_c) / (3 V)
+ *   d eps = -(beta_T / tau_p) (P0_c - P_int) dt  +  sqrt(2 kT_c beta_T dt / (V tau_p)) xi_b
+ *   mu    = exp(d eps / 3)
+ *   x <- mu x,   v <- v / mu,   cell <- mu cell,   K_c <- K_c / mu^2
+ * all in fp64.  kinetic fp64 [C] (Hartree; what anihip_md_kick left, UPDATED), virial fp64 [C][9] (Hartree, dE/d strain of
+ * the last force evaluation, row-major), kT fp32 [C] (Hartree, the thermostat's), pressure fp64 [C] (P0, Hartree / Angstrom^3),
+ * beta_T the isothermal compressibility in Angstrom^3 / Hartree, tau_p the barostat time in fs.  By Ito's formula the equation
+ * in eps carries no kT / V term.  x is the pair coords + coords_lo: the sum is formed in fp64 (exactly), multiplied by mu and
+ * stored as coords = (float)x, coords_lo = (float)(x - coords).  cell64 fp64 [C][9] is the master copy of the cell (rows are the
+ * cell vectors), cell32 fp32 [C][9] = (float)cell64 is written for the neighbor builders.  scale fp64 [C] OUT: mu of this move.
+ * xi_b is the xi_x of anihip_md_noise, widened to fp64, at atom index 0 with the molecule's replica id (replica_ids may be
+ * NULL as above) and the step word ANIHIP_MD_BAROSTAT_STEP | params->step: drift steps stay below 2^62 and the Maxwell-
+ * Boltzmann draws of the Python layer have bit 63 set, so the three streams are disjoint.  Atoms with active != 0 are scaled;
+ * padding and fixed atoms are not touched.  The caller runs it between anihip_md_drift and the force evaluation with the
+ * params->step of that drift: it uses the virial of the previous evaluation and the kinetic energy of the previous kick, and
+ * the forces that anihip_md_kick then reads belong to the rescaled coordinates.  Requires dt, beta_T, tau_p > 0, the
+ * ANIHIP_MD_LANGEVIN flag (the noise needs kT) and step < 2^62.  Two launches, one thread per molecule and then one per atom;
+ * no atomics, no host synchronization, bit-identical run to run. */
+#define ANIHIP_MD_BAROSTAT_STEP (1ull << 62)
+int anihip_md_barostat(void *stream, const anihip_md_params *params, double beta_T, double tau_p, const uint8_t *active,
+                       const float *kT, const double *pressure, const int64_t *replica_ids, const double *virial,
+                       double *kinetic, double *cell64, float *cell32, float *coords, float *coords_lo, float *velocities,
+                       double *scale);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -6,6 +6,9 @@
     python tools/md_bench.py --integrator device --constraints none rigid-water --dt 2 ...
                                                                            the device integrator without and with bond-length
                                                                            constraints (md.hydrogen_constraints), alternating
+    python tools/md_bench.py --integrator device --langevin --barostat ...  NVT, NVT with the virial-carrying evaluation, and NPT
+                                                                           (stochastic cell rescaling), alternating: the cost of
+                                                                           the barostat split into the evaluation's and its own
 
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
@@ -38,7 +41,9 @@ def load_system(args, dev):
 
 
 def make_driver(kind, args, model, sp, x, cell, pbc, masses):
-    """kind: "host", "device", or "device+hydrogens" / "device+rigid-water" for the device integrator with constraints."""
+    """kind: "host", "device", "device+hydrogens" / "device+rigid-water" for the device integrator with constraints,
+    "device+virial" for NVT whose evaluations carry the virial, "device+npt" for the barostat."""
+    from torchani_amd.geomopt import ModelEvaluator
     from torchani_amd.md import BatchedDynamics, MolecularDynamics, hydrogen_constraints
 
     temperature = 300.0 if args.langevin else None
@@ -46,11 +51,19 @@ def make_driver(kind, args, model, sp, x, cell, pbc, masses):
         md = MolecularDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1)
     else:
         constraints = None
-        if "+" in kind:   # (species are ANI-2x element indices: H = 0, O = 3)
+        if kind.endswith(("hydrogens", "rigid-water")):   # (species are ANI-2x element indices: H = 0, O = 3)
             constraints = hydrogen_constraints(sp, x, cell, pbc, rigid_water=kind.endswith("rigid-water"), hydrogen=0, oxygen=3)
         md = BatchedDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1,
-                             constraints=constraints)
+                             constraints=constraints, pressure=1.0 if kind == "device+npt" else None,
+                             barostat_time=args.barostat_time)
+        if kind == "device+virial":   # the NVT step with the evaluation that the barostat needs, and nothing else of it
+            md._model_eval = ModelEvaluator(model, sp, cell, pbc, stress=True)
     md.set_temperature(300.0)
+    if kind == "device+npt":
+        # (the seed-0 weights are no physical potential: at 1 bar the box would run away and the step time with its density;
+        # by default the target is the pressure the box starts with)
+        md.pressure.copy_(md.pressures() if args.pressure is None else torch.full_like(md.pressure, args.pressure))
+        md.volume0 = md.volumes().item()
     return md
 
 
@@ -75,6 +88,11 @@ def main():
     ap.add_argument("--constraints", nargs="+", choices=("none", "hydrogens", "rigid-water"), default=["none"],
                     help="device integrator: X-H bonds (hydrogens) or whole waters (rigid-water) held rigid; several values are "
                          "timed against each other in one process")
+    ap.add_argument("--barostat", action="store_true",
+                    help="device integrator with --langevin: NVT, NVT with the virial-carrying evaluation and NPT timed against "
+                         "each other in one process")
+    ap.add_argument("--pressure", type=float, default=None, help="--barostat: target in bar (default: the initial pressure)")
+    ap.add_argument("--barostat-time", type=float, default=1000.0, help="--barostat: relaxation time, fs")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
@@ -94,6 +112,10 @@ def main():
             ap.error("--constraints needs the device integrator")
         kinds = tuple(k for k in kinds if k != "device") + tuple("device" if c == "none" else "device+" + c
                                                                  for c in args.constraints)
+    if args.barostat:
+        if kinds != ("device",) or not args.langevin or cell is None:
+            ap.error("--barostat needs --integrator device, --langevin and a periodic system, and no --constraints")
+        kinds = ("device", "device+virial", "device+npt")
     for nl in lists:
         drivers = {}
         for kind in kinds:   # (a model each: the automatic HIP graph of a small system belongs to one species tensor)
@@ -119,7 +141,10 @@ def main():
                 it = md.constraint_iterations.double().mean(dim=0).tolist()
                 extra += (f", {int(md.n_constraints.sum())} constraints in {md.constraint_iterations.shape[0]} clusters, mean "
                           f"iterations of the last step: positions {it[0]:.2f}, velocities {it[1]:.2f}")
-            print(f"{nl:17s} {kind:6s} {'langevin' if args.langevin else 'nve':8s} dt {args.dt:g} fs {n_atoms} atoms: "
+            if getattr(md, "barostat", False):
+                extra += (f", target {md.pressure.item():.4g} bar, P = {md.pressures().item():.4g} bar, V / V0 = "
+                          f"{md.volumes().item() / md.volume0:.5f}")
+            print(f"{nl:17s} {kind:13s} {'langevin' if args.langevin else 'nve':8s} dt {args.dt:g} fs {n_atoms} atoms: "
                   f"{np.median(t):.3f} ms/step{spread} = {n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M atom*steps/s, "
                   f"{args.dt / (np.median(t) * 1e-3):.0f} fs simulated per second, T = {md.temperatures().mean().item():.0f} K{extra}")
 

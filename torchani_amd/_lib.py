@@ -44,6 +44,7 @@ BLOCK_HESSIAN_BAD_INDEX, BLOCK_HESSIAN_NO_PARTNER, BLOCK_HESSIAN_NO_DIAGONAL = 1
 LBFGS_MAX_MEMORY = 256   # ANIHIP_LBFGS_MAX_MEMORY
 MD_LANGEVIN = 1   # ANIHIP_MD_LANGEVIN
 MD_ATOM_CLUSTER, MD_CLUSTER_ATOMS, MD_CLUSTER_BONDS = 2, 8, 12   # ANIHIP_MD_ATOM_CLUSTER, ANIHIP_MD_CLUSTER_*
+MD_BAROSTAT_STEP = 1 << 62   # ANIHIP_MD_BAROSTAT_STEP
 
 
 class AevParams(C.Structure):
@@ -280,8 +281,11 @@ def lib() -> C.CDLL:
     L.anihip_md_constrain_drift.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp, vp, vp, vp, vp]
     L.anihip_md_constrain_kick.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp, vp]
     L.anihip_md_project_velocities.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp]
+    L.anihip_md_barostat.argtypes = [vp, C.POINTER(MdParams), C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     vp, vp]
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
-                 "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities"):
+                 "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
+                 "anihip_md_barostat"):
         getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
@@ -314,7 +318,7 @@ EXPORTED_SYMBOLS = [
     "anihip_aev_jvp_strain_items", "anihip_aev_backward_second_strain_items", "anihip_pair_analytic_hvp_strain",
     "anihip_lbfgs_workspace_bytes", "anihip_lbfgs_step",
     "anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
-    "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
+    "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities", "anihip_md_barostat",
 ]
 
 

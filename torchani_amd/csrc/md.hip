@@ -6,6 +6,8 @@
 //   k_md_kick      one thread per atom: v += dt/2 f / m, and the fp64 kinetic energy of each 256-atom chunk
 //   k_md_sum       one workgroup per molecule: the chunk sums added in chunk order (only for molecules of more than one chunk)
 //   k_md_momentum, k_md_sum, k_md_sub_vcm   anihip_md_remove_drift: sum m v and sum m per chunk, per molecule, then v -= v_cm
+//   k_md_barostat_cell, k_md_barostat_scale   anihip_md_barostat (stochastic cell rescaling): one thread per molecule draws the
+//                  volume move and rescales the cell, then one thread per atom rescales positions and velocities, all in fp64
 //   k_md_constrain<mode, atoms, constraints>   one thread per cluster of bond-length constraints (SHAKE / RATTLE in fp64, the cluster staged in LDS):
 //                  the drift, the kick or the velocity projection alone of the atoms that clusters own (active == 2), which
 //                  k_md_drift and the kick of k_md_kick skip
@@ -416,6 +418,61 @@ __global__ __launch_bounds__(MDC_BLOCK) void k_md_constrain(MdArgs a, anihip_md_
     }
 }
 
+// ---- stochastic cell rescaling (include/anihip.h has the definition) -------------------------------------------------------
+// Two launches because the move of a molecule is one number that every atom of it needs: the first forms mu from the cell, the
+// kinetic energy and the virial as they are and rescales the cell; the second reads mu from `scale`.  (One launch would have
+// atoms read a cell that another workgroup is rewriting.)
+
+struct MdBarostat {
+    double beta_over_tau;   // beta_T / tau_p, Angstrom^3 / (Hartree fs)
+    const double *pressure, *virial;
+    double *kinetic, *cell64, *scale;
+    float *cell32;
+};
+
+__global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_cell(MdArgs a, MdBarostat b, int64_t n_mol)
+{
+    const int64_t c = (int64_t)blockIdx.x * MD_BLOCK + threadIdx.x;
+    if (c >= n_mol) return;
+    double h[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) h[k] = b.cell64[9 * c + k];
+    const double V = fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6])
+                          + h[2] * (h[3] * h[7] - h[4] * h[6]));
+    const double *W = b.virial + 9 * c;
+    const double K = b.kinetic[c], p_int = (2.0 * K - (W[0] + W[4] + W[8])) / (3.0 * V);
+    float xi[3];
+    md_normals(a, 0u, md_replica(a, c), xi);
+    const double rate = b.beta_over_tau * a.dtd;
+    const double deps = -rate * (b.pressure[c] - p_int) + sqrt(2.0 * (double)a.kT[c] * rate / V) * (double)xi[0];
+    const double mu = exp(deps / 3.0);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double hk = mu * h[k];
+        b.cell64[9 * c + k] = hk;
+        b.cell32[9 * c + k] = (float)hk;
+    }
+    b.kinetic[c] = K / (mu * mu);
+    b.scale[c] = mu;
+}
+
+__global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_scale(MdArgs a, const double *scale)
+{
+    const int64_t c = blockIdx.x / a.Gc, i = (blockIdx.x % a.Gc) * MD_BLOCK + threadIdx.x;
+    if (i >= a.A) return;
+    const int64_t at = c * a.A + i;
+    if (!a.active[at]) return;
+    const double mu = scale[c], inv_mu = 1.0 / mu;
+    float *x = a.coords + 3 * at, *lo = a.coords_lo + 3 * at, *v = a.vel + 3 * at;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double xk = mu * ((double)x[k] + (double)lo[k]);   // (the sum of the pair is exact in fp64)
+        const float hi = (float)xk;
+        x[k] = hi, lo[k] = (float)(xk - (double)hi);
+        v[k] = (float)((double)v[k] * inv_mu);
+    }
+}
+
 static int md_args(const anihip_md_params *params, MdArgs &a)
 {
     ANIHIP_REQUIRE(params, "null pointer argument");
@@ -525,6 +582,31 @@ extern "C" int anihip_md_remove_drift(void *stream, const anihip_md_params *para
         ANIHIP_CHECK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_md_sub_vcm, md_grid(params, a), dim3(MD_BLOCK), 0, s, a);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_md_barostat(void *stream, const anihip_md_params *params, double beta_T, double tau_p,
+                                  const uint8_t *active, const float *kT, const double *pressure, const int64_t *replica_ids,
+                                  const double *virial, double *kinetic, double *cell64, float *cell32, float *coords,
+                                  float *coords_lo, float *velocities, double *scale)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(beta_T > 0.0 && tau_p > 0.0, "beta_T and tau_p must be > 0");
+    ANIHIP_REQUIRE(a.langevin, "the barostat needs Langevin dynamics (ANIHIP_MD_LANGEVIN): its noise is scaled by kT");
+    ANIHIP_REQUIRE(params->step < ANIHIP_MD_BAROSTAT_STEP, "step must stay below 2^62");
+    ANIHIP_REQUIRE(active && kT && pressure && virial && kinetic && cell64 && cell32 && coords && coords_lo && velocities && scale,
+                   "null pointer argument");
+    a.step1 |= (uint32_t)(ANIHIP_MD_BAROSTAT_STEP >> 32);   // a stream of its own, apart from every drift's
+    a.active = active, a.kT = kT, a.replica_ids = replica_ids;
+    a.coords = coords, a.coords_lo = coords_lo, a.vel = velocities;
+    const MdBarostat b = {beta_T / tau_p, pressure, virial, kinetic, cell64, scale, cell32};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_md_barostat_cell, dim3((unsigned)((params->n_mol + MD_BLOCK - 1) / MD_BLOCK)), dim3(MD_BLOCK), 0, s, a, b,
+                       (int64_t)params->n_mol);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_md_barostat_scale, md_grid(params, a), dim3(MD_BLOCK), 0, s, a, (const double *)scale);
     ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -69,12 +69,17 @@ class ModelEvaluator:
     """Energies [C] (fp64) and forces [C, A, 3] (fp32) of a model at fp32 coordinates that the caller updates in place, queued
     on the stream without a host synchronization (GeometryOptimizer, md.BatchedDynamics).  The model is an ``ANI`` model
     (``energies_and_forces`` with ``check_overflow=False`` and the same species tensor at every call, so small systems replay
-    the automatic HIP graph) or a standalone pair potential, evaluated through its ``accumulate`` on its own neighbor rows."""
+    the automatic HIP graph) or a standalone pair potential, evaluated through its ``accumulate`` on its own neighbor rows.
 
-    def __init__(self, model, species: Tensor, cell: tp.Optional[Tensor], pbc) -> None:
+    ``stress=True`` also keeps ``virial`` (fp64 [3, 3], Hartree: dE/d strain of all atoms together) of every evaluation, from
+    ``energies_and_forces(stress=True)`` or the ``virial=`` argument of ``accumulate``.  An evaluation that carries the virial
+    is not replayed from the automatic HIP graph."""
+
+    def __init__(self, model, species: Tensor, cell: tp.Optional[Tensor], pbc, stress: bool = False) -> None:
         from .potentials import _Standalone
 
         self.model, self.species, self.cell = model, species, cell
+        self.stress, self.virial = bool(stress), None
         # (a host tuple once: a pbc tensor would cost a synchronization at every evaluation)
         self.pbc = pbc_tuple(pbc)
         self.standalone = isinstance(model, _Standalone)
@@ -88,10 +93,16 @@ class ModelEvaluator:
             rows = self.model._standalone_rows(self._species32, coordinates, self.cell, self.pbc)
             atomic = torch.zeros(Cn * A, dtype=torch.float32, device=coordinates.device)
             grad = torch.zeros((Cn * A, 3), dtype=torch.float32, device=coordinates.device)
-            self.model.accumulate(self._species32, rows, atomic, grad)
+            if self.stress:
+                self.virial = torch.zeros((3, 3), dtype=torch.float64, device=coordinates.device)
+            self.model.accumulate(self._species32, rows, atomic, grad, virial=self.virial)
             self._rows = rows
             return atomic.view(Cn, A).to(torch.float64).sum(dim=1), grad.neg_().view(Cn, A, 3)
-        out = self.model.energies_and_forces(self.species, coordinates, self.cell, self.pbc, check_overflow=False)
+        # (``stress`` is passed only when asked for: the default call is the one any model with this method takes)
+        kw = {"stress": True} if self.stress else {}
+        out = self.model.energies_and_forces(self.species, coordinates, self.cell, self.pbc, check_overflow=False, **kw)
+        if self.stress:
+            self.virial = out.virial
         return out.energies, out.forces.to(torch.float32).contiguous()
 
     def raise_on_overflow(self) -> None:

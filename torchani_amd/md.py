@@ -11,7 +11,8 @@ elementwise updates.  ``BatchedDynamics`` keeps the state on the device and inte
 three launches around the force evaluation, no host synchronization in a step, a temperature and a friction per molecule,
 fixed atoms, noise that is a pure function of (seed, step, replica id, atom) and coordinates kept as pairs of floats.
 Bond-length constraints (``BondConstraints``, ``hydrogen_constraints``: SHAKE / RATTLE per cluster of coupled constraints) add
-one launch to each half of the step.
+one launch to each half of the step.  ``pressure=`` adds an isotropic stochastic-cell-rescaling barostat (Bernetti and Bussi
+2020) between the drift and the force evaluation: two launches that rescale the cell, the positions and the velocities.
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ from . import _lib
 # CODATA 2018: 1 Ha = 4.3597447222071e-18 J, 1 amu = 1.66053906660e-27 kg  ->  (Ha / Angstrom) / amu in Angstrom / fs^2
 ACC_UNIT = 4.3597447222071e-18 / 1e-10 / 1.66053906660e-27 * 1e10 * 1e-30
 KB_HARTREE = 3.166811563e-6          # Boltzmann constant, Ha / K
+BAR_PER_HARTREE_ANGSTROM3 = 4.3597447222071e7   # 1 Ha / Angstrom^3 = 4.3597447222071e-18 J / 1e-30 m^3, in bar (1e5 Pa)
 ATOMIC_MASS = {1: 1.008, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998, 16: 32.06, 17: 35.45}   # amu
 
 
@@ -350,6 +352,19 @@ class BatchedDynamics:
     the sweeps allowed; ``run()`` raises when a cluster used them all.  ``temperatures()`` takes one degree of freedom off per
     constraint.  None, or pairs that are all padding, leaves the trajectory bit-identical to the unconstrained one.
 
+    pressure: None (the cell never changes), or the target pressure in bar (a number or a [1] tensor) of an isotropic
+    stochastic-cell-rescaling barostat (Bernetti and Bussi 2020; include/anihip.h has the exact move), with ``compressibility``
+    the isothermal compressibility in 1 / bar (default: water's) and ``barostat_time`` the relaxation time in fs.  ``step()``
+    becomes drift, barostat, evaluation, kick: the move uses the virial of the previous evaluation and the kinetic energy of
+    the previous kick, and the forces always belong to the rescaled coordinates.  It needs Langevin dynamics (its noise is
+    scaled by kT), one system (C = 1) in a cell periodic in all three directions, no fixed atoms and no constraints (the
+    virial of the constraint forces is not computed).  ``cell`` is then an fp32 clone that the dynamics owns and updates in
+    place, ``cell64`` its fp64 master, and ``pressure`` an fp64 [1] device tensor in bar that may be overwritten between
+    steps; ``volumes()`` and ``pressures()`` are the observables.  Every evaluation carries the virial (``stress=True``), which
+    turns off the automatic HIP graph of small systems; ``neighborlist="verlet_cell_list"`` compares the cell with the one of
+    its list on the host at every step, so it synchronizes and rebuilds whenever the cell has moved; a box that shrinks until
+    a neighbor row overflows is caught by the overflow check of ``run()``.
+
     Attributes: ``coordinates`` (fp32, updated in place; ``coordinates_lo`` is the residual of the two-float position),
     ``velocities`` (Angstrom / fs), ``forces`` and ``potential_energies`` at the coordinates, ``steps_done``.  ``step()`` never
     synchronizes with the host; ``run()`` reads the neighbor overflow status every ``check_every`` steps.
@@ -359,8 +374,10 @@ class BatchedDynamics:
                  dt: float = 0.5, masses: tp.Optional[Tensor] = None, temperature=None, friction=0.002,
                  fixed: tp.Optional[Tensor] = None, replica_ids: tp.Optional[Tensor] = None, seed: int = 0,
                  remove_drift: bool = True, constraints: tp.Optional[BondConstraints] = None,
-                 constraint_tolerance: float = 1e-8, constraint_max_iterations: int = 64) -> None:
+                 constraint_tolerance: float = 1e-8, constraint_max_iterations: int = 64, pressure=None,
+                 compressibility: float = 4.57e-5, barostat_time: float = 1000.0) -> None:
         from .geomopt import ModelEvaluator
+        from .utils import pbc_tuple
 
         if species.dim() != 2 or tuple(coordinates.shape) != (species.shape[0], species.shape[1], 3):
             raise ValueError("expected species [C, A] and coordinates [C, A, 3]")
@@ -384,10 +401,37 @@ class BatchedDynamics:
             raise ValueError(f"constraints must hold pairs of shape ({Cn}, K, 2), got {tuple(constraints.pairs.shape)}")
         if not constraint_tolerance > 0 or constraint_max_iterations < 1:
             raise ValueError("constraint_tolerance must be > 0 and constraint_max_iterations >= 1")
+        self.barostat = pressure is not None
+        if self.barostat:
+            if temperature is None:
+                raise ValueError("the barostat needs Langevin dynamics (its noise is scaled by kT): pass temperature, not NVE")
+            if Cn != 1:
+                raise ValueError(f"the barostat handles one system (C = 1: the engine takes one cell per batch), got C = {Cn}")
+            if cell is None or pbc is None or not all(pbc_tuple(pbc)):
+                raise ValueError("the barostat needs a cell that is periodic in all three directions")
+            if fixed is not None and bool(fixed.any()):
+                raise ValueError("the barostat cannot rescale a system with fixed atoms")
+            if constraints is not None and bool((constraints.pairs >= 0).any()):
+                raise ValueError("the barostat does not support constraints: the virial of the constraint forces is not computed")
+            if not compressibility > 0 or not barostat_time > 0:
+                raise ValueError("compressibility and barostat_time must be > 0")
+            pressure = torch.as_tensor(pressure, dtype=torch.float64)
+            if pressure.dim() == 0:
+                pressure = pressure.expand(Cn)
+            if tuple(pressure.shape) != (Cn,):
+                raise ValueError(f"pressure must be a number or a tensor of shape ({Cn},), got {tuple(pressure.shape)}")
         if not (species.is_cuda and coordinates.is_cuda):
             raise ValueError("BatchedDynamics needs tensors on a ROCm device (no CPU fallback)")
         dev = coordinates.device
-        self._model_eval = ModelEvaluator(model, species, cell, pbc)
+        if self.barostat:
+            self.cell64 = cell.detach().to(device=dev, dtype=torch.float64).clone().contiguous()
+            cell = self.cell64.to(torch.float32).contiguous()   # (owned: anihip_md_barostat rewrites it, the engine reads it)
+            self.pressure = pressure.to(dev).contiguous()
+            self._p0 = torch.empty_like(self.pressure)        # Hartree / Angstrom^3
+            self._beta_T = float(compressibility) * BAR_PER_HARTREE_ANGSTROM3   # Angstrom^3 / Hartree
+            self._tau_p = float(barostat_time)
+            self.barostat_scale = torch.ones(Cn, dtype=torch.float64, device=dev)   # mu of the last move
+        self._model_eval = ModelEvaluator(model, species, cell, pbc, stress=self.barostat)
         self.model, self.species, self.cell, self.pbc = model, species, cell, self._model_eval.pbc
         self.dt, self.seed, self.remove_drift = float(dt), int(seed), bool(remove_drift)
         self.coordinates = coordinates.detach().to(torch.float32).clone().contiguous()
@@ -521,9 +565,30 @@ class BatchedDynamics:
             self.forces.data_ptr(), self._kinetic.data_ptr(), self._workspace.data_ptr(), self._workspace.numel()))
         self._kinetic_stale = False
 
+    def _barostat(self) -> None:
+        """The volume move (anihip_md_barostat) on the virial and the kinetic energy held (``step()`` refreshes a stale one
+        before the drift), with the noise step of the drift before it: rescales cell64, cell, coordinates and velocities."""
+        from .engine import _stream
+
+        torch.div(self.pressure, BAR_PER_HARTREE_ANGSTROM3, out=self._p0)   # (every step: ``pressure`` is the user's to overwrite)
+        rid = None if self._replica_ids is None else self._replica_ids.data_ptr()
+        _lib.check(_lib.lib().anihip_md_barostat(
+            _stream(), C.byref(self._params), self._beta_T, self._tau_p, self._active.data_ptr(), self._kT.data_ptr(),
+            self._p0.data_ptr(), rid, self._model_eval.virial.data_ptr(), self._kinetic.data_ptr(), self.cell64.data_ptr(),
+            self.cell.data_ptr(), self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(), self.velocities.data_ptr(),
+            self.barostat_scale.data_ptr()))
+
     def step(self) -> None:
-        """One time step: drift, energies and forces at the new coordinates, kick.  No host synchronization."""
+        """One time step: drift, the barostat's move if there is one, energies and forces at the new coordinates, kick.  No
+        host synchronization."""
+        if self.barostat and self._kinetic_stale:
+            # velocities set since the last kick: the barostat takes the kinetic energy of before the drift, the same sum as
+            # kinetic_energies() on the device, no host read
+            self._kinetic.copy_(self.kinetic_energies())
+            self._kinetic_stale = False
         self._drift()
+        if self.barostat:
+            self._barostat()
         self._evaluate()
         self._kick()
 
@@ -594,6 +659,21 @@ class BatchedDynamics:
 
     def total_energies(self) -> Tensor:
         return self.potential_energies + self.kinetic_energies()
+
+    def volumes(self) -> Tensor:
+        """fp64 [1], Angstrom^3: |det| of the cell, of which a batch has one (the fp64 master under a barostat)."""
+        if self.cell is None:
+            raise ValueError("volumes() needs a cell")
+        h = (self.cell64 if self.barostat else self.cell.to(device=self.coordinates.device, dtype=torch.float64)).reshape(9)
+        det = h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6])
+        return det.abs().reshape(1)
+
+    def pressures(self) -> Tensor:
+        """fp64 [1], bar: (2 KE - tr W) / (3 V) from the current kinetic energy and the virial W of the last evaluation."""
+        if not self.barostat:
+            raise ValueError("pressures() needs the virial, which only a dynamics with pressure= evaluates")
+        p = (2.0 * self.kinetic_energies() - self._model_eval.virial.diagonal().sum()) / (3.0 * self.volumes())
+        return p * BAR_PER_HARTREE_ANGSTROM3
 
     def temperatures(self) -> Tensor:
         """2 KE / (dof k_B), dof = 3 (active atoms) less the molecule's constraints, less 3 where the centre-of-mass velocity has been removed
