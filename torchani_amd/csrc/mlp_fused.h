@@ -78,6 +78,7 @@ struct FusedSpecies {
 
 struct FusedArgs {
     FusedSpecies sp[MAX_S];
+    FusedSpecies one;          // = sp[only_species], set by launch_fused: the compile-time-width instantiations read their network here
     const int *ctl;
     unsigned *amax;
     const float *aev;          // [n_atoms][L]

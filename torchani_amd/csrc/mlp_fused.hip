@@ -3,6 +3,7 @@
 // preparation kernels).  Replaces mnp::run (csrc/mnp.cpp:32-232) and BmmEnsemble (nn/_infer.py:61-216).
 #include "mlp_fused.h"
 
+#include <cassert>
 #include <type_traits>
 
 namespace anihip {
@@ -97,26 +98,39 @@ typedef v4f Acc16[4];             // the four 16 x 16 tiles of a unit
 #else
 #define FR_FENCE() do { } while (0)
 #endif
+// Addressing: everything a ring reads lies in the weight pack, and what differs between the lanes of a wave is only where a
+// lane sits inside a fragment pair (wring_lane_off: below 4 KB).  So a request is a WAVE-UNIFORM 64-bit base -- member, column
+// block and k2 step, formed on the scalar unit -- plus this 32-bit lane offset plus a compile-time immediate (the
+// global_load's scalar-base form): no 64-bit vector add per request and no vector register pair per ring.  (The AEV and
+// d E / d AEV rows differ per lane by an atom index times the row length and keep their 64-bit vector addresses.)
 template <int D2>
 struct WRing {
     h8 hi[D2][2], lo[D2][2];
-    const _Float16 *base;   // fragment (cb, k2 step 0, plane 0) + this lane's offset (wring_lane_off)
+    const _Float16 *base;   // fragment (cb, k2 step 0, plane 0): the same in every lane
+    uint32_t loff;          // bytes from there to this lane's 16 bytes of column half 0 (wring_lane_off)
     __device__ __forceinline__ void load(int slot, int s2)   // (slot: compile-time after unrolling)
     {
-        const _Float16 *p = base + (int64_t)s2 * (4 * FRAG);
+        const char *p = reinterpret_cast<const char *>(base + (int64_t)s2 * (4 * FRAG));
+        // (base and lane offset of a request are opaque to the optimizer: left visible, the sums are re-associated into 64-bit
+        // vector adds that serve several requests, or the widened lane offset is hoisted out of the block as a register pair)
+        // (the lane offset is redefined in place: a copy would cost the move the add was)
+        asm("" : "+s"(p), "+v"(loff));
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
-            hi[slot][ct] = *(const gh8 *)(p + ct * 128);
-            lo[slot][ct] = *(const gh8 *)(p + ct * 128 + FRAG);
+            hi[slot][ct] = *(const gh8 *)(p + loff + ct * 256);
+            lo[slot][ct] = *(const gh8 *)(p + loff + ct * 256 + 2 * FRAG);
         }
     }
 };
-// halves from the start of a (column block, even k step) fragment pair to the 16 bytes lane (m, c4) of column half 0 needs
-__device__ __forceinline__ int wring_lane_off(int lane)
+// bytes from the start of a (column block, even k step) fragment pair to the 16 bytes lane (m, c4) of column half 0 needs
+__device__ __forceinline__ uint32_t wring_lane_off(int lane)
 {
     const int m = lane & 15, c4 = lane >> 4;
-    return (c4 >> 1) * (2 * FRAG) + (m + 32 * (c4 & 1)) * 8;
+    return (uint32_t)(((c4 >> 1) * (2 * FRAG) + (m + 32 * (c4 & 1)) * 8) * 2);
 }
+// (the base stays a 64-bit scalar pair, so the extent of the pack sets no limit; the 32-bit part of a request is the lane
+// offset plus the immediates, which must fit the 13-bit offset field of global_load together with nothing else: checked here)
+static_assert(2 * (2 * FRAG + 47 * 8) < (1u << 31) && 256 + 2 * FRAG < 4096, "lane offset in 32 bits, immediates in the load's offset field");
 
 // activation fragments {hi, lo} x {row half 0, 1} of one 32-row block for one k2 step
 struct AFrag {
@@ -171,7 +185,8 @@ __device__ __forceinline__ void fr_ring(WRing<D2> &r, const _Float16 *w, int64_t
                                         int lane, int nblk)
 {
     const int KS2 = KS >> 1;
-    r.base = w + (int64_t)m * member_halves + (int64_t)(nblk > 0 ? cb : 0) * KS * (2 * FRAG) + wring_lane_off(lane);
+    r.base = w + (int64_t)m * member_halves + (int64_t)(nblk > 0 ? cb : 0) * KS * (2 * FRAG);
+    r.loff = wring_lane_off(lane);
 #pragma unroll
     for (int sl = 0; sl < D2; ++sl) r.load(sl, min(sl, KS2 - 1));
 }
@@ -267,16 +282,19 @@ __device__ __forceinline__ void fr_gemm(Acc16 (&acc)[2], const _Float16 *xa, int
 }
 
 // The same for ONE 16-column half of a column block and all 64 rows (phase 5: eight halves of four slabs on eight waves): ring
-// of {hi, lo} of the one column half, four tiles t = 2 rb + rt.  base already points at the column half (+ ct * 128).
+// of {hi, lo} of the one column half, four tiles t = 2 rb + rt.  base already points at the column half (+ ct * 128 halves).
 template <int D2>
 struct WRingHalf {
     h8 hi[D2], lo[D2];
-    const _Float16 *base;
+    const _Float16 *base;   // (wave-uniform, like WRing's)
+    uint32_t loff;
     __device__ __forceinline__ void load(int slot, int s2)
     {
-        const _Float16 *p = base + (int64_t)s2 * (4 * FRAG);
-        hi[slot] = *(const gh8 *)p;
-        lo[slot] = *(const gh8 *)(p + FRAG);
+        const char *p = reinterpret_cast<const char *>(base + (int64_t)s2 * (4 * FRAG));
+        // (opaque base and lane offset: see WRing::load)
+        asm("" : "+s"(p), "+v"(loff));
+        hi[slot] = *(const gh8 *)(p + loff);
+        lo[slot] = *(const gh8 *)(p + loff + 2 * FRAG);
     }
 };
 template <int D2, bool TWO = false>
@@ -454,14 +472,35 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
     _Float16 *fsm = fsm_all + C::FIXED_HALVES;                            // X1 | XU; staging slots 1..3 overlay
     auto slot = [&](int k) { return k == 0 ? slot0 : fsm + (k - 1) * (FR_GROUP * SLAB); };
 
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (in an SGPR: the unit tests below are scalar branches)
+    // (in an SGPR: the unit tests below are scalar branches.  Opaque again at the head of every phase, with the units dealt from
+    // it: what is derived from a loop-invariant wave number -- column-block offsets, dealing flags -- is otherwise hoisted out
+    // of the item loop and, there being no scalar registers for it, parked in vector lanes)
+    int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // (re-derived from an opaque copy of threadIdx.x at the head of every item: hoisted out of the item loop, the
     // per-lane addresses built from these cost more registers than the kernel has)
     int tid = threadIdx.x, lane = tid & 63;
     int n16 = lane & 15, c4 = lane >> 4;   // this lane in an MFMA tile: row n16, k chunk / column run c4
     // staging role of this thread: row srow, 16-B piece spc (4 of a slab's 32 columns)
     int srow = tid >> 3, spc = tid & 7;
-    const int KS0 = g.n_slabs * 2;
+    // The kernel's arguments are READ WHERE THEY ARE USED.  Read as plain members of g, every pointer and constant the item loop
+    // touches -- the argument block's own fields and the per-species table's -- is loaded once and held across the loop: far
+    // more than the scalar register file takes, so they were spilled to the lanes of a vector register and came back through
+    // v_readlane (and s_nop padding) all over the item.  ka is an opaque copy of the kernel-argument pointer, renewed at the
+    // head of the item and of every phase: the loads behind a renewal cannot be merged with earlier ones, are issued there as
+    // s_load with immediate offsets and live to the end of the phase (k_aev_bwd's tab1 / tab2 do the same).  A per-species
+    // launch (compile-time widths) reads its network from FusedArgs::one at fixed offsets, not through the species index.
+    typedef const __attribute__((address_space(4))) FusedArgs KArgs;
+    typedef const __attribute__((address_space(4))) FusedSpecies KSpecies;
+    auto args_here = []() {
+        KArgs *p = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();   // (the argument block is the kernel's only parameter)
+        asm volatile("" : "+s"(p));
+        return p;
+    };
+    auto species_of = [](KArgs *p, int s_) -> KSpecies * {
+        if constexpr (H1C > 0) return &p->one;
+        else return &p->sp[s_];
+    };
+    KArgs *ka = args_here();
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
     // the d0 scale of the layer-0 backward GEMM comes from the weight-norm bounds too (amax stage 5)
@@ -480,8 +519,9 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             const bool live = rem_a != 0u;
             const int slab = live ? (int)__builtin_ctz(rem_a) : 0;
             rem_a &= rem_a - 1u;
-            const int c0 = g.kp_rad ? kp_col(g.kp_rad, slab) : 32 * slab;
-            const int nv = g.kp_rad ? kp_valid(g.kp_rad, slab) : min(32, (int)g.L - 32 * slab);
+            const int kp_rad = ka->kp_rad;
+            const int c0 = kp_rad ? kp_col(kp_rad, slab) : 32 * slab;
+            const int nv = kp_rad ? kp_valid(kp_rad, slab) : min(32, (int)ka->L - 32 * slab);
             const bool ok = live && spc * 4 < nv;
             v[j] = *(const gf4 *)(arow + (ok ? c0 : 0));
             if (!ok) v[j] = v4f{0.f, 0.f, 0.f, 0.f};
@@ -558,7 +598,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
     // the compiler can see counts as a possible write to every table this kernel reads through scalar loads -- tile entries,
     // bounds, biases -- and turns them all into per-lane vector loads: 116 spilled registers)
     constexpr bool DYN = L0B && !B2;
-#define FR_DYN() (DYN && g.queue != nullptr)
+#define FR_DYN() (DYN && ka->queue != nullptr)
     auto draw_tile = [&]() {   // one lane: the next position of the queue
         unsigned q;
         const int zero = 0, one = 1;
@@ -566,7 +606,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         // vector lanes in this kernel -- and a vector-memory instruction must not read a scalar register a vector instruction
         // wrote less than five wait states earlier; the compiler pads its own instructions, not the inside of an asm block)
         asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0\n\ts_waitcnt vmcnt(0)"
-                     : "=&v"(q) : "v"(zero), "v"(one), "s"(g.queue));
+                     : "=&v"(q) : "v"(zero), "v"(one), "s"(ka->queue));
         return q;
     };
     if (FR_DYN() && threadIdx.x == 0) s_tab[1] = draw_tile();
@@ -595,7 +635,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
     v4f va[FR_GROUP], vb[FR_GROUP];
     // slabs 0..5 of an item -> registers (rem_a = the rest)
     auto prefetch_aev = [&](const int4 &t, int atom) {
-        arow = g.aev + (int64_t)atom * g.L + spc * 4;
+        arow = ka->aev + (int64_t)atom * ka->L + spc * 4;
         rem_a = (uint32_t)t.w;
         fetch_group(va);
         fetch_group(vb);
@@ -612,14 +652,16 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
     // first D weight fragments of layer 0 of an item
     auto prefetch_w0 = [&](const int4 &t, int m) {
         const int s = t.x;
-        const FusedSpecies &fs = g.sp[s];
+        KSpecies *fs = species_of(ka, s);
+        const int H1_ = H1C ? H1C : fs->H1, KS0 = ka->n_slabs * 2;
         tmask = (uint32_t)t.w;
         rem_w = tmask;
         // every ring register is written on every path (a wave without a block: block 0), or the ring of the previous item
         // would stay live through the whole item
-        const FusedUnit u = fused_unit<RB, NB>(fs.H1, wave);
-        const _Float16 *wm = fs.w0 + (int64_t)m * (fs.H1 >> 5) * KS0 * (2 * FRAG) + wring_lane_off(lane);
+        const FusedUnit u = fused_unit<RB, NB>(H1_, wave);
+        const _Float16 *wm = fs->w0 + (int64_t)m * (H1_ >> 5) * KS0 * (2 * FRAG);
         rg.base = wm + (int64_t)u.cb * KS0 * (2 * FRAG);
+        rg.loff = wring_lane_off(lane);
 #pragma unroll
         for (int sl = 0; sl < D; ++sl) rg.load(sl, next_s2());
     };
@@ -642,15 +684,16 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
     for (;;) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63; n16 = lane & 15; c4 = lane >> 4; srow = tid >> 3; spc = tid & 7;
-        float alpha = g.alpha, inv_alpha = g.inv_alpha;   // (same reason: their vector copies and products)
-        int Mi = g.M;
-        asm volatile("" : "+s"(alpha), "+s"(inv_alpha), "+s"(Mi));
+        ka = args_here();   // (head of the item: what the layer-0 loop and its epilogue need)
+        asm volatile("" : "+s"(wave));
+        const float alpha = ka->alpha, inv_alpha = ka->inv_alpha;
+        const int Mi = ka->M;
         // entry and atom rows of the next item (the last item of a workgroup prefetches itself again: loads
         // stay unconditional)
         int mem_n = mem, tile_n = tile + (int)gridDim.x;
         bool has_next;
         int gj_n = gj, gsz_n = gsz;
-        if (g.owner) {   // the group's next tile, then the group's first tile with the next member, then the next group
+        if (ka->owner) {   // the group's next tile, then the group's first tile with the next member, then the next group
             mem_n = mem; tile_n = tile + (int)gridDim.x; gj_n = gj + 1;
             if (gj_n >= gsz) {
                 gj_n = 0;
@@ -661,7 +704,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                     // (the tile drawn while the tile before this one was in its last member)
                     // (the counter starts at zero: position q of the queue is tile t_lo + grid + q of the launch's range)
                     if (FR_DYN()) tile_n = min(t_lo + (int)gridDim.x + __builtin_amdgcn_readfirstlane((int)s_tab[1]), n_tiles);
-                    gsz_n = min(g.owner, (n_tiles - 1 - tile_n) / (int)gridDim.x + 1);
+                    gsz_n = min(ka->owner, (n_tiles - 1 - tile_n) / (int)gridDim.x + 1);
                 }
             }
             has_next = tile_n < n_tiles;
@@ -670,21 +713,21 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             has_next = mem_n < Mi;
         }
         if (!has_next) { mem_n = mem; tile_n = tile; }
-        const int4 te_n = g.tile_tab[tile_n];
-        const int atom_n = g.tile_rows[(size_t)tile_n * ROWS + srow];
+        const int4 te_n = ka->tile_tab[tile_n];
+        const int atom_n = ka->tile_rows[(size_t)tile_n * ROWS + srow];
 #ifdef ANIHIP_DEV_TRACE
-        if (g.trace && lane == 0) {
-            g.trace[((size_t)item * 8 + wave) * 32 + 0] = __builtin_readcyclecounter();
+        if (ka->trace && lane == 0) {
+            ka->trace[((size_t)item * 8 + wave) * 32 + 0] = __builtin_readcyclecounter();
             // placement: HW_REG_HW_ID (cu / sh / se) and HW_REG_XCC_ID, for co-residency analysis
-            g.trace[((size_t)item * 8 + wave) * 32 + 14] = 1 + (((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4)) |
+            ka->trace[((size_t)item * 8 + wave) * 32 + 14] = 1 + (((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4)) |
                                                    ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32));
         }
 #endif
         const int m = mem, s = te.x, n_rows = te.z, p0 = te.y;
-        const FusedSpecies &fs = g.sp[s];
+        KSpecies *fs = species_of(ka, s);
         const int64_t tm_base = s_tmb[s];
         const int rel_tile = p0 - s_off[s];
-        const int H1 = H1C ? H1C : fs.H1, H2 = H2C ? H2C : fs.H2, H3 = H3C ? H3C : fs.H3;
+        const int H1 = H1C ? H1C : fs->H1, H2 = H2C ? H2C : fs->H2, H3 = H3C ? H3C : fs->H3;
         // LDS carve (halves): X1 planes [2][ROWS][H2+16] | XU = max(X0 planes [2][ROWS][H1+16], X2 planes)
         const int ld0 = H1 + FR_XPAD, ld1 = H2 + FR_XPAD, ld2 = H3 + FR_XPAD;
         const int x0_plane = ROWS * ld0, x1_plane = ROWS * ld1, x2_plane = ROWS * ld2;
@@ -692,7 +735,18 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         _Float16 *XU = fsm + 2 * ROWS * ld1;
         _Float16 *X0 = XU, *X2 = XU;
         // this wave's part of the phases producing H1 / H2 / H3 columns (fused_unit)
-        const FusedUnit u1 = fused_unit<RB, NB>(H1, wave), u2 = fused_unit<RB, NB>(H2, wave), u3 = fused_unit<RB, NB>(H3, wave);
+        FusedUnit u1 = fused_unit<RB, NB>(H1, wave), u2 = fused_unit<RB, NB>(H2, wave), u3 = fused_unit<RB, NB>(H3, wave);
+        // Head of a phase: the argument pointer, the species' network, the wave number and the units dealt from it are renewed
+        // (see args_here), so that what a phase reads is loaded / derived at its head and dies at its end.  Called ahead of the
+        // GEMMs of phases 1 to 4 and behind the one of phase 4 (the rest of the item: phase 5 and the next item's prefetches).
+        // With a single renewal per item the compile-time-width instantiations keep 14 scalars in vector lanes across the
+        // loop; with these five, none (profiles/fused_isa_budget.txt).  (A macro on purpose: as a lambda capturing the same six
+        // variables by reference it compiles to 32 more register copies in the 192 / 160 / 128 instantiation.)
+#define PHASE_HEAD() do {                                                                                                  \
+            ka = args_here(); fs = species_of(ka, s);                                                                      \
+            asm volatile("" : "+s"(wave));                                                                                 \
+            u1 = fused_unit<RB, NB>(H1, wave); u2 = fused_unit<RB, NB>(H2, wave); u3 = fused_unit<RB, NB>(H3, wave);       \
+        } while (0)
         // accumulator element (rb, r = 4 q + e) of this lane, q = 2 ct + rt  <->  tile row urow(u, rb, q), column ucol(u, q) + e
         auto urow = [&](const FusedUnit &u, int rb, int q) { return (u.rb0 + rb) * 32 + 16 * (q & 1) + n16; };
         auto ucol = [&](const FusedUnit &u, int q) { return u.cb * 32 + 16 * (q >> 1) + 4 * c4; };
@@ -702,7 +756,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             return u.cb * 32 + (((2 * (q >> 1) + (c4 >> 1)) ^ ((n16 >> 2) & 1)) << 3) + (c4 & 1) * 4;
         };
 #ifdef ANIHIP_DEV_TRACE
-        unsigned long long *trace = g.trace ? g.trace + ((size_t)item * 8 + wave) * 32 : nullptr;
+        unsigned long long *trace = ka->trace ? ka->trace + ((size_t)item * 8 + wave) * 32 : nullptr;
 #endif
         ANIHIP_STAMP(trace, 1);
 
@@ -721,6 +775,12 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         };
         // acc * scale -> split planes of X (row stride ldx): this lane's runs of 4 columns of its unit
         auto put_acc = [&](_Float16 *X, int plane, int ldx, float scale, const FusedUnit &u) {
+            // this lane's run 0 of the unit (halves from X), formed ONCE per call and opaque from there on: the eight runs of a row
+            // block differ from it by compile-time multiples of ldx and of 16 columns (the swizzle touches bit 0 of the chunk index
+            // only, the column half adds two chunks) -- immediates of the ds_write.  Left visible, the whole sum is rebuilt from
+            // the lane number inside every row block's branch: 12 to 25 vector instructions per sixteen elements.
+            int run0 = urow(u, 0, 0) * ldx + xcol(u, 0);
+            asm("" : "+v"(run0));
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 if (rb >= u.nrb || u.nba < 1) continue;
@@ -747,7 +807,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         lo[e] = l[0];
                         lo[e + 1] = l[1];
                     }
-                    _Float16 *d = X + urow(u, rb, q) * ldx + xcol(u, q);
+                    _Float16 *d = X + run0 + (32 * rb + 16 * (q & 1)) * ldx + 16 * (q >> 1);
                     *reinterpret_cast<h4 *>(d) = hi;
                     *reinterpret_cast<h4 *>(d + plane) = lo;
                 }
@@ -761,7 +821,12 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
-                    const v4f t = *(const gf4 *)(base + (nb < u.nba ? u.cb * 32 : 0) + 16 * ct + 4 * c4);
+                    // (wave-uniform base + this lane's 32-bit offset, like the rings.  NOT opaque: the compiler picks the
+                    // scalar-base form for these loads or shares one 64-bit add between the two of a call, and forcing the form
+                    // with the rings' empty asm costs more register copies than it saves adds -- +26 vector instructions
+                    // in the 192 / 160 / 128 instantiation, tried)
+                    const char *pb = reinterpret_cast<const char *>(base + (nb < u.nba ? u.cb * 32 : 0));
+                    const v4f t = *(const gf4 *)(pb + (uint32_t)(16 * c4) + 64 * ct);
 #pragma unroll
                     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -786,7 +851,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         };
 
         // =============== layer 0: act0 = celu(aev x W0^T + b0) over the flagged slabs ===============
-        const v4f bnd = *(const gf4 *)(fs.bounds + 8 * m);   // operand bounds of this member
+        const v4f bnd = *(const gf4 *)(fs->bounds + 8 * m);   // operand bounds of this member
         // (round 5: the layer-0 biases are fetched behind the layer-0 k loop, not ahead of it -- sixteen registers less through
         // the loop, one spilled register less, -0.8 % of the stage in a same-box A/B)
         float bias0[NB][16];
@@ -850,7 +915,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         ANIHIP_STAMP(trace, 3);
         // weights of phase 1 start streaming during the layer-0 epilogue
         Ring r1;
-        fr_ring<D>(r1, fs.w1, (int64_t)(H2 >> 5) * (H1 >> 4) * 2 * FRAG, m, H1 >> 4, u2.cb, lane, u2.nba);
+        fr_ring<D>(r1, fs->w1, (int64_t)(H2 >> 5) * (H1 >> 4) * 2 * FRAG, m, H1 >> 4, u2.cb, lane, u2.nba);
         // celu and its derivative from one exponential: x > 0: (x, 1), else (alpha (e - 1), e), e = exp(x / alpha)
         const float ia_log2e = inv_alpha * 1.44269504f;
         // two elements at a time: bias + scale, the exponent argument and alpha (e - 1) as packed fp32 operations
@@ -878,9 +943,9 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         float d0f[NE][16];   // celu'(act0) of this lane's elements
         float a0max;         // tile max of |act0|
         {
-            load_cols(fs.b0 + (int64_t)m * H1, bias0, u1);
+            load_cols(fs->b0 + (int64_t)m * H1, bias0, u1);
             ANIHIP_STAMP(trace, 22);
-            const float oscale = fs.is0 * 0.25f;
+            const float oscale = fs->is0 * 0.25f;
             // tile maximum of |act0| for the split scale: act0 >= -alpha (CELU) / >= -0.17 (GELU), so max(floor, max act0)
             // bounds it -- one v_max3_f32 per element pair instead of two |.| and three max (a quarter of this epilogue's
             // VALU instructions went into the absolute values)
@@ -910,7 +975,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         for (int r = 0; r < 16; ++r) d0f[rb * NB + nb][r] = 0.f;
                 }
             }
-            if constexpr (TRAIN) store_rows(g.tr_act[0], g.tr_ld[0], H1, u1);
+            if constexpr (TRAIN) store_rows(ka->tr_act[0], ka->tr_ld[0], H1, u1);
             ANIHIP_STAMP(trace, 23);
             a0max = tile_max(vmax);   // (barriers: every wave is past the staging slots)
             if constexpr (TRAIN) {
@@ -920,7 +985,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                 if (tid == 0) {
                     const int off = ((AMAX_STAGE_ACT0 * MAX_S + s) * AMAX_SLOTS + (int)(blockIdx.x & (AMAX_SLOTS - 1))) * 4;
                     const unsigned bits = __float_as_uint(a0max);
-                    asm volatile("s_nop 4\n\tglobal_atomic_umax %0, %1, %2" : : "v"(off), "v"(bits), "s"(g.amax));
+                    asm volatile("s_nop 4\n\tglobal_atomic_umax %0, %1, %2" : : "v"(off), "v"(bits), "s"(ka->amax));
                 }
             }
             ANIHIP_STAMP(trace, 24);
@@ -937,17 +1002,18 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         // (every thread has also read the queue position at the head of this item: the last member draws the one after it)
         if (FR_DYN() && tid == 0 && mem == Mi - 1) s_tab[1] = draw_tile();
         ANIHIP_STAMP(trace, 4);
+        PHASE_HEAD();
 
         // =============== phase 1: act1 = celu(act0 x W1^T + b1) ===============
         float bias1[NB][16];   // (per-column parameters travel during the GEMM)
-        load_cols(fs.b1 + (int64_t)m * H2, bias1, u2);
+        load_cols(fs->b1 + (int64_t)m * H2, bias1, u2);
         FR_UNIT(u2, (fr_gemm<RBA, D>(acc, X0 + u2.rb0 * 32 * ld0, ld0, x0_plane, r1, H1 >> 5, lane)))
         ANIHIP_STAMP(trace, 5);
         Ring r2;
-        fr_ring<D>(r2, fs.w2, (int64_t)(H3 >> 5) * (H2 >> 4) * 2 * FRAG, m, H2 >> 4, u3.cb, lane, u3.nba);
+        fr_ring<D>(r2, fs->w2, (int64_t)(H3 >> 5) * (H2 >> 4) * 2 * FRAG, m, H2 >> 4, u3.cb, lane, u3.nba);
         float d1f[NE][16];   // celu'(act1) of this lane's elements
         {
-            const float oscale = fs.is1 / s0;
+            const float oscale = fs->is1 / s0;
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 if (rb < u2.nrb) {   // (one branch per row block: see the layer-0 epilogue)
@@ -969,28 +1035,29 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         for (int r = 0; r < 16; ++r) d1f[rb * NB + nb][r] = 0.f;
                 }
             }
-            if constexpr (TRAIN) store_rows(g.tr_act[1], g.tr_ld[1], H2, u2);
+            if constexpr (TRAIN) store_rows(ka->tr_act[1], ka->tr_ld[1], H2, u2);
             ANIHIP_STAMP(trace, 26);
             put_acc(X1, x1_plane, ld1, s1, u2);
             ANIHIP_STAMP(trace, 27);
         }
         __syncthreads();  // X1 complete; every wave is done reading X0 -> XU reusable
         ANIHIP_STAMP(trace, 6);
+        PHASE_HEAD();
 
         // =============== phase 2: act2 = celu(act1 x W2^T + b2); output layer; backward seed ===============
         float bias2[NB][16], w3[NB][16];
         // (fetching these behind the GEMM as well frees 32 registers and the last two spills, and is 0.4 % SLOWER: measured)
-        load_cols(fs.b2 + (int64_t)m * H3, bias2, u3);
-        load_cols(fs.w3 + (int64_t)m * H3, w3, u3);
+        load_cols(fs->b2 + (int64_t)m * H3, bias2, u3);
+        load_cols(fs->w3 + (int64_t)m * H3, w3, u3);
         FR_UNIT(u3, (fr_gemm<RBA, D>(acc, X1 + u3.rb0 * 32 * ld1, ld1, x1_plane, r2, H2 >> 5, lane)))
         ANIHIP_STAMP(trace, 7);
         Ring r3;   // (also without want_grad: see fr_ring)
-        fr_ring<D>(r3, fs.w2t, (int64_t)(H2 >> 5) * (H3 >> 4) * 2 * FRAG, m, H3 >> 4, u2.cb, lane, u2.nba);
+        fr_ring<D>(r3, fs->w2t, (int64_t)(H2 >> 5) * (H3 >> 4) * 2 * FRAG, m, H3 >> 4, u2.cb, lane, u2.nba);
         {
             // e = sum_col act2 * w3 (+ b3): per-lane partial over its columns of each of its two rows of a row block, the four
             // lanes of a row (c4 = 0..3) combined with two lane swaps, the waves through LDS in a fixed order (deterministic sum).
             // seed: d act2 = w3 * celu'(act2) / M, kept in the accumulators
-            const float osc2 = fs.is2 / s1;
+            const float osc2 = fs->is2 / s1;
             const float invM = 1.0f / (float)Mi;
             float e_loc[RB];   // [row block]: lanes with c4 = rt hold the sum of row half rt
 #pragma unroll
@@ -1010,7 +1077,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                             ACC(acc[i], r + 1) = invM * w3[nb][r + 1] * dy1;
                             if constexpr (TRAIN) {   // act2 leaves from here (the accumulators take the backward seed)
                                 const int row = urow(u3, rb, r >> 2);
-                                float *dst = g.tr_act[2] + (int64_t)(p0 + min(row, n_rows - 1)) * g.tr_ld[2] + (int64_t)m * H3 +
+                                float *dst = ka->tr_act[2] + (int64_t)(p0 + min(row, n_rows - 1)) * ka->tr_ld[2] + (int64_t)m * H3 +
                                              ucol(u3, r >> 2) + (r & 3);
                                 if (row < n_rows) *reinterpret_cast<float2 *>(dst) = make_float2(y0, y1);
                             }
@@ -1034,31 +1101,32 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                     if (t - u3.rb0 == rb && rb < u3.nrb) v = e_loc[rb];
                 if (c4 < 2) s_e[wave * ROWS + t * 32 + 16 * c4 + n16] = v;   // (lanes 0..31: row 16 c4 + n16 = lane)
             }
-            if constexpr (TRAIN) store_rows(g.tr_dlt[2], g.tr_ld[2], H3, u3);
+            if constexpr (TRAIN) store_rows(ka->tr_dlt[2], ka->tr_ld[2], H3, u3);
             ANIHIP_STAMP(trace, 28);
-            if (g.want_grad) put_acc(X2, x2_plane, ld2, s2, u3);   // (XU: X0 is dead since the last barrier)
+            if (ka->want_grad) put_acc(X2, x2_plane, ld2, s2, u3);   // (XU: X0 is dead since the last barrier)
             ANIHIP_STAMP(trace, 29);
         }
         __syncthreads();
         if (tid < n_rows) {
-            float e = fs.b3[m];
+            float e = fs->b3[m];
 #pragma unroll
             for (int w8 = 0; w8 < NW; ++w8) e += s_e[w8 * ROWS + tid];
-            g.member_part[(int64_t)(p0 + tid) * Mi + m] = e;
+            ka->member_part[(int64_t)(p0 + tid) * Mi + m] = e;
         }
         ANIHIP_STAMP(trace, 9);
+        PHASE_HEAD();
 
         Ring r4;
-        if (g.want_grad) {
+        if (ka->want_grad) {
             // =============== phase 3: d act1 = (d act2 x W2) * celu'(act1) ===============
             // (no zero fill: the first k2 step of fr_gemm writes the accumulators)
             FR_UNIT(u2, (fr_gemm<RBA, D, B2>(acc, X2 + u2.rb0 * 32 * ld2, ld2, x2_plane, r3, H3 >> 5, lane)))
             ANIHIP_STAMP(trace, 10);
         }
-        fr_ring<D>(r4, fs.w1t, (int64_t)(H1 >> 5) * (H2 >> 4) * 2 * FRAG, m, H2 >> 4, u1.cb, lane, u1.nba);
-        if (g.want_grad) {
+        fr_ring<D>(r4, fs->w1t, (int64_t)(H1 >> 5) * (H2 >> 4) * 2 * FRAG, m, H2 >> 4, u1.cb, lane, u1.nba);
+        if (ka->want_grad) {
             if (u2.nrb > 0) {
-                const float osc3 = fs.is2 / s2;
+                const float osc3 = fs->is2 / s2;
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
                     if (rb >= u2.nrb) continue;
@@ -1067,7 +1135,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) ACC(acc[rb * NB + nb], r) *= osc3 * d1f[rb * NB + nb][r];
                 }
-                if constexpr (TRAIN) store_rows(g.tr_dlt[1], g.tr_ld[1], H2, u2);
+                if constexpr (TRAIN) store_rows(ka->tr_dlt[1], ka->tr_ld[1], H2, u2);
                 ANIHIP_STAMP(trace, 30);
                 put_acc(X1, x1_plane, ld1, s3, u2);   // (X1: its last readers finished before the previous barrier)
                 ANIHIP_STAMP(trace, 31);
@@ -1081,11 +1149,13 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         if constexpr (!L0B) prefetch_w0(te_n, mem_n);
         __syncthreads();
         ANIHIP_STAMP(trace, 11);
+        PHASE_HEAD();
         // =============== phase 4: d act0 = (d act1 x W1) * celu'(act0)  -> global, or -> LDS for phase 5 ===============
-        if (g.want_grad && u1.nrb > 0) {
+        if (ka->want_grad && u1.nrb > 0) {
             FR_UNIT(u1, (fr_gemm<RBA, D, B2>(acc, X1 + u1.rb0 * 32 * ld1, ld1, x1_plane, r4, H2 >> 5, lane)))
         }
         ANIHIP_STAMP(trace, 12);
+        PHASE_HEAD();
         if constexpr (L0B) {
             {
             // =============== phase 5 (l0b): d E / d AEV += d act0 x W0 over the tile's flagged slabs ===============
@@ -1094,7 +1164,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             // K = this member's H1 columns.  The workgroup OWNS the tile through all members (owner order), so the sum
             // over the members is a plain read-add-write of the same lane on the same address, member after member in
             // a fixed order: no atomics, no d act0 round trip through HBM, no separate GEMM launch.
-            const float s4 = pow2_scale_for(fs.bounds[8 * m + 4] * (ACT == 1 ? 1.13f : 1.0f));   // |d act0| <= [4] max act'
+            const float s4 = pow2_scale_for(fs->bounds[8 * m + 4] * (ACT == 1 ? 1.13f : 1.0f));   // |d act0| <= [4] max act'
             // Work of a pass: FOUR flagged slabs x both row blocks x K = eight 16-column halves, one per wave: wave w takes column
             // half w & 1 of the pass's slab w >> 1 for all 64 rows and the whole of K -- four 16 x 16 tiles per wave, every weight
             // fragment {hi, lo} of its column half crosses the CU's 64 B/clk L2 port once and feeds twelve MFMAs.  (Rounds 4-5 split
@@ -1104,7 +1174,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             // columns 4 c4 .. of its column half, t = 0..3: a store instruction covers 16 rows x 64 contiguous bytes, half a cache
             // line per row, and the wave of the other column half writes the other half of the same lines.
             const int KS5 = H1 >> 4;
-            const int64_t mh5 = (int64_t)g.n_slabs * KS5 * (2 * FRAG);
+            const int64_t mh5 = (int64_t)ka->n_slabs * KS5 * (2 * FRAG);
             auto nth_slab = [&](int c) {   // c-th flagged slab of the tile (scalar), -1 past the end
                 uint32_t mk = tmask_cur;
                 for (int t = 0; t < c; ++t) mk &= mk - 1u;
@@ -1113,15 +1183,16 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             const int ct5 = wave & 1;
             WRingHalf<D> r5;
             auto ring5 = [&](int sl_) {   // the first D k2 steps of slab sl_, this wave's column half
-                r5.base = fs.w0t + (int64_t)m * mh5 + (int64_t)sl_ * KS5 * (2 * FRAG) + wring_lane_off(lane) + ct5 * 128;
+                r5.base = fs->w0t + (int64_t)m * mh5 + (int64_t)sl_ * KS5 * (2 * FRAG) + ct5 * 128;
+                r5.loff = wring_lane_off(lane);
 #pragma unroll
                 for (int sl = 0; sl < D; ++sl) r5.load(sl, min(sl, (KS5 >> 1) - 1));
             };
             int slab = nth_slab(wave >> 1);
             ring5(max(slab, 0));   // (travels during the epilogue below; requested behind it instead: no faster, measured)
             ANIHIP_STAMP(trace, 16);
-            if (g.want_grad && u1.nrb > 0) {
-                const float osc4 = fs.is1 / s3;
+            if (ka->want_grad && u1.nrb > 0) {
+                const float osc4 = fs->is1 / s3;
 #pragma unroll
                 for (int i = 0; i < NE; ++i)
 #pragma unroll
@@ -1131,23 +1202,23 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             ANIHIP_STAMP(trace, 17);
             __syncthreads();   // d act0 complete
             ANIHIP_STAMP(trace, 13);
-            if (g.want_grad) {
-                const float osc5 = fs.is0 / s4;
+            if (ka->want_grad) {
+                const float osc5 = fs->is0 / s4;
                 // (wave-uniform) a single-pass tile in owner order over single tiles: the members' sum stays in registers (gsum) and
                 // only the last member needs the row pointers (LDS reads + 64-bit address arithmetic: 1.3 k clocks per item)
-                const bool regsum_tile = nact <= 4 && g.owner == 1;
+                const bool regsum_tile = nact <= 4 && ka->owner == 1;
                 float *orow[4];
                 bool rok[4];
                 if (!regsum_tile || m == Mi - 1) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int row = 16 * t + n16;
-                        orow[t] = g.grad_aev + (int64_t)s_orow[par * ROWS + row] * g.L + 16 * ct5 + 4 * c4;
+                        orow[t] = ka->grad_aev + (int64_t)s_orow[par * ROWS + row] * ka->L + 16 * ct5 + 4 * c4;
                         rok[t] = row < n_rows;    // (short tiles repeat their last atom: one writer per row only)
                     }
                 } else {   // (defined on every path)
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) { orow[t] = g.grad_aev; rok[t] = false; }
+                    for (int t = 0; t < 4; ++t) { orow[t] = ka->grad_aev; rok[t] = false; }
                 }
                 // (the last pass -- the only one of a water tile -- is peeled: what it prefetches for the next item must not be
                 // defined under a condition inside a loop, or it is carried around the loop in registers)
@@ -1155,8 +1226,8 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                     constexpr bool LAST = decltype(last_)::value;
                     const bool live = slab >= 0;
                     const int sl = max(slab, 0);
-                    const int col5 = g.kp_rad ? kp_col(g.kp_rad, sl) : 32 * sl;
-                    const int nv5 = g.kp_rad ? kp_valid(g.kp_rad, sl) : min(32, (int)g.L - 32 * sl);
+                    const int col5 = ka->kp_rad ? kp_col(ka->kp_rad, sl) : 32 * sl;
+                    const int nv5 = ka->kp_rad ? kp_valid(ka->kp_rad, sl) : min(32, (int)ka->L - 32 * sl);
                     const bool cok = live && 16 * ct5 + 4 * c4 < nv5;
                     // (wave-uniform) the members' sum of a single-pass tile stays in registers (gsum)
                     const bool regsum = LAST && c0 == 0 && regsum_tile;
@@ -1169,7 +1240,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                             // (lanes with nothing to read -- the first member, waves without a slab -- read a line that is hot in
                             // L2: loads return in order, and a miss to HBM here would hold up the weight ring's requests behind it)
                             const bool ok = cok && rok[t] && m > 0;
-                            prev[t] = *(const gf4 *)(ok ? orow[t] + col5 : fs.bounds);
+                            prev[t] = *(const gf4 *)(ok ? orow[t] + col5 : fs->bounds);
                             if (!ok) prev[t] = v4f{0.f, 0.f, 0.f, 0.f};
                         }
                     } else {
@@ -1229,8 +1300,8 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         prefetch_aev(te_n, atom_n);
         // every wave is done with the LDS of this item: the next one may stage its slabs
         __syncthreads();
-        if (g.want_grad && u1.nrb > 0) {
-            const float osc4 = fs.is1 / s3;
+        if (ka->want_grad && u1.nrb > 0) {
+            const float osc4 = fs->is1 / s3;
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 if (rb >= u1.nrb) continue;
@@ -1240,11 +1311,11 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {   // run q = 2 ct + rt: tile row 16 rt + n16 of the row block, columns 16 ct + 4 c4 ..
                         const int row = urow(u1, rb, q);
-                        float *dst = g.d0 + (int64_t)(p0 + min(row, n_rows - 1)) * g.ld0 + (int64_t)m * H1 + ucol(u1, q);
-                        if (g.d0_tm) {
+                        float *dst = ka->d0 + (int64_t)(p0 + min(row, n_rows - 1)) * ka->ld0 + (int64_t)m * H1 + ucol(u1, q);
+                        if (ka->d0_tm) {
                             // fragment order of the 32 x 16 A operand the layer-0 backward GEMMs read (tm_unit): column half ct = its
                             // k step, lane slot (columns 8 ..: 32 +) row of the block, floats (c4 & 1) * 4 ..
-                            dst = g.d0 + tm_base + (int64_t)(((rel_tile >> 6) * Mi + m) * 64) * H1 +
+                            dst = ka->d0 + tm_base + (int64_t)(((rel_tile >> 6) * Mi + m) * 64) * H1 +
                                   tm_unit(u1.cb, ((rel_tile >> 5) & 1) + u1.rb0 + rb, q >> 1) +
                                   ((c4 >> 1) * 32 + 16 * (q & 1) + n16) * 8 + 4 * (c4 & 1);
                         }
@@ -1265,10 +1336,11 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         mem = mem_n;
         tile = tile_n;
         gj = gj_n; gsz = gsz_n;
-        item = g.owner ? tile * Mi + mem : mem * n_tiles + tile;
+        item = ka->owner ? tile * Mi + mem : mem * n_tiles + tile;
     }
 }
 #undef FR_UNIT
+#undef PHASE_HEAD
 #undef FR_DYN
 
 const void *fused_kernel(int variant)
@@ -1286,8 +1358,15 @@ const void *fused_kernel(int variant)
     }
 }
 
-void launch_fused(int variant, unsigned grid, size_t lds_bytes, hipStream_t stream, const FusedArgs &f)
+void launch_fused(int variant, unsigned grid, size_t lds_bytes, hipStream_t stream, const FusedArgs &args)
 {
+    // the compile-time-width instantiations read their network from FusedArgs::one: filled HERE, so that no caller can launch
+    // one of them on an empty network; they exist for launches restricted to one species
+    FusedArgs f = args;
+    if (variant >= FUSED_CELU_L0B_256) {
+        assert(f.only_species >= 0 && f.only_species < f.S && "a compile-time-width launch takes the tiles of ONE species");
+        f.one = f.sp[f.only_species];
+    }
     switch (variant) {
         case FUSED_CELU_L0B: hipLaunchKernelGGL((k_mlp_fused<2, 1, 0, true>), dim3(grid), dim3(512), lds_bytes, stream, f); break;
         case FUSED_CELU_L0B_B2: hipLaunchKernelGGL((k_mlp_fused<2, 1, 0, true, false, true>), dim3(grid), dim3(512), lds_bytes, stream, f); break;
