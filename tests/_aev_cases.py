@@ -16,6 +16,9 @@ one or more labellings:
          same-species pair of that species, 1 x n mixed blocks)
   pad    255 neighbors of the centre whose seven per-species counts are 33, 33, 33, 33, 41, 41, 41 (all = 1 mod 8): the
          largest padded radial list k_aev_fwd3 can see, 255 + 49 slots
+
+images12_pbc is a periodic cell smaller than the cutoffs: every atom sits in every row several times through its images,
+in the angular and in the far group, so in different 64-entry chunks of a row (tests/_second_order_ref.py).
 """
 from __future__ import annotations
 
@@ -124,6 +127,20 @@ def _pad_case() -> AevCase:
     return AevCase("chunk255_open/pad", sp, base.coords, None, None, 7, centre=0, general=True)
 
 
+IMAGES_CELL = nc._cell([[3.7, 0, 0], [0.3, 3.6, 0], [0.1, 0.2, 5.5]])
+
+
+def _images_case() -> AevCase:
+    """12 atoms on a jittered 2 x 2 x 3 grid of a 3.7 x 3.6 x 5.5 A triclinic cell, the four species cycling: about 100
+    entries per row, each atom about eight times."""
+    rs = np.random.RandomState(23)
+    k = np.stack(np.meshgrid(np.arange(2), np.arange(2), np.arange(3), indexing="ij"), axis=-1).reshape(-1, 3)
+    frac = (k + 0.5) / np.array([2.0, 2.0, 3.0]) + rs.uniform(-0.06, 0.06, (12, 3))
+    x = (frac @ IMAGES_CELL.astype(np.float64)).astype(np.float32)
+    sp = (np.arange(12, dtype=np.int32) % 4).reshape(1, 12)
+    return AevCase("images12_pbc/built", sp, x.reshape(1, 12, 3), IMAGES_CELL, nc.TTT, 4)
+
+
 @functools.lru_cache(maxsize=1)
 def all_cases() -> tp.Tuple[AevCase, ...]:
     nbr = {c.name: c for c in nc.chunk_cases() + nc.limit_cases()}
@@ -153,6 +170,7 @@ def all_cases() -> tp.Tuple[AevCase, ...]:
     out.append(AevCase("lattice", sp.astype(np.int32), x, None, None, 7))
     sp, x = dense_cluster()
     out.append(AevCase("dense", sp, x, None, None, 7, variants=("smooth", "bent")))
+    out.append(_images_case())
     for name in ("ang128_over_open", "spec255_over_open", "rad256_over_open"):
         out.append(_from_nbr(nbr[name], "built"))
     names = [c.name for c in out]

@@ -13,7 +13,9 @@ sqrt(empirical charge) values of resources/atomic_constants.json and resources/f
 (published D3 parameters), not code.
 
 Each fixture: per-atom energies (atomic=True), molecular energies and forces with cutoff 8.0 A and the smooth
-envelope, functional wB97X (the recipe of arch.py:1177-1181 for a wB97X model), and for water_pbc also b973c.
+envelope, functional wB97X (the recipe of arch.py:1177-1181 for a wB97X model), and for water_pbc also b973c.  Also the
+two long-row cases of gen_golden_pairs2.LONG_ROWS (``long_rows`` as the only argument writes those alone and leaves
+d3_refs.npz as it is).
 """
 import json
 import os
@@ -96,8 +98,9 @@ def write_refs():
 
 
 def run(name, functional, tag, cutoff=8.0, cutoff_fn="smooth"):
-    with np.load(os.path.join(HERE, name + ".npz")) as z:
-        g = {k: z[k] for k in z.files}
+    import gen_golden_pairs2 as gp
+
+    g = gp.load_inputs(name)
     symbols = [str(s) for s in g["symbols"]]
     pot = TwoBodyDispersionD3.from_functional(symbols=symbols, functional=functional, cutoff=cutoff,
                                               cutoff_fn=cutoff_fn).double()
@@ -111,13 +114,16 @@ def run(name, functional, tag, cutoff=8.0, cutoff_fn="smooth"):
     (grad,) = torch.autograd.grad(e.sum(), coords)
     out = dict(cutoff=np.asarray(cutoff), cutoff_fn=np.asarray(cutoff_fn), functional=np.asarray(functional),
                atomic_energies=atomic.detach().numpy(), energies=e.detach().numpy(), forces=(-grad).numpy())
-    path = os.path.join(HERE, f"d3_{tag}{name}.npz")
+    path = os.path.join(HERE, f"d3_{tag}{gp.file_name(name)}.npz")
     np.savez_compressed(path, **out)
     print(f"{path}: pairs={neighbors.indices.shape[1]} E[0]={e[0].item():+.9f} |F|max={grad.abs().max().item():.6f}")
 
 
 if __name__ == "__main__":
-    write_refs()
-    for nm in ("rand_batch_ani2x", "water_pbc_ani2x", "small_ani2x", "triclinic_pbc_ani2x"):
+    if sys.argv[1:] != ["long_rows"]:
+        write_refs()
+        for nm in ("rand_batch_ani2x", "water_pbc_ani2x", "small_ani2x", "triclinic_pbc_ani2x"):
+            run(nm, "wb97x", "")
+        run("water_pbc_ani2x", "b973c", "b973c_")
+    for nm in ("chunk256_open/seven", "chunk129_pbc/built"):   # gen_golden_pairs2.LONG_ROWS
         run(nm, "wb97x", "")
-    run("water_pbc_ani2x", "b973c", "b973c_")

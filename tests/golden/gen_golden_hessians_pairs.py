@@ -13,8 +13,13 @@ Standalone potentials (tests/golden/hess_pairs_<base>.npz): RepulsionXTB (cosine
 cutoffs on the molecules), and the potentials and constructor arguments of gen_golden_pairs2.cases, on the reference's
 all_pairs list with the potential's cutoff, as in gen_golden_pairs2: ``<key>_hess`` on the sampled rows ``hess_rows``.
 
+Long rows (tests/golden/hess_pairs_<case>.npz, ``/`` of the case name replaced by ``_``): the same standalone potentials
+on two cases of tests/_aev_cases.py whose rows hold up to 256 entries (species index -> symbol in the ANI-2x order), with
+the three rows of the centre (the atom with the long row) among the stored ones; 257 atoms make 12 rows of 11 potentials
+300 KiB.
+
 H is stored in float32 (the rounding, 6e-8 of an entry, is far below the tests' gate of 2e-5 of max |H|) to keep every file
-in the tens of KiB.
+in the tens of KiB (the long-row cases: see above).
 """
 import math
 import os
@@ -40,12 +45,12 @@ MODELS = (("ani2xr", "rand_batch_ani2x", 21, 12), ("ani2xr", "water_pbc_ani2x", 
           ("anir2s", "rand_batch_ani2x", 24, 12), ("anir2s", "dense90_ani2x", 25, 16))
 VIB = ("ani2xr", "rand_batch_ani2x", 21, 0)   # the molecule whose whole H and vibrational analysis are stored
 STANDALONE = {"rand_batch_ani2x": 6, "water_pbc_ani2x": 12, "triclinic_pbc_ani2x": 12}   # base: sampled rows
+LONG_ROWS = {name: 12 for name in gp.LONG_ROWS}   # rows stored: the three of the centre (atom 0), then a seeded sample
 ZNUM = {"H": 1, "C": 6, "N": 7, "O": 8, "S": 16, "F": 9, "Cl": 17}
 
 
 def load(base):
-    with np.load(os.path.join(HERE, base + ".npz")) as z:
-        return {k: z[k] for k in z.files}
+    return gp.load_inputs(base)
 
 
 def standalone_cases(symbols, periodic):
@@ -166,6 +171,8 @@ def run_standalone(base, count):
     cell = torch.from_numpy(g["cell"]).double() if "cell" in g else None
     pbc = torch.from_numpy(g["pbc"]) if "pbc" in g else None
     rows = sample_rows(3 * coords.shape[1], count)
+    if base in LONG_ROWS:   # the centre's walk is the long one: its three rows, then a sample of the others
+        rows = np.concatenate([np.arange(3), 3 + sample_rows(3 * coords.shape[1] - 3, count - 3)]).astype(np.int64)
     out = {"base": np.asarray(base), "hess_rows": rows}
     for key, (cls, kw) in standalone_cases(symbols, cell is not None).items():
         pot = cls(symbols=symbols, **kw).double()
@@ -176,7 +183,9 @@ def run_standalone(base, count):
         H = hessian_rows(energy, coords, rows)
         out[key + "_hess"] = H.detach().numpy().astype(np.float32)
         print(f"hess_pairs_{base} {key:12s} |H|max={H.abs().max().item():.4e}")
-    path = os.path.join(HERE, f"hess_pairs_{base}.npz")
+    if base in LONG_ROWS:
+        out["species"], out["coords"] = g["species"], g["coords"]
+    path = os.path.join(HERE, f"hess_pairs_{gp.file_name(base)}.npz")
     np.savez_compressed(path, **out)
     print(f"{os.path.basename(path)} -> {os.path.getsize(path) / 1024:.0f} KiB")
 
@@ -186,6 +195,9 @@ def main():
     only = sys.argv[1:]
     if not only or "standalone" in only:
         for base, count in STANDALONE.items():
+            run_standalone(base, count)
+    if not only or "long_rows" in only:
+        for base, count in LONG_ROWS.items():
             run_standalone(base, count)
     if not only or "vib" in only:
         run_vib(*VIB)

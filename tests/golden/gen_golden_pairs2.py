@@ -4,6 +4,10 @@ float64 (zbl.py, lj.py, fixed_coulomb.py; envelope / halves of core.py) on the c
     python tests/golden/gen_golden_pairs2.py      -> tests/golden/pairs2_<case>.npz
 
 Per potential: per-atom energies (atomic=True) and forces; constructor arguments are stored with the values.
+
+LONG_ROWS: two cases of tests/_aev_cases.py whose rows hold up to 256 entries at these cutoffs (species index -> symbol in
+the ANI-2x order; ``/`` of the case name becomes ``_`` in the file name).  load_inputs serves the other pair generators too;
+``long_rows`` as the only argument writes those fixtures alone.
 """
 import os
 import sys
@@ -39,9 +43,31 @@ def cases(symbols):
     }
 
 
-def run(name):
+LONG_ROWS = ("chunk256_open/seven", "chunk129_pbc/built")
+ANI2X_SYMBOLS = ("H", "C", "N", "O", "S", "F", "Cl")
+
+
+def load_inputs(name):
+    """symbols, species, coords (and cell, pbc) of a golden case, or of a long-row case of tests/_aev_cases.py."""
+    if name in LONG_ROWS:
+        sys.path.insert(0, os.path.dirname(HERE))
+        import _aev_cases as ac
+
+        c = ac.case_by_name(name)
+        g = {"symbols": np.asarray(ANI2X_SYMBOLS), "species": c.species.astype(np.int64), "coords": c.coords}
+        if c.periodic:
+            g["cell"], g["pbc"] = c.cell, np.asarray(c.pbc)
+        return g
     with np.load(os.path.join(HERE, name + ".npz")) as z:
-        g = {k: z[k] for k in z.files}
+        return {k: z[k] for k in z.files}
+
+
+def file_name(name):
+    return name.replace("/", "_")
+
+
+def run(name):
+    g = load_inputs(name)
     symbols = [str(s) for s in g["symbols"]]
     elem = torch.from_numpy(g["species"].astype(np.int64))
     cell = torch.from_numpy(g["cell"]).double() if "cell" in g else None
@@ -56,9 +82,10 @@ def run(name):
         out[key + "_atomic"] = atomic.detach().numpy()
         out[key + "_forces"] = (-grad).numpy()
         print(f"{name} {key:8s} E[0]={atomic.sum(dim=1)[0].item():+.9f} |F|max={grad.abs().max().item():.5f}")
-    np.savez_compressed(os.path.join(HERE, f"pairs2_{name}.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, f"pairs2_{file_name(name)}.npz"), **out)
 
 
 if __name__ == "__main__":
-    for nm in ("rand_batch_ani2x", "water_pbc_ani2x", "triclinic_pbc_ani2x"):
+    for nm in LONG_ROWS if sys.argv[1:] == ["long_rows"] else ("rand_batch_ani2x", "water_pbc_ani2x",
+                                                               "triclinic_pbc_ani2x") + LONG_ROWS:
         run(nm)

@@ -20,6 +20,8 @@ GATE = 2e-5   # max |H - H_ref| <= GATE * max |H_ref|, as test_gpu_hessians.py
 MODEL_CASES = [("ani2xr", "rand_batch_ani2x"), ("ani2xr", "water_pbc_ani2x"), ("ani2xr", "small_ani2x"),
                ("anir2s", "rand_batch_ani2x"), ("anir2s", "dense90_ani2x")]
 STANDALONE_BASES = ("rand_batch_ani2x", "water_pbc_ani2x", "triclinic_pbc_ani2x")
+# cases of tests/_aev_cases.py with rows of up to 256 entries at the pair cutoffs (the fourth 64-entry round of k_pair_hvp)
+LONG_ROW_CASES = ("chunk256_open/seven", "chunk129_pbc/built")
 
 
 def report(line):
@@ -187,6 +189,63 @@ def test_standalone_hessians_match_reference(dev, base):
                f"max|H_autograd - H_ref| = {err_a:.2e}, max|H_ref| = {np.abs(ref).max():.2e}")
         assert err_b <= bound and err_a <= bound, key
         _check_structure(Hb.double(), sp, bound)
+
+
+@pytest.mark.parametrize("case", LONG_ROW_CASES)
+def test_standalone_hessians_on_long_rows(dev, case):
+    """Every standalone potential on rows of up to 256 entries against the reference's fp64 Hessian rows
+    (tests/golden/hess_pairs_<case>.npz) within 2e-5 max |H_ref|.  Row 3 i + c of H is the walk of central atom i, so the
+    stored rows start with the three of the centre, the only atom of the shell cases whose row passes 192 entries at 5.2 A
+    (at 7.5 A and without a cutoff every atom of chunk256_open/seven has one): k_pair_hvp's fourth 64-entry round in dense
+    form, for every potential.  The item form runs through the block-sparse Hessian of a model carrying the potential, on
+    the AEV's rows; only zbl_cos (4.0 A) fits inside the AEV cutoff, so there the fourth round walks entries past the
+    potential's own cutoff.  First-order values: tests/test_gpu_parity.py."""
+    import _aev_cases as ac
+    from torchani_amd import grad
+    from torchani_amd.models import ANI2x
+    from torchani_amd.weights import arch_spec
+
+    c = ac.case_by_name(case)
+    h = _npz("hess_pairs_" + case.replace("/", "_"))
+    assert np.array_equal(h["coords"], c.coords) and np.array_equal(h["species"], c.species)
+    rows = h["hess_rows"]
+    assert c.centre == 0 and rows[:3].tolist() == [0, 1, 2]
+    symbols = list(arch_spec("ani2x")[0])
+    sp = torch.from_numpy(c.species.astype(np.int64)).to(dev)
+    x = torch.from_numpy(c.coords).to(dev).double()
+    cell = None if c.cell is None else torch.from_numpy(c.cell).to(dev)
+    pbc = None if c.pbc is None else torch.from_numpy(np.asarray(c.pbc)).to(dev)
+    pots = _standalone_pots(symbols, cell is not None)
+    assert sorted(pots) == sorted(k[:-len("_hess")] for k in h if k.endswith("_hess"))
+    model = ANI2x(seed=3, device=dev, periodic_table_index=False, neighborlist="cell" if c.periodic else "batch",
+                  row_capacity=256)
+    model.set_enabled("nnp", False)
+    sparse_keys = []
+    for key, pot in pots.items():
+        pot = pot.to(dev)
+        z = _atomic_numbers(pot, sp)
+        ref = h[key + "_hess"].astype(np.float64)
+        bound = GATE * np.abs(ref).max()
+        Hb = grad.energies_forces_and_hessians(pot, z, x, cell=cell, pbc=pbc).hessians
+        d = np.abs(Hb[:, rows].double().cpu().numpy() - ref)
+        err_b, err_c = d.max(), d[:, :3].max()
+        line = (f"pair long rows {case} {key}: max|H_batched - H_ref| = {err_b:.2e} (the centre's rows {err_c:.2e}; max|H_ref| "
+                f"= {np.abs(ref).max():.2e}, on the centre's rows {np.abs(ref[:, :3]).max():.2e})")
+        err_s = None
+        if pot.cutoff <= model.aev_computer.radial.cutoff + 1e-6:
+            model.add_pair_potential("long_rows_" + key, pot)
+            Hs = grad.energies_forces_and_sparse_hessians(model, sp, x, cell=cell, pbc=pbc).hessians.to_dense()
+            model.set_enabled("long_rows_" + key, False)
+            err_s = np.abs(Hs[:, rows].double().cpu().numpy() - ref).max()
+            line += f", max|H_sparse - H_ref| = {err_s:.2e}"
+            _check_structure(Hs.double(), sp, bound)
+            sparse_keys.append(key)
+        report(line)
+        assert err_b <= bound and (err_s is None or err_s <= bound), key
+        # the centre's rows at their own scale (they are small beside the shell atoms'): the same relative gate
+        assert err_c <= GATE * np.abs(ref[:, :3]).max(), key
+        _check_structure(Hb.double(), sp, bound)
+    assert sparse_keys == ["zbl_cos"]
 
 
 def _fd_columns(force_fn, x, cols, h=3e-4):

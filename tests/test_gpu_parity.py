@@ -78,6 +78,22 @@ def to_dev(g, dev):
     return sp, x, cell, pbc
 
 
+LONG_ROW_PAIR_CASES = ("chunk256_open/seven", "chunk129_pbc/built")   # tests/golden/gen_golden_pairs2.py: LONG_ROWS
+
+
+def pair_inputs(case):
+    """load_golden(case), or the inputs of a long-row case of tests/_aev_cases.py (rows of up to 256 entries at the pair
+    cutoffs; species index -> symbol in the ANI-2x order).  Those have no network reference: "forces" is None and the pair
+    tests stop after the potential's own values."""
+    if case not in LONG_ROW_PAIR_CASES:
+        return load_golden(case)
+    import _aev_cases as ac
+
+    c = ac.case_by_name(case)
+    return dict(species=c.species.astype(np.int64), coords=c.coords, cell=c.cell, pbc=c.pbc, kind="ani2x", seed=31,
+                symbols=["H", "C", "N", "O", "S", "F", "Cl"], energies=None, forces=None)
+
+
 def unpack_rows(nbrs, n):
     meta = nbrs.meta.cpu().numpy().view(np.uint32).reshape(n, 6)
     ent = nbrs.ent.cpu().numpy().reshape(-1, 4)
@@ -1630,7 +1646,7 @@ def test_config3_reference_inputs(dev, name):
 
 
 @pytest.mark.parametrize("case", ["rand_batch_ani2x", "water_pbc_ani2x", "small_ani2x", "triclinic_pbc_ani2x",
-                                  "cos_water_pbc_ani2x"])
+                                  "cos_water_pbc_ani2x"] + list(LONG_ROW_PAIR_CASES))
 def test_xtb_repulsion_matches_reference(dev, case):
     """RepulsionXTB (potentials/xtb.py) on the engine's neighbor rows against the reference's fp64 values
     (tests/golden/gen_golden_pairs.py): per-atom halves, molecular energies, forces; alone, through the model's autograd
@@ -1639,8 +1655,9 @@ def test_xtb_repulsion_matches_reference(dev, case):
     from torchani_amd.potentials import RepulsionXTB
 
     name = case[4:] if case.startswith("cos_") else case
-    g = load_golden(name)
-    ref = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"pairs_{case}.npz")))
+    g = pair_inputs(name)
+    ref = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                    f"pairs_{case.replace('/', '_')}.npz")))
     sp, x, cell, pbc = to_dev(g, dev)
     model = ANI2x(state_dict=seeded_state("ani2x", 8, g["seed"]), device=dev, periodic_table_index=False,
                   neighborlist=modes_for(g)[-1], row_capacity=256)
@@ -1659,6 +1676,8 @@ def test_xtb_repulsion_matches_reference(dev, case):
     fe = np.abs(-gc.cpu().numpy().reshape(ref["forces"].shape) - ref["forces"]).max()
     report(f"xtb   {case:24s} max|e_atom err| = {ea:.2e} (scale {escale:.1f})  |F err| = {fe:.2e} (scale {fscale:.1f})")
     assert ea < 2e-6 * escale and fe < 5e-6 * fscale
+    if g["forces"] is None:   # (a long-row case: no network reference)
+        return
     # inside the model: NN + repulsion
     model.add_pair_potential("repulsion_xtb", pot)
     out = model.energies_and_forces(sp, x, cell, pbc)
@@ -1684,7 +1703,7 @@ def test_xtb_repulsion_matches_reference(dev, case):
     assert np.abs(out0.forces.cpu().numpy() - g["forces"]).max() < F_TOL
 
 
-@pytest.mark.parametrize("case", ["rand_batch_ani2x", "water_pbc_ani2x", "triclinic_pbc_ani2x"])
+@pytest.mark.parametrize("case", ["rand_batch_ani2x", "water_pbc_ani2x", "triclinic_pbc_ani2x"] + list(LONG_ROW_PAIR_CASES))
 def test_analytic_pair_potentials_match_reference(dev, case):
     """RepulsionZBL, LennardJones / RepulsionLJ / DispersionLJ, FixedCoulomb and FixedMNOK (potentials/zbl.py, lj.py,
     fixed_coulomb.py) on the engine's neighbor rows against the reference's own classes in fp64
@@ -1700,8 +1719,8 @@ def test_analytic_pair_potentials_match_reference(dev, case):
     src = open(spec.origin).read().split("def cases(symbols):")[0].split("CHARGES = ")[1]
     ns: dict = {}
     exec("CHARGES = " + src, ns)   # the element constants of the generator (its imports need the reference)
-    g = load_golden(case)
-    ref = dict(np.load(os.path.join(gdir, f"pairs2_{case}.npz")))
+    g = pair_inputs(case)
+    ref = dict(np.load(os.path.join(gdir, f"pairs2_{case.replace('/', '_')}.npz")))
     sp, x, cell, pbc = to_dev(g, dev)
     symbols = list(g["symbols"])
     q = tuple(ns["CHARGES"][s] for s in symbols)
@@ -1734,6 +1753,8 @@ def test_analytic_pair_potentials_match_reference(dev, case):
         report(f"pair2 {case:20s} {key:8s} max|e_atom err| = {ea:.2e} (scale {escale:.1e})  |F err| = {fe:.2e} (scale {fscale:.1e})")
         # (fp32: the 12th power alone carries ~12 roundings of the distance)
         assert ea < 5e-6 * escale and fe < 1e-5 * fscale, key
+    if g["forces"] is None:   # (a long-row case: no network reference)
+        return
     # through the model's autograd path: networks + one of them
     model.add_pair_potential("zbl", pots["zbl"].to(dev))
     xs = x.clone().requires_grad_(True)
@@ -1747,19 +1768,25 @@ def test_analytic_pair_potentials_match_reference(dev, case):
 
 
 @pytest.mark.parametrize("case", ["rand_batch_ani2x", "water_pbc_ani2x", "small_ani2x", "triclinic_pbc_ani2x",
-                                  "b973c_water_pbc_ani2x"])
+                                  "b973c_water_pbc_ani2x"] + list(LONG_ROW_PAIR_CASES))
 def test_d3_dispersion_matches_reference(dev, case):
     """TwoBodyDispersionD3 (potentials/dftd3.py) against the reference's fp64 values (tests/golden/gen_golden_d3.py:
     cutoff 8 A, smooth envelope): per-atom halves, molecular energies, forces including the dependence of C6 on the
     coordination numbers; alone, as a shard (lo .. hi), inside energies_and_forces together with the networks and the
-    xTB repulsion (the ANI-2xr recipe, arch.py:1176-1181), through autograd, and the virial by finite strain."""
+    xTB repulsion (the ANI-2xr recipe, arch.py:1176-1181), through autograd, and the virial by finite strain.
+
+    The two long-row cases (rows of 256 and 129 entries at 8 A; the potential's own values only) are held to the same
+    gates.  They found that the hardware exponential (__expf) in the coordination-number count and in the Gaussian
+    reference weights cost 9.5e-7 Ha / 1.57e-4 Ha/A on chunk129_pbc/built (both gates missed) and 4.99e-5 Ha/A on
+    chunk256_open/seven, 10 to 1000 times what fp32 rounding of the formula costs; with expf they measure 7.8e-9 / 7.5e-7
+    and 4.2e-10 / 2.5e-8."""
     from torchani_amd.models import ANI2x
     from torchani_amd.potentials import RepulsionXTB, TwoBodyDispersionD3
 
     name = case[6:] if case.startswith("b973c_") else case
-    g = load_golden(name)
+    g = pair_inputs(name)
     gdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    ref = dict(np.load(os.path.join(gdir, f"d3_{case}.npz")))
+    ref = dict(np.load(os.path.join(gdir, f"d3_{case.replace('/', '_')}.npz")))
     sp, x, cell, pbc = to_dev(g, dev)
     model = ANI2x(state_dict=seeded_state("ani2x", 8, g["seed"]), device=dev, periodic_table_index=False,
                   neighborlist=modes_for(g)[-1], row_capacity=256)
@@ -1789,22 +1816,27 @@ def test_d3_dispersion_matches_reference(dev, case):
     pot.accumulate(sp32, rows, ae2, gc2, lo=lo, hi=hi)
     assert torch.equal(ae2[lo:hi], ae[lo:hi]) and torch.equal(gc2[lo:hi], gc[lo:hi])
     assert ae2[:lo].abs().max() == 0 and gc2[hi:].abs().max() == 0
-    # inside the model: networks + repulsion + dispersion
-    rep = dict(np.load(os.path.join(gdir, f"pairs_{name}.npz")))
-    model.add_pair_potential("repulsion_xtb", RepulsionXTB(g["symbols"], cutoff=float(rep["cutoff"]),
-                                                           cutoff_fn=str(rep["cutoff_fn"])).to(dev))
-    model.add_pair_potential("dispersion_d3", pot)
-    out = model.energies_and_forces(sp, x, cell, pbc)
-    e_ref = g["energies"] + rep["energies"] + ref["energies"]
-    f_ref = g["forces"] + rep["forces"] + ref["forces"]
-    assert np.abs(out.energies.cpu().numpy() - e_ref).max() < 1e-5 * max(1.0, np.abs(e_ref).max() * 1e-2) + 1e-5
-    assert np.abs(out.forces.cpu().numpy() - f_ref).max() < F_TOL
-    xs = x.clone().requires_grad_(True)
-    pbc_t = None if pbc is None else torch.tensor(pbc)
-    e = model((sp, xs), cell, pbc_t).energies
-    (gx,) = torch.autograd.grad(e.sum(), xs)
-    assert np.abs(-gx.cpu().numpy() - f_ref).max() < F_TOL
-    if cell is not None and all(pbc):
+    if g["forces"] is not None:   # (a long-row case has no network reference)
+        # inside the model: networks + repulsion + dispersion
+        rep = dict(np.load(os.path.join(gdir, f"pairs_{name}.npz")))
+        model.add_pair_potential("repulsion_xtb", RepulsionXTB(g["symbols"], cutoff=float(rep["cutoff"]),
+                                                               cutoff_fn=str(rep["cutoff_fn"])).to(dev))
+        model.add_pair_potential("dispersion_d3", pot)
+        out = model.energies_and_forces(sp, x, cell, pbc)
+        e_ref = g["energies"] + rep["energies"] + ref["energies"]
+        f_ref = g["forces"] + rep["forces"] + ref["forces"]
+        assert np.abs(out.energies.cpu().numpy() - e_ref).max() < 1e-5 * max(1.0, np.abs(e_ref).max() * 1e-2) + 1e-5
+        assert np.abs(out.forces.cpu().numpy() - f_ref).max() < F_TOL
+        xs = x.clone().requires_grad_(True)
+        pbc_t = None if pbc is None else torch.tensor(pbc)
+        e = model((sp, xs), cell, pbc_t).energies
+        (gx,) = torch.autograd.grad(e.sum(), xs)
+        assert np.abs(-gx.cpu().numpy() - f_ref).max() < F_TOL
+    # (not on the periodic long-row case: the Gaussian reference weights make the energy of its shells too nonlinear in the
+    # strain for this difference -- the reference's fp64 gives -0.43027 at h = 2e-3 and -0.42352 at 1e-4 for component (0, 0),
+    # exact -0.42350 -- and fp32 energies are too coarse for a smaller step; the kernel's virial there is -0.42350 and
+    # 0.013536 for (1, 2), the reference's exact 0.013536)
+    if cell is not None and all(pbc) and g["forces"] is not None:
         # virial of the dispersion term alone = strain derivative of its energy (central differences)
         w = torch.zeros((3, 3), dtype=torch.float64, device=dev)
         pot.accumulate(sp32, rows, None, gc2, w)

@@ -394,7 +394,7 @@ __device__ __forceinline__ void d3_envelope(float r, float cutoff, int smooth, f
 // count(d) and d count / d d (d in Bohr)
 __device__ __forceinline__ float d3_count(float rsum, float d, float &dcnt)
 {
-    const float t = __expf(-D3_K1 * (D3_K2 * rsum / d - 1.0f));
+    const float t = expf(-D3_K1 * (D3_K2 * rsum / d - 1.0f));
     const float c = 1.0f / (1.0f + t);
     dcnt = -c * (1.0f - c) * D3_K1 * D3_K2 * rsum / (d * d);
     return c;
@@ -472,11 +472,11 @@ __global__ __launch_bounds__(256) void k_d3_pair(int64_t n, int64_t lo, int64_t 
             for (int q = 0; q < nv; ++q) {
                 const float4 ref = t[q];
                 const float da = cni - ref.y, db = cnj - ref.z;
-                const float L = __expf(amin - D3_K3 * (da * da + db * db));
+                const float L = expf(amin - D3_K3 * (da * da + db * db));
                 W += L; Z += ref.x * L;
                 dW += L * da; dZ += ref.x * L * da;
             }
-            const float sc = __expf(-amin);   // (0 when there is no reference at all: C6 = eps / eps = 1 like the reference)
+            const float sc = expf(-amin);   // (0 when there is no reference at all: C6 = eps / eps = 1 like the reference)
             W = W * sc + D3_EPS; Z = Z * sc + D3_EPS;
             const float iW = 1.0f / W;
             const float c6 = Z * iW;
