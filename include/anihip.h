@@ -628,7 +628,9 @@ typedef struct {
     int32_t aev_radial_len; /* R of the slab order of wh[0] / wth[0] (0 = plain order) */
     int32_t flags;          /* ANIHIP_MLP_FLAG_* (0 = let the library choose); the library reads no environment */
     int32_t activation;     /* ANIHIP_ACT_CELU (celu_alpha) or ANIHIP_ACT_GELU (torch.nn.GELU(), exact; energies and
-                             * input gradients through the fused network kernel only: 3 hidden layers <= 256 wide) */
+                             * input gradients through the fused network kernel only: 3 hidden layers <= 256 wide whose
+                             * 64-atom tile fits the 160 KB of LDS: padded widths with H2 + max(H1, H3) <= 448.  256 / 192 / 256
+                             * fits, 256 / 256 / 256 does not: a CELU pack with such a species runs layer by layer, all of it) */
     anihip_species_net net[ANIHIP_MAX_SPECIES];
 } anihip_mlp_desc;
 
@@ -693,7 +695,8 @@ int anihip_mlp_forward_backward(void *stream, const anihip_mlp_desc *d, int64_t 
  * as in anihip_mlp_forward_backward; grad_aev (optional) = d Loss / d aev rows, i.e. already scaled by grad_atomic_e.
  * Arithmetic, by descriptor (sums over atoms use float atomics either way: the last bits depend on the execution order):
  *   ANIHIP_MLP_FP32 (any shape, CELU or GELU): exact fp32 on v_mfma_f32_32x32x2_f32, layer by layer; only w / wt / bias are read.
- *   ANIHIP_MLP_F16X3, CELU, three hidden layers <= 256 wide (ANI-1x / ANI-2x) -- the FAST training path (round 5): the forward
+ *   ANIHIP_MLP_F16X3, CELU, three hidden layers <= 256 wide with H2 + max(H1, H3) <= 448 (the fused kernel's LDS budget, see
+ *     anihip_mlp_desc.activation; ANI-1x / ANI-2x) -- the FAST training path (round 5): the forward
  *     and the backward down to d e / d z0 run as ONE launch of the fused network kernel (split-fp16 MFMA, the arithmetic of
  *     inference: per-atom energies within 1e-7 Ha of fp64) for a unit upstream gradient, leaving activations and d e / d z in
  *     the workspace; the weight gradients dW_l = sum_atoms g_a (d e / d z_l)^T x_{l-1} are one launch per layer on

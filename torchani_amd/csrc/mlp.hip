@@ -1836,16 +1836,33 @@ static int check_desc(const anihip_mlp_desc *d)
     return 0;
 }
 
-// widths the fused network kernel covers: 8 waves x one 32-column block
+// dynamic LDS bytes of the fused network kernel for tiles of `rows` atoms of a network with the padded widths H1, H2, H3: the
+// fixed part, then the split planes X1 [2][rows][H2 + pad] | XU [2][rows][max(H1, H3) + pad] (staging slots 1..3 overlay them)
+static size_t fused_lds_bytes(int H1, int H2, int H3, int rows)
+{
+    const size_t xu = H1 > H3 ? H1 : H3;
+    size_t halves = 2 * (size_t)rows * (H2 + FR_XPAD) + 2 * (size_t)rows * (xu + FR_XPAD);
+    const size_t slab = 2 * (size_t)rows * FR_SLAB_LD;
+    if (halves < 3 * FR_GROUP * slab) halves = 3 * FR_GROUP * slab;   // staging slots 1..3
+    halves += FusedCfg<2, 1>::FIXED_HALVES;
+    return halves * 2;
+}
+
+// what a workgroup can have of the CU's LDS on gfx950
+constexpr size_t FUSED_LDS_MAX = 160 * 1024;
+
+// widths the fused network kernel covers: 8 waves x one 32-column block, and a 64-atom tile's activation planes inside the LDS:
+// H2 + max(H1, H3) <= 448 (256 / 192 / 256 fits, as ANI-2x's 256 / 192 / 160 does; 256 / 256 / 256 would need 174.6 KB and
+// cannot be launched: such networks take the layer-by-layer kernels)
 static bool fused_dims_supported(int H1, int H2, int H3)
 {
-    return H1 <= FR_MAXH && H2 <= FR_MAXH && H3 <= FR_MAXH;
+    return H1 <= FR_MAXH && H2 <= FR_MAXH && H3 <= FR_MAXH && fused_lds_bytes(H1, H2, H3, 64) <= FUSED_LDS_MAX;
 }
 
 // Which kernels one anihip_mlp_forward_backward call over n central atoms runs -- decided from the descriptor, n and
 // whether d E / d AEV is wanted alone, so that the workspace query and the call agree.
 struct FbPlan {
-    bool fused;       // k_mlp_fused (f16x3, three hidden layers of width <= 256, at most 32 AEV slabs)
+    bool fused;       // k_mlp_fused (f16x3, three hidden layers of width <= 256 that fit the LDS, at most 32 AEV slabs)
     bool fused_l0b;   // ... with the layer-0 backward as its phase 5 (no d E / d act0 buffer)
     bool big_tiles;   // 256 x 256 tiles for the layer-0 GEMMs outside the fused kernel
     int fused_rows;   // atoms per tile of the fused kernel
@@ -2128,12 +2145,8 @@ static size_t fused_args(const anihip_mlp_desc *d, const MlpWorkspace &w, const 
         fs.is0 = 1.0f / nn.wh_scale[0]; fs.is1 = 1.0f / nn.wh_scale[1]; fs.is2 = 1.0f / nn.wh_scale[2];
         fs.b0 = nn.bias[0]; fs.b1 = nn.bias[1]; fs.b2 = nn.bias[2]; fs.w3 = nn.w[3]; fs.b3 = nn.bias[3];
         fs.bounds = nn.fused_bounds;
-        const size_t xu = fs.H1 > fs.H3 ? fs.H1 : fs.H3;
-        size_t halves = 2 * (size_t)rows * (fs.H2 + FR_XPAD) + 2 * (size_t)rows * (xu + FR_XPAD);
-        const size_t slab = 2 * (size_t)rows * FR_SLAB_LD;
-        if (halves < 3 * FR_GROUP * slab) halves = 3 * FR_GROUP * slab;   // staging slots 1..3
-        halves += FusedCfg<2, 1>::FIXED_HALVES;
-        lds = lds > halves * 2 ? lds : halves * 2;
+        const size_t need = fused_lds_bytes(fs.H1, fs.H2, fs.H3, rows);
+        lds = lds > need ? lds : need;
     }
     f.ctl = w.ctl; f.amax = w.amax; f.aev = aev; f.L = d->aev_len; f.perm = w.perm;
     f.kp_rad = d->aev_radial_len; f.n_slabs = layer0_width(d, true) / 32;
@@ -2169,7 +2182,7 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
     const bool fused = plan.fused;
     // (the layer-by-layer kernels, the 32-atom tiling and the training passes implement CELU only)
     ANIHIP_REQUIRE(d->activation == ANIHIP_ACT_CELU || fused,
-                   "GELU networks run through the fused network kernel only: f16x3 precision, 3 hidden layers <= 256 wide");
+                   "GELU networks run through the fused network kernel only: f16x3 precision, 3 hidden layers <= 256 wide with H2 + max(H1, H3) <= 448");
     // 256 x 256 tiles for the layer-0 GEMMs once there are enough rows to fill the chip with them
     int d0_tm = 0;
     const bool big_tiles = plan.big_tiles;
@@ -2220,7 +2233,7 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
 
     // layer-0 backward inside the fused kernel (fb_plan)
     const bool fused_l0b = plan.fused_l0b;
-    if (d->flags & ANIHIP_MLP_FLAG_FUSED_L0B)
+    if ((d->flags & ANIHIP_MLP_FLAG_FUSED_L0B) && grad_aev)   // (a call without a gradient has no backward to place)
         ANIHIP_REQUIRE(fused_l0b, "ANIHIP_MLP_FLAG_FUSED_L0B needs the fused kernel with CELU networks, wthf[0], first hidden layers of >= 64 and second hidden layers of >= 128 columns");
 
     FinishArgs fin{};
@@ -2437,7 +2450,7 @@ static int train_forward(hipStream_t stream, const anihip_mlp_desc *d, int64_t n
 }
 
 // Does the training pass of this descriptor run through the fused network kernel?  A split-fp16 CELU pack of the shape the
-// fused kernel covers (three hidden layers <= 256 wide, <= 32 AEV slabs, every fragment-ordered plane present).
+// fused kernel covers (three hidden layers <= 256 wide inside its LDS budget, <= 32 AEV slabs, every fragment-ordered plane present).
 static bool train_fused(const anihip_mlp_desc *d)
 {
     if (d->precision != ANIHIP_MLP_F16X3 || d->activation != ANIHIP_ACT_CELU || d->net[0].n_layers != 4) return false;

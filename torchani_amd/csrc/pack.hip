@@ -218,8 +218,10 @@ extern "C" int anihip_mlp_pack(void *stream, const anihip_mlp_shape *sh, const f
                 }
             }
             if (!g.f16) continue;
-            // power-of-two scale putting the largest weight into [2^13, 2^14); planes {hi, lo}
-            const float scale = amax > 0.f ? ldexpf(1.0f, 13 - (int)floorf(log2f(amax))) : 1.0f;
+            // power-of-two scale putting the largest weight into [2^13, 2^14); planes {hi, lo}.  (The exponent from ilogbf:
+            // log2f rounds the largest float below a power of two -- 0x1.fffffep-5 among +-1 / sqrt(256) weights -- up to the
+            // power itself, and the scale came out half of what this line promises)
+            const float scale = amax > 0.f ? ldexpf(1.0f, 13 - ilogbf(amax)) : 1.0f;
             net.wh_scale[l] = scale;
             const int kred = l == 0 ? g.K0h : kin;
             const size_t n_el = (size_t)M * kout * kred;

@@ -961,9 +961,11 @@ class PackedNetworks:
 
     def fast_training(self) -> bool:
         """Do the training passes of this pack run through the fused network kernel (anihip.h: ANIHIP_MLP_F16X3, CELU, three
-        hidden layers <= 256 wide)?"""
+        hidden layers <= 256 wide whose 64-atom tile fits the LDS: H2 + max(H1, H3) <= 448 padded columns)?"""
+        nets = [self.desc.net[s].dims for s in range(self.S)]
         return (self.precision == "f16x3" and self.activation == "celu" and self.nl == 4
-                and all(self.desc.net[s].dims[l] <= 256 for s in range(self.S) for l in (1, 2, 3))
+                and all(dm[l] <= 256 for dm in nets for l in (1, 2, 3))
+                and all(dm[2] + max(dm[1], dm[3]) <= 448 for dm in nets)
                 and self.aev_len <= 1024)
 
     def _freshen_layouts(self, fused_route: bool) -> None:
