@@ -718,6 +718,12 @@ typedef struct {
 } anihip_species_grads;
 
 size_t anihip_mlp_train_workspace_bytes(const anihip_mlp_desc *d, int64_t n_central);
+/* 1 if the training passes of this descriptor take the FAST path above, else 0 (also for a NULL or invalid descriptor): the
+ * library's own rule -- ANIHIP_MLP_F16X3, CELU, the shape the fused network kernel covers (the test anihip_mlp_forward_backward
+ * applies before its flags: depth, widths and LDS budget, at most 32 AEV slabs, every fragment-ordered plane and fused_bounds
+ * present).  Reads the descriptor only and makes no device call: valid for a descriptor packed into host memory.  A caller that
+ * refreshes only the fused layouts of a pack (anihip_mlp_repack, ANIHIP_REPACK_FUSED_ONLY) asks this before it lets a pass read them. */
+int anihip_mlp_fast_training(const anihip_mlp_desc *d);
 int anihip_mlp_weight_grads(void *stream, const anihip_mlp_desc *d, int64_t n_atoms, int64_t lo, int64_t hi,
                             const int32_t *species, const float *aev, const float *grad_atomic_e,
                             void *workspace, size_t workspace_bytes, const anihip_species_grads *grads /* [num_species] */,

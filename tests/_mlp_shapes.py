@@ -32,11 +32,14 @@ species) the columns that only neighbors of the species without atoms could fill
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 import zlib
 
 import numpy as np
 import torch
+
+from torchani_amd import _lib
 
 SHAPES = {
     # name: (K0, hidden widths per species, members)
@@ -82,6 +85,39 @@ def l0b_shape(name):
     return fused_shape(name) and all(pad32(h[0]) >= 64 and pad32(h[1]) >= 128 for h in SHAPES[name][1])
 
 
+# ---- what the library says about its route ---------------------------------------------------------------------------------
+def fb_route(packed, n, flags=0):
+    """"layers" | "fused" (d E / d act0 handed to a layer-0 backward GEMM) | "fused_l0b", from the workspace a
+    forward_backward call of n atoms touches without and with a gradient (csrc/mlp.hip: fb_plan, mlp_carve)"""
+    L = _lib.lib()
+    d = packed.desc
+    old = d.flags
+    d.flags = flags
+    try:
+        need0 = L.anihip_mlp_forward_backward_workspace_bytes(C.byref(d), n, 0)
+        need1 = L.anihip_mlp_forward_backward_workspace_bytes(C.byref(d), n, 1)
+    finally:
+        d.flags = old
+    act0 = 4 * packed.M * max(d.net[s].dims[1] for s in range(packed.S)) * n   # the first hidden layer of every member
+    assert 0 < need0 <= need1 <= L.anihip_mlp_workspace_bytes(C.byref(d), n)
+    if need0 >= act0:
+        assert need1 == need0
+        return "layers"
+    if need1 - need0 >= act0:
+        return "fused"
+    assert need1 == need0
+    return "fused_l0b"
+
+
+VARIANTS = {"f16x3": ("f16x3", 0), "f16x3-unfused": ("f16x3", _lib.MLP_FLAG_NO_FUSED), "f16x3-bigtile": ("f16x3", _lib.MLP_FLAG_BIG_TILES),
+            "f16x3-l0b": ("f16x3", _lib.MLP_FLAG_FUSED_L0B), "fp32": ("fp32", 0)}
+
+
+def expected_route(name, variant):
+    """(a forced layer-0 backward the shape cannot serve leaves the query at "fused": the call itself is refused)"""
+    if variant in ("fp32", "f16x3-unfused") or not fused_shape(name):
+        return "layers"
+    return "fused_l0b" if variant == "f16x3-l0b" and l0b_shape(name) else "fused"
 class Case:
     """name, rot, K0, hidden, M, S, nl; dims [S][nl + 1], flat (fp64 copy of the fp32 parameters, oracle.pack_networks order);
     species int32 [n], aev float32 [n][K0], g_atom float32 [n] (upstream of the training pass), tangent float32 [n][K0];

@@ -21,15 +21,14 @@ gradient arrays (include/anihip.h), which _unpack_grads slices away before anyon
 Atoms that tests/_util.py:celu_kink_atoms flags (a hidden pre-activation within 1e-6 of its scale of zero: CELU's second
 derivative jumps there) get a zero tangent in the second-order comparisons, at most 5 % of a case's atoms (host test).
 """
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from _mlp_shapes import (CASE_IDS, ROTATIONS, SHAPES, fused_shape, l0b_shape, make_case, parameter_lists, stage_stress,
-                         torch_reference)
+from _mlp_shapes import (CASE_IDS, ROTATIONS, SHAPES, VARIANTS, expected_route, fb_route, fused_shape, l0b_shape, make_case,
+                         parameter_lists, stage_stress, torch_reference)
 from _pack_reference import pack_reference
 from _util import block_error_ratios, celu_kink_atoms, grad_blocks, mlp_magnitude_pass
 from test_gpu_hessians import GATE as HVP_GATE
@@ -118,40 +117,6 @@ def oracle_wg(oracle64):
         return made[case_id]
 
     return get
-
-
-# ---- what the library says about its route ---------------------------------------------------------------------------------
-def fb_route(packed, n, flags=0):
-    """"layers" | "fused" (d E / d act0 handed to a layer-0 backward GEMM) | "fused_l0b", from the workspace a
-    forward_backward call of n atoms touches without and with a gradient (csrc/mlp.hip: fb_plan, mlp_carve)"""
-    L = _lib.lib()
-    d = packed.desc
-    old = d.flags
-    d.flags = flags
-    try:
-        need0 = L.anihip_mlp_forward_backward_workspace_bytes(C.byref(d), n, 0)
-        need1 = L.anihip_mlp_forward_backward_workspace_bytes(C.byref(d), n, 1)
-    finally:
-        d.flags = old
-    act0 = 4 * packed.M * max(d.net[s].dims[1] for s in range(packed.S)) * n   # the first hidden layer of every member
-    assert 0 < need0 <= need1 <= L.anihip_mlp_workspace_bytes(C.byref(d), n)
-    if need0 >= act0:
-        assert need1 == need0
-        return "layers"
-    if need1 - need0 >= act0:
-        return "fused"
-    assert need1 == need0
-    return "fused_l0b"
-
-
-VARIANTS = {"f16x3": ("f16x3", 0), "f16x3-unfused": ("f16x3", _lib.MLP_FLAG_NO_FUSED), "f16x3-bigtile": ("f16x3", _lib.MLP_FLAG_BIG_TILES),
-            "f16x3-l0b": ("f16x3", _lib.MLP_FLAG_FUSED_L0B), "fp32": ("fp32", 0)}
-
-
-def expected_route(name, variant):
-    if variant in ("fp32", "f16x3-unfused") or not fused_shape(name):
-        return "layers"
-    return "fused_l0b" if variant == "f16x3-l0b" else "fused"
 
 
 def fb_params():

@@ -9,11 +9,15 @@ reference cannot decide a GPU test.  Measured here: energies 1e-16, member energ
 torch.nn.functional.celu in the torch reference the derivatives differed by 3e-10 (d E / d AEV) to 1e-8 (tangent gradients):
 its backward holds 1 / alpha in fp32 -- tests/_mlp_shapes.py writes CELU out for that reason.
 """
+import ctypes
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from _mlp_shapes import CASE_IDS, ROTATIONS, SHAPES, fused_shape, l0b_shape, make_case, pad32, torch_reference
+from _mlp_shapes import (CASE_IDS, ROTATIONS, SHAPES, VARIANTS, expected_route, fb_route, fused_shape, l0b_shape, make_case, pad32,
+                         torch_reference)
 from _util import celu_kink_atoms, grad_blocks, mlp_magnitude_pass
 from test_abi_and_host import _check_pack_against_reference
 
@@ -106,6 +110,65 @@ def test_pack_layout_of_every_shape(name):
     assert fp.radial_len == 0 and not fp.fast_training()
     if fused_shape(name):
         _check_pack_against_reference(W, B, c.K0, activation="gelu")
+
+
+@functools.lru_cache(maxsize=None)
+def host_pack(name, precision="f16x3", activation="celu"):
+    """the shape's first case packed into host memory: the route questions below read the descriptor alone"""
+    from torchani_amd.engine import PackedNetworks
+
+    c = make_case(f"{name}-r0")
+    W, B = c.weights()
+    return PackedNetworks(W, B, c.K0, 0.1, torch.device("cpu"), precision=precision, activation=activation)
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_route_of_every_shape_and_variant(name, variant):
+    """The route the GPU tests assert before they run a case (tests/test_gpu_network_shapes.py), from the workspace query alone:
+    it is host code (csrc/mlp.hip: fb_plan), so every shape x variant is checked here without a device."""
+    precision, flags = VARIANTS[variant]
+    n = make_case(f"{name}-r0").species.size
+    assert fb_route(host_pack(name, precision), n, flags) == expected_route(name, variant)
+
+
+L0B_MIN_ATOMS = 24000   # csrc/mlp_fused.h: FUSED_L0B_MIN_ATOMS
+
+
+def test_layer0_backward_moves_inside_the_fused_kernel_at_its_threshold():
+    """Default flags: below FUSED_L0B_MIN_ATOMS atoms d E / d act0 is handed to a layer-0 backward GEMM, from it on the backward
+    runs inside the kernel -- unless a flag says no, or the networks are GELU (that instantiation has no phase 5)."""
+    from torchani_amd import _lib
+
+    names = [name for name in SHAPES if l0b_shape(name)]
+    assert names
+    for name in names:
+        pk = host_pack(name)
+        assert fb_route(pk, L0B_MIN_ATOMS - 1) == "fused"
+        assert fb_route(pk, L0B_MIN_ATOMS) == "fused_l0b"
+        assert fb_route(pk, L0B_MIN_ATOMS, _lib.MLP_FLAG_NO_FUSED_L0B) == "fused"
+        assert fb_route(pk, L0B_MIN_ATOMS, _lib.MLP_FLAG_SMALL_TILES) == "fused"
+        assert fb_route(host_pack(name, activation="gelu"), L0B_MIN_ATOMS) == "fused"
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_fast_training_is_the_library_rule(name):
+    """PackedNetworks.fast_training() is anihip_mlp_fast_training: true exactly where forward_backward of a split-fp16 CELU pack
+    runs fused, false for fp32 and GELU packs; and the library looks at the planes, not only at the widths."""
+    from torchani_amd import _lib
+
+    pk = host_pack(name)
+    assert pk.fast_training() == (fb_route(pk, 1 << 16) != "layers") == fused_shape(name)
+    assert not host_pack(name, "fp32").fast_training()
+    L = _lib.lib()
+    assert L.anihip_mlp_fast_training(None) == 0
+    if fused_shape(name):
+        gelu = host_pack(name, activation="gelu")
+        assert fb_route(gelu, 1 << 16) == "fused" and not gelu.fast_training()
+        d = _lib.MlpDesc.from_buffer_copy(pk.desc)
+        assert L.anihip_mlp_fast_training(ctypes.byref(d)) == 1
+        d.net[pk.S - 1].whf[1] = None   # (a descriptor without one fragment-ordered plane: no fused kernel, whatever the widths)
+        assert L.anihip_mlp_fast_training(ctypes.byref(d)) == 0
 
 
 def test_refusals_on_the_host_path():

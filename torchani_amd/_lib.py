@@ -220,6 +220,8 @@ def lib() -> C.CDLL:
                                               vp, vp]
     L.anihip_mlp_train_workspace_bytes.restype = sz
     L.anihip_mlp_train_workspace_bytes.argtypes = [C.POINTER(MlpDesc), i64]
+    L.anihip_mlp_fast_training.restype = C.c_int
+    L.anihip_mlp_fast_training.argtypes = [C.POINTER(MlpDesc)]
     L.anihip_mlp_weight_grads.argtypes = [vp, C.POINTER(MlpDesc), i64, i64, i64, vp, vp, vp, vp, sz,
                                           C.POINTER(SpeciesGrads), vp, vp, i32]
     L.anihip_mlp_tangent_workspace_bytes.restype = sz
@@ -305,6 +307,7 @@ EXPORTED_SYMBOLS = [
     "anihip_nbr_build_batch", "anihip_nbr_build_cell", "anihip_nbr_half_workspace_bytes", "anihip_nbr_from_half", "anihip_nbr_from_full",
     "anihip_nbr_refresh", "anihip_aev_forward", "anihip_aev_forward_update", "anihip_aev_backward", "anihip_aev_backward_virial", "anihip_aev_jvp",
     "anihip_mlp_workspace_bytes", "anihip_mlp_forward_backward_workspace_bytes", "anihip_mlp_forward_backward", "anihip_mlp_train_workspace_bytes",
+    "anihip_mlp_fast_training",
     "anihip_mlp_weight_grads", "anihip_mlp_train_forward", "anihip_mlp_repack", "anihip_adam_step", "anihip_energy_reduce",
     "anihip_mlp_tangent_workspace_bytes", "anihip_mlp_tangent_weight_grads", "anihip_pair_xtb_repulsion",
     "anihip_pair_d3", "anihip_pair_analytic", "anihip_energy_forces_finish", "anihip_mlp_pack_bytes", "anihip_mlp_pack",

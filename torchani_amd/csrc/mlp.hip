@@ -7,7 +7,7 @@
 //   A. split-fp16 ("f16x3", default), three hidden layers of width <= 256 (ANI-1x / ANI-2x):
 //        >= 16384 atoms: k_tile_table -> k_mlp_fused<RB,NB> -> k_fused_finish -> k_gemm_l0b + k_gemm_h2<EPI_SCATTER>
 //        >= 24000 atoms: k_tile_table (-> k_tile_order: tiles by falling cost, drawn from a queue) -> k_mlp_fused<2,1,ACT,L0B = true>
-//                        (layer-0 backward inside: phase 5; ANIHIP_MLP_FLAG_SHAPED: one launch per species with compile-time widths,
+//                        (layer-0 backward inside: phase 5; with the SHAPED flag: one launch per species with compile-time widths,
 //                        queued on two streams from four rounds of tiles on) -> k_fused_finish
 //        fewer:          k_small_prep (bucketing + tile table + padding rows) -> k_mlp_fused -> k_gemm_l0s (+ finish)
 //      one fused kernel from the AEV rows to d E / d act0 (layer 0 only over the AEV slabs flagged non-zero,
@@ -1859,33 +1859,65 @@ static bool fused_dims_supported(int H1, int H2, int H3)
     return H1 <= FR_MAXH && H2 <= FR_MAXH && H3 <= FR_MAXH && fused_lds_bytes(H1, H2, H3, 64) <= FUSED_LDS_MAX;
 }
 
-// Which kernels one anihip_mlp_forward_backward call over n central atoms runs -- decided from the descriptor, n and
-// whether d E / d AEV is wanted alone, so that the workspace query and the call agree.
+// atoms per tile of the fused kernel: 64 atoms x 8 waves, one workgroup per CU (the 32-atom / two-workgroups-per-CU tiling of
+// rounds 1-4 was 3 % slower and spilled 300 registers: removed in round 5)
+constexpr int FUSED_ROWS = 64;
+// upper bound of the fused kernel's tiles over n sorted atoms: one partly filled tile per species
+static int64_t fused_tile_count(int64_t n, int S) { return (n + FUSED_ROWS - 1) / FUSED_ROWS + S; }
+// the flags of n_slabs layer-0 slabs, all set
+static uint32_t all_slabs_mask(int n_slabs) { return n_slabs >= 32 ? 0xFFFFFFFFu : ((1u << n_slabs) - 1u); }
+
+// Is this a pack the fused network kernel covers?  Split-fp16, three hidden layers <= 256 wide inside its LDS budget, at most 32
+// AEV slabs, every fragment-ordered plane and the operand bounds present.  Of the descriptor alone, not of its flags: inference
+// (fb_plan) and the training passes (train_fused, anihip_mlp_fast_training) ask the same question.
+static bool fused_shape(const anihip_mlp_desc *d)
+{
+    bool ok = d->precision == ANIHIP_MLP_F16X3 && d->net[0].n_layers == 4 && layer0_width(d, true) <= 32 * 32 && d->aev_len % 4 == 0;
+    for (int s = 0; s < d->num_species && ok; ++s) {
+        const anihip_species_net &nn = d->net[s];
+        ok = nn.whf[0] && nn.whf[1] && nn.whf[2] && nn.wthf[1] && nn.wthf[2] && nn.fused_bounds && fused_dims_supported(nn.dims[1], nn.dims[2], nn.dims[3]);
+    }
+    return ok;
+}
+
+// The route of one anihip_mlp_forward_backward call: every decision that follows from the descriptor (its flags included), the
+// number n of central atoms, whether d E / d AEV is wanted and whether the caller gave slab flags -- made here, once, so that the
+// workspace query and the stages of the call agree.  (The CU count and the grid, a stream capture and whether the workspace has
+// a sorted tile table depend on the device, the stream or the buffer: decided where they are launched.)
 struct FbPlan {
-    bool fused;       // k_mlp_fused (f16x3, three hidden layers of width <= 256 that fit the LDS, at most 32 AEV slabs)
-    bool fused_l0b;   // ... with the layer-0 backward as its phase 5 (no d E / d act0 buffer)
-    bool big_tiles;   // 256 x 256 tiles for the layer-0 GEMMs outside the fused kernel
-    int fused_rows;   // atoms per tile of the fused kernel
-    int n_act;        // hidden-layer buffers of the workspace this call touches (mlp_carve)
+    const char *refusal;   // why the call cannot be served (NULL: it can); the workspace query ignores it
+    bool small_prep;       // bucketing, tile table and padding rows in one launch
+    int K0p, kp_rad, n_slabs;   // layer-0 reduction length, radial part of the slab order (0: plain order), K0p / 32
+    uint32_t all_slabs; int64_t fused_tiles;
+    // who honours the caller's per-atom slab flags: the tile table of the fused kernel (the ANI slab order of anihip_aev_forward's
+    // flags, or -- kp_rad = 0, rows of at most 1024 columns -- the plain 32-column slabs of the general AEV kernel), the layer-0
+    // forward in 256 x 256 tiles, the layer-0 backward (it compacts its output columns in both tilings)
+    bool mask_tab, mask_l0f, mask_l0b;
+    bool fused;            // k_mlp_fused (fused_shape) from the AEV rows to d E / d act0, then the layer-0 backward GEMM
+    bool fused_l0b;        // ... with the layer-0 backward as its phase 5 (no d E / d act0 buffer)
+    int variant;           // FusedVariant of the launch
+    bool shaped;           // one launch per species with compile-time widths
+    bool tile_queue_ok;    // tiles by falling cost, drawn from a queue (if the workspace has the table and they outnumber the grid)
+    bool d0_tm;            // tile-major hand-over to the 256 x 256 layer-0 backward GEMM (the 128 x 128 kernels read rows)
+    bool big_tiles;        // 256 x 256 tiles for the layer-0 GEMMs outside the fused kernel
+    bool use_l0s;          // few atoms: the backward in the 8-wave 128 x 128 kernel (needs the slab flags for its column compaction)
+    int n_act;             // hidden-layer buffers this call touches (mlp_carve); independent of have_slab_mask
 };
-static FbPlan fb_plan(const anihip_mlp_desc *d, int64_t n, bool want_grad)
+static FbPlan fb_plan(const anihip_mlp_desc *d, int64_t n, bool want_grad, bool have_slab_mask)
 {
     FbPlan p{};
-    const int S = d->num_species, nh = d->net[0].n_layers - 1, L = d->aev_len;
-    const bool h3 = d->precision == ANIHIP_MLP_F16X3;
-    const int K0p = layer0_width(d, h3);
-    p.fused = h3 && nh == 3 && K0p <= 32 * 32 && L % 4 == 0;
-    for (int s = 0; s < S && p.fused; ++s) {
-        const anihip_species_net &nn = d->net[s];
-        p.fused = p.fused && nn.whf[0] && nn.whf[1] && nn.whf[2] && nn.wthf[1] && nn.wthf[2] && nn.fused_bounds &&
-                  fused_dims_supported(nn.dims[1], nn.dims[2], nn.dims[3]);
-    }
-    if (d->flags & ANIHIP_MLP_FLAG_NO_FUSED) p.fused = false;
+    const int S = d->num_species, nh = d->net[0].n_layers - 1;
+    const unsigned fl = (unsigned)d->flags;
+    const bool h3 = d->precision == ANIHIP_MLP_F16X3, celu = d->activation == ANIHIP_ACT_CELU;
+    p.small_prep = n <= SMALL_PREP_MAX;
+    p.kp_rad = h3 ? d->aev_radial_len : 0; p.K0p = layer0_width(d, h3);
+    p.n_slabs = p.K0p / 32; p.all_slabs = all_slabs_mask(p.n_slabs);
+    p.fused_tiles = fused_tile_count(n, S);
+    p.fused = fused_shape(d) && !(fl & ANIHIP_MLP_FLAG_NO_FUSED);
     // 256 x 256 tiles for the layer-0 GEMMs once there are enough rows to fill the chip with them
     p.big_tiles = h3 && n >= 16384;
-    if (d->flags & ANIHIP_MLP_FLAG_BIG_TILES) p.big_tiles = h3;
-    if (d->flags & ANIHIP_MLP_FLAG_SMALL_TILES) p.big_tiles = false;
-    p.fused_rows = 64;   // (the 32-atom / two-workgroups-per-CU tiling of rounds 1-4 was 3 % slower and spilled 300 registers: removed in round 5)
+    if (fl & ANIHIP_MLP_FLAG_BIG_TILES) p.big_tiles = h3;
+    if (fl & ANIHIP_MLP_FLAG_SMALL_TILES) p.big_tiles = false;
     // Layer-0 backward INSIDE the fused kernel (its phase 5): a workgroup owns a tile through all members and adds the
     // members' d E / d AEV in place -- no d act0 round trip through HBM (8 KB per atom written and read back), no layer-0
     // backward launch.  Tiles are then the unit of work (not tile x member items), so it needs enough of them to balance
@@ -1896,20 +1928,37 @@ static FbPlan fb_plan(const anihip_mlp_desc *d, int64_t n, bool want_grad)
     auto l0b_ok = [&](int s) { return d->net[s].wthf[0] != nullptr && d->net[s].dims[2] >= 128 && d->net[s].dims[1] >= 64; };
     // (CELU networks: the GELU instantiation with phase 5 spilled registers and served ANI-2xr on > 65 536 atoms only --
     // removed in round 5, those systems take the d act0 hand-over + layer-0 backward GEMM)
-    const bool celu = d->activation == ANIHIP_ACT_CELU;
     p.fused_l0b = p.fused && want_grad && celu && n >= FUSED_L0B_MIN_ATOMS &&
-                  !(d->flags & (ANIHIP_MLP_FLAG_NO_FUSED_L0B | ANIHIP_MLP_FLAG_SMALL_TILES));
-    if (d->flags & ANIHIP_MLP_FLAG_FUSED_L0B)   // (forced, e.g. by the tests on small inputs; the call checks that it can)
+                  !(fl & (ANIHIP_MLP_FLAG_NO_FUSED_L0B | ANIHIP_MLP_FLAG_SMALL_TILES));
+    if (fl & ANIHIP_MLP_FLAG_FUSED_L0B)   // (forced, e.g. by the tests on small inputs)
         p.fused_l0b = p.fused && want_grad && celu;
     for (int s = 0; s < S && p.fused_l0b; ++s) p.fused_l0b = l0b_ok(s);
+    // (two products off by default: the backward GEMMs of the large-system path -- forces then differ from the three-product
+    // result by ~1e-6 Ha/A, inside north_star's 1e-4 gate and outside this package's 5e-6 regression gate)
+    p.variant = p.fused_l0b ? ((fl & ANIHIP_MLP_FLAG_BWD_TWO_PRODUCTS) ? FUSED_CELU_L0B_B2 : FUSED_CELU_L0B)
+                            : (celu ? FUSED_CELU : FUSED_GELU);
+    p.shaped = p.variant == FUSED_CELU_L0B && (fl & ANIHIP_MLP_FLAG_SHAPED);
+    p.tile_queue_ok = ANIHIP_TILE_QUEUE && FUSED_OWNER_GROUP == 1 && p.variant == FUSED_CELU_L0B && !p.shaped &&
+                      p.fused_tiles <= FUSED_TILE_QUEUE_MAX && !p.small_prep;
+    p.d0_tm = p.fused && p.big_tiles && want_grad && !(fl & ANIHIP_MLP_FLAG_D0_ROWS);
+    const bool masked = have_slab_mask && !(fl & ANIHIP_MLP_FLAG_NO_SLAB_MASK), k_fits = p.K0p <= 32 * 32;
+    p.mask_tab = masked && (p.kp_rad > 0 || (h3 && k_fits));
+    p.mask_l0b = masked && p.kp_rad > 0 && k_fits;
+    p.mask_l0f = p.mask_l0b && p.big_tiles;
+    p.use_l0s = want_grad && !p.fused_l0b && !p.big_tiles && p.mask_l0b;
     p.n_act = !p.fused ? nh : ((want_grad && !p.fused_l0b) ? 1 : 0);
+    // (the layer-by-layer kernels and the training passes implement CELU only)
+    if (!celu && !p.fused)
+        p.refusal = "GELU networks run through the fused network kernel only: f16x3 precision, 3 hidden layers <= 256 wide with H2 + max(H1, H3) <= 448";
+    else if ((fl & ANIHIP_MLP_FLAG_FUSED_L0B) && want_grad && !p.fused_l0b)   // (a call without a gradient has no backward to place)
+        p.refusal = "ANIHIP_MLP_FLAG_FUSED_L0B needs the fused kernel with CELU networks, wthf[0], first hidden layers of >= 64 and second hidden layers of >= 128 columns";
     return p;
 }
 
 extern "C" size_t anihip_mlp_forward_backward_workspace_bytes(const anihip_mlp_desc *d, int64_t n_central, int want_grad)
 {
     if (!d || n_central < 0 || d->net[0].n_layers < 2 || d->net[0].n_layers > ANIHIP_MAX_LAYERS) return 0;
-    return mlp_carve(d, n_central, nullptr, nullptr, fb_plan(d, n_central, want_grad != 0).n_act);
+    return mlp_carve(d, n_central, nullptr, nullptr, fb_plan(d, n_central, want_grad != 0, false).n_act);
 }
 
 #ifndef ANIHIP_SHAPED_OVERLAP
@@ -2155,268 +2204,229 @@ static size_t fused_args(const anihip_mlp_desc *d, const MlpWorkspace &w, const 
     return lds;
 }
 
+// what k_fused_finish (or the extra workgroups of k_gemm_l0s) needs to sum the per-member energies of the fused kernel
+static FinishArgs finish_args(const anihip_mlp_desc *d, const MlpWorkspace &w, int64_t n_atoms, float *atomic_e, float *member_e)
+{
+    return FinishArgs{w.ctl, w.perm, w.member_part, atomic_e, member_e, n_atoms, d->num_species, d->n_members, /* first_block */ 0};
+}
+
+// the arguments of one anihip_mlp_forward_backward call, as its stages below see them (n = hi - lo)
+struct FbCall {
+    hipStream_t stream; const anihip_mlp_desc *d; int64_t n_atoms, lo, hi, n;
+    const int32_t *species; const float *aev; const uint32_t *slab_mask; float *atomic_e, *grad_aev, *member_e;
+};
+
+// bucket by species (+ the tile table of the fused kernel and the padding rows, one launch for small inputs)
+static int fb_prepare(const FbCall &c, const FbPlan &p, const MlpWorkspace &w)
+{
+    const int S = c.d->num_species, M = c.d->n_members, L = c.d->aev_len;
+    const uint32_t *tab_mask = p.mask_tab ? c.slab_mask : nullptr;
+    if (p.small_prep)
+        return launch_small_prep(c.stream, c.lo, c.hi, c.species, S, w.ctl, w.perm, tab_mask, p.all_slabs, (int)p.fused_tiles,
+                                 FUSED_ROWS, p.fused ? w.tile_tab : (int4 *)nullptr, w.tile_rows, c.atomic_e, c.grad_aev, L,
+                                 c.member_e, M, c.n_atoms);
+    // (scratch of the counting sort: the per-member energies buffer is written only later)
+    launch_bucketing(c.stream, c.lo, c.hi, c.species, S, w.ctl, CTL_WORDS + AMAX_WORDS, reinterpret_cast<int *>(w.member_part), w.perm,
+                     c.atomic_e, c.grad_aev, L, c.member_e, M, c.n_atoms);
+    if (p.fused)
+        launch_tile_table(c.stream, w.ctl, S, w.perm, tab_mask, p.all_slabs, (int)p.fused_tiles, FUSED_ROWS, w.tile_tab, w.tile_rows);
+    return 0;
+}
+
+// layer by layer: forward through the hidden layers, then the output layer (+ seed of the backward pass, in place over the last activations)
+static int fb_layers_forward(const FbCall &c, const FbPlan &p, const MlpWorkspace &w)
+{
+    const anihip_mlp_desc *d = c.d;
+    const int nh = d->net[0].n_layers - 1;
+    const bool h3 = d->precision == ANIHIP_MLP_F16X3;
+    for (int l = 0; l < nh; ++l) {
+        GemmArgs g = gemm_args(d, w.ctl, c.n);
+        fwd_problems(g, d, l, true, h3, p.K0p);
+        g.C = w.act[l]; g.ldc = w.ld[l];
+        if (l == 0) { g.A = c.aev; g.lda = d->aev_len; g.a_gather = w.perm; g.kp_rad = p.kp_rad; g.stage_mask = p.mask_l0f ? c.slab_mask : nullptr; }
+        else { g.A = w.act[l - 1]; g.lda = w.ld[l - 1]; }
+        g.amax = w.amax; g.amax_out = h3 ? l : -1; g.amax_in = (h3 && l > 0) ? l - 1 : -1;
+        g.a_static_scale = 4.0f;  // layer-0 input: |aev| < 16376 by construction (see include/anihip.h)
+        if (l > 0 || !p.big_tiles) launch_gemm<EPI_BIAS_CELU>(c.stream, g, h3);
+        else if (int rc = launch_gemm_big<EPI_BIAS_CELU>(c.stream, g, c.n)) return rc;
+    }
+    HeadArgs h{};
+    h.atomic_e = c.atomic_e; h.member_e = c.member_e; h.want_grad = c.grad_aev ? 1 : 0; h.amax = h3 ? w.amax : nullptr; h.amax_out = 3;
+    launch_head(c.stream, d, w, c.n_atoms, c.n, h);
+    return 0;
+}
+
+// One launch of the fused kernel per species, restricted to its tiles, with the network widths as compile-time constants where an
+// instantiation exists (every ANI-2x network and ANI-1x hydrogen); a species without atoms exits at once.  Every launch ends with a
+// partly filled last round of the CUs (the hydrogen tiles of the 2.34 M-atom water box: 16 of 256 workgroups, eight items long).
+// The launches alternate between the caller's stream and a second one (forked and joined with events; they touch disjoint atoms)
+// and draw their tiles from a queue per species: the next species' workgroups start on the CUs as they come free and take fewer
+// tiles the later they start.  (Without the queue the overlap buys nothing: a late workgroup then carries its static share to the
+// end.)  Not inside a stream capture (the step then stays a chain of kernel nodes).
+// (the shaped variants' LDS limits are set before the fork: nothing between the fork and the join may return, or
+// the work queued on the process-wide second stream would never be joined back to the caller's stream)
+static int fb_fused_per_species(hipStream_t stream, const MlpWorkspace &w, FusedArgs &f, int64_t grid, size_t lds)
+{
+    static const int known[4][4] = {{256, 192, 160, FUSED_CELU_L0B_256}, {192, 160, 128, FUSED_CELU_L0B_192},
+                                    {224, 192, 160, FUSED_CELU_L0B_224}, {160, 128, 96, FUSED_CELU_L0B_160}};
+    const int S = f.S;
+    int shaped[MAX_S];
+    for (int s = 0; s < S; ++s) {
+        const FusedSpecies &fs = f.sp[s];
+        int v = FUSED_CELU_L0B;
+        for (const auto &k : known) if (fs.H1 == k[0] && fs.H2 == k[1] && fs.H3 == k[2]) v = k[3];
+        if (v != FUSED_CELU_L0B) ANIHIP_CHECK_HIP(hipFuncSetAttribute(fused_kernel(v), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        shaped[s] = v;
+    }
+    OverlapSet *ov = nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    // (from four rounds of tiles on: below, the fork / join and the draws cost more than they balance -- water boxes of
+    // 24 000 / 41 472 atoms 0.399 / 0.606 ms against 0.385 / 0.581 with plain launches; 81 000: 1.01 against 1.10)
+    if (ANIHIP_SHAPED_OVERLAP && f.tiles_total >= 4 * grid && S <= CTL_WORDS - CTL_QUEUE) {
+        if (hipStreamIsCapturing(stream, &cap) != hipSuccess)
+            (void)hipGetLastError();   // (not a reason to fail the call: plain launches)
+        else if (cap == hipStreamCaptureStatusNone)
+            ov = overlap_resources();
+    }
+    std::unique_lock<std::mutex> ov_lock;
+    hipStream_t aux = nullptr;
+    if (ov) {
+        ov_lock = std::unique_lock<std::mutex>(ov->mu);
+        aux = ov->st;
+        ANIHIP_CHECK_HIP(hipEventRecord(ov->fork, stream));
+        ANIHIP_CHECK_HIP(hipStreamWaitEvent(aux, ov->fork, 0));
+    }
+    for (int s = 0; s < S; ++s) {
+        f.only_species = s;
+        f.queue = aux ? w.ctl + CTL_QUEUE + s : nullptr;   // (zeroed with the control block by the bucketing)
+        launch_fused(shaped[s], (unsigned)grid, lds, (aux && (s & 1)) ? aux : stream, f);
+    }
+    if (ov) {
+        ANIHIP_CHECK_HIP(hipEventRecord(ov->join, aux));
+        ANIHIP_CHECK_HIP(hipStreamWaitEvent(stream, ov->join, 0));
+    }
+    return 0;
+}
+
+// fused network kernel: one kernel from the AEV rows to d E / d act0 (or, with the layer-0 backward inside, to d E / d AEV),
+// then the sum of the per-member energies
+static int fb_fused(const FbCall &c, const FbPlan &p, const MlpWorkspace &w)
+{
+    const anihip_mlp_desc *d = c.d;
+    FusedArgs f{};
+    const size_t lds = fused_args(d, w, c.aev, FUSED_ROWS, f);
+    f.slab_mask = p.mask_tab ? c.slab_mask : nullptr;
+    f.d0 = p.fused_l0b ? nullptr : w.act[0]; f.ld0 = w.ld[0]; f.d0_tm = p.d0_tm ? 1 : 0;
+    f.want_grad = c.grad_aev ? 1 : 0; f.l0b = p.fused_l0b ? 1 : 0; f.grad_aev = c.grad_aev;
+    f.owner = p.fused_l0b ? FUSED_OWNER_GROUP : 0;   // (member-major sweep, or -- layer-0 backward inside -- owner order)
+    ANIHIP_CHECK_HIP(hipFuncSetAttribute(fused_kernel(p.variant), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t tiles = p.fused_tiles; f.tiles_total = (int)tiles;
+    // persistent workgroups over the (member, tile) items, as many as are resident at once
+    int n_cus;
+    if (int rc = cu_count(&n_cus)) return rc;
+    const int64_t items = tiles * d->n_members;
+    const int64_t resident = (int64_t)n_cus * (2 * lds <= 160 * 1024 ? 2 : 1);
+    const int64_t units = f.owner ? tiles : items;
+    const int64_t grid = units < resident ? units : resident;
+#ifdef ANIHIP_DEV_TRACE   // development builds only (tools/fused_trace.py): per-item phase stamps, allocates and synchronises
+    const char *trace_path = getenv("ANIHIP_FUSED_TRACE");
+    const size_t trace_words = (size_t)32 * 8 * items;   // [item][wave][32]
+    if (trace_path) {
+        ANIHIP_CHECK_HIP(hipMalloc((void **)&f.trace, sizeof(unsigned long long) * trace_words));
+        ANIHIP_CHECK_HIP(hipMemset(f.trace, 0, sizeof(unsigned long long) * trace_words));
+    }
+#endif
+    f.only_species = -1; f.queue = nullptr;
+    if (p.tile_queue_ok && w.tile_tab2 && tiles > grid) {
+        TileOrderArgs to{};
+        to.tile_tab = w.tile_tab; to.tile_rows = w.tile_rows; to.tile_tab2 = w.tile_tab2; to.tile_rows2 = w.tile_rows2;
+        to.tiles_total = (int)tiles;
+        for (int s = 0; s < f.S; ++s) to.H1[s] = f.sp[s].H1;
+        launch_tile_order(c.stream, to);
+        f.tile_tab = w.tile_tab2; f.tile_rows = w.tile_rows2; f.queue = w.ctl + CTL_QUEUE;
+    }
+    if (p.shaped) {
+        if (int rc = fb_fused_per_species(c.stream, w, f, grid, lds)) return rc;
+    } else {
+        launch_fused(p.variant, (unsigned)grid, lds, c.stream, f);
+    }
+#ifdef ANIHIP_DEV_TRACE
+    if (trace_path) {
+        ANIHIP_CHECK_HIP(hipStreamSynchronize(c.stream));
+        std::vector<unsigned long long> host(trace_words);
+        ANIHIP_CHECK_HIP(hipMemcpy(host.data(), f.trace, host.size() * 8, hipMemcpyDeviceToHost));
+        ANIHIP_CHECK_HIP(hipFree(f.trace));
+        if (FILE *fp = fopen(trace_path, "wb")) {
+            fwrite(host.data(), 8, host.size(), fp);
+            fclose(fp);
+        }
+    }
+#endif
+    // (the 8-wave layer-0 backward of small inputs sums the energies in extra workgroups)
+    if (!p.use_l0s) launch_fused_finish(c.stream, finish_args(d, w, c.n_atoms, c.atomic_e, c.member_e), c.n);
+    return 0;
+}
+
+// backward to the AEV rows: from the seed of the output layer, or -- fused -- the layer-0 backward of d E / d act0 alone
+static int fb_backward(const FbCall &c, const FbPlan &p, const MlpWorkspace &w)
+{
+    const anihip_mlp_desc *d = c.d;
+    const int S = d->num_species, M = d->n_members, nh = d->net[0].n_layers - 1, L = d->aev_len;
+    const bool h3 = d->precision == ANIHIP_MLP_F16X3;
+    for (int l = p.fused ? 0 : nh - 1; l >= 0; --l) {
+        GemmArgs g = gemm_args(d, w.ctl, c.n);
+        g.act = ANIHIP_ACT_CELU;   // (a GELU network gets here for the layer-0 backward only: no activation)
+        bwd_problems(g, d, l, p.K0p, h3);
+        g.A = w.act[l]; g.lda = w.ld[l];
+        g.amax = w.amax; g.amax_in = h3 ? 3 + (nh - 1 - l) : -1; g.amax_out = (h3 && l > 0) ? 3 + (nh - l) : -1;
+        g.a_static_scale = 1.0f;
+        if (l > 0) {
+            g.C = w.act[l - 1]; g.ldc = w.ld[l - 1];
+            launch_gemm<EPI_DCELU>(c.stream, g, h3);
+            continue;
+        }
+        g.C = c.grad_aev; g.ldc = L; g.c_scatter = w.perm; g.n_store = L;
+        g.kp_rad = p.kp_rad; g.stage_mask = p.mask_l0b ? c.slab_mask : nullptr;
+        if (p.d0_tm) g.a_tm_members = M;
+        for (int s = 0; s < S && p.d0_tm; ++s) g.a_tm_h[s] = d->net[s].dims[1];
+        if (p.big_tiles) {
+            if (int rc = launch_gemm_big<EPI_SCATTER>(c.stream, g, c.n)) return rc;
+        } else if (p.use_l0s) {
+            const int64_t total = (int64_t)g.nrow_tiles_ub * g.ncol_max;
+            const size_t lds = sizeof(_Float16) * L0S_BUFS * 4 * H_PLANE;
+            ANIHIP_CHECK_HIP(hipFuncSetAttribute((const void *)k_gemm_l0s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            FinishArgs fin{};   // (behind the fused kernel: extra workgroups that sum its per-member energies)
+            if (p.fused) { fin = finish_args(d, w, c.n_atoms, c.atomic_e, c.member_e); fin.first_block = (int)total; }
+            const int64_t fb = p.fused ? (c.n + L0S_THREADS - 1) / L0S_THREADS : 0;
+            hipLaunchKernelGGL(k_gemm_l0s, dim3((unsigned)(total + fb)), dim3(L0S_THREADS), lds, c.stream, g, fin);
+        } else {
+            launch_gemm<EPI_SCATTER>(c.stream, g, h3);
+        }
+    }
+    return 0;
+}
+
 extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc *d, int64_t n_atoms,
                                            int64_t lo, int64_t hi, const int32_t *species, const float *aev,
                                            const uint32_t *slab_mask, void *workspace, size_t workspace_bytes,
                                            float *atomic_e, float *grad_aev, float *member_e)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = check_desc(d)) return rc;
+    if (int rc = check_desc(d)) return rc;   // 1. validate
     ANIHIP_REQUIRE(species && aev && workspace && atomic_e, "null pointer argument");
     ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
-    const int64_t n = hi - lo;
-    if (n == 0) return 0;
-    const FbPlan plan = fb_plan(d, n, grad_aev != nullptr);
-    ANIHIP_REQUIRE(workspace_bytes >= mlp_carve(d, n, nullptr, nullptr, plan.n_act),
+    const FbCall c{(hipStream_t)stream_, d, n_atoms, lo, hi, hi - lo, species, aev, slab_mask, atomic_e, grad_aev, member_e};
+    if (c.n == 0) return 0;
+    const FbPlan plan = fb_plan(d, c.n, grad_aev != nullptr, slab_mask != nullptr);   // 2. plan (refusals before the first launch)
+    ANIHIP_REQUIRE(!plan.refusal, "%s", plan.refusal);
+    ANIHIP_REQUIRE(workspace_bytes >= mlp_carve(d, c.n, nullptr, nullptr, plan.n_act),
                    "workspace too small (anihip_mlp_forward_backward_workspace_bytes)");
     MlpWorkspace w;
-    mlp_carve(d, n, (char *)workspace, &w, plan.n_act);
-    const int S = d->num_species, M = d->n_members, nh = d->net[0].n_layers - 1;
-    const int L = d->aev_len;
-    const bool h3 = d->precision == ANIHIP_MLP_F16X3;
-    const int kp_rad = h3 ? d->aev_radial_len : 0;
-    const int K0p = layer0_width(d, h3);
-
-    // fused network kernel (f16x3, three hidden layers of width <= 256, at most 32 AEV slabs): one kernel
-    // from the AEV rows to d E / d act0, then the layer-0 backward GEMM
-    const bool fused = plan.fused;
-    // (the layer-by-layer kernels, the 32-atom tiling and the training passes implement CELU only)
-    ANIHIP_REQUIRE(d->activation == ANIHIP_ACT_CELU || fused,
-                   "GELU networks run through the fused network kernel only: f16x3 precision, 3 hidden layers <= 256 wide with H2 + max(H1, H3) <= 448");
-    // 256 x 256 tiles for the layer-0 GEMMs once there are enough rows to fill the chip with them
-    int d0_tm = 0;
-    const bool big_tiles = plan.big_tiles;
-    // per-atom slab flags: honoured by the 256 x 256 kernels on slab-ordered planes
-    const uint32_t *smask = (big_tiles && kp_rad > 0 && K0p <= 32 * 32) ? slab_mask : nullptr;
-    if (d->flags & ANIHIP_MLP_FLAG_NO_SLAB_MASK) smask = nullptr;
-
-    // 1. bucket by species (+ the tile table of the fused kernel and the padding rows, one launch for small inputs)
-    const int fused_rows = plan.fused_rows;
-    const int64_t fused_tiles = (n + fused_rows - 1) / fused_rows + S;
-    const int n_slabs = K0p / 32;
-    // per-atom slab flags for the fused kernel's tile masks: the ANI slab order (kp_rad > 0: anihip_aev_forward's flags for
-    // the 16 / 32-column grids) or, for any other row layout, the plain 32-column slabs (kp_rad = 0: the flags of the
-    // general AEV kernel; rows of at most 1024 columns)
-    const uint32_t *tab_mask = ((kp_rad > 0 || (h3 && K0p <= 32 * 32)) && !(d->flags & ANIHIP_MLP_FLAG_NO_SLAB_MASK)) ? slab_mask : nullptr;
-    const uint32_t all_slabs = n_slabs >= 32 ? 0xFFFFFFFFu : ((1u << n_slabs) - 1u);
-    const bool small_prep = n <= SMALL_PREP_MAX;
-    if (small_prep) {
-        if (int rc = launch_small_prep(stream, lo, hi, species, S, w.ctl, w.perm, tab_mask, all_slabs, (int)fused_tiles, fused_rows,
-                                       fused ? w.tile_tab : (int4 *)nullptr, w.tile_rows, atomic_e, grad_aev, L, member_e, M,
-                                       n_atoms))
-            return rc;
-    } else {
-        // (scratch of the counting sort: the per-member energies buffer is written only later)
-        launch_bucketing(stream, lo, hi, species, S, w.ctl, CTL_WORDS + AMAX_WORDS, reinterpret_cast<int *>(w.member_part), w.perm,
-                         atomic_e, grad_aev, L, member_e, M, n_atoms);
-    }
-
-    // 2. forward through the hidden layers
-    for (int l = 0; l < (fused ? 0 : nh); ++l) {
-        GemmArgs g = gemm_args(d, w.ctl, n);
-        fwd_problems(g, d, l, true, h3, K0p);
-        g.C = w.act[l]; g.ldc = w.ld[l];
-        if (l == 0) {
-            g.A = aev; g.lda = L; g.a_gather = w.perm;
-        } else {
-            g.A = w.act[l - 1]; g.lda = w.ld[l - 1];
-        }
-        g.amax = w.amax; g.amax_out = h3 ? l : -1; g.amax_in = (h3 && l > 0) ? l - 1 : -1;
-        g.a_static_scale = 4.0f;  // layer-0 input: |aev| < 16376 by construction (see include/anihip.h)
-        if (l == 0) { g.kp_rad = kp_rad; g.stage_mask = smask; }
-        if (h3 && l == 0 && big_tiles) {
-            if (int rc = launch_gemm_big<EPI_BIAS_CELU>(stream, g, n)) return rc;
-        } else {
-            launch_gemm<EPI_BIAS_CELU>(stream, g, h3);
-        }
-    }
-
-    // layer-0 backward inside the fused kernel (fb_plan)
-    const bool fused_l0b = plan.fused_l0b;
-    if ((d->flags & ANIHIP_MLP_FLAG_FUSED_L0B) && grad_aev)   // (a call without a gradient has no backward to place)
-        ANIHIP_REQUIRE(fused_l0b, "ANIHIP_MLP_FLAG_FUSED_L0B needs the fused kernel with CELU networks, wthf[0], first hidden layers of >= 64 and second hidden layers of >= 128 columns");
-
-    FinishArgs fin{};
-    // few atoms: the layer-0 backward runs in the 8-wave 128 x 128 kernel (needs the slab flags for its column compaction)
-    const bool use_l0s = grad_aev && !fused_l0b && h3 && !big_tiles && kp_rad > 0 && K0p <= 32 * 32 && slab_mask &&
-                         !(d->flags & ANIHIP_MLP_FLAG_NO_SLAB_MASK);
-    if (fused) {
-        FusedArgs f{};
-        // tiling: 64 atoms x 8 waves, one workgroup per CU
-        const int rows = fused_rows;
-        const size_t lds = fused_args(d, w, aev, rows, f);
-        f.slab_mask = tab_mask;
-        f.d0 = w.act[0]; f.ld0 = w.ld[0];
-        // tile-major hand-over to the 256 x 256 layer-0 backward GEMM (the 128 x 128 kernel of small inputs reads rows)
-        f.d0_tm = (big_tiles && grad_aev) ? 1 : 0;
-        if (d->flags & ANIHIP_MLP_FLAG_D0_ROWS) f.d0_tm = 0;
-        d0_tm = f.d0_tm;
-        f.want_grad = grad_aev ? 1 : 0;
-        f.owner = 0;   // (member-major sweep; the layer-0 backward inside the kernel switches to owner order below)
-        f.l0b = fused_l0b ? 1 : 0;
-        f.grad_aev = grad_aev;
-        if (fused_l0b) { f.owner = FUSED_OWNER_GROUP; f.d0 = nullptr; }
-        const bool gelu = d->activation == ANIHIP_ACT_GELU;
-        // (off by default: the backward GEMMs of the large-system path with two products -- forces then differ from the
-        // three-product result by ~1e-6 Ha/A, inside north_star's 1e-4 gate and outside this package's 5e-6 regression gate)
-        const bool bwd2 = fused_l0b && (d->flags & ANIHIP_MLP_FLAG_BWD_TWO_PRODUCTS);
-        const int variant = fused_l0b ? (bwd2 ? FUSED_CELU_L0B_B2 : FUSED_CELU_L0B) : (gelu ? FUSED_GELU : FUSED_CELU);
-        const void *kfn = fused_kernel(variant);
-        ANIHIP_CHECK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int64_t tiles = fused_tiles;
-        f.tiles_total = (int)tiles;
-        // persistent workgroups over the (member, tile) items, as many as are resident at once
-        int n_cus;
-        if (int rc = cu_count(&n_cus)) return rc;
-        const int64_t items = tiles * M;
-        const int64_t resident = (int64_t)n_cus * (2 * lds <= 160 * 1024 ? 2 : 1);
-        const int64_t units = f.owner ? tiles : items;
-        const int64_t grid = units < resident ? units : resident;
-        if (!small_prep)
-            launch_tile_table(stream, w.ctl, S, w.perm, f.slab_mask, all_slabs, (int)tiles, rows, w.tile_tab, w.tile_rows);
-#ifdef ANIHIP_DEV_TRACE   // development builds only (tools/fused_trace.py): per-item phase stamps, allocates and synchronises
-        const char *trace_path = getenv("ANIHIP_FUSED_TRACE");
-        const size_t trace_words = (size_t)32 * 8 * items;   // [item][wave][32]
-        if (trace_path) {
-            ANIHIP_CHECK_HIP(hipMalloc((void **)&f.trace, sizeof(unsigned long long) * trace_words));
-            ANIHIP_CHECK_HIP(hipMemset(f.trace, 0, sizeof(unsigned long long) * trace_words));
-        }
-#endif
-        f.only_species = -1;
-        f.queue = nullptr;
-        if (ANIHIP_TILE_QUEUE && f.owner == 1 && variant == FUSED_CELU_L0B && !(d->flags & ANIHIP_MLP_FLAG_SHAPED) && rows == 64 && w.tile_tab2 &&
-            tiles <= FUSED_TILE_QUEUE_MAX && tiles > grid && !small_prep) {
-            TileOrderArgs to{};
-            to.tile_tab = w.tile_tab; to.tile_rows = w.tile_rows; to.tile_tab2 = w.tile_tab2; to.tile_rows2 = w.tile_rows2;
-            to.tiles_total = (int)tiles;
-            for (int s = 0; s < S; ++s) to.H1[s] = f.sp[s].H1;
-            launch_tile_order(stream, to);
-            f.tile_tab = w.tile_tab2; f.tile_rows = w.tile_rows2; f.queue = w.ctl + CTL_QUEUE;
-        }
-        if (variant == FUSED_CELU_L0B && (d->flags & ANIHIP_MLP_FLAG_SHAPED)) {
-            // one launch per species, restricted to its tiles, with the network widths as compile-time constants where an
-            // instantiation exists (every ANI-2x network and ANI-1x hydrogen); a species without atoms exits at once.
-            // Every launch ends with a partly filled last round of the CUs (the hydrogen tiles of the 2.34 M-atom water box: 16
-            // of 256 workgroups, eight items long).  The launches alternate between the caller's stream and a second one
-            // (forked and joined with events; they touch disjoint atoms) and draw their tiles from a queue per species: the next
-            // species' workgroups start on the CUs as they come free and take fewer tiles the later they start.  (Without the
-            // queue the overlap buys nothing: a late workgroup then carries its static share to the end.)  Not inside a stream
-            // capture (the step then stays a chain of kernel nodes).
-            // (the shaped variants' LDS limits are set before the fork: nothing between the fork and the join may return, or
-            // the work queued on the process-wide second stream would never be joined back to the caller's stream)
-            int shaped[MAX_S];
-            for (int s = 0; s < S; ++s) {
-                const FusedSpecies &fs = f.sp[s];
-                int v = FUSED_CELU_L0B;
-                if (fs.H1 == 256 && fs.H2 == 192 && fs.H3 == 160) v = FUSED_CELU_L0B_256;
-                else if (fs.H1 == 192 && fs.H2 == 160 && fs.H3 == 128) v = FUSED_CELU_L0B_192;
-                else if (fs.H1 == 224 && fs.H2 == 192 && fs.H3 == 160) v = FUSED_CELU_L0B_224;
-                else if (fs.H1 == 160 && fs.H2 == 128 && fs.H3 == 96) v = FUSED_CELU_L0B_160;
-                if (v != FUSED_CELU_L0B) ANIHIP_CHECK_HIP(hipFuncSetAttribute(fused_kernel(v), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                shaped[s] = v;
-            }
-            OverlapSet *ov = nullptr;
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            // (from four rounds of tiles on: below, the fork / join and the draws cost more than they balance -- water boxes of
-            // 24 000 / 41 472 atoms 0.399 / 0.606 ms against 0.385 / 0.581 with plain launches; 81 000: 1.01 against 1.10)
-            if (ANIHIP_SHAPED_OVERLAP && tiles >= 4 * grid && S <= CTL_WORDS - CTL_QUEUE) {
-                if (hipStreamIsCapturing(stream, &cap) != hipSuccess)
-                    (void)hipGetLastError();   // (not a reason to fail the call: plain launches)
-                else if (cap == hipStreamCaptureStatusNone)
-                    ov = overlap_resources();
-            }
-            std::unique_lock<std::mutex> ov_lock;
-            hipStream_t aux = nullptr;
-            if (ov) {
-                ov_lock = std::unique_lock<std::mutex>(ov->mu);
-                aux = ov->st;
-                ANIHIP_CHECK_HIP(hipEventRecord(ov->fork, stream));
-                ANIHIP_CHECK_HIP(hipStreamWaitEvent(aux, ov->fork, 0));
-            }
-            for (int s = 0; s < S; ++s) {
-                f.only_species = s;
-                f.queue = aux ? w.ctl + CTL_QUEUE + s : nullptr;   // (zeroed with the control block by the bucketing)
-                launch_fused(shaped[s], (unsigned)grid, lds, (aux && (s & 1)) ? aux : stream, f);
-            }
-            if (ov) {
-                ANIHIP_CHECK_HIP(hipEventRecord(ov->join, aux));
-                ANIHIP_CHECK_HIP(hipStreamWaitEvent(stream, ov->join, 0));
-            }
-        } else {
-            launch_fused(variant, (unsigned)grid, lds, stream, f);
-        }
-#ifdef ANIHIP_DEV_TRACE
-        if (trace_path) {
-            ANIHIP_CHECK_HIP(hipStreamSynchronize(stream));
-            std::vector<unsigned long long> host(trace_words);
-            ANIHIP_CHECK_HIP(hipMemcpy(host.data(), f.trace, host.size() * 8, hipMemcpyDeviceToHost));
-            ANIHIP_CHECK_HIP(hipFree(f.trace));
-            if (FILE *fp = fopen(trace_path, "wb")) {
-                fwrite(host.data(), 8, host.size(), fp);
-                fclose(fp);
-            }
-        }
-#endif
-        fin.ctl = w.ctl; fin.perm = w.perm; fin.member_part = w.member_part; fin.atomic_e = atomic_e;
-        fin.member_e = member_e; fin.n_atoms = n_atoms; fin.S = S; fin.M = M; fin.first_block = 0;
-        if (!use_l0s) launch_fused_finish(stream, fin, n);   // (the 8-wave layer-0 backward of small inputs does this in extra workgroups)
-    }
-
-    // 3. output layer (+ seed of the backward pass, written in place over the last activations)
-    if (!fused) {
-        HeadArgs h{};
-        h.atomic_e = atomic_e; h.member_e = member_e; h.want_grad = grad_aev ? 1 : 0;
-        h.amax = h3 ? w.amax : nullptr; h.amax_out = 3;
-        launch_head(stream, d, w, n_atoms, n, h);
-    }
-
-    // 4. backward to the AEV rows
-    if (grad_aev && !fused_l0b) {
-        for (int l = fused ? 0 : nh - 1; l >= 0; --l) {
-            GemmArgs g = gemm_args(d, w.ctl, n);
-            g.act = ANIHIP_ACT_CELU;   // (a GELU network gets here for the layer-0 backward only: no activation)
-            bwd_problems(g, d, l, K0p, h3);
-            g.A = w.act[l]; g.lda = w.ld[l];
-            if (l == 0) {
-                g.C = grad_aev; g.ldc = L; g.c_scatter = w.perm; g.n_store = L;
-            } else {
-                g.C = w.act[l - 1]; g.ldc = w.ld[l - 1];
-            }
-            g.amax = w.amax;
-            g.amax_in = h3 ? 3 + (nh - 1 - l) : -1;
-            g.amax_out = (h3 && l > 0) ? 3 + (nh - l) : -1;
-            g.a_static_scale = 1.0f;
-            if (l == 0) {
-                // (the layer-0 backward compacts its output columns in both tilings; the forward honours the flags only
-                // in the 256 x 256 kernel)
-                g.kp_rad = kp_rad;
-                g.stage_mask = (h3 && kp_rad > 0 && K0p <= 32 * 32 && !(d->flags & ANIHIP_MLP_FLAG_NO_SLAB_MASK)) ? slab_mask : nullptr;
-            }
-            if (l == 0 && d0_tm) {
-                g.a_tm_members = M;
-                for (int s = 0; s < S; ++s) g.a_tm_h[s] = d->net[s].dims[1];
-            }
-            if (l == 0 && h3 && big_tiles) {
-                if (int rc = launch_gemm_big<EPI_SCATTER>(stream, g, n)) return rc;
-            } else if (l == 0 && use_l0s) {
-                const int64_t total = (int64_t)g.nrow_tiles_ub * g.ncol_max;
-                const size_t lds = sizeof(_Float16) * L0S_BUFS * 4 * H_PLANE;
-                ANIHIP_CHECK_HIP(hipFuncSetAttribute((const void *)k_gemm_l0s, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)lds));
-                int64_t fb = 0;
-                if (fused) {
-                    fb = (n + L0S_THREADS - 1) / L0S_THREADS;
-                    fin.first_block = (int)total;
-                }
-                hipLaunchKernelGGL(k_gemm_l0s, dim3((unsigned)(total + fb)), dim3(L0S_THREADS), lds, stream, g, fin);
-            } else if (l == 0) {
-                launch_gemm<EPI_SCATTER>(stream, g, h3);
-            } else {
-                launch_gemm<EPI_DCELU>(stream, g, h3);
-            }
-        }
-    }
-    ANIHIP_CHECK_HIP(hipGetLastError());
+    mlp_carve(d, c.n, (char *)workspace, &w, plan.n_act);   // 3. carve
+    if (int rc = fb_prepare(c, plan, w)) return rc;          // 4. species buckets (+ tile table)
+    if (int rc = plan.fused ? fb_fused(c, plan, w) : fb_layers_forward(c, plan, w)) return rc;   // 5. energies
+    if (grad_aev && !plan.fused_l0b)                         // 6. backward to the AEV rows (phase 5 of the fused kernel did it already)
+        if (int rc = fb_backward(c, plan, w)) return rc;
+    ANIHIP_CHECK_HIP(hipGetLastError());                     // 7.
     return 0;
 }
 
@@ -2449,15 +2459,10 @@ static int train_forward(hipStream_t stream, const anihip_mlp_desc *d, int64_t n
     return 0;
 }
 
-// Does the training pass of this descriptor run through the fused network kernel?  A split-fp16 CELU pack of the shape the
-// fused kernel covers (three hidden layers <= 256 wide inside its LDS budget, <= 32 AEV slabs, every fragment-ordered plane present).
-static bool train_fused(const anihip_mlp_desc *d)
-{
-    if (d->precision != ANIHIP_MLP_F16X3 || d->activation != ANIHIP_ACT_CELU || d->net[0].n_layers != 4) return false;
-    anihip_mlp_desc c = *d;
-    c.flags = 0;
-    return fb_plan(&c, 1 << 16, true).fused;
-}
+// Does the training pass of this descriptor run through the fused network kernel?  A CELU pack of the shape the kernel covers.
+static bool train_fused(const anihip_mlp_desc *d) { return d->activation == ANIHIP_ACT_CELU && fused_shape(d); }
+
+extern "C" int anihip_mlp_fast_training(const anihip_mlp_desc *d) { return check_desc(d) == 0 && train_fused(d) ? 1 : 0; }
 
 // First half of a training step on the fast path: species buckets, tile table, ONE k_mlp_fused<.., TRAIN> launch (split-fp16
 // MFMA like inference: forward AND the backward down to d e / d z0 for a unit upstream gradient -- the backward does not
@@ -2470,17 +2475,15 @@ static int train_forward_fused(hipStream_t stream, const anihip_mlp_desc *d, int
     const int S = d->num_species, M = d->n_members, L = d->aev_len;
     const int64_t n = hi - lo;
     const int kp_rad = d->aev_radial_len;
-    const int n_slabs = layer0_width(d, true) / 32;
-    const uint32_t all_slabs = n_slabs >= 32 ? 0xFFFFFFFFu : ((1u << n_slabs) - 1u);
-    constexpr int rows = 64;
+    const uint32_t all_slabs = all_slabs_mask(layer0_width(d, true) / 32);
     launch_bucketing(stream, lo, hi, species, S, w.ctl, CTL_WORDS + AMAX_WORDS, reinterpret_cast<int *>(w.member_part), w.perm,
                      atomic_e, (float *)nullptr, L, (float *)nullptr, M, n_atoms);
-    const int64_t tiles = (n + rows - 1) / rows + S;
+    const int64_t tiles = fused_tile_count(n, S);
     // (species that do not occur in the system flag nothing: valid when the call covers the whole system)
     const int ani_species = (lo == 0 && hi == n_atoms && kp_rad == 16 * S && kp_rad > 0) ? S : 0;
-    launch_tile_table(stream, w.ctl, S, w.perm, nullptr, all_slabs, (int)tiles, rows, w.tile_tab, w.tile_rows, ani_species);
+    launch_tile_table(stream, w.ctl, S, w.perm, nullptr, all_slabs, (int)tiles, FUSED_ROWS, w.tile_tab, w.tile_rows, ani_species);
     FusedArgs f{};
-    const size_t lds = fused_args(d, w, aev, rows, f);
+    const size_t lds = fused_args(d, w, aev, FUSED_ROWS, f);
     f.slab_mask = nullptr;
     f.d0 = dlt[0]; f.ld0 = w.ld[0]; f.d0_tm = 0;
     f.want_grad = 1; f.owner = 0; f.l0b = 0; f.grad_aev = nullptr;
@@ -2493,10 +2496,7 @@ static int train_forward_fused(hipStream_t stream, const anihip_mlp_desc *d, int
     const int64_t items = tiles * M;
     const int64_t grid = items < n_cus ? items : n_cus;
     launch_fused(FUSED_TRAIN, (unsigned)grid, lds, stream, f);
-    FinishArgs fin{};
-    fin.ctl = w.ctl; fin.perm = w.perm; fin.member_part = w.member_part; fin.atomic_e = atomic_e;
-    fin.member_e = nullptr; fin.n_atoms = n_atoms; fin.S = S; fin.M = M; fin.first_block = 0;
-    launch_fused_finish(stream, fin, n);
+    launch_fused_finish(stream, finish_args(d, w, n_atoms, atomic_e, nullptr), n);
     return 0;
 }
 

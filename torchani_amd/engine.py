@@ -816,6 +816,7 @@ class PackedNetworks:
         self.desc = d
         self._ws: tp.Optional[Tensor] = None
         self._train_ws: tp.Optional[Tensor] = None
+        self._fast_training: tp.Optional[bool] = None
 
     def array(self, ptr: int, shape: tp.Sequence[int], dtype: torch.dtype = torch.float32) -> Tensor:
         """View of one packed array (a pointer of ``desc``) inside the buffer anihip_mlp_pack filled."""
@@ -960,19 +961,19 @@ class PackedNetworks:
         return bool(host[0])
 
     def fast_training(self) -> bool:
-        """Do the training passes of this pack run through the fused network kernel (anihip.h: ANIHIP_MLP_F16X3, CELU, three
-        hidden layers <= 256 wide whose 64-atom tile fits the LDS: H2 + max(H1, H3) <= 448 padded columns)?"""
-        nets = [self.desc.net[s].dims for s in range(self.S)]
-        return (self.precision == "f16x3" and self.activation == "celu" and self.nl == 4
-                and all(dm[l] <= 256 for dm in nets for l in (1, 2, 3))
-                and all(dm[2] + max(dm[1], dm[3]) <= 448 for dm in nets)
-                and self.aev_len <= 1024)
+        """Do the training passes of this pack run through the fused network kernel?  The library's answer
+        (anihip_mlp_fast_training: the rule its own training entry points apply), asked once: shapes and planes do not change
+        after construction."""
+        if self._fast_training is None:
+            self._fast_training = bool(_lib.lib().anihip_mlp_fast_training(C.byref(self.desc)))
+        return self._fast_training
 
     def _freshen_layouts(self, fused_route: bool) -> None:
         """A refresh(..., fused_only=True) leaves the layer-by-layer layouts (w / wt / wh / wth) at the parameters of the pack
         before it.  A call that the library serves layer by layer -- anything but the fused training pass without d Loss /
-        d aev -- must not read them: run the full repack from the parameter table of the last refresh first (round-5
-        advice: the C side decides the route from the descriptor on its own, so the guard sits where both are known)."""
+        d aev -- must not read them: run the full repack from the parameter table of the last refresh first.  Which route a
+        pack takes is the library's answer (fast_training() = anihip_mlp_fast_training, the rule anihip_mlp_train_forward and
+        anihip_mlp_weight_grads apply themselves), so this guard and the C side cannot drift apart."""
         if getattr(self, "stale_layouts", False) and not fused_route:
             _lib.check(_lib.lib().anihip_mlp_repack(_stream(), C.byref(self.desc), _ptr(self._src_tab),
                                                     self._out_in.ctypes.data, _ptr(getattr(self, "_repack_status", None)), 0))
