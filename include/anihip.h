@@ -157,7 +157,11 @@ int anihip_nbr_rows_to_half(void *stream, int64_t n_atoms, int64_t lo, int64_t h
  * csrc/aev.cu:1048-1126, call site aev/_computer.py:420-438): listed atom ilist[g] has the numneigh[g] neighbors
  * jlist[start[g] .. start[g] + numneigh[g]) (start = exclusive prefix sum of numneigh, int64).  Displacements are
  * r_j - r_i from coords [n_atoms, 3]; neighbors beyond Rcr, padding atoms and j == i are dropped.  Atoms that are
- * not listed get empty rows (zero AEVs).  ent_capacity = n_atoms * row capacity. */
+ * not listed get empty rows (zero AEVs).  ent_capacity = n_atoms * row capacity.
+ * Indices outside 0 .. n_atoms: a jlist entry is skipped like a neighbor beyond the cutoff (no flag: the row is what it
+ * would be without it); an ilist entry sets ANIHIP_ST_ENTRY_OVERFLOW and that list entry is skipped, every other listed
+ * atom gets its row.  A neighbor named twice in one atom's list is entered twice.  The rows are NOT symmetric (a ghost
+ * has no row): consumers must push (no ANIHIP_BWD_SYMMETRIC, ANIHIP_PAIR_PUSH). */
 int anihip_nbr_from_full(void *stream, const anihip_aev_params *p, int64_t n_atoms, const int32_t *species,
                          const float *coords, int64_t n_listed, const int32_t *ilist, const int32_t *numneigh,
                          const int64_t *start, const int32_t *jlist, uint32_t *meta, float *ent,

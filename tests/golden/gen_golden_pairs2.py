@@ -8,6 +8,9 @@ Per potential: per-atom energies (atomic=True) and forces; constructor arguments
 LONG_ROWS: two cases of tests/_aev_cases.py whose rows hold up to 256 entries at these cutoffs (species index -> symbol in
 the ANI-2x order; ``/`` of the case name becomes ``_`` in the file name).  load_inputs serves the other pair generators too;
 ``long_rows`` as the only argument writes those fixtures alone.
+
+PUSH_ROWS: three open shell cases in the four-species labelling of tests/_nbr_cases.py, for the pair kernel on rows from a
+full list (ANIHIP_PAIR_PUSH, tests/test_gpu_neighbors_external.py); ``push_rows`` as the only argument writes them alone.
 """
 import os
 import sys
@@ -44,12 +47,13 @@ def cases(symbols):
 
 
 LONG_ROWS = ("chunk256_open/seven", "chunk129_pbc/built")
+PUSH_ROWS = ("chunk129_open/built", "chunk256_open/built", "ang128_at_open/built")
 ANI2X_SYMBOLS = ("H", "C", "N", "O", "S", "F", "Cl")
 
 
 def load_inputs(name):
     """symbols, species, coords (and cell, pbc) of a golden case, or of a long-row case of tests/_aev_cases.py."""
-    if name in LONG_ROWS:
+    if name in LONG_ROWS + PUSH_ROWS:
         sys.path.insert(0, os.path.dirname(HERE))
         import _aev_cases as ac
 
@@ -86,6 +90,6 @@ def run(name):
 
 
 if __name__ == "__main__":
-    for nm in LONG_ROWS if sys.argv[1:] == ["long_rows"] else ("rand_batch_ani2x", "water_pbc_ani2x",
-                                                               "triclinic_pbc_ani2x") + LONG_ROWS:
+    only = {"long_rows": LONG_ROWS, "push_rows": PUSH_ROWS}.get(sys.argv[1] if len(sys.argv) == 2 else "")
+    for nm in only or ("rand_batch_ani2x", "water_pbc_ani2x", "triclinic_pbc_ani2x") + LONG_ROWS + PUSH_ROWS:
         run(nm)
