@@ -527,6 +527,50 @@ int anihip_md_barostat(void *stream, const anihip_md_params *params, double beta
                        double *kinetic, double *cell64, float *cell32, float *coords, float *coords_lo, float *velocities,
                        double *scale);
 
+/* Molecular cell rescaling: the barostat above for a system with bond-length constraints.  Atomic scaling x <- mu x would
+ * change every constrained length by mu, and the multipliers of a geodesic BAOAB step have no single virial; instead every
+ * SCALING GROUP is moved as a rigid body by rescaling its centre of mass.  The groups of molecule c are the clusters of the
+ * anihip_md_clusters tables and, each on its own, the free atoms (active == 1).  A cluster with a slot of w = 0 (a fixed
+ * anchor) neither moves nor enters any sum.  For a cluster q, with m_i = mass[at] (fp32, amu, as anihip_md_kick reads it),
+ * M_q = sum m_i and x = coords + coords_lo read exactly, all in fp64:
+ *   X_q = sum m_i x_i / M_q        V_q = sum m_i v_i / M_q
+ *   K_mol,c = sum over free atoms of 1/2 m v^2 / ANIHIP_MD_ACC_UNIT  +  sum_q 1/2 M_q |V_q|^2 / ANIHIP_MD_ACC_UNIT
+ *   G_c     = sum_q sum_{i in q} f_i . (x_i - X_q)
+ * tr W + G is the derivative of the energy under a strain of the cell and of the group centres with the groups translated
+ * rigidly (W the atomic dE/d strain, f the forces of the same evaluation at the same coordinates); constraint forces are
+ * internal to a group and drop out of it exactly.
+ *
+ * anihip_md_group_terms writes kinetic_mol fp64 [C] = K_mol (Hartree) and virial_mol fp64 [C] = G (Hartree).  They belong to
+ * the state after anihip_md_kick, when x, the projected v and f are those of one evaluation: the caller runs it then (or after
+ * setting velocities), not after the drift, whose coordinates the forces held no longer match.  scratch: caller-owned,
+ * ANIHIP_MD_GROUP_SCRATCH_BYTES(n_mol, atoms_per_mol) bytes, no state: fp64 [C][A][2], where each cluster leaves its two terms
+ * at the atom of slot 0 and zeros at its other atoms, then fp64 [C][ceil(A / 256)][2] sums of 256-atom chunks.  One thread per
+ * cluster, then one per atom; 2 launches for A <= 256 and 3 beyond (one less without clusters).  A cluster whose table entries
+ * are out of range is skipped (its atoms then read unset scratch: the tables are the caller's to get right).
+ *
+ * anihip_md_barostat_groups is anihip_md_barostat with
+ *   P_int = (2 K_mol - (tr W + G)) / (3 V),   d eps and mu as above (the same xi_b, the same step word)
+ *   free atom:     x <- mu x,                   v <- v / mu
+ *   cluster atom:  x_i <- x_i + (mu - 1) X_q,   v_i <- v_i + (1 / mu - 1) V_q
+ *   cell <- mu cell,   kinetic <- kinetic - (1 - mu^-2) K_mol (formed as (kinetic - K_mol) + K_mol / mu^2),   K_mol <- K_mol / mu^2
+ * Bond vectors and relative velocities are those of before the move (up to the rounding of the two-float pair and of fp32),
+ * so the constraints hold without another solver pass.  kinetic_mol is UPDATED, virial_mol is read.  With n_clusters = 0,
+ * kinetic_mol = kinetic and virial_mol = 0 the result is that of anihip_md_barostat bit for bit.  Three launches (two without
+ * clusters): one thread per molecule, per atom, per cluster.  Both entry points: no atomics, every sum in a fixed order, no
+ * host synchronization, bit-identical run to run; the clusters need not be sorted by molecule; tolerance, max_iterations and
+ * iterations of the tables are not used. */
+#define ANIHIP_MD_GROUP_SCRATCH_BYTES(n_mol, atoms_per_mol) \
+    ((size_t)(n_mol) * ((size_t)(atoms_per_mol) + ((size_t)(atoms_per_mol) + 255) / 256) * 2 * sizeof(double))
+int anihip_md_group_terms(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                          const uint8_t *active, const float *mass, const float *coords, const float *coords_lo,
+                          const float *velocities, const float *forces, double *scratch, double *kinetic_mol,
+                          double *virial_mol);
+int anihip_md_barostat_groups(void *stream, const anihip_md_params *params, double beta_T, double tau_p, const uint8_t *active,
+                              const float *kT, const double *pressure, const int64_t *replica_ids, const double *virial,
+                              double *kinetic, double *cell64, float *cell32, float *coords, float *coords_lo,
+                              float *velocities, double *scale, const anihip_md_clusters *clusters, const float *mass,
+                              double *kinetic_mol, const double *virial_mol);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

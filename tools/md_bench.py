@@ -9,6 +9,9 @@
     python tools/md_bench.py --integrator device --langevin --barostat ...  NVT, NVT with the virial-carrying evaluation, and NPT
                                                                            (stochastic cell rescaling), alternating: the cost of
                                                                            the barostat split into the evaluation's and its own
+    python tools/md_bench.py --integrator device --langevin --barostat --constraints rigid-water --dt 2 ...
+                                                                           the same three with rigid waters (or X-H bonds): NPT by
+                                                                           molecular cell rescaling (barostat_scaling="molecular")
 
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
@@ -42,7 +45,8 @@ def load_system(args, dev):
 
 def make_driver(kind, args, model, sp, x, cell, pbc, masses):
     """kind: "host", "device", "device+hydrogens" / "device+rigid-water" for the device integrator with constraints,
-    "device+virial" for NVT whose evaluations carry the virial, "device+npt" for the barostat."""
+    "device+virial" for NVT whose evaluations carry the virial, "device+npt" for the barostat; the last two also with
+    constraints ("device+npt+rigid-water": molecular cell rescaling)."""
     from torchani_amd.geomopt import ModelEvaluator
     from torchani_amd.md import BatchedDynamics, MolecularDynamics, hydrogen_constraints
 
@@ -53,13 +57,14 @@ def make_driver(kind, args, model, sp, x, cell, pbc, masses):
         constraints = None
         if kind.endswith(("hydrogens", "rigid-water")):   # (species are ANI-2x element indices: H = 0, O = 3)
             constraints = hydrogen_constraints(sp, x, cell, pbc, rigid_water=kind.endswith("rigid-water"), hydrogen=0, oxygen=3)
+        npt = "+npt" in kind
         md = BatchedDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1,
-                             constraints=constraints, pressure=1.0 if kind == "device+npt" else None,
-                             barostat_time=args.barostat_time)
-        if kind == "device+virial":   # the NVT step with the evaluation that the barostat needs, and nothing else of it
+                             constraints=constraints, pressure=1.0 if npt else None, barostat_time=args.barostat_time,
+                             barostat_scaling="molecular" if npt and constraints is not None else "atomic")
+        if "+virial" in kind:   # the NVT step with the evaluation that the barostat needs, and nothing else of it
             md._model_eval = ModelEvaluator(model, sp, cell, pbc, stress=True)
     md.set_temperature(300.0)
-    if kind == "device+npt":
+    if kind != "host" and npt:
         # (the seed-0 weights are no physical potential: at 1 bar the box would run away and the step time with its density;
         # by default the target is the pressure the box starts with)
         md.pressure.copy_(md.pressures() if args.pressure is None else torch.full_like(md.pressure, args.pressure))
@@ -113,9 +118,10 @@ def main():
         kinds = tuple(k for k in kinds if k != "device") + tuple("device" if c == "none" else "device+" + c
                                                                  for c in args.constraints)
     if args.barostat:
-        if kinds != ("device",) or not args.langevin or cell is None:
-            ap.error("--barostat needs --integrator device, --langevin and a periodic system, and no --constraints")
-        kinds = ("device", "device+virial", "device+npt")
+        if args.integrator != "device" or not args.langevin or cell is None or len(args.constraints) != 1:
+            ap.error("--barostat needs --integrator device, --langevin, a periodic system and at most one kind of --constraints")
+        held = "" if args.constraints == ["none"] else "+" + args.constraints[0]
+        kinds = ("device" + held, "device+virial" + held, "device+npt" + held)
     for nl in lists:
         drivers = {}
         for kind in kinds:   # (a model each: the automatic HIP graph of a small system belongs to one species tensor)
@@ -144,7 +150,7 @@ def main():
             if getattr(md, "barostat", False):
                 extra += (f", target {md.pressure.item():.4g} bar, P = {md.pressures().item():.4g} bar, V / V0 = "
                           f"{md.volumes().item() / md.volume0:.5f}")
-            print(f"{nl:17s} {kind:13s} {'langevin' if args.langevin else 'nve':8s} dt {args.dt:g} fs {n_atoms} atoms: "
+            print(f"{nl:17s} {kind:26s} {'langevin' if args.langevin else 'nve':8s} dt {args.dt:g} fs {n_atoms} atoms: "
                   f"{np.median(t):.3f} ms/step{spread} = {n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M atom*steps/s, "
                   f"{args.dt / (np.median(t) * 1e-3):.0f} fs simulated per second, T = {md.temperatures().mean().item():.0f} K{extra}")
 

@@ -47,6 +47,11 @@ MD_ATOM_CLUSTER, MD_CLUSTER_ATOMS, MD_CLUSTER_BONDS = 2, 8, 12   # ANIHIP_MD_ATO
 MD_BAROSTAT_STEP = 1 << 62   # ANIHIP_MD_BAROSTAT_STEP
 
 
+def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
+    """ANIHIP_MD_GROUP_SCRATCH_BYTES: the scratch of anihip_md_group_terms."""
+    return n_mol * (atoms_per_mol + (atoms_per_mol + 255) // 256) * 2 * 8
+
+
 class AevParams(C.Structure):
     _fields_ = [
         ("num_species", C.c_int32),
@@ -285,9 +290,12 @@ def lib() -> C.CDLL:
     L.anihip_md_project_velocities.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp]
     L.anihip_md_barostat.argtypes = [vp, C.POINTER(MdParams), C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                      vp, vp]
+    L.anihip_md_group_terms.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_md_barostat_groups.argtypes = [vp, C.POINTER(MdParams), C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            vp, vp, vp, C.POINTER(MdClusters), vp, vp, vp]
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
-                 "anihip_md_barostat"):
+                 "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups"):
         getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
@@ -322,6 +330,7 @@ EXPORTED_SYMBOLS = [
     "anihip_lbfgs_workspace_bytes", "anihip_lbfgs_step",
     "anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
     "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities", "anihip_md_barostat",
+    "anihip_md_group_terms", "anihip_md_barostat_groups",
 ]
 
 

@@ -11,6 +11,10 @@
 //   k_md_constrain<mode, atoms, constraints>   one thread per cluster of bond-length constraints (SHAKE / RATTLE in fp64, the cluster staged in LDS):
 //                  the drift, the kick or the velocity projection alone of the atoms that clusters own (active == 2), which
 //                  k_md_drift and the kick of k_md_kick skip
+//   k_md_group_clusters, k_md_group_sum, k_md_group_total   anihip_md_group_terms: the centre-of-mass kinetic energy and the
+//                  internal virial of the scaling groups (constraint clusters and free atoms), per cluster, chunk and molecule
+//   k_md_barostat_groups_cell, k_md_barostat_groups_free, k_md_barostat_groups_move   anihip_md_barostat_groups (molecular cell
+//                  rescaling): the volume move from the molecular pressure, free atoms rescaled, clusters translated rigidly
 //
 // Positions are pairs of floats, coords + coords_lo: every `x +=` is a two-sum, so a step far below one ulp of the coordinate
 // is not lost, and coords (what the engine reads) is the fp32 nearest to the pair.  The noise xi is a pure function of (seed,
@@ -473,6 +477,200 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_scale(MdArgs a, const 
     }
 }
 
+// ---- molecular cell rescaling: the barostat with bond constraints (include/anihip.h has the definition) ---------------------
+// A constraint cluster is a scaling group: the move translates it rigidly by the displacement of its centre of mass, so bond
+// vectors and relative velocities are kept and no solver pass follows.  One thread per cluster in both cluster kernels.  The
+// atoms are read by loops of constant length into registers, the slots past the cluster's own reading slot 0 again with mass
+// 0 (as k_md_constrain reads them): no array of a thread is indexed by a run-time slot, so there is no LDS and no scratch.
+
+struct MdGroup {
+    int n;
+    bool anchored;         // a slot of w = 0: the cluster neither moves nor enters a sum
+    int64_t g[MDC_NA];     // global atom of each slot
+    float m[MDC_NA], xh[MDC_NA][3], xl[MDC_NA][3], v[MDC_NA][3];
+    double X[3], V[3], M;   // centre of mass, its velocity, the total mass
+};
+
+// false: the table entries of cluster q are out of range, and nothing of it may be touched
+__device__ __forceinline__ bool md_group_load(const MdArgs &a, const anihip_md_clusters &cl, int64_t q, int64_t n_atoms, MdGroup &G)
+{
+    G.n = cl.count[2 * q];
+    bool ok = G.n >= 2 && G.n <= MDC_NA;
+    G.anchored = false;
+    double w[MDC_NA];
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {
+        G.g[s] = cl.atoms[MDC_NA * q + s];
+        w[s] = cl.w[MDC_NA * q + s];
+    }
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {
+        const bool in = s < G.n;
+        ok = ok && (!in || (G.g[s] >= 0 && G.g[s] < n_atoms));
+        G.anchored = G.anchored || (in && w[s] == 0.0);
+        if (!in) G.g[s] = G.g[0];
+    }
+    if (!ok) return false;
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {
+        G.m[s] = s < G.n ? a.mass[G.g[s]] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            G.xh[s][k] = a.coords[3 * G.g[s] + k], G.xl[s][k] = a.coords_lo[3 * G.g[s] + k], G.v[s][k] = a.vel[3 * G.g[s] + k];
+    }
+    G.M = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) G.X[k] = G.V[k] = 0.0;
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {   // in slot order
+        const double m = G.m[s];
+        G.M += m;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) G.X[k] += m * ((double)G.xh[s][k] + (double)G.xl[s][k]), G.V[k] += m * (double)G.v[s][k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) G.X[k] /= G.M, G.V[k] /= G.M;
+    return true;
+}
+
+// terms[at] = (1/2 M |V|^2 in amu A^2 / fs^2, sum f . (x - X)) at the atom of slot 0 and zeros at the cluster's other atoms
+__global__ __launch_bounds__(MD_BLOCK) void k_md_group_clusters(MdArgs a, anihip_md_clusters cl, int64_t n_atoms, double *terms)
+{
+    const int64_t q = (int64_t)blockIdx.x * MD_BLOCK + threadIdx.x;
+    if (q >= cl.n_clusters) return;
+    MdGroup G;
+    if (!md_group_load(a, cl, q, n_atoms, G)) return;
+    float f[MDC_NA][3];
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) f[s][k] = a.forces[3 * G.g[s] + k];
+    }
+    double ke = 0.0, vir = 0.0;
+    if (!G.anchored) {
+        ke = 0.5 * G.M * (G.V[0] * G.V[0] + G.V[1] * G.V[1] + G.V[2] * G.V[2]);
+#pragma unroll
+        for (int s = 0; s < MDC_NA; ++s) {
+            if (s >= G.n) break;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) vir += (double)f[s][k] * (((double)G.xh[s][k] + (double)G.xl[s][k]) - G.X[k]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {
+        if (s >= G.n) break;
+        terms[2 * G.g[s]] = s == 0 ? ke : 0.0;
+        terms[2 * G.g[s] + 1] = s == 0 ? vir : 0.0;
+    }
+}
+
+struct MdGroupSums {
+    double *kinetic_mol, *virial_mol;   // [C] each
+};
+
+// per 256-atom chunk: the free atoms' own 1/2 m v^2 (the expression of k_md_kick) and what the clusters left in `terms`
+__global__ __launch_bounds__(MD_BLOCK) void k_md_group_sum(MdArgs a, const double *terms, MdGroupSums o)
+{
+    const int64_t c = blockIdx.x / a.Gc, b = blockIdx.x % a.Gc, i = b * MD_BLOCK + threadIdx.x;
+    double s[2] = {0.0, 0.0};
+    if (i < a.A) {
+        const int64_t at = c * a.A + i;
+        if (a.active[at] == ANIHIP_MD_ATOM_CLUSTER) {
+            s[0] = terms[2 * at], s[1] = terms[2 * at + 1];
+        } else if (a.active[at]) {
+            const float *v = a.vel + 3 * at;
+            const float vx = v[0], vy = v[1], vz = v[2];
+            s[0] = 0.5 * (double)a.mass[at] * ((double)vx * vx + (double)vy * vy + (double)vz * vz);
+        }
+    }
+    md_block_sum<2>(s);
+    if (threadIdx.x != 0) return;
+    if (a.Gc == 1) {
+        o.kinetic_mol[c] = s[0] * (1.0 / ANIHIP_MD_ACC_UNIT), o.virial_mol[c] = s[1];
+    } else {
+        a.part[(c * a.Gc + b) * 2] = s[0], a.part[(c * a.Gc + b) * 2 + 1] = s[1];
+    }
+}
+
+// molecules of more than one chunk: the chunk sums added as k_md_sum adds them, the two totals to their own arrays
+__global__ __launch_bounds__(MD_BLOCK) void k_md_group_total(MdArgs a, MdGroupSums o)
+{
+    const int64_t c = blockIdx.x;
+    double s[2] = {0.0, 0.0};
+    for (int64_t q = threadIdx.x; q < a.Gc; q += MD_BLOCK) s[0] += a.part[(c * a.Gc + q) * 2], s[1] += a.part[(c * a.Gc + q) * 2 + 1];
+    md_block_sum<2>(s);
+    if (threadIdx.x == 0) o.kinetic_mol[c] = s[0] * (1.0 / ANIHIP_MD_ACC_UNIT), o.virial_mol[c] = s[1];
+}
+
+// k_md_barostat_cell with the molecular pressure; the kinetic energy loses what its centre-of-mass part loses
+__global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_groups_cell(MdArgs a, MdBarostat b, MdGroupSums o, int64_t n_mol)
+{
+    const int64_t c = (int64_t)blockIdx.x * MD_BLOCK + threadIdx.x;
+    if (c >= n_mol) return;
+    double h[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) h[k] = b.cell64[9 * c + k];
+    const double V = fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6])
+                          + h[2] * (h[3] * h[7] - h[4] * h[6]));
+    const double *W = b.virial + 9 * c;
+    const double K = o.kinetic_mol[c], p_int = (2.0 * K - ((W[0] + W[4] + W[8]) + o.virial_mol[c])) / (3.0 * V);
+    float xi[3];
+    md_normals(a, 0u, md_replica(a, c), xi);
+    const double rate = b.beta_over_tau * a.dtd;
+    const double deps = -rate * (b.pressure[c] - p_int) + sqrt(2.0 * (double)a.kT[c] * rate / V) * (double)xi[0];
+    const double mu = exp(deps / 3.0);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double hk = mu * h[k];
+        b.cell64[9 * c + k] = hk;
+        b.cell32[9 * c + k] = (float)hk;
+    }
+    const double K1 = K / (mu * mu);
+    b.kinetic[c] = (b.kinetic[c] - K) + K1;   // = kinetic - (1 - mu^-2) K_mol: the part internal to the groups stays
+    o.kinetic_mol[c] = K1;
+    b.scale[c] = mu;
+}
+
+// k_md_barostat_scale for the free atoms alone
+__global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_groups_free(MdArgs a, const double *scale)
+{
+    const int64_t c = blockIdx.x / a.Gc, i = (blockIdx.x % a.Gc) * MD_BLOCK + threadIdx.x;
+    if (i >= a.A) return;
+    const int64_t at = c * a.A + i;
+    if (a.active[at] != 1) return;
+    const double mu = scale[c], inv_mu = 1.0 / mu;
+    float *x = a.coords + 3 * at, *lo = a.coords_lo + 3 * at, *v = a.vel + 3 * at;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double xk = mu * ((double)x[k] + (double)lo[k]);
+        const float hi = (float)xk;
+        x[k] = hi, lo[k] = (float)(xk - (double)hi);
+        v[k] = (float)((double)v[k] * inv_mu);
+    }
+}
+
+// x_i += (mu - 1) X, v_i += (1 / mu - 1) V: every atom of the cluster gets the same two vectors
+__global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_groups_move(MdArgs a, anihip_md_clusters cl, int64_t n_atoms,
+                                                                      const double *scale)
+{
+    const int64_t q = (int64_t)blockIdx.x * MD_BLOCK + threadIdx.x;
+    if (q >= cl.n_clusters) return;
+    MdGroup G;
+    if (!md_group_load(a, cl, q, n_atoms, G) || G.anchored) return;
+    const double mu = scale[G.g[0] / a.A], dx = mu - 1.0, dv = 1.0 / mu - 1.0;   // (a cluster lies in one molecule)
+#pragma unroll
+    for (int s = 0; s < MDC_NA; ++s) {
+        if (s >= G.n) break;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double xk = ((double)G.xh[s][k] + (double)G.xl[s][k]) + dx * G.X[k];
+            const float hi = (float)xk;
+            a.coords[3 * G.g[s] + k] = hi, a.coords_lo[3 * G.g[s] + k] = (float)(xk - (double)hi);
+            a.vel[3 * G.g[s] + k] = (float)((double)G.v[s][k] + dv * G.V[k]);
+        }
+    }
+}
+
 static int md_args(const anihip_md_params *params, MdArgs &a)
 {
     ANIHIP_REQUIRE(params, "null pointer argument");
@@ -672,4 +870,69 @@ extern "C" int anihip_md_project_velocities(void *stream, const anihip_md_params
     ANIHIP_REQUIRE(coords && coords_lo && velocities, "null pointer argument");
     a.coords = const_cast<float *>(coords), a.coords_lo = const_cast<float *>(coords_lo), a.vel = velocities;
     return md_constrain<MDC_PROJECT>(stream, params, clusters, a);
+}
+
+extern "C" int anihip_md_group_terms(void *stream, const anihip_md_params *params, const anihip_md_clusters *clusters,
+                                     const uint8_t *active, const float *mass, const float *coords, const float *coords_lo,
+                                     const float *velocities, const float *forces, double *scratch, double *kinetic_mol,
+                                     double *virial_mol)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    if (int rc = md_clusters(clusters)) return rc;
+    ANIHIP_REQUIRE(active && mass && coords && coords_lo && velocities && forces && scratch && kinetic_mol && virial_mol,
+                   "null pointer argument");
+    a.active = active, a.mass = mass, a.forces = forces;
+    a.coords = const_cast<float *>(coords), a.coords_lo = const_cast<float *>(coords_lo), a.vel = const_cast<float *>(velocities);
+    const int64_t n_atoms = (int64_t)params->n_mol * a.A;
+    a.part = scratch + 2 * n_atoms;   // [C][A][2] per-atom terms, then [C][Gc][2] chunk sums
+    const MdGroupSums o = {kinetic_mol, virial_mol};
+    hipStream_t s = (hipStream_t)stream;
+    if (clusters->n_clusters > 0) {
+        hipLaunchKernelGGL(k_md_group_clusters, dim3((unsigned)((clusters->n_clusters + MD_BLOCK - 1) / MD_BLOCK)), dim3(MD_BLOCK), 0,
+                           s, a, *clusters, n_atoms, scratch);
+        ANIHIP_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_md_group_sum, md_grid(params, a), dim3(MD_BLOCK), 0, s, a, (const double *)scratch, o);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    if (a.Gc > 1) {
+        hipLaunchKernelGGL(k_md_group_total, dim3((unsigned)params->n_mol), dim3(MD_BLOCK), 0, s, a, o);
+        ANIHIP_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int anihip_md_barostat_groups(void *stream, const anihip_md_params *params, double beta_T, double tau_p,
+                                         const uint8_t *active, const float *kT, const double *pressure,
+                                         const int64_t *replica_ids, const double *virial, double *kinetic, double *cell64,
+                                         float *cell32, float *coords, float *coords_lo, float *velocities, double *scale,
+                                         const anihip_md_clusters *clusters, const float *mass, double *kinetic_mol,
+                                         const double *virial_mol)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(beta_T > 0.0 && tau_p > 0.0, "beta_T and tau_p must be > 0");
+    ANIHIP_REQUIRE(a.langevin, "the barostat needs Langevin dynamics (ANIHIP_MD_LANGEVIN): its noise is scaled by kT");
+    ANIHIP_REQUIRE(params->step < ANIHIP_MD_BAROSTAT_STEP, "step must stay below 2^62");
+    if (int rc = md_clusters(clusters)) return rc;
+    ANIHIP_REQUIRE(active && kT && pressure && virial && kinetic && cell64 && cell32 && coords && coords_lo && velocities && scale
+                       && mass && kinetic_mol && virial_mol,
+                   "null pointer argument");
+    a.step1 |= (uint32_t)(ANIHIP_MD_BAROSTAT_STEP >> 32);   // the stream of anihip_md_barostat
+    a.active = active, a.kT = kT, a.replica_ids = replica_ids, a.mass = mass;
+    a.coords = coords, a.coords_lo = coords_lo, a.vel = velocities;
+    const MdBarostat b = {beta_T / tau_p, pressure, virial, kinetic, cell64, scale, cell32};
+    const MdGroupSums o = {kinetic_mol, const_cast<double *>(virial_mol)};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_md_barostat_groups_cell, dim3((unsigned)((params->n_mol + MD_BLOCK - 1) / MD_BLOCK)), dim3(MD_BLOCK), 0, s,
+                       a, b, o, (int64_t)params->n_mol);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_md_barostat_groups_free, md_grid(params, a), dim3(MD_BLOCK), 0, s, a, (const double *)scale);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    if (clusters->n_clusters > 0) {
+        hipLaunchKernelGGL(k_md_barostat_groups_move, dim3((unsigned)((clusters->n_clusters + MD_BLOCK - 1) / MD_BLOCK)),
+                           dim3(MD_BLOCK), 0, s, a, *clusters, (int64_t)params->n_mol * a.A, (const double *)scale);
+        ANIHIP_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
 }

@@ -13,6 +13,8 @@ fixed atoms, noise that is a pure function of (seed, step, replica id, atom) and
 Bond-length constraints (``BondConstraints``, ``hydrogen_constraints``: SHAKE / RATTLE per cluster of coupled constraints) add
 one launch to each half of the step.  ``pressure=`` adds an isotropic stochastic-cell-rescaling barostat (Bernetti and Bussi
 2020) between the drift and the force evaluation: two launches that rescale the cell, the positions and the velocities.
+With constraints, ``barostat_scaling="molecular"`` moves every constraint cluster as a rigid body instead (three launches, and
+two or three after the kick for the centre-of-mass kinetic energy and the internal virial of the clusters).
 """
 from __future__ import annotations
 
@@ -357,13 +359,20 @@ class BatchedDynamics:
     the isothermal compressibility in 1 / bar (default: water's) and ``barostat_time`` the relaxation time in fs.  ``step()``
     becomes drift, barostat, evaluation, kick: the move uses the virial of the previous evaluation and the kinetic energy of
     the previous kick, and the forces always belong to the rescaled coordinates.  It needs Langevin dynamics (its noise is
-    scaled by kT), one system (C = 1) in a cell periodic in all three directions, no fixed atoms and no constraints (the
-    virial of the constraint forces is not computed).  ``cell`` is then an fp32 clone that the dynamics owns and updates in
-    place, ``cell64`` its fp64 master, and ``pressure`` an fp64 [1] device tensor in bar that may be overwritten between
-    steps; ``volumes()`` and ``pressures()`` are the observables.  Every evaluation carries the virial (``stress=True``), which
+    scaled by kT), one system (C = 1) in a cell periodic in all three directions, no fixed atoms and, with the default
+    ``barostat_scaling="atomic"``, no constraints (x <- mu x would rescale every bond).  ``cell`` is then an fp32 clone that
+    the dynamics owns and updates in place, ``cell64`` its fp64 master, and ``pressure`` an fp64 [1] device tensor in bar that
+    may be overwritten between steps; ``volumes()`` and ``pressures()`` are the observables.  Every evaluation carries the virial (``stress=True``), which
     turns off the automatic HIP graph of small systems; ``neighborlist="verlet_cell_list"`` compares the cell with the one of
     its list on the host at every step, so it synchronizes and rebuilds whenever the cell has moved; a box that shrinks until
     a neighbor row overflows is caught by the overflow check of ``run()``.
+
+    barostat_scaling: "atomic" (the default: every atom is rescaled), or "molecular", which accepts ``constraints``: every
+    constraint cluster is translated rigidly by the displacement of its rescaled centre of mass, every other atom is rescaled
+    as before, and the pressure is the molecular one, from the centre-of-mass kinetic energy of the clusters and the virial
+    under that same scaling (anihip_md_group_terms and anihip_md_barostat_groups in include/anihip.h).  Bond vectors and
+    relative velocities are untouched, so the constraints hold without another solver pass.  ``pressures()`` is then the
+    molecular pressure; ``temperatures()`` is unchanged.  Every other restriction of the barostat stays.
 
     Attributes: ``coordinates`` (fp32, updated in place; ``coordinates_lo`` is the residual of the two-float position),
     ``velocities`` (Angstrom / fs), ``forces`` and ``potential_energies`` at the coordinates, ``steps_done``.  ``step()`` never
@@ -375,7 +384,7 @@ class BatchedDynamics:
                  fixed: tp.Optional[Tensor] = None, replica_ids: tp.Optional[Tensor] = None, seed: int = 0,
                  remove_drift: bool = True, constraints: tp.Optional[BondConstraints] = None,
                  constraint_tolerance: float = 1e-8, constraint_max_iterations: int = 64, pressure=None,
-                 compressibility: float = 4.57e-5, barostat_time: float = 1000.0) -> None:
+                 compressibility: float = 4.57e-5, barostat_time: float = 1000.0, barostat_scaling: str = "atomic") -> None:
         from .geomopt import ModelEvaluator
         from .utils import pbc_tuple
 
@@ -401,7 +410,12 @@ class BatchedDynamics:
             raise ValueError(f"constraints must hold pairs of shape ({Cn}, K, 2), got {tuple(constraints.pairs.shape)}")
         if not constraint_tolerance > 0 or constraint_max_iterations < 1:
             raise ValueError("constraint_tolerance must be > 0 and constraint_max_iterations >= 1")
+        if barostat_scaling not in ("atomic", "molecular"):
+            raise ValueError(f'barostat_scaling must be "atomic" or "molecular", got {barostat_scaling!r}')
+        if barostat_scaling == "molecular" and pressure is None:
+            raise ValueError('barostat_scaling="molecular" is a mode of the barostat: pass pressure=')
         self.barostat = pressure is not None
+        self.molecular = barostat_scaling == "molecular"
         if self.barostat:
             if temperature is None:
                 raise ValueError("the barostat needs Langevin dynamics (its noise is scaled by kT): pass temperature, not NVE")
@@ -411,8 +425,9 @@ class BatchedDynamics:
                 raise ValueError("the barostat needs a cell that is periodic in all three directions")
             if fixed is not None and bool(fixed.any()):
                 raise ValueError("the barostat cannot rescale a system with fixed atoms")
-            if constraints is not None and bool((constraints.pairs >= 0).any()):
-                raise ValueError("the barostat does not support constraints: the virial of the constraint forces is not computed")
+            if not self.molecular and constraints is not None and bool((constraints.pairs >= 0).any()):
+                raise ValueError("the barostat with atomic scaling does not support constraints (x <- mu x would rescale every "
+                                 'bond): pass barostat_scaling="molecular", which moves every constraint cluster as a rigid body')
             if not compressibility > 0 or not barostat_time > 0:
                 raise ValueError("compressibility and barostat_time must be > 0")
             pressure = torch.as_tensor(pressure, dtype=torch.float64)
@@ -470,6 +485,14 @@ class BatchedDynamics:
         if constraints is not None and bool((constraints.pairs >= 0).any()):
             self._set_constraints(constraints, fixed, float(constraint_tolerance), int(constraint_max_iterations))
         self._evaluate()
+        if self.molecular:
+            # the scaling groups are the constraint clusters (none: a table of no clusters) and the free atoms
+            self._group_clusters = self._clusters if self._clusters is not None else _lib.MdClusters(
+                0, None, None, None, None, None, None, 1.0, 1, 0, 0, 0)
+            self._kinetic_mol = torch.zeros(Cn, dtype=torch.float64, device=dev)
+            self._virial_mol = torch.zeros(Cn, dtype=torch.float64, device=dev)
+            self._group_scratch = torch.empty(_lib.md_group_scratch_bytes(Cn, A), dtype=torch.uint8, device=dev)
+            self._group_terms()
 
     def _set_constraints(self, constraints: BondConstraints, fixed: tp.Optional[Tensor], tolerance: float,
                          max_iterations: int) -> None:
@@ -564,19 +587,37 @@ class BatchedDynamics:
             _stream(), C.byref(self._params), self._active.data_ptr(), self.masses.data_ptr(), self.velocities.data_ptr(),
             self.forces.data_ptr(), self._kinetic.data_ptr(), self._workspace.data_ptr(), self._workspace.numel()))
         self._kinetic_stale = False
+        if self.molecular:
+            self._group_terms()
+
+    def _group_terms(self) -> None:
+        """The centre-of-mass kinetic energy and the internal virial of the scaling groups (anihip_md_group_terms) from the
+        coordinates, velocities and forces held, which must belong together: after a kick, or after velocities were set."""
+        from .engine import _stream
+
+        _lib.check(_lib.lib().anihip_md_group_terms(
+            _stream(), C.byref(self._params), C.byref(self._group_clusters), self._active.data_ptr(), self.masses.data_ptr(),
+            self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(), self.velocities.data_ptr(), self.forces.data_ptr(),
+            self._group_scratch.data_ptr(), self._kinetic_mol.data_ptr(), self._virial_mol.data_ptr()))
 
     def _barostat(self) -> None:
-        """The volume move (anihip_md_barostat) on the virial and the kinetic energy held (``step()`` refreshes a stale one
-        before the drift), with the noise step of the drift before it: rescales cell64, cell, coordinates and velocities."""
+        """The volume move (anihip_md_barostat, or anihip_md_barostat_groups under molecular scaling) on the virial and the
+        kinetic energy held (``step()`` refreshes a stale one before the drift), with the noise step of the drift before it:
+        rescales cell64, cell, coordinates and velocities."""
         from .engine import _stream
 
         torch.div(self.pressure, BAR_PER_HARTREE_ANGSTROM3, out=self._p0)   # (every step: ``pressure`` is the user's to overwrite)
         rid = None if self._replica_ids is None else self._replica_ids.data_ptr()
-        _lib.check(_lib.lib().anihip_md_barostat(
-            _stream(), C.byref(self._params), self._beta_T, self._tau_p, self._active.data_ptr(), self._kT.data_ptr(),
-            self._p0.data_ptr(), rid, self._model_eval.virial.data_ptr(), self._kinetic.data_ptr(), self.cell64.data_ptr(),
-            self.cell.data_ptr(), self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(), self.velocities.data_ptr(),
-            self.barostat_scale.data_ptr()))
+        args = (_stream(), C.byref(self._params), self._beta_T, self._tau_p, self._active.data_ptr(), self._kT.data_ptr(),
+                self._p0.data_ptr(), rid, self._model_eval.virial.data_ptr(), self._kinetic.data_ptr(), self.cell64.data_ptr(),
+                self.cell.data_ptr(), self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(), self.velocities.data_ptr(),
+                self.barostat_scale.data_ptr())
+        if self.molecular:   # (the group terms held are those of the last kick, or of the refresh in front of the drift)
+            _lib.check(_lib.lib().anihip_md_barostat_groups(
+                *args, C.byref(self._group_clusters), self.masses.data_ptr(), self._kinetic_mol.data_ptr(),
+                self._virial_mol.data_ptr()))
+        else:
+            _lib.check(_lib.lib().anihip_md_barostat(*args))
 
     def step(self) -> None:
         """One time step: drift, the barostat's move if there is one, energies and forces at the new coordinates, kick.  No
@@ -586,6 +627,8 @@ class BatchedDynamics:
             # kinetic_energies() on the device, no host read
             self._kinetic.copy_(self.kinetic_energies())
             self._kinetic_stale = False
+            if self.molecular:   # (the forces held are those of the coordinates held)
+                self._group_terms()
         self._drift()
         if self.barostat:
             self._barostat()
@@ -669,9 +712,15 @@ class BatchedDynamics:
         return det.abs().reshape(1)
 
     def pressures(self) -> Tensor:
-        """fp64 [1], bar: (2 KE - tr W) / (3 V) from the current kinetic energy and the virial W of the last evaluation."""
+        """fp64 [1], bar: (2 KE - tr W) / (3 V) from the current kinetic energy and the virial W of the last evaluation; with
+        ``barostat_scaling="molecular"`` the molecular pressure (2 K_mol - (tr W + G)) / (3 V) of the scaling groups."""
         if not self.barostat:
             raise ValueError("pressures() needs the virial, which only a dynamics with pressure= evaluates")
+        if self.molecular:
+            if self._kinetic_stale:   # velocities set since the last kick
+                self._group_terms()
+            p = (2.0 * self._kinetic_mol - (self._model_eval.virial.diagonal().sum() + self._virial_mol)) / (3.0 * self.volumes())
+            return p * BAR_PER_HARTREE_ANGSTROM3
         p = (2.0 * self.kinetic_energies() - self._model_eval.virial.diagonal().sum()) / (3.0 * self.volumes())
         return p * BAR_PER_HARTREE_ANGSTROM3
 
