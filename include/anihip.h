@@ -571,6 +571,53 @@ int anihip_md_barostat_groups(void *stream, const anihip_md_params *params, doub
                               float *velocities, double *scale, const anihip_md_clusters *clusters, const float *mass,
                               double *kinetic_mol, const double *virial_mol);
 
+/* Ring polymers: path-integral MD over the beads of a batch (torchani_amd.md.RingPolymerDynamics).  The batch has
+ * C = R P entries; entries r P .. r P + P - 1 are the beads j = 0 .. P - 1 of ring polymer r, and all beads of a polymer have
+ * the same species, masses and active mask (those of the first bead are read).  With the physical temperature T_r the beads
+ * are sampled at P T_r (the convention of Ceriotti et al., J. Chem. Phys. 133, 124104 (2010)):
+ *   H_P = sum_j [ sum_i 1/2 m_i v_ij^2 + V(q_j) ] + sum_j sum_i 1/2 m_i w_P^2 (q_ij - q_i,j+1)^2,  w_P = P k_B T_r / hbar,
+ * bead P being bead 0.  Normal modes k = 0 .. P - 1 of a bead vector y_j:  y = C u, C real and orthogonal,
+ *   C_jk = 1 / sqrt(P) (k = 0),  sqrt(2 / P) cos(2 pi j k / P) (0 < k < P / 2),  (-1)^j / sqrt(P) (k = P / 2, P even),
+ *   sqrt(2 / P) sin(2 pi j k / P) (k > P / 2),  with  w_k = 2 w_P sin(k pi / P).
+ * A step is BAOAB with an exact A (the "BAOAB-PILE" of Liu, Li and Liu 2016), in the shape of the classical one: the ring-
+ * polymer drift, the forces of all beads at the new coordinates, anihip_md_kick (unchanged: the closing B and the kinetic
+ * energy of every bead).  The drift, per active atom and Cartesian component of a polymer:
+ *   B        v_j += dt/2 f_j inv_mass
+ *            (u_k, w_k) = the modes of (q_j, v_j)
+ *   A(h)     k = 0: u += h w;  k > 0: (u, w) <- (u cos w_k h + (w / w_k) sin w_k h,  -u w_k sin w_k h + w cos w_k h)
+ *   O        w_k = c_k w_k + sqrt(P kT_r (1 - c_k^2) inv_mass) xi_k,  c_k = exp(-gamma_k dt),  gamma_0 = friction_r (0 leaves the
+ *            centroid without a thermostat),  gamma_k = 2 pile_lambda w_k for k > 0 (pile_lambda 1: PIMD, 0.5: TRPMD)
+ *   A(h)     and back to beads.
+ * With ANIHIP_MD_LANGEVIN h = dt/2; without it (RPMD) there is no O and one A(dt).  xi_k is the value of anihip_md_noise at
+ * (atom i, the replica id of batch entry r P + k, step): the noise tensor of a step is used row for row, row r P + k driving
+ * mode k.  kT fp32 [C] = k_B T in Hartree of the PHYSICAL temperature and friction fp32 [C] are read at the polymer's first
+ * bead; kT is needed without the thermostat too (w_P), friction may then be NULL.  Velocities are written as fp32, positions
+ * as the two-float pair with coords the fp32 nearest to it.  Inactive atoms keep their coordinates bit for bit and get v = 0.
+ * Atoms of constraint clusters (active == 2) are not supported: the kernel has no error channel and leaves them untouched,
+ * and RingPolymerDynamics refuses constraints.  Requires 2 <= beads <= ANIHIP_MD_RP_MAX_BEADS and n_mol a multiple of beads.
+ *
+ * Precision: c_k, 1 - c_k^2 (expm1), sin and cos of w_k h and the matrix C are formed in fp64 once per workgroup.  The centroid
+ * is the fp64 mean of the pairs and moves in fp64; modes k > 0 are formed from the offsets from the centroid (and from the
+ * mean velocity), in fp64: equal beads have modes that are exactly zero and stay equal bit for bit.  One launch, one thread
+ * per (mode, atom, component), the beads and modes of 1024 / beads consecutive floats staged in LDS; one instance for every
+ * P, which is read at run time.
+ *
+ * anihip_md_rp_estimators writes, in fp64 and with every sum in a fixed order (no atomics, bit-identical run to run):
+ *   estimators[r][0] = S_r = sum_j sum_i 1/2 m_i w_P^2 |q_ij - q_i,j+1|^2 / ANIHIP_MD_ACC_UNIT   (the spring energy, Hartree)
+ *   estimators[r][1] = W_r = sum_j sum_i (q_ij - qbar_i) . f_ij                                  (the centroid-virial sum, Hartree)
+ *   centroids[r][i]  = qbar_i = sum_j q_ij / P  of every atom, active or not (fp64 [R][A][3])
+ * S and W run over the active atoms; mass fp32 [C][A] in amu, forces those of the coordinates held.  workspace: the
+ * anihip_md_workspace_bytes of (n_mol, atoms_per_mol), no state.  One launch, two for polymers of more than 256 atoms. */
+#define ANIHIP_MD_HBAR 0.024188843265857   /* Hartree fs */
+#define ANIHIP_MD_RP_MAX_BEADS 64
+int anihip_md_rp_drift(void *stream, const anihip_md_params *params, int32_t beads, double pile_lambda, const uint8_t *active,
+                       const float *inv_mass, const float *kT, const float *friction, const int64_t *replica_ids,
+                       float *coords, float *coords_lo, float *velocities, const float *forces);
+int anihip_md_rp_estimators(void *stream, const anihip_md_params *params, int32_t beads, const uint8_t *active,
+                            const float *mass, const float *kT, const float *coords, const float *coords_lo,
+                            const float *forces, double *estimators, double *centroids, void *workspace,
+                            size_t workspace_bytes);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -12,6 +12,10 @@
     python tools/md_bench.py --integrator device --langevin --barostat --constraints rigid-water --dt 2 ...
                                                                            the same three with rigid waters (or X-H bonds): NPT by
                                                                            molecular cell rescaling (barostat_scaling="molecular")
+    python tools/md_bench.py --beads 32 --system molecules --repeats 7 ...  path-integral MD (md.RingPolymerDynamics, PILE) against
+    python tools/md_bench.py --beads 8 --side 10 --repeats 7 ...            the classical Langevin step of md.BatchedDynamics on the
+                                                                           same [R beads, A] batch: the first 256 / beads molecules
+                                                                           of config 2 as ring polymers, or beads copies of the box
 
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
@@ -72,6 +76,49 @@ def make_driver(kind, args, model, sp, x, cell, pbc, masses):
     return md
 
 
+def bench_beads(args, dev):
+    """RingPolymerDynamics (PILE, --temperature) against BatchedDynamics (Langevin at beads x that, what the beads are sampled at) on one
+    [R beads, A] batch, in one process, the repeats alternating.  Both run the same evaluation, kick and launch count; they
+    differ in the drift kernel."""
+    from torchani_amd.md import BatchedDynamics, RingPolymerDynamics
+    from torchani_amd.models import ANI2x
+
+    P = args.beads
+    sp, x, cell, pbc, lists = load_system(args, dev)
+    if args.system == "molecules":
+        sp, x = sp[:sp.shape[0] // P], x[:sp.shape[0] // P]
+    # (a batch of boxes goes through the all-pairs builder: the cell list handles one system at a time)
+    nl = args.neighborlist or ("auto" if cell is not None else lists[0])
+    masses = torch.tensor(ELEMENT_MASSES, device=dev)[sp.clamp(min=0)]
+    R, A = sp.shape
+    rep = lambda t: t.repeat_interleave(P, dim=0)   # noqa: E731
+    drivers = {}
+    for kind in ("classical", "ring-polymer"):
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl, row_capacity=256)
+        if kind == "classical":
+            md = BatchedDynamics(model, rep(sp), rep(x), cell, pbc, dt=args.dt, masses=rep(masses), temperature=P * args.temperature, seed=1)
+            md.set_temperature(P * args.temperature)
+        else:
+            md = RingPolymerDynamics(model, sp, x, cell, pbc, beads=P, dt=args.dt, masses=masses, temperature=args.temperature, seed=1)
+            md.set_temperature(args.temperature)
+        md.run(args.warmup)
+        drivers[kind] = md
+    times = {kind: [] for kind in drivers}
+    for _ in range(args.repeats):
+        for kind, md in drivers.items():
+            times[kind].append(timed(md, args.steps))
+    n_atoms = int((sp >= 0).sum()) * P
+    for kind, md in drivers.items():
+        t = np.array(times[kind]) * 1e3
+        extra = ""
+        if kind == "ring-polymer":
+            extra = (f", spring energy {md.spring_energies().mean().item():.4f} Ha, centroid-virial kinetic energy "
+                     f"{md.quantum_kinetic_energies().mean().item():.4f} Ha per polymer")
+        print(f"{nl:17s} {kind:12s} {R} x {P} beads x {A} atoms, dt {args.dt:g} fs, {n_atoms} bead atoms: {np.median(t):.3f} ms/step "
+              f"(fastest {t.min():.3f}, slowest {t.max():.3f} of {len(t)} repeats of {args.steps} steps) = "
+              f"{n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M bead-atom*steps/s, bead T = {md.temperatures().mean().item():.0f} K{extra}")
+
+
 def timed(md, steps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -98,6 +145,9 @@ def main():
                          "each other in one process")
     ap.add_argument("--pressure", type=float, default=None, help="--barostat: target in bar (default: the initial pressure)")
     ap.add_argument("--barostat-time", type=float, default=1000.0, help="--barostat: relaxation time, fs")
+    ap.add_argument("--beads", type=int, default=None,
+                    help="path-integral MD with this many beads against the classical Langevin step on the same batch")
+    ap.add_argument("--temperature", type=float, default=300.0, help="--beads: the physical temperature, K")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
@@ -106,6 +156,8 @@ def main():
     from torchani_amd.models import ANI2x
 
     dev = torch.device("cuda:0")
+    if args.beads is not None:
+        return bench_beads(args, dev)
     sp, x, cell, pbc, lists = load_system(args, dev)
     if args.neighborlist is not None and args.system == "water":
         lists = (args.neighborlist,)

@@ -45,6 +45,8 @@ LBFGS_MAX_MEMORY = 256   # ANIHIP_LBFGS_MAX_MEMORY
 MD_LANGEVIN = 1   # ANIHIP_MD_LANGEVIN
 MD_ATOM_CLUSTER, MD_CLUSTER_ATOMS, MD_CLUSTER_BONDS = 2, 8, 12   # ANIHIP_MD_ATOM_CLUSTER, ANIHIP_MD_CLUSTER_*
 MD_BAROSTAT_STEP = 1 << 62   # ANIHIP_MD_BAROSTAT_STEP
+MD_HBAR = 0.024188843265857   # ANIHIP_MD_HBAR, Hartree fs
+MD_RP_MAX_BEADS = 64   # ANIHIP_MD_RP_MAX_BEADS
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -293,9 +295,12 @@ def lib() -> C.CDLL:
     L.anihip_md_group_terms.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdClusters), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.anihip_md_barostat_groups.argtypes = [vp, C.POINTER(MdParams), C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                             vp, vp, vp, C.POINTER(MdClusters), vp, vp, vp]
+    L.anihip_md_rp_drift.argtypes = [vp, C.POINTER(MdParams), i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_md_rp_estimators.argtypes = [vp, C.POINTER(MdParams), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
-                 "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups"):
+                 "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
+                 "anihip_md_rp_estimators"):
         getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
@@ -330,7 +335,7 @@ EXPORTED_SYMBOLS = [
     "anihip_lbfgs_workspace_bytes", "anihip_lbfgs_step",
     "anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
     "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities", "anihip_md_barostat",
-    "anihip_md_group_terms", "anihip_md_barostat_groups",
+    "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift", "anihip_md_rp_estimators",
 ]
 
 

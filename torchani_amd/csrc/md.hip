@@ -15,6 +15,9 @@
 //                  internal virial of the scaling groups (constraint clusters and free atoms), per cluster, chunk and molecule
 //   k_md_barostat_groups_cell, k_md_barostat_groups_free, k_md_barostat_groups_move   anihip_md_barostat_groups (molecular cell
 //                  rescaling): the volume move from the molecular pressure, free atoms rescaled, clusters translated rigidly
+//   k_md_rp_drift, k_md_rp_estimators   anihip_md_rp_drift / anihip_md_rp_estimators (ring polymers over the beads of a batch):
+//                  B, the exact free ring-polymer propagation in normal modes with the PILE thermostat on them, one thread per
+//                  (mode, atom, component); the spring energy, the centroid-virial sum and the centroids of every polymer
 //
 // Positions are pairs of floats, coords + coords_lo: every `x +=` is a two-sum, so a step far below one ulp of the coordinate
 // is not lost, and coords (what the engine reads) is the fp32 nearest to the pair.  The noise xi is a pure function of (seed,
@@ -671,6 +674,169 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_barostat_groups_move(MdArgs a, 
     }
 }
 
+// ---- ring polymers: path-integral MD over the beads of a batch (include/anihip.h has the definition) -----------------------
+// k_md_rp_drift: one thread per (bead or mode, atom, Cartesian component).  A workgroup of RP_BLOCK = 1024 threads takes NE =
+// 1024 / P consecutive floats of the polymer's [A][3] layout, thread t = m NE + el the element el of bead m: a bead is read and
+// written in contiguous runs of NE floats (128 bytes at P = 32, 64 at P = 64).  The positions (the exact fp64 sum of the pair)
+// and the kicked velocities go to LDS; after a barrier thread (m, el) forms mode m of its element by a dot product of P terms,
+// propagates it (A [O A]), and the modes go back through LDS the same way: P terms per thread and transform, not P^2, which is
+// what matters for the latency of a small batch.  Before that the workgroup builds in LDS, in fp64, the P values of cos and
+// sin(2 pi m / P), from them the mode matrix C, and the propagator and thermostat coefficients of every mode (thread k those
+// of mode k: one sin, one sincos, one exp and one expm1 per mode and workgroup).  The thread of mode k draws the Philox block
+// of (atom, stream of entry r P + k) itself and takes its component.  Any P in 2 .. 64 at run time, one instance.
+//
+// Precision: everything between the loads and the stores is fp64 (gfx950 issues fp64 FMAs at the fp32 rate), so the only
+// roundings of a step are the final ones to the pair and to fp32.  Mode 0 is the centroid itself, the fp64 mean of the pairs,
+// so a centroid step far below one ulp of the coordinate is kept as k_md_drift keeps it; modes k > 0 are formed from the
+// offsets q_j - centroid and v_j - mean v: beads that are equal give offsets, and with them modes, that are exactly zero, and
+// the beads stay equal bit for bit.
+
+constexpr int RP_BLOCK = 1024, RP_MAX = ANIHIP_MD_RP_MAX_BEADS;
+
+struct RpArgs {
+    int P, NE;        // beads, 2 .. RP_MAX, and elements per workgroup, RP_BLOCK / P
+    int64_t Gr;       // workgroups per polymer
+    double lambda;    // PILE: gamma_k = 2 lambda omega_k
+};
+
+__global__ __launch_bounds__(RP_BLOCK) void k_md_rp_drift(MdArgs a, RpArgs rp)
+{
+    __shared__ double sC[RP_MAX][RP_MAX + 1];   // sC[k][j] = C_jk for 0 < k < P (the row padded: a wave reads several k at one j); row 0 is 1, the centroid's share of every bead
+    __shared__ double sTrig[RP_MAX][2];         // cos and sin(2 pi m / P)
+    __shared__ double sA[RP_MAX][3];            // A(h) of mode k: cos(w h), sin(w h) / w, -w sin(w h); mode 0: 1, h, 0
+    __shared__ double sO[RP_MAX][2];            // O of mode k: c_k and sqrt(P kT (1 - c_k^2)); mode 0, the centroid velocity: sqrt(kT (1 - c_0^2))
+    __shared__ double sQ[RP_BLOCK], sV[RP_BLOCK];   // [bead or mode][el]
+    const int t = threadIdx.x, P = rp.P, NE = rp.NE;
+    const int m = t / NE, el = t % NE;
+    const int64_t r = blockIdx.x / rp.Gr, chunk = blockIdx.x % rp.Gr;
+    const int64_t c0 = r * P;   // the polymer's first bead
+    const double h = a.langevin ? 0.5 * a.dtd : a.dtd;
+    if (t < P) {
+        double co, si, cs = 1.0, sw = h, ws = 0.0, ck = 1.0, sk = 0.0;
+        sincospi(2.0 * (double)t / (double)P, &si, &co);
+        const double kT = a.kT[c0], wP = (double)P * kT / ANIHIP_MD_HBAR, wk = 2.0 * wP * sinpi((double)t / (double)P);
+        if (t > 0) {
+            double s;
+            sincos(wk * h, &s, &cs);
+            sw = s / wk, ws = -wk * s;
+        }
+        if (a.langevin) {
+            const double gdt = (t == 0 ? (double)a.friction[c0] : 2.0 * rp.lambda * wk) * a.dtd;
+            ck = exp(-gdt);
+            sk = sqrt((t == 0 ? 1.0 : (double)P) * kT * -expm1(-2.0 * gdt));
+        }
+        sTrig[t][0] = co, sTrig[t][1] = si;
+        sA[t][0] = cs, sA[t][1] = sw, sA[t][2] = ws;
+        sO[t][0] = ck, sO[t][1] = sk;
+    }
+    __syncthreads();
+    {
+        const double n1 = sqrt(1.0 / (double)P), n2 = sqrt(2.0 / (double)P);
+        for (int q = t; q < P * P; q += RP_BLOCK) {
+            const int k = q / P, j = q % P, mm = (j * k) % P;
+            // (k = P / 2: mm is 0 or P / 2, cos = +-1)
+            sC[k][j] = k == 0 ? 1.0 : 2 * k < P ? n2 * sTrig[mm][0] : 2 * k == P ? n1 * sTrig[mm][0] : n2 * sTrig[mm][1];
+        }
+    }
+    const int64_t A3 = 3 * a.A, e = chunk * NE + el;
+    const bool in = m < P && e < A3;
+    const int64_t i = in ? e / 3 : 0, at0 = c0 * a.A + i, g = in ? (c0 + m) * A3 + e : 0;
+    const uint8_t act = in ? a.active[at0] : 0;
+    const bool move = act == 1;   // (0: padding or fixed, v = 0 and the coordinates untouched; an atom of a constraint cluster is not moved at all)
+    double im = 0.0, x = 0.0, y = 0.0;
+    if (move) {
+        im = a.inv_mass[at0];
+        const float hi = a.coords[g], lo = a.coords_lo[g], v0 = a.vel[g], f0 = a.forces[g];
+        x = (double)hi + (double)lo;                  // exact
+        y = (double)v0 + 0.5 * a.dtd * im * (double)f0;   // B
+    }
+    sQ[t] = x, sV[t] = y;
+    __syncthreads();
+    double u = 0.0, w = 0.0;
+    if (move) {
+        double qbar = 0.0, vbar = 0.0;
+        for (int j = 0; j < P; ++j) qbar += sQ[j * NE + el], vbar += sV[j * NE + el];
+        qbar /= (double)P, vbar /= (double)P;
+        if (m == 0) {
+            u = qbar, w = vbar;
+        } else {
+            for (int j = 0; j < P; ++j) {
+                const double c = sC[m][j];
+                u += c * (sQ[j * NE + el] - qbar), w += c * (sV[j * NE + el] - vbar);
+            }
+        }
+        // A(h) [O A(h)]: the centroid drifts freely, every other mode turns in its own phase space
+        const double cs = sA[m][0], sw = sA[m][1], ws = sA[m][2];
+        double u1 = u * cs + w * sw, w1 = u * ws + w * cs;
+        if (a.langevin) {
+            float xi[3];
+            md_normals(a, (uint32_t)i, md_replica(a, c0 + m), xi);
+            const int comp = (int)(e - 3 * i);
+            w1 = sO[m][0] * w1 + sO[m][1] * sqrt(im) * (double)(comp == 0 ? xi[0] : comp == 1 ? xi[1] : xi[2]);
+            const double u2 = u1 * cs + w1 * sw;
+            w1 = u1 * ws + w1 * cs, u1 = u2;
+        }
+        u = u1, w = w1;
+    }
+    __syncthreads();   // every thread has read the beads
+    sQ[t] = u, sV[t] = w;
+    __syncthreads();
+    if (move) {
+        x = 0.0, y = 0.0;
+        for (int k = 0; k < P; ++k) {   // k = 0 first: the centroid, then the offsets
+            const double c = sC[k][m];
+            x += c * sQ[k * NE + el], y += c * sV[k * NE + el];
+        }
+        const float xh = (float)x;
+        a.coords[g] = xh, a.coords_lo[g] = (float)(x - (double)xh);
+        a.vel[g] = (float)y;
+    } else if (in && !act) {
+        a.vel[g] = 0.f;
+    }
+}
+
+// per atom: the centroid, and over the active atoms the spring and centroid-virial terms of its P beads, summed per chunk as
+// k_md_kick sums the kinetic energy (out[r] = (S_r, W_r); polymers of more than one chunk through k_md_sum<2>)
+__global__ __launch_bounds__(MD_BLOCK) void k_md_rp_estimators(MdArgs a, int P, double *centroids)
+{
+    const int64_t r = blockIdx.x / a.Gc, b = blockIdx.x % a.Gc, i = b * MD_BLOCK + threadIdx.x;
+    double s[2] = {0.0, 0.0};
+    if (i < a.A) {
+        const int64_t c0 = r * P, at0 = c0 * a.A + i;
+        double qbar[3] = {0.0, 0.0, 0.0};
+        for (int j = 0; j < P; ++j) {
+            const int64_t g = 3 * (at0 + j * a.A);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) qbar[k] += (double)a.coords[g + k] + (double)a.coords_lo[g + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            qbar[k] /= (double)P;
+            centroids[3 * (r * a.A + i) + k] = qbar[k];
+        }
+        if (a.active[at0]) {
+            double q0[3], prev[3], spring = 0.0;
+            for (int j = 0; j < P; ++j) {
+                const int64_t g = 3 * (at0 + j * a.A);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double q = (double)a.coords[g + k] + (double)a.coords_lo[g + k];
+                    s[1] += (q - qbar[k]) * (double)a.forces[g + k];
+                    if (j == 0) q0[k] = q;
+                    else spring += (q - prev[k]) * (q - prev[k]);
+                    prev[k] = q;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) spring += (q0[k] - prev[k]) * (q0[k] - prev[k]);   // bead P - 1 to bead 0
+            const double wP = (double)P * (double)a.kT[c0] / ANIHIP_MD_HBAR;
+            s[0] = 0.5 * (double)a.mass[at0] * wP * wP * spring * (1.0 / ANIHIP_MD_ACC_UNIT);
+        }
+    }
+    md_block_sum<2>(s);
+    md_store_sums<2>(a, r, b, s, 1.0);
+}
+
 static int md_args(const anihip_md_params *params, MdArgs &a)
 {
     ANIHIP_REQUIRE(params, "null pointer argument");
@@ -932,6 +1098,56 @@ extern "C" int anihip_md_barostat_groups(void *stream, const anihip_md_params *p
     if (clusters->n_clusters > 0) {
         hipLaunchKernelGGL(k_md_barostat_groups_move, dim3((unsigned)((clusters->n_clusters + MD_BLOCK - 1) / MD_BLOCK)),
                            dim3(MD_BLOCK), 0, s, a, *clusters, (int64_t)params->n_mol * a.A, (const double *)scale);
+        ANIHIP_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+static int md_rp_args(const anihip_md_params *params, int32_t beads, MdArgs &a)
+{
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(beads >= 2 && beads <= ANIHIP_MD_RP_MAX_BEADS, "beads must be in 2 .. %d, got %d", ANIHIP_MD_RP_MAX_BEADS, beads);
+    ANIHIP_REQUIRE(params->n_mol % beads == 0, "n_mol = %d is no multiple of beads = %d", params->n_mol, beads);
+    return 0;
+}
+
+extern "C" int anihip_md_rp_drift(void *stream, const anihip_md_params *params, int32_t beads, double pile_lambda,
+                                  const uint8_t *active, const float *inv_mass, const float *kT, const float *friction,
+                                  const int64_t *replica_ids, float *coords, float *coords_lo, float *velocities,
+                                  const float *forces)
+{
+    MdArgs a;
+    if (int rc = md_rp_args(params, beads, a)) return rc;
+    ANIHIP_REQUIRE(active && inv_mass && kT && coords && coords_lo && velocities && forces, "null pointer argument");
+    ANIHIP_REQUIRE(!a.langevin || friction, "the PILE thermostat needs friction");
+    ANIHIP_REQUIRE(pile_lambda >= 0.0, "pile_lambda must be >= 0");
+    a.active = active, a.inv_mass = inv_mass, a.kT = kT, a.friction = friction, a.replica_ids = replica_ids;
+    a.coords = coords, a.coords_lo = coords_lo, a.vel = velocities, a.forces = forces;
+    const int NE = RP_BLOCK / beads;
+    const RpArgs rp = {beads, NE, (3 * a.A + NE - 1) / NE, pile_lambda};
+    hipLaunchKernelGGL(k_md_rp_drift, dim3((unsigned)((params->n_mol / beads) * rp.Gr)), dim3(RP_BLOCK), 0, (hipStream_t)stream, a,
+                       rp);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int anihip_md_rp_estimators(void *stream, const anihip_md_params *params, int32_t beads, const uint8_t *active,
+                                       const float *mass, const float *kT, const float *coords, const float *coords_lo,
+                                       const float *forces, double *estimators, double *centroids, void *workspace,
+                                       size_t workspace_bytes)
+{
+    MdArgs a;
+    if (int rc = md_rp_args(params, beads, a)) return rc;
+    ANIHIP_REQUIRE(active && mass && kT && coords && coords_lo && forces && estimators && centroids, "null pointer argument");
+    if (int rc = md_workspace(params, a, workspace, workspace_bytes)) return rc;   // (sized for n_mol entries: R of them are used)
+    a.active = active, a.mass = mass, a.kT = kT, a.forces = forces, a.out = estimators;
+    a.coords = const_cast<float *>(coords), a.coords_lo = const_cast<float *>(coords_lo);
+    const unsigned R = (unsigned)(params->n_mol / beads);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_md_rp_estimators, dim3((unsigned)(R * a.Gc)), dim3(MD_BLOCK), 0, s, a, (int)beads, centroids);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    if (a.Gc > 1) {
+        hipLaunchKernelGGL(k_md_sum<2>, dim3(R), dim3(MD_BLOCK), 0, s, a, 1.0);
         ANIHIP_CHECK_HIP(hipGetLastError());
     }
     return 0;

@@ -15,6 +15,8 @@ one launch to each half of the step.  ``pressure=`` adds an isotropic stochastic
 2020) between the drift and the force evaluation: two launches that rescale the cell, the positions and the velocities.
 With constraints, ``barostat_scaling="molecular"`` moves every constraint cluster as a rigid body instead (three launches, and
 two or three after the kick for the centre-of-mass kinetic energy and the internal virial of the clusters).
+``RingPolymerDynamics`` is path-integral MD on the same machinery: the batch holds the beads of R ring polymers, and its drift is
+one launch that propagates the free ring polymer exactly in its normal modes with the PILE thermostat on them.
 """
 from __future__ import annotations
 
@@ -729,3 +731,144 @@ class BatchedDynamics:
         (``set_temperature`` with ``remove_drift``, or ``remove_center_of_mass_velocity()``, since the velocities were last
         set) and the momentum is conserved (NVE, no fixed atom in the molecule)."""
         return 2.0 * self.kinetic_energies() / ((self._dof_at_rest if self._drift_removed else self._dof) * KB_HARTREE)
+
+
+class RingPolymerDynamics(BatchedDynamics):
+    """Path-integral MD (PIMD, TRPMD, RPMD) of R systems as ring polymers of ``beads`` = P copies each, integrated on the
+    device: BAOAB with the free ring polymer propagated exactly in its normal modes and the path-integral Langevin thermostat
+    (PILE) acting on those modes (anihip_md_rp_drift; include/anihip.h has the exact definition).
+
+    species [R, A]; coordinates [R, A, 3] (all beads start on that point) or [R, P, A, 3] (a restart); species, masses and
+    ``fixed`` are replicated over the beads.  The batch the base class integrates has C = R P entries, entry r P + j the bead
+    j of polymer r, so one evaluation of the model gives the forces of all beads; with a cell, the P beads of the box share it.
+    ``coordinates``, ``velocities``, ``forces`` and ``potential_energies`` are those of the batch, [R P, ...].
+
+    temperature (required): the PHYSICAL temperature in K, a number or [R]; the beads are sampled at P T (the convention of
+    Ceriotti et al. 2010).  It becomes the device tensor ``temperature`` [R P], the value repeated per bead, which may be
+    overwritten between steps (the drift reads each polymer's first entry).  thermostat: "pile" (``friction`` in 1 / fs, a number
+    or [R], damps the centroid, 0 leaves it alone; mode k > 0 gets 2 ``pile_lambda`` omega_k: 1 for PIMD, 0.5 for TRPMD), or None
+    for RPMD, which conserves ``ring_polymer_energies()``.  replica_ids int64 [R]: polymer r draws the noise streams
+    r P .. r P + P - 1, which must stay below 2^32; mode k of a polymer is driven by the stream of its entry r P + k.
+    ``set_temperature(kelvin)`` draws the bead velocities at P kelvin.  remove_drift (default off) would remove the centre-of-
+    mass velocity of every bead on its own.  Bond constraints and the barostat are not available with beads.
+
+    ``step()``, ``run()``, the evaluator, the kick, the overflow check and the absence of host synchronization are the base
+    class's.  ``kinetic_energies()`` and ``temperatures()`` keep their meaning per batch entry, that is per bead: they
+    equilibrate at P T, not T.  The physical observables are ``quantum_kinetic_energies()``, ``centroids()``,
+    ``spring_energies()`` and ``ring_polymer_energies()``, none of which reads on the host.
+    """
+
+    def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
+                 beads: int, temperature=None, dt: float = 0.5, friction=0.002, pile_lambda: float = 1.0,
+                 thermostat: tp.Optional[str] = "pile", masses: tp.Optional[Tensor] = None,
+                 fixed: tp.Optional[Tensor] = None, replica_ids: tp.Optional[Tensor] = None, seed: int = 0,
+                 remove_drift: bool = False, constraints=None, pressure=None) -> None:
+        if constraints is not None:
+            raise ValueError("RingPolymerDynamics does not support constraints: bond constraints (SHAKE / RATTLE) with beads "
+                             "are not implemented")
+        if pressure is not None:
+            raise ValueError("RingPolymerDynamics does not support pressure: the barostat with beads is not implemented")
+        if isinstance(beads, bool) or int(beads) != beads or not 2 <= beads <= _lib.MD_RP_MAX_BEADS:
+            raise ValueError(f"beads must be an integer in 2 .. {_lib.MD_RP_MAX_BEADS}, got {beads}")
+        P = int(beads)
+        if temperature is None:
+            raise ValueError("RingPolymerDynamics needs temperature, the physical one: it sets the spring frequency "
+                             "P k_B T / hbar with and without a thermostat")
+        if thermostat not in ("pile", None):
+            raise ValueError(f'thermostat must be "pile" or None, got {thermostat!r}')
+        if not pile_lambda >= 0:
+            raise ValueError(f"pile_lambda must be >= 0, got {pile_lambda}")
+        if species.dim() != 2:
+            raise ValueError("expected species [R, A]")
+        R, A = species.shape
+        if tuple(coordinates.shape) == (R, A, 3):
+            coordinates = coordinates.unsqueeze(1).expand(R, P, A, 3)
+        elif tuple(coordinates.shape) != (R, P, A, 3):
+            raise ValueError(f"coordinates must have shape {(R, A, 3)} (all beads on one point) or {(R, P, A, 3)} (a restart), "
+                             f"got {tuple(coordinates.shape)}")
+        temperature = _per_molecule(temperature, "temperature", R)
+        friction = _per_molecule(friction, "friction", R)
+        if not bool((temperature > 0).all()):
+            raise ValueError("temperature must be > 0")
+        for t, name in ((masses, "masses"), (fixed, "fixed")):
+            if t is not None and tuple(t.shape) != (R, A):
+                raise ValueError(f"{name} must have shape {(R, A)}, got {tuple(t.shape)}")
+        if replica_ids is None:
+            replica_ids = torch.arange(R, dtype=torch.int64)
+        if tuple(replica_ids.shape) != (R,):
+            raise ValueError(f"replica_ids must have shape ({R},), got {tuple(replica_ids.shape)}")
+        replica_ids = replica_ids.detach().cpu().to(torch.int64)
+        if not bool(((replica_ids >= 0) & (replica_ids * P + (P - 1) < 1 << 32)).all()):
+            raise ValueError(f"replica_ids r map to the noise streams r * beads + k, which must stay in 0 .. 2^32 - 1: with "
+                             f"beads = {P} they must be in 0 .. {((1 << 32) - P) // P}")
+        per_bead = lambda t: None if t is None else t.repeat_interleave(P, dim=0)   # noqa: E731
+        super().__init__(model, per_bead(species), coordinates.reshape(R * P, A, 3), cell, pbc, dt=dt, masses=per_bead(masses),
+                         temperature=per_bead(temperature), friction=per_bead(friction), fixed=per_bead(fixed),
+                         replica_ids=(replica_ids.view(R, 1) * P + torch.arange(P)).reshape(-1), seed=seed,
+                         remove_drift=remove_drift)
+        self.beads, self.n_polymers, self.pile_lambda, self.thermostat = P, R, float(pile_lambda), thermostat
+        # (the base class took temperature for Langevin dynamics: no degree of freedom is removed, which is right for RPMD
+        # too, where the springs exchange momentum between the beads)
+        self.langevin = thermostat == "pile"
+        self._params.flags = _lib.MD_LANGEVIN if self.langevin else 0
+        dev = self.coordinates.device
+        self._n_active = (self._active.view(R, P, A)[:, 0] != 0).sum(dim=1).double()
+        self._estimators = torch.zeros((R, 2), dtype=torch.float64, device=dev)
+        self._centroids = torch.zeros((R, A, 3), dtype=torch.float64, device=dev)
+
+    def _drift(self) -> None:
+        """B, the exact free ring-polymer propagation with the PILE thermostat in the middle (anihip_md_rp_drift) on the
+        forces held; advances the noise step."""
+        from .engine import _stream
+
+        torch.mul(self.temperature, KB_HARTREE, out=self._kT)   # (every step: ``temperature`` is the user's to overwrite)
+        self._params.step = self.steps_done
+        _lib.check(_lib.lib().anihip_md_rp_drift(
+            _stream(), C.byref(self._params), self.beads, self.pile_lambda, self._active.data_ptr(), self._inv_mass.data_ptr(),
+            self._kT.data_ptr(), self.friction.data_ptr(), self._replica_ids.data_ptr(), self.coordinates.data_ptr(),
+            self.coordinates_lo.data_ptr(), self.velocities.data_ptr(), self.forces.data_ptr()))
+        self.steps_done += 1
+
+    def set_temperature(self, kelvin) -> None:
+        """Maxwell-Boltzmann bead velocities for the physical temperature ``kelvin`` (a number or [R]): drawn at P kelvin, as
+        the base class draws them.  The thermostat's ``temperature`` is left alone."""
+        kelvin = _per_molecule(kelvin, "temperature", self.n_polymers)
+        super().set_temperature((self.beads * kelvin).repeat_interleave(self.beads))
+
+    # ---- observables of the polymers (Hartree, Angstrom), no host read ------------------------------------------------
+    def _estimate(self) -> Tensor:
+        """anihip_md_rp_estimators on the coordinates and forces held: (S_r, W_r) [R, 2], and the centroids."""
+        from .engine import _stream
+
+        torch.mul(self.temperature, KB_HARTREE, out=self._kT)
+        _lib.check(_lib.lib().anihip_md_rp_estimators(
+            _stream(), C.byref(self._params), self.beads, self._active.data_ptr(), self.masses.data_ptr(), self._kT.data_ptr(),
+            self.coordinates.data_ptr(), self.coordinates_lo.data_ptr(), self.forces.data_ptr(), self._estimators.data_ptr(),
+            self._centroids.data_ptr(), self._workspace.data_ptr(), self._workspace.numel()))
+        return self._estimators
+
+    def centroids(self) -> Tensor:
+        """fp64 [R, A, 3]: the mean of each atom's beads."""
+        self._estimate()
+        return self._centroids.clone()
+
+    def spring_energies(self) -> Tensor:
+        """fp64 [R], Hartree: sum_j sum_i 1/2 m_i omega_P^2 |q_ij - q_i,j+1|^2 with omega_P = P k_B T / hbar."""
+        return self._estimate()[:, 0].clone()
+
+    def quantum_kinetic_energies(self, estimator: str = "centroid_virial") -> Tensor:
+        """fp64 [R], Hartree: the instantaneous value of the quantum kinetic energy estimator, to be averaged along the run.
+        "centroid_virial": 3 N kT / 2 - W / (2 P), W = sum_j sum_i (q_ij - centroid_i) . f_ij; "primitive": 3 N P kT / 2 - S / P,
+        S the spring energy.  N is the number of active atoms and T the physical temperature."""
+        if estimator not in ("centroid_virial", "primitive"):
+            raise ValueError(f'estimator must be "centroid_virial" or "primitive", got {estimator!r}')
+        est, P = self._estimate(), self.beads
+        kT = KB_HARTREE * self.temperature.view(self.n_polymers, P)[:, 0].double()
+        if estimator == "centroid_virial":
+            return 1.5 * self._n_active * kT - est[:, 1] / (2.0 * P)
+        return 1.5 * self._n_active * P * kT - est[:, 0] / P
+
+    def ring_polymer_energies(self) -> Tensor:
+        """fp64 [R], Hartree: sum_j (KE_j + V_j) + S, what ``thermostat=None`` conserves."""
+        beads = (self.kinetic_energies() + self.potential_energies).view(self.n_polymers, self.beads).sum(dim=1)
+        return beads + self.spring_energies()
