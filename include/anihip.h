@@ -618,6 +618,67 @@ int anihip_md_rp_estimators(void *stream, const anihip_md_params *params, int32_
                             const float *forces, double *estimators, double *centroids, void *workspace,
                             size_t workspace_bytes);
 
+/* Temperature replica exchange (parallel tempering) between the entries of a batch (torchani_amd.md.ReplicaExchangeDynamics).
+ * TEMPERATURES are swapped, not coordinates: forces, neighbor state, the two-float coordinates and the noise streams stay with
+ * the batch entry, only [C]-sized state and a velocity rescale move, and nothing is evaluated again.  A batch of C entries
+ * holds L ladders of at most K rungs (all of one ladder the same system).  State, device memory:
+ *   slot        int32 [L][K]    the batch entry at rung k; -1 in the unused tail of a shorter ladder            UPDATED
+ *   count       int32 [L]       the rungs of each ladder, 0 .. K (clamped); rungs k >= count[l] are not read
+ *   rung_of     int32 [C]       the rung of each entry, -1 for an entry in no ladder                            UPDATED
+ *   rung_kT     fp32  [L][K]    k_B T of each rung in HARTREE, strictly increasing along a ladder
+ *   ladder_ids  int64 [L]       the Philox stream of each ladder (values below 2^32), or NULL for l: a ladder draws the same
+ *                               decisions wherever it sits
+ *   attempts, accepts  int64 [L][K - 1]   per pair (k, k + 1), ADDED TO
+ *   direction   int8  [C], round_trips int32 [C]   the round-trip state below                                   UPDATED
+ *   scale       fp64  [C]       OUT: the velocity factor of this attempt for every entry of a ladder (1: the rung is kept)
+ *   energies    fp64  [C]       potential energies at the coordinates held (Hartree)
+ *   kinetic     fp64  [C]       what anihip_md_kick left, UPDATED;   velocities fp32 [C][A][3], UPDATED
+ * (The caller also keeps ladder_of int32 [C], the ladder of each entry, to gather temperatures through rung_of; no kernel
+ * reads it.)  Attempt n = params->step pairs the rungs (k, k + 1) with k = n (mod 2) in every ladder; an unpaired top rung, or
+ * rung 0 at odd n, sits the attempt out.  For a = slot[l][k] and b = slot[l][k + 1], all in fp64:
+ *   arg = (1 / kT_k - 1 / kT_{k+1}) (E_a - E_b)
+ *   u   = p(u0) of Philox4x32-10 with key (seed low, seed high) and counter (k, ladder id, step low, step high),
+ *         step = ANIHIP_MD_EXCHANGE_STEP | n, p the uniform of anihip_md_noise
+ *   accept iff ln u < arg
+ * Bit 61 keeps the stream apart from the drifts', the barostat's (bit 62) and the Maxwell-Boltzmann draws' (bit 63): drift
+ * steps and attempts stay below 2^61.  On accept the two slot entries and the two rung_of values are swapped; entry a gets
+ * v <- v (float)sqrt(kT_{k+1} / kT_k) on every atom with active != 0 and kinetic[a] *= kT_{k+1} / kT_k, entry b the inverse
+ * ratio; attempts and accepts are added to by the one thread that owns the pair; an entry that reaches the top rung
+ * (count[l] - 1) gets direction -1, one that reaches rung 0 gets round_trips += 1 if its direction was -1 and then direction
+ * +1.  (The caller starts with direction +1 at rung 0, -1 at the top rung and 0 between.)  A uniform velocity scale keeps
+ * r_ij . (v_i - v_j) = 0, so constrained velocities need no projection.  Friction stays with the entry.  Entries in no ladder,
+ * unpaired rungs and rejected pairs are not written at all: their velocities and kinetic energies stay bit-identical.  The
+ * caller then sets the thermostat's kT of entry c to rung_kT[ladder_of[c]][rung_of[c]].
+ *
+ * Two launches: one thread per pair writes the tables, kinetic and scale; one thread per atom, in 256-atom chunks, rescales
+ * the velocities where scale is not exactly 1.  No atomics, no host synchronization, bit-identical run to run.  Requires
+ * max_rungs >= 2, the ANIHIP_MD_LANGEVIN flag and step < 2^61.  A slot must lie in -1 .. n_mol - 1.  WITHOUT
+ * ANIHIP_MD_LADDERS_CHECK THE CALL RETURNS 0 FOR A TABLE THAT BREAKS THIS: it reads nothing on the host and cannot see it.  The
+ * kernel then leaves a pair with a slot out of range undecided: nothing is counted, and the member whose slot is in range keeps
+ * its rung, its velocities and its kinetic energy (scale 1).  An entry that no slot names although its rung_of is >= 0 -- the
+ * one that the bad value displaced -- gets no scale from the attempt, and its velocities are multiplied by what scale[c] held
+ * before the call: such a table is outside the contract.  With ANIHIP_MD_LADDERS_CHECK in flags the call first copies slot to
+ * the host -- the one synchronization, for a caller that did not build the table itself -- and returns nonzero for such a
+ * slot before anything is launched. */
+#define ANIHIP_MD_EXCHANGE_STEP (1ull << 61)
+#define ANIHIP_MD_LADDERS_CHECK 1
+typedef struct {
+    int32_t n_ladders, max_rungs;   /* L >= 1, K >= 2 */
+    int32_t flags;                  /* ANIHIP_MD_LADDERS_CHECK or 0 */
+    int32_t reserved;               /* 0 */
+    int32_t *slot;
+    const int32_t *count;
+    int32_t *rung_of;
+    const float *rung_kT;
+    const int64_t *ladder_ids;      /* or NULL */
+    int64_t *attempts, *accepts;
+    int8_t *direction;
+    int32_t *round_trips;
+    double *scale;
+} anihip_md_ladders;
+int anihip_md_exchange(void *stream, const anihip_md_params *params, const anihip_md_ladders *ladders, const double *energies,
+                       const uint8_t *active, float *velocities, double *kinetic);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -17,6 +17,11 @@
                                                                            same [R beads, A] batch: the first 256 / beads molecules
                                                                            of config 2 as ring polymers, or beads copies of the box
 
+    python tools/md_bench.py --exchange-every 1 --rungs 8 --system molecules --repeats 7 ...
+                                                                           temperature replica exchange (md.ReplicaExchangeDynamics):
+                                                                           every molecule of config 2 as a ladder of --rungs replicas,
+                                                                           the exchanging step against exchange_every=0 on one batch
+
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
 median, the fastest and the slowest repeat are printed: the spread to hold a difference against.  Whenever the device integrator
@@ -119,6 +124,49 @@ def bench_beads(args, dev):
               f"{n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M bead-atom*steps/s, bead T = {md.temperatures().mean().item():.0f} K{extra}")
 
 
+def bench_exchange(args, dev):
+    """ReplicaExchangeDynamics with --exchange-every against the same class with exchange_every=0 (the step of BatchedDynamics)
+    on one [molecules x rungs, A] batch, in one process, the repeats alternating: every molecule is a ladder of --rungs
+    replicas on a geometric ladder from --temperature to twice that.  The difference is the attempt's two launches and the
+    gather of the temperatures, once per --exchange-every steps."""
+    from torchani_amd.md import ReplicaExchangeDynamics, temperature_ladder
+    from torchani_amd.models import ANI2x
+
+    K = args.rungs
+    sp, x, cell, pbc, lists = load_system(args, dev)
+    nl = args.neighborlist or ("auto" if cell is not None else lists[0])
+    masses = torch.tensor(ELEMENT_MASSES, device=dev)[sp.clamp(min=0)]
+    L, A = sp.shape
+    rep = lambda t: t.repeat_interleave(K, dim=0)   # noqa: E731
+    T = temperature_ladder(args.temperature, 2.0 * args.temperature, K).repeat(L)
+    drivers = {}
+    for kind, every in (("no exchange", 0), (f"every {args.exchange_every}", args.exchange_every)):
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl, row_capacity=256)
+        md = ReplicaExchangeDynamics(model, rep(sp), rep(x), cell, pbc, dt=args.dt, masses=rep(masses), temperature=T, seed=1,
+                                     ladders=torch.arange(L * K).view(L, K), exchange_every=every)
+        md.set_temperature(T)
+        md.run(args.warmup)
+        drivers[kind] = md
+    times = {kind: [] for kind in drivers}
+    for _ in range(args.repeats):
+        for kind, md in drivers.items():
+            times[kind].append(timed(md, args.steps))
+    n_atoms = int((sp >= 0).sum()) * K
+    med = {}
+    for kind, md in drivers.items():
+        t = np.array(times[kind]) * 1e3
+        med[kind] = np.median(t)
+        extra = ""
+        if md.exchange_every:
+            extra = (f", {md.attempts_done} attempts, acceptance {md.acceptance_rates().mean().item():.3f}, "
+                     f"{int(md.round_trips().sum())} round trips")
+        print(f"{nl:17s} {kind:12s} {L} ladders x {K} rungs x {A} atoms, dt {args.dt:g} fs, {n_atoms} atoms: {np.median(t):.3f} ms/step "
+              f"(fastest {t.min():.3f}, slowest {t.max():.3f} of {len(t)} repeats of {args.steps} steps) = "
+              f"{n_atoms / (np.median(t) * 1e-3) / 1e6:.2f} M atom*steps/s{extra}")
+    a, b = med.values()
+    print(f"the attempts cost {(b - a) * 1e3:+.1f} us per step at one attempt per {args.exchange_every} steps (medians)")
+
+
 def timed(md, steps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -147,7 +195,11 @@ def main():
     ap.add_argument("--barostat-time", type=float, default=1000.0, help="--barostat: relaxation time, fs")
     ap.add_argument("--beads", type=int, default=None,
                     help="path-integral MD with this many beads against the classical Langevin step on the same batch")
-    ap.add_argument("--temperature", type=float, default=300.0, help="--beads: the physical temperature, K")
+    ap.add_argument("--temperature", type=float, default=300.0,
+                    help="--beads: the physical temperature, K; --exchange-every: the lowest rung (the highest is twice that)")
+    ap.add_argument("--exchange-every", type=int, default=None,
+                    help="temperature replica exchange with one attempt per this many steps against the same step without")
+    ap.add_argument("--rungs", type=int, default=8, help="--exchange-every: replicas per ladder")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
@@ -158,6 +210,10 @@ def main():
     dev = torch.device("cuda:0")
     if args.beads is not None:
         return bench_beads(args, dev)
+    if args.exchange_every is not None:
+        if args.exchange_every < 1 or args.rungs < 2:
+            ap.error("--exchange-every must be >= 1 and --rungs >= 2")
+        return bench_exchange(args, dev)
     sp, x, cell, pbc, lists = load_system(args, dev)
     if args.neighborlist is not None and args.system == "water":
         lists = (args.neighborlist,)

@@ -47,6 +47,8 @@ MD_ATOM_CLUSTER, MD_CLUSTER_ATOMS, MD_CLUSTER_BONDS = 2, 8, 12   # ANIHIP_MD_ATO
 MD_BAROSTAT_STEP = 1 << 62   # ANIHIP_MD_BAROSTAT_STEP
 MD_HBAR = 0.024188843265857   # ANIHIP_MD_HBAR, Hartree fs
 MD_RP_MAX_BEADS = 64   # ANIHIP_MD_RP_MAX_BEADS
+MD_EXCHANGE_STEP = 1 << 61   # ANIHIP_MD_EXCHANGE_STEP
+MD_LADDERS_CHECK = 1   # ANIHIP_MD_LADDERS_CHECK
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -135,6 +137,14 @@ class MdClusters(C.Structure):
     _fields_ = [("n_clusters", C.c_int64), ("atoms", C.c_void_p), ("count", C.c_void_p), ("bonds", C.c_void_p),
                 ("d2", C.c_void_p), ("w", C.c_void_p), ("iterations", C.c_void_p), ("tolerance", C.c_double),
                 ("max_iterations", C.c_int32), ("max_atoms", C.c_int32), ("max_bonds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MdLadders(C.Structure):
+    """anihip_md_ladders (include/anihip.h)."""
+    _fields_ = [("n_ladders", C.c_int32), ("max_rungs", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("slot", C.c_void_p), ("count", C.c_void_p), ("rung_of", C.c_void_p), ("rung_kT", C.c_void_p),
+                ("ladder_ids", C.c_void_p), ("attempts", C.c_void_p), ("accepts", C.c_void_p), ("direction", C.c_void_p),
+                ("round_trips", C.c_void_p), ("scale", C.c_void_p)]
 
 
 class MlpShape(C.Structure):
@@ -297,10 +307,11 @@ def lib() -> C.CDLL:
                                             vp, vp, vp, C.POINTER(MdClusters), vp, vp, vp]
     L.anihip_md_rp_drift.argtypes = [vp, C.POINTER(MdParams), i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.anihip_md_rp_estimators.argtypes = [vp, C.POINTER(MdParams), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+    L.anihip_md_exchange.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdLadders), vp, vp, vp, vp]
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
-                 "anihip_md_rp_estimators"):
+                 "anihip_md_rp_estimators", "anihip_md_exchange"):
         getattr(L, name).restype = C.c_int
     L.anihip_pair_d3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, C.POINTER(D3Params), C.c_float, i32, vp, vp, vp, vp, vp]
     L.anihip_pair_d3.restype = C.c_int
@@ -336,6 +347,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
     "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities", "anihip_md_barostat",
     "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift", "anihip_md_rp_estimators",
+    "anihip_md_exchange",
 ]
 
 

@@ -18,11 +18,16 @@
 //   k_md_rp_drift, k_md_rp_estimators   anihip_md_rp_drift / anihip_md_rp_estimators (ring polymers over the beads of a batch):
 //                  B, the exact free ring-polymer propagation in normal modes with the PILE thermostat on them, one thread per
 //                  (mode, atom, component); the spring energy, the centroid-virial sum and the centroids of every polymer
+//   k_md_exchange_pairs, k_md_exchange_scale   anihip_md_exchange (temperature replica exchange between the entries of a batch):
+//                  one thread per pair of neighboring rungs decides the swap of their temperatures and writes the tables, then
+//                  one thread per atom rescales the velocities of the entries that changed rung
 //
 // Positions are pairs of floats, coords + coords_lo: every `x +=` is a two-sum, so a step far below one ulp of the coordinate
 // is not lost, and coords (what the engine reads) is the fp32 nearest to the pair.  The noise xi is a pure function of (seed,
 // step, replica id, atom index): Philox4x32-10 and Box-Muller (md_normals), the same for a replica wherever it sits in the batch.
 // No atomics and every sum in a fixed order: trajectories are bit-identical run to run for bit-identical forces.
+#include <vector>
+
 #include "anihip_common.h"
 
 namespace anihip {
@@ -837,6 +842,69 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_rp_estimators(MdArgs a, int P, 
     md_store_sums<2>(a, r, b, s, 1.0);
 }
 
+// ---- temperature replica exchange (include/anihip.h has the definition) ----------------------------------------------------
+// Two launches, as the barostat: the decision of a pair is one number per entry that every atom of the entry needs.  The first
+// has one thread per pair of rungs (k, k + 1), k = 2 j + parity; a thread owns its two slots and its two entries, so no
+// thread reads what another writes.  It writes scale[c] for every entry of a ladder, 1 for those that keep their rung; the
+// second launch rescales the velocities of the entries whose scale is not 1 and writes nothing else.
+
+__global__ __launch_bounds__(MD_BLOCK) void k_md_exchange_pairs(MdArgs a, anihip_md_ladders ld, const double *energies,
+                                                                double *kinetic, int64_t n_mol)
+{
+    const int K = ld.max_rungs, per_ladder = K / 2 + 1, parity = (int)(a.step0 & 1u);
+    const int64_t t = (int64_t)blockIdx.x * MD_BLOCK + threadIdx.x, l = t / per_ladder;
+    if (l >= ld.n_ladders) return;
+    const int j = (int)(t % per_ladder), n = min(max(ld.count[l], 0), K), k = 2 * j + parity;
+    int32_t *slot = ld.slot + l * K;
+    if (parity == 1 && j == 0 && n > 0) {   // rung 0 sits an odd attempt out
+        const int32_t e0 = slot[0];
+        if (e0 >= 0 && e0 < n_mol) ld.scale[e0] = 1.0;
+    }
+    if (k >= n) return;
+    const int32_t ea = slot[k], eb = k + 1 < n ? slot[k + 1] : -1;
+    const bool has_a = ea >= 0 && ea < n_mol, has_b = eb >= 0 && eb < n_mol;
+    if (!has_a || !has_b || eb == ea) {   // an unpaired top rung, or a slot out of range: whoever is there keeps its rung
+        if (has_a) ld.scale[ea] = 1.0;
+        if (has_b) ld.scale[eb] = 1.0;
+        return;
+    }
+    const double kT_lo = (double)ld.rung_kT[l * K + k], kT_hi = (double)ld.rung_kT[l * K + k + 1];
+    const double arg = (1.0 / kT_lo - 1.0 / kT_hi) * (energies[ea] - energies[eb]);
+    uint32_t c[4] = {(uint32_t)k, ld.ladder_ids ? (uint32_t)ld.ladder_ids[l] : (uint32_t)l, a.step0, a.step1};
+    philox4x32_10(c, a.key0, a.key1);
+    const bool accept = log((double)md_uniform(c[0])) < arg;
+    const int64_t pair = l * (K - 1) + k;
+    ld.attempts[pair] += 1;
+    if (!accept) {
+        ld.scale[ea] = ld.scale[eb] = 1.0;
+        return;
+    }
+    ld.accepts[pair] += 1;
+    slot[k] = eb, slot[k + 1] = ea;
+    ld.rung_of[ea] = k + 1, ld.rung_of[eb] = k;
+    const double up = kT_hi / kT_lo, down = kT_lo / kT_hi;
+    kinetic[ea] *= up, kinetic[eb] *= down;
+    ld.scale[ea] = sqrt(up), ld.scale[eb] = sqrt(down);
+    if (k + 1 == n - 1) ld.direction[ea] = -1;
+    if (k == 0) {
+        if (ld.direction[eb] == -1) ld.round_trips[eb] += 1;
+        ld.direction[eb] = 1;
+    }
+}
+
+__global__ __launch_bounds__(MD_BLOCK) void k_md_exchange_scale(MdArgs a, const int32_t *rung_of, const double *scale)
+{
+    const int64_t c = blockIdx.x / a.Gc, i = (blockIdx.x % a.Gc) * MD_BLOCK + threadIdx.x;
+    if (i >= a.A || rung_of[c] < 0) return;   // (an entry in no ladder has no scale)
+    const double s = scale[c];
+    const int64_t at = c * a.A + i;
+    if (s == 1.0 || !a.active[at]) return;
+    const float sf = (float)s;
+    float *v = a.vel + 3 * at;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] *= sf;
+}
+
 static int md_args(const anihip_md_params *params, MdArgs &a)
 {
     ANIHIP_REQUIRE(params, "null pointer argument");
@@ -1150,5 +1218,41 @@ extern "C" int anihip_md_rp_estimators(void *stream, const anihip_md_params *par
         hipLaunchKernelGGL(k_md_sum<2>, dim3(R), dim3(MD_BLOCK), 0, s, a, 1.0);
         ANIHIP_CHECK_HIP(hipGetLastError());
     }
+    return 0;
+}
+
+extern "C" int anihip_md_exchange(void *stream, const anihip_md_params *params, const anihip_md_ladders *ladders,
+                                  const double *energies, const uint8_t *active, float *velocities, double *kinetic)
+{
+    MdArgs a;
+    if (int rc = md_args(params, a)) return rc;
+    ANIHIP_REQUIRE(ladders, "null pointer argument");
+    const anihip_md_ladders &ld = *ladders;
+    ANIHIP_REQUIRE(ld.n_ladders >= 1 && ld.max_rungs >= 2, "a ladder needs at least 2 rungs (n_ladders %d, max_rungs %d)",
+                   ld.n_ladders, ld.max_rungs);
+    ANIHIP_REQUIRE((int64_t)ld.n_ladders * (ld.max_rungs / 2 + 1) < ((int64_t)1 << 31) * MD_BLOCK, "n_ladders x max_rungs out of range");
+    ANIHIP_REQUIRE(a.langevin, "replica exchange needs Langevin dynamics (ANIHIP_MD_LANGEVIN): the rungs are temperatures");
+    ANIHIP_REQUIRE(params->step < ANIHIP_MD_EXCHANGE_STEP, "step (the attempt number) must stay below 2^61");
+    ANIHIP_REQUIRE(ld.slot && ld.count && ld.rung_of && ld.rung_kT && ld.attempts && ld.accepts && ld.direction && ld.round_trips
+                       && ld.scale && energies && active && velocities && kinetic,
+                   "null pointer argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (ld.flags & ANIHIP_MD_LADDERS_CHECK) {   // the one host read of this file, and only on request
+        std::vector<int32_t> slot((size_t)ld.n_ladders * ld.max_rungs);
+        ANIHIP_CHECK_HIP(hipMemcpyAsync(slot.data(), ld.slot, slot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        ANIHIP_CHECK_HIP(hipStreamSynchronize(s));
+        for (size_t q = 0; q < slot.size(); ++q)
+            ANIHIP_REQUIRE(slot[q] >= -1 && slot[q] < params->n_mol, "slot[%zu][%zu] = %d is outside -1 .. n_mol - 1 = %d",
+                           q / ld.max_rungs, q % ld.max_rungs, slot[q], params->n_mol - 1);
+    }
+    a.step1 |= (uint32_t)(ANIHIP_MD_EXCHANGE_STEP >> 32);   // a stream of its own, apart from the drifts' and the barostat's
+    a.active = active, a.vel = velocities;
+    const int64_t threads = (int64_t)ld.n_ladders * (ld.max_rungs / 2 + 1);
+    hipLaunchKernelGGL(k_md_exchange_pairs, dim3((unsigned)((threads + MD_BLOCK - 1) / MD_BLOCK)), dim3(MD_BLOCK), 0, s, a, ld,
+                       energies, kinetic, (int64_t)params->n_mol);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_md_exchange_scale, md_grid(params, a), dim3(MD_BLOCK), 0, s, a, (const int32_t *)ld.rung_of,
+                       (const double *)ld.scale);
+    ANIHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }

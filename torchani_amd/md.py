@@ -17,6 +17,8 @@ With constraints, ``barostat_scaling="molecular"`` moves every constraint cluste
 two or three after the kick for the centre-of-mass kinetic energy and the internal virial of the clusters).
 ``RingPolymerDynamics`` is path-integral MD on the same machinery: the batch holds the beads of R ring polymers, and its drift is
 one launch that propagates the free ring polymer exactly in its normal modes with the PILE thermostat on them.
+``ReplicaExchangeDynamics`` is temperature replica exchange over the entries of the batch: every ``exchange_every`` steps two
+launches swap the temperatures of neighboring rungs of every ladder by the Metropolis rule and rescale the velocities.
 """
 from __future__ import annotations
 
@@ -872,3 +874,199 @@ class RingPolymerDynamics(BatchedDynamics):
         """fp64 [R], Hartree: sum_j (KE_j + V_j) + S, what ``thermostat=None`` conserves."""
         beads = (self.kinetic_energies() + self.potential_energies).view(self.n_polymers, self.beads).sum(dim=1)
         return beads + self.spring_energies()
+
+
+def temperature_ladder(t_min: float, t_max: float, n: int) -> Tensor:
+    """fp64 [n]: a geometric ladder t_min (t_max / t_min)^(k / (n - 1)), the spacing of equal acceptance for a constant heat
+    capacity."""
+    if isinstance(n, bool) or int(n) != n or n < 2:
+        raise ValueError(f"a ladder needs n >= 2 rungs, got {n}")
+    if not 0 < t_min < t_max:
+        raise ValueError(f"expected 0 < t_min < t_max, got {t_min} and {t_max}")
+    k = torch.arange(int(n), dtype=torch.float64) / (int(n) - 1)
+    return float(t_min) * (float(t_max) / float(t_min)) ** k
+
+
+class LadderTables(tp.NamedTuple):
+    """The tables of anihip_md_exchange (include/anihip.h) on the host."""
+    slot: Tensor          # int32 [L, K]: the batch entry at each rung, -1 past the end of a shorter ladder
+    count: Tensor         # int32 [L]: rungs of each ladder
+    rung_of: Tensor       # int32 [C]: -1 for an entry in no ladder
+    ladder_of: Tensor     # int32 [C]: 0 for an entry in no ladder (never read for it)
+    rung_temperatures: Tensor   # fp32 [L, K], K; 0 past the end of a shorter ladder
+    direction: Tensor     # int8 [C]: +1 at rung 0, -1 at the top rung, 0 between
+
+
+def build_ladders(ladders: tp.Optional[Tensor], temperature: Tensor, species: tp.Optional[Tensor] = None,
+                  fixed: tp.Optional[Tensor] = None) -> LadderTables:
+    """The ladder tables of ``ReplicaExchangeDynamics`` from ``ladders`` (None: one ladder of all C entries in batch order, or
+    int64 [L, K] of batch indices, -1 padding the tail of a shorter ladder) and the initial ``temperature`` [C] in K.  Rung
+    order is column order.  Raises ValueError for a ladder of fewer than two rungs, an index outside the batch, padding that
+    is not a tail, an entry in two ladders, temperatures that are not strictly increasing along a ladder, and ``species``
+    [C, A] or ``fixed`` [C, A] that differ within a ladder.  Host tensors; reads no device."""
+    temperature = temperature.detach().cpu().to(torch.float32)
+    Cn = temperature.shape[0]
+    if ladders is None:
+        ladders = torch.arange(Cn, dtype=torch.int64).view(1, Cn)
+    ladders = torch.as_tensor(ladders).detach().cpu()
+    if ladders.dim() != 2 or ladders.dtype not in (torch.int64, torch.int32):
+        raise ValueError("ladders must be an integer tensor [L, K] of batch indices (-1 padding)")
+    ladders = ladders.to(torch.int64)
+    L, K = ladders.shape
+    if L < 1 or K < 2:
+        raise ValueError(f"ladders must hold at least one ladder of at least 2 rungs, got shape {(L, K)}")
+    if bool(((ladders < -1) | (ladders >= Cn)).any()):
+        raise ValueError(f"ladders must hold batch indices in 0 .. {Cn - 1}, or -1 as padding")
+    used = ladders >= 0
+    count = used.sum(dim=1)
+    if bool((used != (torch.arange(K).view(1, K) < count.view(L, 1))).any()):
+        raise ValueError("the -1 padding of a ladder must be its tail: rung order is column order, without gaps")
+    if bool((count < 2).any()):
+        raise ValueError(f"ladder {int((count < 2).nonzero()[0])} has fewer than 2 rungs")
+    members = ladders[used]
+    if members.unique().numel() != members.numel():
+        seen = torch.bincount(members, minlength=Cn)
+        raise ValueError(f"batch entry {int((seen > 1).nonzero()[0])} is in two ladders (or twice in one)")
+    rung_t = torch.where(used, temperature[ladders.clamp(min=0)], torch.zeros(()))
+    if bool((rung_t[used] <= 0).any()):
+        raise ValueError("the temperatures of a ladder must be > 0")
+    falling = used[:, 1:] & ~(rung_t[:, 1:] > rung_t[:, :-1])
+    if bool(falling.any()):
+        l, k = (int(t) for t in falling.nonzero()[0])
+        raise ValueError(f"the initial temperatures must be strictly increasing along each ladder: ladder {l} has "
+                         f"{float(rung_t[l, k]):g} K at rung {k} and {float(rung_t[l, k + 1]):g} K at rung {k + 1}")
+    first = ladders[:, :1].expand(L, K)[used]
+    for t, name in ((species, "species"), (fixed, "fixed")):
+        if t is not None:
+            t = t.detach().cpu()
+            if bool((t[members] != t[first]).any()):
+                raise ValueError(f"{name} differ within a ladder: the rungs of a ladder are replicas of one system")
+    rung_of = torch.full((Cn,), -1, dtype=torch.int32)
+    ladder_of = torch.zeros(Cn, dtype=torch.int32)
+    rung_of[members] = torch.arange(K, dtype=torch.int32).view(1, K).expand(L, K)[used]
+    ladder_of[members] = torch.arange(L, dtype=torch.int32).view(L, 1).expand(L, K)[used]
+    direction = torch.zeros(Cn, dtype=torch.int8)
+    direction[ladders[:, 0]] = 1
+    direction[ladders[torch.arange(L), count - 1]] = -1
+    return LadderTables(ladders.to(torch.int32), count.to(torch.int32), rung_of, ladder_of, rung_t, direction)
+
+
+class ReplicaExchangeDynamics(BatchedDynamics):
+    """Temperature replica exchange (parallel tempering) on the device: the batch holds L ladders of replicas of one system
+    each, every replica a Langevin trajectory of ``BatchedDynamics`` at the temperature of its rung, and every
+    ``exchange_every`` steps neighboring rungs of every ladder try to swap their TEMPERATURES by the Metropolis rule on the
+    potential energies held (anihip_md_exchange; include/anihip.h has the exact definition).  Coordinates, forces, neighbor
+    state and noise streams stay with the batch entry; an accepted swap rescales the two entries' velocities by
+    sqrt(T_new / T_old), so nothing is evaluated again and no step reads on the host.
+
+    species [C, A], coordinates, cell, pbc and every keyword of ``BatchedDynamics`` keep their meaning.  temperature
+    (required): a [C] tensor in K, the initial temperature of every entry.  ladders: None for one ladder of all C entries in
+    batch order, or int64 [L, K] of batch indices, rung order being column order and -1 padding the tail of a shorter ladder;
+    the initial temperatures must increase strictly along a ladder, no entry may be in two, and the entries of a ladder must
+    have the same species and ``fixed`` mask.  Entries in no ladder are plain Langevin trajectories.  ladder_ids: int64 [L]
+    in 0 .. 2^32 - 1, the stream of each ladder's decisions (default: its index) -- with ``replica_ids`` a ladder follows the
+    same trajectory wherever it sits in the batch.  NVE (no temperature) is refused, and so is ``pressure=``: the barostat
+    handles one system (C = 1) and a ladder has at least two entries.
+
+    ``step()`` is the inherited step and then, when ``steps_done`` is a multiple of ``exchange_every``, one attempt with the
+    attempt number ``attempts_done``: even attempts pair the rungs (0, 1), (2, 3), ..., odd ones (1, 2), (3, 4), ....  After
+    an attempt ``temperature`` of every ladder member is rewritten from ``rung_temperatures`` (fp32 [L, K], K, a device tensor
+    that may be overwritten between steps and is converted to kT at every attempt) through the rung of the entry.
+    ``exchange_every=0`` never exchanges and is bit-identical to ``BatchedDynamics``.  Friction stays with the entry.
+    Constraints are allowed: a uniform velocity scale keeps the RATTLE condition, so no projection follows.
+
+    Observables, device tensors read without host synchronization: ``rungs()`` int32 [C] (-1: in no ladder),
+    ``replicas_at_rungs()`` int32 [L, K] (-1 padding), ``exchange_attempts`` and ``exchange_accepts`` int64 [L, K - 1] per pair
+    (k, k + 1), ``acceptance_rates()``, ``round_trips()`` int32 [C] (rung 0 to the top rung and back) and ``by_rung(t)``,
+    which gathers any [C, ...] tensor to [L, K, ...] (zeros in the padding).
+    """
+
+    def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
+                 temperature=None, ladders: tp.Optional[Tensor] = None, exchange_every: int = 100,
+                 ladder_ids: tp.Optional[Tensor] = None, pressure=None, **kw) -> None:
+        if temperature is None:
+            raise ValueError("ReplicaExchangeDynamics needs temperature, a [C] tensor: NVE has no temperatures to exchange")
+        if pressure is not None:
+            raise ValueError("ReplicaExchangeDynamics does not support pressure: the barostat handles one system (C = 1) and a "
+                             "ladder has at least two entries")
+        if isinstance(exchange_every, bool) or int(exchange_every) != exchange_every or exchange_every < 0:
+            raise ValueError(f"exchange_every must be an integer >= 0, got {exchange_every}")
+        if species.dim() != 2:
+            raise ValueError("expected species [C, A]")
+        Cn = species.shape[0]
+        temperature = torch.as_tensor(temperature)
+        if tuple(temperature.shape) != (Cn,):
+            raise ValueError(f"temperature must be a tensor of shape ({Cn},), one per batch entry, got {tuple(temperature.shape)}")
+        tables = build_ladders(ladders, temperature, species, kw.get("fixed"))
+        L, K = tables.slot.shape
+        if ladder_ids is not None:
+            ladder_ids = torch.as_tensor(ladder_ids).detach().cpu().to(torch.int64)
+            if tuple(ladder_ids.shape) != (L,) or not bool(((ladder_ids >= 0) & (ladder_ids < 1 << 32)).all()):
+                raise ValueError(f"ladder_ids must be {L} integers in 0 .. 2^32 - 1 (one Philox counter word)")
+        super().__init__(model, species, coordinates, cell, pbc, temperature=temperature, **kw)
+        dev = self.coordinates.device
+        self.exchange_every, self.attempts_done = int(exchange_every), 0
+        self.n_ladders, self.max_rungs = L, K
+        self._slot, self._count, self._rung_of, self._ladder_of, self.rung_temperatures, self._direction = (
+            t.to(dev).contiguous() for t in tables)
+        self._rung_kT = torch.empty_like(self.rung_temperatures)
+        self._ladder_ids = None if ladder_ids is None else ladder_ids.to(dev).contiguous()
+        self.exchange_attempts = torch.zeros((L, K - 1), dtype=torch.int64, device=dev)
+        self.exchange_accepts = torch.zeros((L, K - 1), dtype=torch.int64, device=dev)
+        self._round_trips = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self._exchange_scale = torch.ones(Cn, dtype=torch.float64, device=dev)
+        # the gather of ``temperature`` after an attempt: members [M], their ladders [M] (int64: index tensors, no host read)
+        self._members = (self._rung_of >= 0).nonzero().view(-1)
+        self._member_ladders = self._ladder_of[self._members].long()
+        self._ladders = _lib.MdLadders(
+            L, K, 0, 0, self._slot.data_ptr(), self._count.data_ptr(), self._rung_of.data_ptr(), self._rung_kT.data_ptr(),
+            None if self._ladder_ids is None else self._ladder_ids.data_ptr(), self.exchange_attempts.data_ptr(),
+            self.exchange_accepts.data_ptr(), self._direction.data_ptr(), self._round_trips.data_ptr(),
+            self._exchange_scale.data_ptr())
+        self._exchange_params = _lib.MdParams(Cn, species.shape[1], _lib.MD_LANGEVIN, 0, self.dt, self.seed, 0)
+
+    def _exchange(self) -> None:
+        """One attempt (anihip_md_exchange) on the potential and kinetic energies held, then ``temperature`` of the ladder
+        members from ``rung_temperatures`` through their new rungs."""
+        from .engine import _stream
+
+        torch.mul(self.rung_temperatures, KB_HARTREE, out=self._rung_kT)   # (every attempt: the user's to overwrite)
+        self._exchange_params.step = self.attempts_done
+        _lib.check(_lib.lib().anihip_md_exchange(
+            _stream(), C.byref(self._exchange_params), C.byref(self._ladders), self.potential_energies.data_ptr(),
+            self._active.data_ptr(), self.velocities.data_ptr(), self._kinetic.data_ptr()))
+        self.attempts_done += 1
+        rung = self._rung_of[self._members].long()
+        self.temperature.index_copy_(0, self._members, self.rung_temperatures[self._member_ladders, rung])
+
+    def step(self) -> None:
+        """The inherited step, then one exchange attempt when ``steps_done`` is a multiple of ``exchange_every``.  No host
+        synchronization."""
+        super().step()
+        if self.exchange_every and self.steps_done % self.exchange_every == 0:
+            self._exchange()
+
+    # ---- observables, no host read ------------------------------------------------------------------------------------
+    def rungs(self) -> Tensor:
+        """int32 [C]: the rung of each batch entry, -1 for an entry in no ladder."""
+        return self._rung_of.clone()
+
+    def replicas_at_rungs(self) -> Tensor:
+        """int32 [L, K]: the batch entry at each rung, -1 past the end of a shorter ladder."""
+        return self._slot.clone()
+
+    def acceptance_rates(self) -> Tensor:
+        """fp64 [L, K - 1]: accepts / attempts of each pair (k, k + 1); 0 where nothing was attempted."""
+        return self.exchange_accepts.double() / self.exchange_attempts.clamp(min=1).double()
+
+    def round_trips(self) -> Tensor:
+        """int32 [C]: how often each entry has come back to rung 0 after reaching the top rung of its ladder."""
+        return self._round_trips.clone()
+
+    def by_rung(self, tensor: Tensor) -> Tensor:
+        """Any [C, ...] tensor gathered to [L, K, ...] through the current occupancy; zeros in the padding."""
+        if tensor.shape[:1] != self._rung_of.shape:
+            raise ValueError(f"expected a tensor of shape [{self._rung_of.shape[0]}, ...], got {tuple(tensor.shape)}")
+        out = tensor[self._slot.clamp(min=0).long()]
+        used = (self._slot >= 0).view(self.n_ladders, self.max_rungs, *([1] * (tensor.dim() - 1)))
+        return torch.where(used, out, torch.zeros((), dtype=out.dtype, device=out.device))
