@@ -679,6 +679,101 @@ typedef struct {
 int anihip_md_exchange(void *stream, const anihip_md_params *params, const anihip_md_ladders *ladders, const double *energies,
                        const uint8_t *active, float *velocities, double *kinetic);
 
+/* Biased MD (torchani_amd.md.BatchedDynamics(bias=...)): restraints on collective variables (CVs) and metadynamics, added to
+ * the forces held between the evaluation and the kick.  A CV lives on atoms of ONE batch entry; differences are the plain
+ * ones of the unwrapped coordinates (no minimum image), and all arithmetic is fp64 on x = coords + coords_lo, read exactly.
+ *   ANIHIP_MD_CV_DISTANCE  i-j       s = |x_i - x_j|                                           grad_i = (x_i - x_j) / s = -grad_j
+ *   ANIHIP_MD_CV_ANGLE     i-j-k     a = x_i - x_j, b = x_k - x_j, n = a x b, s = atan2(|n|, a.b) in [0, pi]
+ *                                    grad_i = a x n / (|a|^2 |n|), grad_k = n x b / (|b|^2 |n|), grad_j = -(grad_i + grad_k):
+ *                                    the form through a x b, finite up to a straight angle, no 1 / sin
+ *   ANIHIP_MD_CV_DIHEDRAL  i-j-k-l   b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k, n1 = b1 x b2, n2 = b2 x b3,
+ *                                    s = atan2(|b2| b1.n2, n1.n2) in (-pi, pi], trans = pi; Blondel and Karplus (1996):
+ *                                    grad_i = -|b2| n1 / |n1|^2, grad_l = |b2| n2 / |n2|^2, p = b1.b2 / |b2|^2, q = b3.b2 / |b2|^2,
+ *                                    grad_j = q grad_l - (1 + p) grad_i, grad_k = p grad_i - (1 + q) grad_l
+ * wrap(d) = d - 2 pi floor((d + pi) / (2 pi)) brings a difference of dihedrals into [-pi, pi).
+ *
+ * Restraint of CV r, restraint[r] = (center, k, half_width), k in Hartree / Angstrom^2 or Hartree / rad^2, k = 0: none:
+ *   d = s - center (wrapped for a dihedral),  e = max(0, |d| - half_width),  E = k e^2 / 2,  dE/ds = k e sign(d)
+ * Metadynamics: entry c with list[c] = g >= 0 carries the bias of the hills h < used[g] of list g on its one or two CVs
+ * meta_cv[c][d] (positions within the entry's CVs, -1: no second one), with the difference wrapped for a dihedral:
+ *   V_c = sum_h heights[g][h] exp(-1/2 sum_d inv_sigma2[c][d] (s_d - centers[g][d][h])^2)
+ * No truncation.  Entries that share a list are the walkers of multiple-walker metadynamics; they must agree in the kinds of
+ * their CVs and in inv_sigma2 (anihip_md_bias_hills reads both from list_entry[g], any member of the list).
+ *
+ * Tables, device memory unless marked HOST (C = params->n_mol, A = params->atoms_per_mol, G = n_lists, Ncv = n_cvs):
+ *   cv_offset    int32 [C + 1]   CSR: entry c owns the CVs cv_offset[c] .. cv_offset[c + 1] - 1, at most ANIHIP_MD_BIAS_MAX_CVS
+ *   kind         int32 [Ncv]     ANIHIP_MD_CV_*
+ *   atoms        int32 [Ncv][4]  global atom index c A + i of i, j(, k(, l)), distinct, all inside entry c; unused slots -1
+ *   restraint    fp64  [Ncv][3]  (center, k >= 0, half_width >= 0)
+ *   meta_cv      int32 [C][2]    see above;  inv_sigma2 fp64 [C][2] 1 / sigma_d^2;  height fp64 [C] Hartree
+ *   list         int32 [C]       g, or -1: no metadynamics;   rank_in_list int32 [C]  0 .. members[g] - 1, distinct within a list
+ *   members      int32 [G]       entries of each list;   list_entry int32 [G] one of them
+ *   bias_factor  fp64  [G]       gamma > 1 (well-tempered), or 0 (plain)
+ *   used         int32 [G]       hills held, UPDATED by the deposit;   dropped int32 [G]  ADDED TO by a deposit that did not fit
+ *   centers      fp64  [G][2][capacity], heights fp64 [G][capacity]   the hills, a structure of arrays; APPENDED TO
+ *   status       int32 [C]       OUT of anihip_md_bias_apply: 0, or ANIHIP_MD_BIAS_BAD_* bits of an entry whose tables are out
+ *                                of range -- such an entry moves nothing: its forces, energies and CV values are not written
+ *   capacity (HOST) hills per list; hills_bound (HOST) the caller's upper bound of every used[g], which sizes the grid of the
+ *   hills kernel (hills past it are not summed), or 0 for capacity.
+ *
+ * anihip_md_bias_apply: forces fp32 [C][A][3] UPDATED, bias_energies fp64 [C] OUT (restraints + V_c), meta_energies fp64 [C]
+ * OUT (V_c), cv_values fp64 [Ncv] OUT.  With n_lists = 0 one launch, else two:
+ *   hills kernel   one workgroup per (entry, chunk of ANIHIP_MD_BIAS_CHUNK hills), those of entries without a list and of
+ *                  chunks past used[g] leaving at once: thread t adds the hills t, t + 256, ... of the chunk in that order, the workgroup sum (lanes, then waves, in a fixed order) of V,
+ *                  dV/ds_0 and dV/ds_1 goes to workspace[c][chunk][3]
+ *   apply kernel   one workgroup per entry: the chunk sums added in chunk order; one thread per CV evaluates it, its gradient
+ *                  and dE/ds (restraint, plus dV/ds_d on the CVs of the metadynamics); one thread per atom of a CV adds
+ *                  f = sum over the entry's CVs that hold the atom, in CV order from 0, of -dE/ds grad, and writes
+ *                  forces = (float)((double)forces + f) once; bias_energies = (sum of E in CV order) + V_c
+ * No atomics on memory: two calls on the same input are bit-identical, and an entry gives the same bits wherever it sits in
+ * the batch.  Forces land on fixed atoms too; the integrator ignores them there.
+ *
+ * anihip_md_bias_deposit (after anihip_md_bias_apply, on its cv_values and meta_energies): every entry with a list appends
+ * one hill at h = used[g] + rank_in_list[c]: centers[g][d][h] = its CV d (0 for a missing second one), heights[g][h] =
+ * height[c], times exp(-V_c / ((bias_factor[g] - 1) kT_c)) for bias_factor[g] > 0, with kT fp32 [C] in Hartree (NULL: every
+ * list deposits the plain height) and V_c = meta_energies[c]: every walker sees the bias of before this round.  Then used[g] +=
+ * members[g].  A list with used[g] + members[g] > capacity deposits nothing, keeps used[g] and adds members[g] to dropped[g];
+ * nothing is ever written past capacity.  An entry whose status is not 0 appends nothing: the slot that the round reserves
+ * for it keeps what it held.  Two launches (one thread per entry, then one per list).
+ *
+ * anihip_md_bias_hills: V (out_V fp64 [n_points]) and dV/ds (out_dV fp64 [n_points][2]) of list `list` at values fp64
+ * [n_points][2], the second column ignored for a list of one CV: one workgroup per point, the chunks summed exactly as
+ * above, so a point at a walker's CV values gives the bits of its meta_energies.  The readout for free energies.  A list
+ * whose list_entry or CV tables are out of range gives NaN.
+ *
+ * anihip_md_bias_workspace_bytes: 0 for n_lists = 0, else C ceil(capacity / ANIHIP_MD_BIAS_CHUNK) 3 doubles.
+ * All of them return nonzero for what the host can see (null pointers, negative counts, a short workspace, a list index
+ * outside 0 .. G - 1); what lives in device memory is checked by the kernels and reported in status. */
+#define ANIHIP_MD_BIAS_MAX_CVS 16
+#define ANIHIP_MD_BIAS_CHUNK 1024
+#define ANIHIP_MD_CV_DISTANCE 0
+#define ANIHIP_MD_CV_ANGLE 1
+#define ANIHIP_MD_CV_DIHEDRAL 2
+#define ANIHIP_MD_BIAS_BAD_OFFSET 1   /* cv_offset outside 0 .. Ncv, falling, or more than ANIHIP_MD_BIAS_MAX_CVS CVs */
+#define ANIHIP_MD_BIAS_BAD_CV 2       /* a kind that is none of the three, an atom outside the entry or given twice */
+#define ANIHIP_MD_BIAS_BAD_LIST 4     /* list, rank_in_list or meta_cv out of range */
+typedef struct {
+    int32_t n_cvs, n_lists, capacity, hills_bound, reserved;
+    int32_t n_entries;   /* C, equal to params->n_mol (anihip_md_bias_hills takes no params) */
+    const int32_t *cv_offset, *kind, *atoms;
+    const double *restraint;
+    const int32_t *meta_cv;
+    const double *inv_sigma2, *height;
+    const int32_t *list, *rank_in_list, *members, *list_entry;
+    const double *bias_factor;
+    int32_t *used, *dropped;
+    double *centers, *heights;
+    int32_t *status;
+} anihip_md_bias;
+size_t anihip_md_bias_workspace_bytes(const anihip_md_params *params, const anihip_md_bias *bias);
+int anihip_md_bias_apply(void *stream, const anihip_md_params *params, const anihip_md_bias *bias, const float *coords,
+                         const float *coords_lo, float *forces, double *bias_energies, double *meta_energies,
+                         double *cv_values, void *workspace, size_t workspace_bytes);
+int anihip_md_bias_deposit(void *stream, const anihip_md_params *params, const anihip_md_bias *bias, const float *kT,
+                           const double *cv_values, const double *meta_energies);
+int anihip_md_bias_hills(void *stream, const anihip_md_bias *bias, int32_t list, int64_t n_points, const double *values,
+                         double *out_V, double *out_dV);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -21,6 +21,13 @@
                                                                            temperature replica exchange (md.ReplicaExchangeDynamics):
                                                                            every molecule of config 2 as a ladder of --rungs replicas,
                                                                            the exchanging step against exchange_every=0 on one batch
+    python tools/md_bench.py --bias restraints --system molecules --langevin --repeats 7 ...
+    python tools/md_bench.py --bias metadynamics --hills 10000 [--shared-walkers] --system molecules --langevin --repeats 7 ...
+                                                                           biased MD (md.BatchedDynamics(bias=...)) against the
+                                                                           unbiased step on one batch: one restraint per system
+                                                                           (a dihedral of each molecule, a distance in the box),
+                                                                           or a static 2-CV metadynamics bias of --hills hills
+                                                                           per list, a list per molecule or one for all walkers
 
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
@@ -167,6 +174,54 @@ def bench_exchange(args, dev):
     print(f"the attempts cost {(b - a) * 1e3:+.1f} us per step at one attempt per {args.exchange_every} steps (medians)")
 
 
+def bench_bias(args, dev):
+    """BatchedDynamics with ``bias=`` against the same step without, in one process, the repeats alternating.  Restraints: one
+    launch more per step.  Metadynamics: --hills hills preloaded per list and pace 0, so the count stays what was asked for and
+    the step is the hills kernel plus the apply kernel; the deposit (two small launches every pace steps) is not in it."""
+    from torchani_amd import md as M
+    from torchani_amd.models import ANI2x
+
+    sp, x, cell, pbc, lists = load_system(args, dev)
+    nl = args.neighborlist or lists[0]
+    masses = torch.tensor(ELEMENT_MASSES, device=dev)[sp.clamp(min=0)]
+    Cn, A = sp.shape
+    temperature = 300.0 if args.langevin else None
+    if args.bias == "restraints":
+        cv = M.dihedral(0, 1, 2, 3) if cell is None else M.distance(0, 3)
+        bias, what = [M.Restraint(cv, 1.0 if cell is None else 3.0, 0.01)], "one restraint per system"
+    else:
+        if cell is not None:
+            raise SystemExit("--bias metadynamics is timed on --system molecules")
+        rs = np.random.RandomState(0)
+        G, H = (1 if args.shared_walkers else Cn), max(1, args.hills)
+        centers = np.stack([rs.uniform(-np.pi, np.pi, (G, H)), rs.uniform(1.0, 5.0, (G, H))], axis=1)
+        hills = (torch.from_numpy(centers), torch.full((G, H), 1e-6, dtype=torch.float64),
+                 torch.full((G,), args.hills, dtype=torch.int64))
+        walkers = torch.zeros(Cn, dtype=torch.int64) if args.shared_walkers else None
+        bias = [M.Metadynamics([M.dihedral(0, 1, 2, 3), M.distance(0, 4)], (0.3, 0.2), 1e-6, 0, walkers=walkers, max_hills=H,
+                               hills=hills)]
+        what = f"2-CV metadynamics, {args.hills} hills per list, {'one list of all walkers' if args.shared_walkers else 'a list per system'}"
+    drivers = {}
+    for kind, b in (("unbiased", None), ("biased", bias)):
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl, row_capacity=256)
+        d = M.BatchedDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1, bias=b)
+        d.set_temperature(300.0)
+        d.run(args.warmup)
+        drivers[kind] = d
+    times = {kind: [] for kind in drivers}
+    for _ in range(args.repeats):
+        for kind, d in drivers.items():
+            times[kind].append(timed(d, args.steps))
+    n_atoms = int((sp >= 0).sum())
+    t = {kind: np.array(v) * 1e3 for kind, v in times.items()}
+    for kind in drivers:
+        print(f"{nl:17s} {kind:9s} {Cn} x {A} atoms ({n_atoms} real), dt {args.dt:g} fs: {np.median(t[kind]):.3f} ms/step (fastest "
+              f"{t[kind].min():.3f}, slowest {t[kind].max():.3f} of {len(t[kind])} repeats of {args.steps} steps)")
+    apart = t["biased"].min() > t["unbiased"].max() or t["biased"].max() < t["unbiased"].min()
+    print(f"{what}: {(np.median(t['biased']) - np.median(t['unbiased'])) * 1e3:+.1f} us per step (medians); the ranges "
+          f"{'separate' if apart else 'overlap: no difference can be claimed'}")
+
+
 def timed(md, steps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -200,6 +255,10 @@ def main():
     ap.add_argument("--exchange-every", type=int, default=None,
                     help="temperature replica exchange with one attempt per this many steps against the same step without")
     ap.add_argument("--rungs", type=int, default=8, help="--exchange-every: replicas per ladder")
+    ap.add_argument("--bias", choices=("restraints", "metadynamics"), default=None,
+                    help="the device integrator with this bias against the same step without")
+    ap.add_argument("--hills", type=int, default=1000, help="--bias metadynamics: hills held by every list")
+    ap.add_argument("--shared-walkers", action="store_true", help="--bias metadynamics: every system a walker of one list")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
@@ -214,6 +273,10 @@ def main():
         if args.exchange_every < 1 or args.rungs < 2:
             ap.error("--exchange-every must be >= 1 and --rungs >= 2")
         return bench_exchange(args, dev)
+    if args.bias is not None:
+        if args.hills < 0:
+            ap.error("--hills must be >= 0")
+        return bench_bias(args, dev)
     sp, x, cell, pbc, lists = load_system(args, dev)
     if args.neighborlist is not None and args.system == "water":
         lists = (args.neighborlist,)

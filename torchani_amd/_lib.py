@@ -14,8 +14,8 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip"]
-HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", os.path.join("..", "..", "include", "anihip.h")]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip"]
+HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
 MAX_SPECIES = 8
@@ -49,6 +49,10 @@ MD_HBAR = 0.024188843265857   # ANIHIP_MD_HBAR, Hartree fs
 MD_RP_MAX_BEADS = 64   # ANIHIP_MD_RP_MAX_BEADS
 MD_EXCHANGE_STEP = 1 << 61   # ANIHIP_MD_EXCHANGE_STEP
 MD_LADDERS_CHECK = 1   # ANIHIP_MD_LADDERS_CHECK
+MD_BIAS_MAX_CVS = 16   # ANIHIP_MD_BIAS_MAX_CVS
+MD_BIAS_CHUNK = 1024   # ANIHIP_MD_BIAS_CHUNK: hills per workgroup of the hills kernel
+MD_CV_DISTANCE, MD_CV_ANGLE, MD_CV_DIHEDRAL = 0, 1, 2   # ANIHIP_MD_CV_*
+MD_BIAS_BAD_OFFSET, MD_BIAS_BAD_CV, MD_BIAS_BAD_LIST = 1, 2, 4   # ANIHIP_MD_BIAS_BAD_*
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -145,6 +149,17 @@ class MdLadders(C.Structure):
                 ("slot", C.c_void_p), ("count", C.c_void_p), ("rung_of", C.c_void_p), ("rung_kT", C.c_void_p),
                 ("ladder_ids", C.c_void_p), ("attempts", C.c_void_p), ("accepts", C.c_void_p), ("direction", C.c_void_p),
                 ("round_trips", C.c_void_p), ("scale", C.c_void_p)]
+
+
+class MdBias(C.Structure):
+    """anihip_md_bias (include/anihip.h)."""
+    _fields_ = [("n_cvs", C.c_int32), ("n_lists", C.c_int32), ("capacity", C.c_int32), ("hills_bound", C.c_int32),
+                ("reserved", C.c_int32), ("n_entries", C.c_int32),
+                ("cv_offset", C.c_void_p), ("kind", C.c_void_p), ("atoms", C.c_void_p), ("restraint", C.c_void_p),
+                ("meta_cv", C.c_void_p), ("inv_sigma2", C.c_void_p), ("height", C.c_void_p), ("list", C.c_void_p),
+                ("rank_in_list", C.c_void_p), ("members", C.c_void_p), ("list_entry", C.c_void_p), ("bias_factor", C.c_void_p),
+                ("used", C.c_void_p), ("dropped", C.c_void_p), ("centers", C.c_void_p), ("heights", C.c_void_p),
+                ("status", C.c_void_p)]
 
 
 class MlpShape(C.Structure):
@@ -308,6 +323,13 @@ def lib() -> C.CDLL:
     L.anihip_md_rp_drift.argtypes = [vp, C.POINTER(MdParams), i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.anihip_md_rp_estimators.argtypes = [vp, C.POINTER(MdParams), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
     L.anihip_md_exchange.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdLadders), vp, vp, vp, vp]
+    L.anihip_md_bias_workspace_bytes.restype = sz
+    L.anihip_md_bias_workspace_bytes.argtypes = [C.POINTER(MdParams), C.POINTER(MdBias)]
+    L.anihip_md_bias_apply.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdBias), vp, vp, vp, vp, vp, vp, vp, sz]
+    L.anihip_md_bias_deposit.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdBias), vp, vp, vp]
+    L.anihip_md_bias_hills.argtypes = [vp, C.POINTER(MdBias), i32, i64, vp, vp, vp]
+    for name in ("anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills"):
+        getattr(L, name).restype = C.c_int
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
@@ -348,6 +370,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities", "anihip_md_barostat",
     "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift", "anihip_md_rp_estimators",
     "anihip_md_exchange",
+    "anihip_md_bias_workspace_bytes", "anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills",
 ]
 
 

@@ -29,10 +29,9 @@
 #include <vector>
 
 #include "anihip_common.h"
+#include "md_sums.h"
 
 namespace anihip {
-
-constexpr int MD_BLOCK = 256;   // atoms per chunk, threads per workgroup
 
 struct MdArgs {
     int64_t A, Gc;
@@ -138,29 +137,6 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_drift(MdArgs a)
         v[k] = vk, x[k] = xk, lo[k] = lk;
     }
 }
-
-// sum of W values per thread over the workgroup, waves and lanes in a fixed order; the result in thread 0
-template <int W>
-__device__ __forceinline__ void md_block_sum(double (&s)[W])
-{
-    __shared__ double sh[MD_BLOCK / WAVE][W];
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s[w] += __shfl_xor(s[w], off);
-    }
-    const int wave = threadIdx.x / WAVE;
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) sh[wave][w] = s[w];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) s[w] = (sh[0][w] + sh[1][w]) + (sh[2][w] + sh[3][w]);
-    }
-}
-static_assert(MD_BLOCK == 4 * WAVE, "md_block_sum adds four waves");
 
 // a molecule of one chunk has its sums written straight to `out`, scaled; a longer one goes through k_md_sum
 template <int W>

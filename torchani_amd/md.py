@@ -19,6 +19,9 @@ two or three after the kick for the centre-of-mass kinetic energy and the intern
 one launch that propagates the free ring polymer exactly in its normal modes with the PILE thermostat on them.
 ``ReplicaExchangeDynamics`` is temperature replica exchange over the entries of the batch: every ``exchange_every`` steps two
 launches swap the temperatures of neighboring rungs of every ladder by the Metropolis rule and rescale the velocities.
+``bias=`` adds restraints on collective variables (``distance``, ``angle``, ``dihedral``; ``Restraint``) and ``Metadynamics`` to
+the forces between the evaluation and the kick (csrc/md_bias.hip): one launch more per evaluation, two with hills, and two per
+deposit.
 """
 from __future__ import annotations
 
@@ -30,6 +33,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .md_bias import (CV, BiasTables, DeviceBias, Metadynamics, Restraint, angle, build_bias_tables, dihedral,  # noqa: F401
+                      distance)
 
 # CODATA 2018: 1 Ha = 4.3597447222071e-18 J, 1 amu = 1.66053906660e-27 kg  ->  (Ha / Angstrom) / amu in Angstrom / fs^2
 ACC_UNIT = 4.3597447222071e-18 / 1e-10 / 1.66053906660e-27 * 1e10 * 1e-30
@@ -378,6 +383,17 @@ class BatchedDynamics:
     relative velocities are untouched, so the constraints hold without another solver pass.  ``pressures()`` is then the
     molecular pressure; ``temperatures()`` is unchanged.  Every other restriction of the barostat stays.
 
+    bias: None, or a sequence of ``Restraint`` and at most one ``Metadynamics`` on collective variables (``distance``,
+    ``angle``, ``dihedral``: atoms of one entry, plain differences of the unwrapped coordinates, fp64; include/anihip.h has
+    the exact definition).  Every evaluation is then the model followed by anihip_md_bias_apply on the forces held, so
+    ``forces`` carries the bias and constraints compose as they are; ``potential_energies`` stays the model's, ``bias_energies``
+    (fp64 [C], restraints + hills) is new and ``total_energies()`` includes it.  With a ``Metadynamics`` of pace p, ``step()``
+    deposits after the kick whenever ``steps_done`` is a multiple of p: every walker appends one hill at its CV values, of the
+    height that the bias just computed gives (all walkers see the bias of before the round), and the hills act from the next
+    evaluation on; nothing is deposited at construction.  ``step()`` raises on the host before a deposit that would not fit
+    ``max_hills``.  A CV may sit on a fixed atom (an anchor).  ``pressure=`` with ``bias=`` raises: the bias has no virial here.
+    None, or a bias with no CV in any entry, launches nothing more and is bit-identical to the unbiased dynamics.
+
     Attributes: ``coordinates`` (fp32, updated in place; ``coordinates_lo`` is the residual of the two-float position),
     ``velocities`` (Angstrom / fs), ``forces`` and ``potential_energies`` at the coordinates, ``steps_done``.  ``step()`` never
     synchronizes with the host; ``run()`` reads the neighbor overflow status every ``check_every`` steps.
@@ -388,7 +404,8 @@ class BatchedDynamics:
                  fixed: tp.Optional[Tensor] = None, replica_ids: tp.Optional[Tensor] = None, seed: int = 0,
                  remove_drift: bool = True, constraints: tp.Optional[BondConstraints] = None,
                  constraint_tolerance: float = 1e-8, constraint_max_iterations: int = 64, pressure=None,
-                 compressibility: float = 4.57e-5, barostat_time: float = 1000.0, barostat_scaling: str = "atomic") -> None:
+                 compressibility: float = 4.57e-5, barostat_time: float = 1000.0, barostat_scaling: str = "atomic",
+                 bias=None) -> None:
         from .geomopt import ModelEvaluator
         from .utils import pbc_tuple
 
@@ -439,6 +456,12 @@ class BatchedDynamics:
                 pressure = pressure.expand(Cn)
             if tuple(pressure.shape) != (Cn,):
                 raise ValueError(f"pressure must be a number or a tensor of shape ({Cn},), got {tuple(pressure.shape)}")
+        bias_tables = None
+        if bias is not None:
+            if pressure is not None:
+                raise ValueError("pressure= with bias= is not supported: the bias has no virial here")
+            bias_tables = build_bias_tables(species, fixed, bias, temperature)
+            self._check_bias(bias_tables)
         if not (species.is_cuda and coordinates.is_cuda):
             raise ValueError("BatchedDynamics needs tensors on a ROCm device (no CPU fallback)")
         dev = coordinates.device
@@ -488,6 +511,9 @@ class BatchedDynamics:
         self._clusters = None
         if constraints is not None and bool((constraints.pairs >= 0).any()):
             self._set_constraints(constraints, fixed, float(constraint_tolerance), int(constraint_max_iterations))
+        # (a bias with no CV in any entry is no bias: nothing more is launched)
+        self._bias = DeviceBias(bias_tables, Cn, A, dev) if bias_tables is not None and bias_tables.kind.numel() else None
+        self.bias_energies = torch.zeros(Cn, dtype=torch.float64, device=dev) if self._bias is None else self._bias.bias_energies
         self._evaluate()
         if self.molecular:
             # the scaling groups are the constraint clusters (none: a table of no clusters) and the free atoms
@@ -556,8 +582,16 @@ class BatchedDynamics:
                                f"{self._clusters.tolerance:g} in {self._clusters.max_iterations} iterations (positions {it[0]}, "
                                f"velocities {it[1]}): a smaller dt, or more iterations")
 
+    def _check_bias(self, tables: BiasTables) -> None:
+        """What a subclass refuses of a bias (host only, before anything is built)."""
+
     def _evaluate(self) -> None:
+        """The model, then the bias on the forces held.  The evaluator hands out a tensor of its own at every call (the
+        automatic HIP graph of small batches clones its static outputs, the eager path accumulates into a fresh buffer), so
+        the bias is added in place: no engine buffer is read again after the step."""
         self.potential_energies, self.forces = self._model_eval(self.coordinates)
+        if self._bias is not None:
+            self._bias.apply(self.coordinates, self.coordinates_lo, self.forces)
 
     # ---- the three pieces of a step (anihip_md_drift, the model, anihip_md_kick) ---------------------------------
     def _drift(self) -> None:
@@ -638,6 +672,9 @@ class BatchedDynamics:
             self._barostat()
         self._evaluate()
         self._kick()
+        if self._bias is not None and self._bias.n_lists and self._bias.pace and self.steps_done % self._bias.pace == 0:
+            # (kT as the drift of this step made it: KB_HARTREE temperature in fp32)
+            self._bias.deposit(self._kT if self.langevin else None)
 
     def raise_on_overflow(self) -> None:
         """Raise if a neighbor row of the last evaluation overflowed (one host synchronization)."""
@@ -705,7 +742,37 @@ class BatchedDynamics:
         return self._kinetic.clone()
 
     def total_energies(self) -> Tensor:
-        return self.potential_energies + self.kinetic_energies()
+        """Potential + bias + kinetic energies, fp64 [C]."""
+        return self.potential_energies + self.bias_energies + self.kinetic_energies()
+
+    # ---- observables of the bias, no host read -------------------------------------------------------------------------
+    def _need_bias(self, lists: bool = False) -> DeviceBias:
+        if self._bias is None or (lists and not self._bias.n_lists):
+            raise ValueError("this dynamics has no " + ("Metadynamics" if lists else "bias"))
+        return self._bias
+
+    def collective_variables(self) -> Tensor:
+        """fp64 [C, n_cv] at the coordinates of the last evaluation: one column per ``Restraint`` in the order given, then
+        one per ``Metadynamics`` CV that no restraint holds; NaN where an entry does not have the CV."""
+        b = self._need_bias()
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=b.cv_values.device)
+        return torch.where(b.cv_index >= 0, b.cv_values[b.cv_index.clamp(min=0)], nan)
+
+    def hills(self) -> tp.Tuple[Tensor, Tensor, Tensor]:
+        """(centers fp64 [G, 2, max_hills], heights fp64 [G, max_hills], used int32 [G]): clones of the hill lists, what
+        ``Metadynamics(hills=...)`` takes to go on from."""
+        b = self._need_bias(lists=True)
+        return b.centers.clone(), b.heights.clone(), b.used.clone()
+
+    def metadynamics_bias(self, values: Tensor, list: int = 0) -> Tensor:   # noqa: A002
+        """fp64 [n]: the bias V of list ``list`` at the CV values ``values`` [n] or [n, n_cv] (anihip_md_bias_hills)."""
+        return self._need_bias(lists=True).hills_at(values, list)[0]
+
+    def free_energies(self, values: Tensor, list: int = 0) -> Tensor:   # noqa: A002
+        """fp64 [n], Hartree, up to a constant: -gamma / (gamma - 1) V for well-tempered metadynamics, -V for plain."""
+        b = self._need_bias(lists=True)
+        scale = -b.gamma / (b.gamma - 1.0) if b.gamma > 0 else -1.0
+        return scale * b.hills_at(values, list)[0]
 
     def volumes(self) -> Tensor:
         """fp64 [1], Angstrom^3: |det| of the cell, of which a batch has one (the fp64 master under a barostat)."""
@@ -752,7 +819,7 @@ class RingPolymerDynamics(BatchedDynamics):
     for RPMD, which conserves ``ring_polymer_energies()``.  replica_ids int64 [R]: polymer r draws the noise streams
     r P .. r P + P - 1, which must stay below 2^32; mode k of a polymer is driven by the stream of its entry r P + k.
     ``set_temperature(kelvin)`` draws the bead velocities at P kelvin.  remove_drift (default off) would remove the centre-of-
-    mass velocity of every bead on its own.  Bond constraints and the barostat are not available with beads.
+    mass velocity of every bead on its own.  Bond constraints, the barostat and ``bias=`` are not available with beads.
 
     ``step()``, ``run()``, the evaluator, the kick, the overflow check and the absence of host synchronization are the base
     class's.  ``kinetic_energies()`` and ``temperatures()`` keep their meaning per batch entry, that is per bead: they
@@ -764,7 +831,10 @@ class RingPolymerDynamics(BatchedDynamics):
                  beads: int, temperature=None, dt: float = 0.5, friction=0.002, pile_lambda: float = 1.0,
                  thermostat: tp.Optional[str] = "pile", masses: tp.Optional[Tensor] = None,
                  fixed: tp.Optional[Tensor] = None, replica_ids: tp.Optional[Tensor] = None, seed: int = 0,
-                 remove_drift: bool = False, constraints=None, pressure=None) -> None:
+                 remove_drift: bool = False, constraints=None, pressure=None, bias=None) -> None:
+        if bias is not None:
+            raise ValueError("RingPolymerDynamics does not support bias: a CV of a ring polymer (its centroid's, or every "
+                             "bead's) is not implemented")
         if constraints is not None:
             raise ValueError("RingPolymerDynamics does not support constraints: bond constraints (SHAKE / RATTLE) with beads "
                              "are not implemented")
@@ -973,7 +1043,9 @@ class ReplicaExchangeDynamics(BatchedDynamics):
     an attempt ``temperature`` of every ladder member is rewritten from ``rung_temperatures`` (fp32 [L, K], K, a device tensor
     that may be overwritten between steps and is converted to kT at every attempt) through the rung of the entry.
     ``exchange_every=0`` never exchanges and is bit-identical to ``BatchedDynamics``.  Friction stays with the entry.
-    Constraints are allowed: a uniform velocity scale keeps the RATTLE condition, so no projection follows.
+    Constraints are allowed: a uniform velocity scale keeps the RATTLE condition, so no projection follows.  ``bias=`` may
+    hold restraints (umbrella windows in every rung): the Metropolis rule then takes ``potential_energies + bias_energies``,
+    summed on the device.  ``Metadynamics`` is refused: its bias would have to follow the rung, not the entry.
 
     Observables, device tensors read without host synchronization: ``rungs()`` int32 [C] (-1: in no ladder),
     ``replicas_at_rungs()`` int32 [L, K] (-1 padding), ``exchange_attempts`` and ``exchange_accepts`` int64 [L, K - 1] per pair
@@ -1024,6 +1096,12 @@ class ReplicaExchangeDynamics(BatchedDynamics):
             self.exchange_accepts.data_ptr(), self._direction.data_ptr(), self._round_trips.data_ptr(),
             self._exchange_scale.data_ptr())
         self._exchange_params = _lib.MdParams(Cn, species.shape[1], _lib.MD_LANGEVIN, 0, self.dt, self.seed, 0)
+        self._exchange_energies = torch.empty(Cn, dtype=torch.float64, device=dev)
+
+    def _check_bias(self, tables: BiasTables) -> None:
+        if tables.members.numel():
+            raise ValueError("ReplicaExchangeDynamics does not support Metadynamics: temperatures are swapped, so the bias "
+                             "would have to follow the rung, not the batch entry; restraints are fine")
 
     def _exchange(self) -> None:
         """One attempt (anihip_md_exchange) on the potential and kinetic energies held, then ``temperature`` of the ladder
@@ -1032,8 +1110,11 @@ class ReplicaExchangeDynamics(BatchedDynamics):
 
         torch.mul(self.rung_temperatures, KB_HARTREE, out=self._rung_kT)   # (every attempt: the user's to overwrite)
         self._exchange_params.step = self.attempts_done
+        energies = self.potential_energies
+        if self._bias is not None:   # (the rungs differ in temperature alone: the restraints count as potential energy)
+            energies = torch.add(self.potential_energies, self.bias_energies, out=self._exchange_energies)
         _lib.check(_lib.lib().anihip_md_exchange(
-            _stream(), C.byref(self._exchange_params), C.byref(self._ladders), self.potential_energies.data_ptr(),
+            _stream(), C.byref(self._exchange_params), C.byref(self._ladders), energies.data_ptr(),
             self._active.data_ptr(), self.velocities.data_ptr(), self._kinetic.data_ptr()))
         self.attempts_done += 1
         rung = self._rung_of[self._members].long()
