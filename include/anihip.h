@@ -1116,7 +1116,8 @@ int anihip_pair_analytic_hvp_items(void *stream, int32_t kind, int64_t n_atoms, 
  * lo / hi select the central atoms whose energies / gradient rows are accumulated (atomic_e[i] += sum_j e_ij / 2,
  * grad_coords[i] += d E / d r_i, both complete for i in lo .. hi: nothing is pushed to other atoms, no atomics,
  * deterministic).  The gradient includes the dependence of C6 on the coordination numbers (the reference gets it from
- * autograd).  cn, gcn: caller-provided scratch, n_atoms floats each.  virial as above (may be NULL). */
+ * autograd).  cn, gcn: caller-provided scratch, n_atoms floats each.  virial as above (may be NULL);
+ * it includes the coordination-number term whether or not grad_coords is given. */
 typedef struct anihip_d3_params {
     float s6, s8, a1, a2;
     float cov_radius_bohr[8];   /* per species index */

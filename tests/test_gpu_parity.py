@@ -1835,7 +1835,8 @@ def test_d3_dispersion_matches_reference(dev, case):
     # (not on the periodic long-row case: the Gaussian reference weights make the energy of its shells too nonlinear in the
     # strain for this difference -- the reference's fp64 gives -0.43027 at h = 2e-3 and -0.42352 at 1e-4 for component (0, 0),
     # exact -0.42350 -- and fp32 energies are too coarse for a smaller step; the kernel's virial there is -0.42350 and
-    # 0.013536 for (1, 2), the reference's exact 0.013536)
+    # 0.013536 for (1, 2), the reference's exact 0.013536; tests/test_gpu_pair_virials.py holds all nine components of that
+    # case to the reference's scaling virial)
     if cell is not None and all(pbc) and g["forces"] is not None:
         # virial of the dispersion term alone = strain derivative of its energy (central differences)
         w = torch.zeros((3, 3), dtype=torch.float64, device=dev)

@@ -99,8 +99,12 @@ __global__ __launch_bounds__(256) void k_pair(int64_t lo, int64_t hi, const int3
             e += 0.5f * eij;
             // d r_ij / d r_i = -u_ij, u = d / r;  the pair contributes e_ij / 2 to BOTH atoms: gradient on i = -de u
             const float ux = d.x * inv, uy = d.y * inv, uz = d.z * inv;
-            gx -= de * ux; gy -= de * uy; gz -= de * uz;
-            if (push && grad_coords) {   // asymmetric rows: this row's half of the pair acts on the neighbor too
+            // (an atom's own periodic image moves with it: the pair has no gradient, only a virial.  Its two signs are both
+            // in the row and would cancel up to the rounding of the lane sums; left out, the zero is exact)
+            const bool image_of_i = (int64_t)(w & IDX_MASK) == i;
+            const float dg = image_of_i ? 0.0f : de;
+            gx -= dg * ux; gy -= dg * uy; gz -= dg * uz;
+            if (push && grad_coords && !image_of_i) {   // asymmetric rows: this row's half of the pair acts on the neighbor too
                 float *gj = grad_coords + 3 * (size_t)(w & IDX_MASK);
                 atomicAdd(gj + 0, 0.5f * de * ux); atomicAdd(gj + 1, 0.5f * de * uy); atomicAdd(gj + 2, 0.5f * de * uz);
             }
@@ -498,7 +502,8 @@ __global__ __launch_bounds__(256) void k_d3_pair(int64_t n, int64_t lo, int64_t 
             if (own) {
                 e += 0.5f * bare * fc;
                 const float ux = d.x * inv, uy = d.y * inv, uz = d.z * inv;
-                gx -= de * ux; gy -= de * uy; gz -= de * uz;
+                const float dg = (int64_t)(w & IDX_MASK) == i ? 0.0f : de;   // (own image: no gradient, as in k_pair)
+                gx -= dg * ux; gy -= dg * uy; gz -= dg * uz;
                 if (virial) {
                     const float h = 0.5f * de;
                     vxx += h * ux * d.x; vyy += h * uy * d.y; vzz += h * uz * d.z;
@@ -559,13 +564,15 @@ __global__ __launch_bounds__(256) void k_d3_cngrad(int64_t lo, int64_t hi, const
             d3_count(p.cov[si] + p.cov[sj], r * A2B, dc);
             const float de = (gi_ + gcn[w & IDX_MASK]) * dc * A2B;   // d E / d r_ij [Angstrom] through the CNs
             const float ux = d.x * inv, uy = d.y * inv, uz = d.z * inv;
-            gx -= de * ux; gy -= de * uy; gz -= de * uz;
+            const float dg = (int64_t)(w & IDX_MASK) == i ? 0.0f : de;   // (own image: no gradient, as in k_pair)
+            gx -= dg * ux; gy -= dg * uy; gz -= dg * uz;
             if (virial) {
                 const float h = 0.5f * de;
                 vxx += h * ux * d.x; vyy += h * uy * d.y; vzz += h * uz * d.z;
                 vxy += h * ux * d.y; vxz += h * ux * d.z; vyz += h * uy * d.z;
             }
         }
+        if (!grad_coords) continue;   // (the virial alone: its coordination-number term still comes from this kernel)
         gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz);
         if (lane == 0) {
             float *gi = grad_coords + 3 * (size_t)i;
@@ -739,7 +746,7 @@ extern "C" int anihip_pair_d3(void *stream, int64_t n_atoms, int64_t lo, int64_t
     hipLaunchKernelGGL(k_d3_pair, dim3(pair_blocks(n_atoms)), dim3(256), 0, st, n_atoms, lo, hi, species, meta,
                        (const float4 *)ent, (const float4 *)c6_table, p, cutoff, smooth, cn, gcn, atomic_e,
                        grad_coords, virial);
-    if (grad_coords && hi > lo)
+    if ((grad_coords || virial) && hi > lo)
         hipLaunchKernelGGL(k_d3_cngrad, dim3(pair_blocks(hi - lo)), dim3(256), 0, st, lo, hi, species, meta,
                            (const float4 *)ent, p, cutoff, gcn, grad_coords, virial);
     ANIHIP_CHECK_HIP(hipGetLastError());

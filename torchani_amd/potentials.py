@@ -562,7 +562,8 @@ class TwoBodyDispersionD3(_Standalone, torch.nn.Module):
                    grad_coords: tp.Optional[Tensor], virial: tp.Optional[Tensor] = None,
                    cutoff: tp.Optional[float] = None, lo: tp.Optional[int] = None, hi: tp.Optional[int] = None) -> None:
         """atomic_e [N] += pair halves, grad_coords [N, 3] += gradient, virial [3, 3] +=, for the central atoms
-        lo .. hi (default: all).  nbrs must hold the rows of ALL atoms and be symmetric."""
+        lo .. hi (default: all).  nbrs must hold the rows of ALL atoms and be symmetric.  The virial includes the
+        coordination-number term with or without grad_coords."""
         _require_cuda(species32, atomic_e, grad_coords, virial)
         n = species32.numel()
         if not nbrs.symmetric or nbrs.lo != 0 or nbrs.hi != n:
