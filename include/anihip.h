@@ -14,6 +14,8 @@
  *     (thread-local), replacing the reference's TORCH_CHECK -> RuntimeError (csrc/aev.cu:1693-1710);
  *   - the CALLER owns all device memory (inputs, outputs, workspaces); the library never allocates,
  *     frees or retains device pointers across calls;
+ *   - the library creates no streams or events and keeps no state between calls apart from the thread-local error
+ *     text: a second stream a call may use is the caller's, handed over in a descriptor (anihip_mlp_desc.aux_stream);
  *   - every call is asynchronous on the given hipStream_t (passed as void*), never synchronises the
  *     host (the reference syncs >= 3 times per forward, csrc/aev.cu:1292,1763-1767);
  *   - capacity overflows are reported through the device-side `status` words (never assert/trap like
@@ -33,7 +35,7 @@
 extern "C" {
 #endif
 
-#define ANIHIP_ABI_VERSION 12
+#define ANIHIP_ABI_VERSION 13
 
 /* status word bits written by the kernels into status[0] */
 #define ANIHIP_ST_ENTRY_OVERFLOW 1u   /* neighbor entries exceeded ent_capacity */
@@ -860,11 +862,12 @@ typedef struct {
                                              * network widths as compile-time constants where an instantiation exists (every ANI-2x network) -- 5-6 % faster
                                              * per tile.  Below four rounds of tiles these are plain launches on the caller's stream, each ending with a
                                              * partly filled last round of the CUs (a species of a handful of atoms still costs a tile through all members);
-                                             * from four rounds on the launches draw their tiles from a queue per species and alternate between the
-                                             * caller's stream and a SECOND STREAM OF THE LIBRARY'S OWN (one per device, created on first use; forked from and
-                                             * joined to the caller's stream with events, so the call stays stream-ordered for the caller; not inside a
-                                             * stream capture).  Whether it pays depends on the composition: the Python host prices both schemes
-                                             * (models.ANI._per_species_launches_pay) -- 2.3 M-atom water box: yes; 46 k-atom solvated protein: no */
+                                             * from four rounds on, IF THE CALLER HANDS OVER A SECOND STREAM in the descriptor (aux_stream, fork_event,
+                                             * join_event below), the launches draw their tiles from a queue per species and alternate between the
+                                             * caller's stream and that second one (forked from and joined to the caller's stream with the two
+                                             * events, so the call stays stream-ordered for the caller).  Without the handles, and inside a stream
+                                             * capture, the launches stay on the caller's stream in static tile order.  Whether it pays depends on the
+                                             * composition: the Python host prices both schemes (models.ANI._per_species_launches_pay) -- 2.3 M-atom water box: yes; 46 k-atom solvated protein: no */
 #define ANIHIP_MLP_FLAG_BWD_TWO_PRODUCTS 2048u /* OFF by default.  With the layer-0 backward inside the fused kernel (>= 24000 atoms,
                                                  * CELU): its backward GEMMs leave out (weight lo) x (gradient hi), i.e. use the weights
                                                  * rounded to fp16 -- energies unchanged, d E/d AEV and the forces differ from the default's
@@ -883,6 +886,16 @@ typedef struct {
                              * 64-atom tile fits the 160 KB of LDS: padded widths with H2 + max(H1, H3) <= 448.  256 / 192 / 256
                              * fits, 256 / 256 / 256 does not: a CELU pack with such a species runs layer by layer, all of it) */
     anihip_species_net net[ANIHIP_MAX_SPECIES];
+    /* (ABI 13) second stream of the per-species launches (ANIHIP_MLP_FLAG_SHAPED) with the events that fork it from and
+     * join it to the stream of the call: created and destroyed by the CALLER, on the device of the call; all three set
+     * or all three NULL (NULL: every launch on the stream of the call; anihip_mlp_pack writes NULL).  aux_stream must
+     * differ from the stream of the call.  Read by anihip_mlp_forward_backward only.  Like a workspace, the handles of
+     * one descriptor may be in use by one call at a time: concurrent callers bring a set each.  Should the join fail after
+     * the launches, the call waits for aux_stream on the host before it returns the error (the one place where a call
+     * synchronises): no kernel of a failed call is left running that nothing orders before the caller's next step. */
+    void *aux_stream; /* hipStream_t */
+    void *fork_event; /* hipEvent_t */
+    void *join_event; /* hipEvent_t */
 } anihip_mlp_desc;
 
 /* Packing a model behind the ABI (replaces what BmmEnsemble / MNPNetworks do at construction, nn/_infer.py:141-161,

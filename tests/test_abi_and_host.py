@@ -28,7 +28,7 @@ def test_library_exports_every_declared_symbol(lib):
     assert declared == set(_lib.EXPORTED_SYMBOLS)
     for sym in declared:
         assert getattr(lib, sym) is not None
-    assert lib.anihip_abi_version() == _lib.ABI_VERSION == 12
+    assert lib.anihip_abi_version() == _lib.ABI_VERSION == 13
 
 
 def test_struct_layouts_match_header(lib):
@@ -38,7 +38,7 @@ def test_struct_layouts_match_header(lib):
 
     assert ctypes.sizeof(_lib.AevParams) == 11 * 4
     assert ctypes.sizeof(_lib.SpeciesNet) == 4 + 5 * 4 + 5 * 4 * 8 + 4 * 4 + 2 * 4 * 8 + 8
-    assert ctypes.sizeof(_lib.MlpDesc) == 8 * 4 + 8 * ctypes.sizeof(_lib.SpeciesNet)   # 7 ints + padding
+    assert ctypes.sizeof(_lib.MlpDesc) == 8 * 4 + 8 * ctypes.sizeof(_lib.SpeciesNet) + 3 * 8   # 7 ints + padding; stream, 2 events
     assert _lib.MlpDesc.flags.offset == 24 and _lib.MlpDesc.net.offset == 32
     d = _lib.MlpDesc()
     d.num_species, d.n_members, d.aev_len, d.celu_alpha = 2, 8, 1008, 0.1
@@ -114,6 +114,32 @@ def test_argument_validation_without_gpu(lib):
     rc = lib.anihip_mlp_forward_backward(None, ctypes.byref(d), 10, 0, 10, addr, addr, None, addr, 4096, addr, None,
                                          None)
     assert rc != 0 and b"num_species" in lib.anihip_last_error()
+
+
+def test_second_stream_handles_validated_without_gpu(lib):
+    """anihip_mlp_desc.aux_stream / fork_event / join_event: all three or none, and aux_stream is not the stream of the call --
+    refused with the other argument checks, before the first HIP call (the handles here are made-up numbers that nothing may
+    touch).  A complete set and an empty one pass them: a call over no atoms then returns 0."""
+    pack = _raw_host_pack(lib)   # (keeps the buffer that the descriptor points into)
+    desc = pack[-1]
+    buf = (ctypes.c_char * 4096)()
+    addr = ctypes.addressof(buf)
+
+    def call(stream, handles, hi=10):
+        desc.aux_stream, desc.fork_event, desc.join_event = handles
+        return lib.anihip_mlp_forward_backward(stream, ctypes.byref(desc), 10, 0, hi, addr, addr, None, addr, 4096, addr, None,
+                                               None)
+
+    for handles in ((0x1000, None, None), (None, 0x2000, None), (None, None, 0x3000),
+                    (0x1000, 0x2000, None), (0x1000, None, 0x3000), (None, 0x2000, 0x3000)):
+        assert call(None, handles) != 0, handles
+        msg = lib.anihip_last_error()
+        assert b"aux_stream" in msg and b"fork_event" in msg and b"join_event" in msg
+    assert call(0x1000, (0x1000, 0x2000, 0x3000)) != 0
+    assert b"aux_stream" in lib.anihip_last_error() and b"stream of the call" in lib.anihip_last_error()
+    assert call(0x4000, (0x1000, 0x2000, 0x3000), hi=0) == 0
+    assert call(None, (0x1000, 0x2000, 0x3000), hi=0) == 0
+    assert call(None, (None, None, None), hi=0) == 0
 
 
 def test_aev_table_pack_matches_constants(lib):
@@ -351,10 +377,28 @@ def test_packed_network_slab_order_cpu():
     _check_pack_against_reference(W4, B4, K0, activation="gelu")
 
 
-def test_mlp_pack_through_raw_ctypes(lib):
-    """The network half of the ABI from ctypes alone (what a reference-side binding would do in place of mnp::run's
-    Tensor lists, csrc/mnp.cpp:238-248): shape struct -> anihip_mlp_pack_bytes -> anihip_mlp_pack into a host buffer ->
-    a descriptor whose pointers lie inside that buffer; bad shapes are refused with a message."""
+def test_a_pack_is_not_copied_or_pickled(lib):
+    """A pack owns what its descriptor points to -- the packed buffer and, once a call needed them, a second stream and two
+    events -- and is single-user like a workspace: no copy of it may carry them along.  ctypes refuses to copy or pickle the
+    descriptor's pointers, so a deep copy or a pickle of a pack (or of a model whose pack cache is filled) raises."""
+    import copy
+    import pickle
+
+    from torchani_amd.engine import PackedNetworks
+
+    rs = np.random.RandomState(1)
+    W = [[[torch.from_numpy(rs.randn(o, i).astype(np.float32)) for i, o in ((64, 32), (32, 1))]]]
+    B = [[[torch.zeros(w.shape[0]) for w in W[0][0]]]]
+    pk = PackedNetworks(W, B, 64, 0.1, torch.device("cpu"))
+    assert pk._second is None and pk.desc.aux_stream is None
+    for clone in (copy.deepcopy, pickle.dumps):
+        with pytest.raises(ValueError, match="pointers"):
+            clone(pk)
+
+
+def _raw_host_pack(lib):
+    """a small network packed into a host buffer through ctypes alone: (shape, weights, biases and their pointer arrays,
+    bytes, buffer, descriptor)"""
     from torchani_amd import _lib
 
     rs = np.random.RandomState(3)
@@ -373,7 +417,19 @@ def test_mlp_pack_through_raw_ctypes(lib):
     assert need > 4 * sum(w.size for w in ws)
     buf = np.zeros(need, dtype=np.uint8)
     desc = _lib.MlpDesc()
+    desc.aux_stream, desc.fork_event, desc.join_event = 1, 2, 3   # (the packer overwrites the whole descriptor)
     assert lib.anihip_mlp_pack(None, ctypes.byref(sh), wp, bp, 0, buf.ctypes.data, need, 0, ctypes.byref(desc)) == 0
+    return sh, ws, bs, wp, bp, need, buf, desc
+
+
+def test_mlp_pack_through_raw_ctypes(lib):
+    """The network half of the ABI from ctypes alone (what a reference-side binding would do in place of mnp::run's
+    Tensor lists, csrc/mnp.cpp:238-248): shape struct -> anihip_mlp_pack_bytes -> anihip_mlp_pack into a host buffer ->
+    a descriptor whose pointers lie inside that buffer and whose stream and events are NULL (the caller's to fill); bad
+    shapes are refused with a message."""
+    sh, ws, bs, wp, bp, need, buf, desc = _raw_host_pack(lib)
+    M, nl = 2, 3
+    assert desc.aux_stream is None and desc.fork_event is None and desc.join_event is None
     assert desc.n_members == M and desc.net[0].n_layers == nl and [desc.net[0].dims[l] for l in range(4)] == [64, 64, 32, 1]
     lo, hi = buf.ctypes.data, buf.ctypes.data + need
     for arr in (desc.net[0].w, desc.net[0].bias, desc.net[0].wh, desc.net[0].whf):

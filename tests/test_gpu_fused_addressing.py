@@ -4,7 +4,9 @@ FusedArgs::one): ``PackedNetworks.forward_backward`` on seeded random ANI-2x wei
 against the package's exact layer-by-layer path (an fp32 pack of the same weights) -- the compile-time-width networks one
 species at a time, the run-time-width kernel on all seven species, partial last tiles and more than one tile per workgroup,
 1 / 4 / 5 / 17 flagged slabs per tile (kept operand, its limit, staged operand, multi-pass phase 5), an atom without
-neighbors, a central range inside a tile, the tile queue on and off, the two-product backward.
+neighbors, a central range inside a tile, the tile queue on and off, the two-product backward; the second stream of the
+queued per-species launches, which is the pack's own (anihip_mlp_desc.aux_stream): with and without it, created lazily, one
+per pack under two host threads.
 
 Tolerances are those of test_gpu_parity.test_mlp_ensemble for the same quantities (per-atom energies 3e-7 Ha, d E / d AEV
 1e-6 + 1e-5 of its largest entry).  Every case is evaluated twice: the kernel sums in a fixed order, so per-atom energies
@@ -15,6 +17,9 @@ is zero outside them -- the reference multiplies every column -- and d E / d AEV
 defines it nowhere else).  The queue needs four rounds of tiles over the CUs (per-species launches) or more tiles than CUs
 (one launch for all species): those two cases are as small as that allows, everything else a few hundred atoms.
 """
+import threading
+import time
+
 import numpy as np
 import pytest
 import torch
@@ -60,6 +65,27 @@ def packs(dev):
         nets.mlp_precision = None
     assert fused.precision == "f16x3" and exact.precision == "fp32" and fused.M == 8 and fused.aev_len == 1008
     return fused, exact
+
+
+def fresh_pack(dev):
+    """a split-fp16 pack of `packs`' weights that no call has touched yet (from a model instance of its own)"""
+    from torchani_amd.models import ANI2x
+
+    model = ANI2x(state_dict=seeded_state("ani2x", 8, SEED), device=dev, periodic_table_index=False)
+    return model.neural_networks._pack(dev)
+
+
+@pytest.fixture(scope="module")
+def queued(dev, packs):
+    """The smallest system whose per-species launches draw their tiles from queues (test_tile_queue_of_the_per_species_launches
+    derives the size), with its result through `packs`' fused pack and that pack's own second stream: (species, AEV rows, slab
+    masks, per-atom energies, d E / d AEV).  Shared by the tests below, which leave it unchanged."""
+    fused, _ = packs
+    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    n = 4 * n_cu * 64 + 3 * 64 + 17
+    sp, aev, mask, _ = make_case(dev, np.where(np.arange(n) % 3 == 2, O, H), 4, 21)
+    e, g = run_fused(fused, sp, aev, mask, _lib.MLP_FLAG_FUSED_L0B, hint=_lib.MLP_FLAG_SHAPED)
+    return sp, aev, mask, e, g
 
 
 def slab_columns(slabs, radial_len=112):
@@ -234,3 +260,93 @@ def test_two_product_backward(dev, packs, species):
     assert float((g2 - g3).abs().max()) > 0.0
     check("two-product backward", e2, g2, e_ref, g_ref, cols, g_abs=BWD2_TOL, g_rel=0.0)
     check("two-product backward, rounding bound", e2, g2, e_ref, g_ref, cols, g_abs=G_ABS, g_rel=BWD2_REL)
+
+
+def test_queued_launches_with_and_without_the_second_stream(dev, packs, queued):
+    """The queued per-species launches with the pack's stream and events in the descriptor (forward_backward put them there at
+    the first call with MLP_FLAG_SHAPED) and with the three fields cleared -- the library then creates nothing and launches on
+    the caller's stream in static tile order: per-atom energies and d E / d AEV equal bit for bit (a tile's result does not
+    depend on who computes it)."""
+    fused, _ = packs
+    sp, aev, mask, e, g = queued
+    d = fused.desc
+    handles = (d.aux_stream, d.fork_event, d.join_event)
+    assert all(handles) and fused._second is not None
+    assert handles[0] != torch.cuda.current_stream(dev).cuda_stream and handles[1] != handles[2]
+    try:
+        d.aux_stream = d.fork_event = d.join_event = None
+        e0, g0 = run_fused(fused, sp, aev, mask, _lib.MLP_FLAG_FUSED_L0B, hint=_lib.MLP_FLAG_SHAPED)
+        assert d.aux_stream is None and d.fork_event is None and d.join_event is None   # (nobody put them back behind our back)
+    finally:
+        d.aux_stream, d.fork_event, d.join_event = handles
+    assert torch.equal(e, e0), "per-atom energies differ with and without the second stream"
+    assert torch.equal(g, g0), "d E / d AEV differs with and without the second stream"
+
+
+def test_second_stream_is_created_lazily(dev, packs):
+    """A pack that has only been called without MLP_FLAG_SHAPED (member packs, training packs, small systems) holds no stream
+    and no events and hands none to the library; the first call with the flag creates them.  Same weights, same kernel: the
+    results equal those of `packs`' fused pack bit for bit."""
+    fused, _ = packs
+    pack = fresh_pack(dev)
+    sp, aev, mask, _ = make_case(dev, [H] * 130 + [O] * 70, 4, 44)
+    d = pack.desc
+    assert d.aux_stream is None and d.fork_event is None and d.join_event is None and pack._second is None
+    e, g = run_fused(pack, sp, aev, mask, _lib.MLP_FLAG_FUSED_L0B)
+    assert d.aux_stream is None and d.fork_event is None and d.join_event is None and pack._second is None
+    e1, g1 = run_fused(pack, sp, aev, mask, _lib.MLP_FLAG_FUSED_L0B, hint=_lib.MLP_FLAG_SHAPED)
+    assert d.aux_stream and d.fork_event and d.join_event
+    assert pack._second[0].cuda_stream == d.aux_stream and d.aux_stream != fused.desc.aux_stream
+    for hint, (ea, ga) in ((0, (e, g)), (_lib.MLP_FLAG_SHAPED, (e1, g1))):
+        eb, gb = run_fused(fused, sp, aev, mask, _lib.MLP_FLAG_FUSED_L0B, hint=hint)
+        assert torch.equal(ea, eb) and torch.equal(ga, gb)
+
+
+def test_two_host_threads_with_a_second_stream_each(dev, queued):
+    """Two packs of the same weights, each with a second stream and events of its own, called from two host threads at once
+    (ctypes releases the GIL), each on a stream of its own as the caller's stream, three queued calls per thread: nothing is
+    shared between them -- the library keeps no stream, event or lock -- and every result equals the single-threaded one bit for
+    bit.  Four streams in all.  The threads are joined with a time limit (three calls per thread, so six single-threaded calls
+    if the device ran them one after the other; ten times that plus 30 s for a busy host), so a stall fails the test instead of
+    blocking it."""
+    sp, aev, mask, e_ref, g_ref = queued
+    twins = [fresh_pack(dev) for _ in range(2)]
+    streams = [torch.cuda.Stream(device=dev) for _ in twins]
+    for pack in twins:
+        pack.flags = _lib.MLP_FLAG_FUSED_L0B
+    torch.cuda.synchronize()
+
+    def calls(k, count, out):
+        try:
+            with torch.cuda.stream(streams[k]):
+                for _ in range(count):
+                    ga = torch.zeros_like(aev)
+                    e, _, _ = twins[k].forward_backward(sp, aev, grad_aev=ga, slab_mask=mask, tile_hint=_lib.MLP_FLAG_SHAPED)
+                    out.append((e, ga))
+                streams[k].synchronize()
+        except BaseException as err:   # (handed to the main thread, which fails the test with it)
+            out.append(err)
+
+    single = []
+    t0 = time.perf_counter()
+    calls(0, 1, single)
+    t_single = time.perf_counter() - t0
+    limit = 30.0 + 10 * 6 * t_single
+    results = [[], []]
+    threads = [threading.Thread(target=calls, args=(k, 3, results[k]), daemon=True) for k in range(2)]
+    t0 = time.perf_counter()
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(max(0.0, limit - (time.perf_counter() - t0)))
+    t_both = time.perf_counter() - t0
+    print(f"two host threads: one call alone {t_single:.3f} s, 2 x 3 calls {t_both:.3f} s (limit {limit:.1f} s)")
+    assert not any(t.is_alive() for t in threads), f"a thread has not come back after {limit:.1f} s"
+    torch.cuda.synchronize()
+    aux = [pack.desc.aux_stream for pack in twins]
+    assert all(aux) and len({*aux, *(s.cuda_stream for s in streams)}) == 4
+    for tag, out in (("alone", single), ("thread 0", results[0]), ("thread 1", results[1])):
+        assert len(out) == (1 if tag == "alone" else 3), f"{tag}: {out[-1] if out else 'no result'}"
+        for e, ga in out:
+            assert torch.equal(e, e_ref), f"{tag}: per-atom energies differ from the single-threaded result"
+            assert torch.equal(ga, g_ref), f"{tag}: d E / d AEV differs from the single-threaded result"

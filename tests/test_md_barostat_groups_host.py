@@ -24,7 +24,7 @@ def test_symbols_are_declared_exported_and_have_prototypes():
     hdr = open(os.path.join(ROOT, "include", "anihip.h")).read()
     src = open(os.path.join(ROOT, "torchani_amd", "csrc", "md.hip")).read()
     text = open(os.path.join(ROOT, "torchani_amd", "_lib.py")).read()
-    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+12\b", hdr) and _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13
     # stream, params, clusters, nine pointers; stream, params, two doubles, twelve pointers, clusters, three pointers
     want = {"anihip_md_group_terms": ["vp", "C.POINTER(MdParams)", "C.POINTER(MdClusters)"] + ["vp"] * 9,
             "anihip_md_barostat_groups": ["vp", "C.POINTER(MdParams)", "C.c_double", "C.c_double"] + ["vp"] * 12

@@ -23,7 +23,7 @@ def test_symbol_is_declared_exported_and_has_a_prototype():
     assert re.search(r"#define\s+ANIHIP_MD_BAROSTAT_STEP\s+\(1ull << 62\)", hdr)
     assert "anihip_md_barostat" in _lib.EXPORTED_SYMBOLS
     assert _lib.MD_BAROSTAT_STEP == bref.BAROSTAT_STEP == 1 << 62
-    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+12\b", hdr) and _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13
     src = open(os.path.join(ROOT, "torchani_amd", "csrc", "md.hip")).read()
     assert re.search(r'extern "C" int anihip_md_barostat\(', src)
     if os.path.exists(_lib.LIB_PATH):   # the built library exports it (no GPU needed to look)

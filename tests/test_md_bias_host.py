@@ -250,7 +250,7 @@ def test_abi_is_declared_and_bound():
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and getattr(L, name) is not None
     assert declared == set(_lib.EXPORTED_SYMBOLS)
     assert "md_bias.hip" in _lib.SOURCES and "md.hip" in _lib.SOURCES and "md_sums.h" in _lib.HEADERS
-    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+12\b", hdr) and _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13
     for name, value in (("MD_BIAS_MAX_CVS", 16), ("MD_BIAS_CHUNK", _lib.MD_BIAS_CHUNK), ("MD_CV_DISTANCE", 0), ("MD_CV_ANGLE", 1),
                         ("MD_CV_DIHEDRAL", 2), ("MD_BIAS_BAD_OFFSET", 1), ("MD_BIAS_BAD_CV", 2), ("MD_BIAS_BAD_LIST", 4)):
         assert re.search(rf"#define\s+ANIHIP_{name}\s+{value}\b", hdr), name

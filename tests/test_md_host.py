@@ -150,7 +150,7 @@ def test_library_exports_the_md_entry_points():
     declared = set(re.findall(r"\b(anihip_[a-z_0-9]+)\s*\(", hdr))
     for name in ("anihip_md_workspace_bytes", "anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise"):
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and getattr(L, name) is not None
-    assert "md.hip" in _lib.SOURCES and _lib.ABI_VERSION == 12
+    assert "md.hip" in _lib.SOURCES and _lib.ABI_VERSION == 13
     # the ctypes mirror and the constants of the header
     assert ctypes.sizeof(_lib.MdParams) == 4 * 4 + 8 + 8 + 8 and _lib.MdParams.dt.offset == 16
     assert float(re.search(r"#define ANIHIP_MD_ACC_UNIT (\S+)", hdr).group(1)) == md.ACC_UNIT == ref.ACC_UNIT

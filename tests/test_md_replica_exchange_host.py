@@ -27,7 +27,7 @@ def test_entry_point_is_declared_and_bound():
     assert _lib.MD_EXCHANGE_STEP == rx.EXCHANGE_STEP == 1 << 61
     # disjoint from the barostat's bit and the Maxwell-Boltzmann bit
     assert _lib.MD_EXCHANGE_STEP & (_lib.MD_BAROSTAT_STEP | 1 << 63) == 0
-    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+12\b", hdr) and _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+ANIHIP_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13
     assert re.search(r"#define\s+ANIHIP_MD_LADDERS_CHECK\s+1\b", hdr) and _lib.MD_LADDERS_CHECK == 1
     # the struct of the header, field for field: four int32 and ten pointers
     body = re.search(r"typedef struct \{([^}]*)\} anihip_md_ladders;", code).group(1)

@@ -21,7 +21,7 @@ def test_header_declares_exported_symbols():
     assert "anihip_pair_analytic_hvp" in declared
     assert declared == set(_lib.EXPORTED_SYMBOLS)
     assert len(_lib.EXPORTED_SYMBOLS) == len(set(_lib.EXPORTED_SYMBOLS))
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
 
 
 def test_only_d3_has_no_hessian():

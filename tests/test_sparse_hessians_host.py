@@ -23,7 +23,7 @@ def test_header_declares_the_sparse_entry_points():
     for name in NEW:
         assert name in declared and name in _lib.EXPORTED_SYMBOLS
     assert "hess_sparse.hip" in _lib.SOURCES
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
 
 
 def _hand_built(seed=0):

@@ -24,7 +24,7 @@ def test_header_declares_the_mode_entry_points():
     for name in NEW:
         assert name in declared and name in _lib.EXPORTED_SYMBOLS
     assert "hess_modes.hip" in _lib.SOURCES
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
     assert re.search(r"#define ANIHIP_BLOCK_HESSIAN_MAX_VECTORS (\d+)", src).group(1) == str(_lib.BLOCK_HESSIAN_MAX_VECTORS)
 
 

@@ -34,7 +34,7 @@ def test_header_and_ctypes_list_the_strain_entry_points():
     for name in NEW_SYMBOLS:
         assert re.search(r"\bint " + name + r"\(", header), name
         assert name in _lib.EXPORTED_SYMBOLS, name
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
 
 
 def test_unit_conversion():

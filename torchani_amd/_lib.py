@@ -37,7 +37,7 @@ MLP_FLAG_NO_FUSED, MLP_FLAG_BIG_TILES, MLP_FLAG_SMALL_TILES, MLP_FLAG_NO_SLAB_MA
 MLP_FLAG_FUSED_L0B, MLP_FLAG_NO_FUSED_L0B = 512, 1024
 MLP_FLAG_SHAPED = 4096   # one fused launch per species with compile-time network widths (include/anihip.h)
 MLP_FLAG_BWD_TWO_PRODUCTS = 2048   # off by default: two-product backward GEMMs of the large-system path (include/anihip.h)
-ABI_VERSION = 12
+ABI_VERSION = 13
 REPACK_FUSED_ONLY = 1
 BLOCK_HESSIAN_MAX_VECTORS = 64   # ANIHIP_BLOCK_HESSIAN_MAX_VECTORS
 BLOCK_HESSIAN_BAD_INDEX, BLOCK_HESSIAN_NO_PARTNER, BLOCK_HESSIAN_NO_DIAGONAL = 1, 2, 4
@@ -121,6 +121,9 @@ class MlpDesc(C.Structure):
         ("flags", C.c_int32),
         ("activation", C.c_int32),
         ("net", SpeciesNet * MAX_SPECIES),
+        ("aux_stream", C.c_void_p),   # hipStream_t / hipEvent_t of the caller (NULL: none), see include/anihip.h
+        ("fork_event", C.c_void_p),
+        ("join_event", C.c_void_p),
     ]
 
 

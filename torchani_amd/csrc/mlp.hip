@@ -40,7 +40,6 @@
 #include <type_traits>
 #include <vector>
 #include <cstdio>
-#include <mutex>
 
 namespace anihip {
 
@@ -1964,35 +1963,6 @@ extern "C" size_t anihip_mlp_forward_backward_workspace_bytes(const anihip_mlp_d
 #ifndef ANIHIP_SHAPED_OVERLAP
 #define ANIHIP_SHAPED_OVERLAP 1   // 0: the per-species launches of the fused kernel one after the other, static tile order (development A/B)
 #endif
-// second stream + fork / join events of the per-species launches, one set per device, created on first use (never destroyed:
-// they live as long as the process; NULL on failure -- the launches then stay on the caller's stream).  A caller holds the
-// set's mutex from its fork to its join: two host threads of one process share the stream and the events, and an event
-// re-recorded by the other thread between a record and its wait would order the second stream behind the wrong work.
-struct OverlapSet {
-    hipStream_t st;
-    hipEvent_t fork, join;
-    int state;
-    std::mutex mu;
-};
-static OverlapSet *overlap_resources()
-{
-    static OverlapSet res[64];
-    static std::mutex create;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lock(create);
-    OverlapSet &r = res[dev];
-    if (r.state == 0) {
-        r.state = -1;
-        if (hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&r.fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&r.join, hipEventDisableTiming) == hipSuccess)
-            r.state = 1;
-        else
-            (void)hipGetLastError();
-    }
-    return r.state == 1 ? &r : nullptr;
-}
 
 template <int EPI>
 static int launch_gemm_big(hipStream_t stream, GemmArgs &g, int64_t n_rows_total)
@@ -2259,13 +2229,17 @@ static int fb_layers_forward(const FbCall &c, const FbPlan &p, const MlpWorkspac
 // One launch of the fused kernel per species, restricted to its tiles, with the network widths as compile-time constants where an
 // instantiation exists (every ANI-2x network and ANI-1x hydrogen); a species without atoms exits at once.  Every launch ends with a
 // partly filled last round of the CUs (the hydrogen tiles of the 2.34 M-atom water box: 16 of 256 workgroups, eight items long).
-// The launches alternate between the caller's stream and a second one (forked and joined with events; they touch disjoint atoms)
-// and draw their tiles from a queue per species: the next species' workgroups start on the CUs as they come free and take fewer
-// tiles the later they start.  (Without the queue the overlap buys nothing: a late workgroup then carries its static share to the
-// end.)  Not inside a stream capture (the step then stays a chain of kernel nodes).
-// (the shaped variants' LDS limits are set before the fork: nothing between the fork and the join may return, or
-// the work queued on the process-wide second stream would never be joined back to the caller's stream)
-static int fb_fused_per_species(hipStream_t stream, const MlpWorkspace &w, FusedArgs &f, int64_t grid, size_t lds)
+// From four rounds of tiles on, with a second stream of the caller's in the descriptor (aux_stream, forked and joined with its two
+// events; the launches touch disjoint atoms), the launches alternate between the caller's stream and that one and draw their tiles
+// from a queue per species: the next species' workgroups start on the CUs as they come free and take fewer tiles the later they
+// start.  (Without the queue the overlap buys nothing: a late workgroup then carries its static share to the end.)  Not inside a
+// stream capture (the step then stays a chain of kernel nodes), and without the handles: plain launches in static tile order.
+// Errors: everything that can fail without work on the second stream (the shaped variants' LDS limits) is in front of the fork, and
+// a failed fork returns at once -- nothing is queued on the second stream by then.  A failed join would leave kernels on the
+// caller's second stream that nothing orders before the caller's next use of the outputs and the workspace: on that path alone the
+// call waits for the second stream on the host, then returns the error.
+static int fb_fused_per_species(hipStream_t stream, const anihip_mlp_desc *d, const MlpWorkspace &w, FusedArgs &f, int64_t grid,
+                                size_t lds)
 {
     static const int known[4][4] = {{256, 192, 160, FUSED_CELU_L0B_256}, {192, 160, 128, FUSED_CELU_L0B_192},
                                     {224, 192, 160, FUSED_CELU_L0B_224}, {160, 128, 96, FUSED_CELU_L0B_160}};
@@ -2278,32 +2252,31 @@ static int fb_fused_per_species(hipStream_t stream, const MlpWorkspace &w, Fused
         if (v != FUSED_CELU_L0B) ANIHIP_CHECK_HIP(hipFuncSetAttribute(fused_kernel(v), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         shaped[s] = v;
     }
-    OverlapSet *ov = nullptr;
+    hipStream_t aux = nullptr;
+    const hipEvent_t fork = (hipEvent_t)d->fork_event, join = (hipEvent_t)d->join_event;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     // (from four rounds of tiles on: below, the fork / join and the draws cost more than they balance -- water boxes of
     // 24 000 / 41 472 atoms 0.399 / 0.606 ms against 0.385 / 0.581 with plain launches; 81 000: 1.01 against 1.10)
-    if (ANIHIP_SHAPED_OVERLAP && f.tiles_total >= 4 * grid && S <= CTL_WORDS - CTL_QUEUE) {
+    if (ANIHIP_SHAPED_OVERLAP && d->aux_stream && f.tiles_total >= 4 * grid && S <= CTL_WORDS - CTL_QUEUE) {
         if (hipStreamIsCapturing(stream, &cap) != hipSuccess)
             (void)hipGetLastError();   // (not a reason to fail the call: plain launches)
         else if (cap == hipStreamCaptureStatusNone)
-            ov = overlap_resources();
+            aux = (hipStream_t)d->aux_stream;
     }
-    std::unique_lock<std::mutex> ov_lock;
-    hipStream_t aux = nullptr;
-    if (ov) {
-        ov_lock = std::unique_lock<std::mutex>(ov->mu);
-        aux = ov->st;
-        ANIHIP_CHECK_HIP(hipEventRecord(ov->fork, stream));
-        ANIHIP_CHECK_HIP(hipStreamWaitEvent(aux, ov->fork, 0));
+    if (aux) {
+        ANIHIP_CHECK_HIP(hipEventRecord(fork, stream));
+        ANIHIP_CHECK_HIP(hipStreamWaitEvent(aux, fork, 0));
     }
     for (int s = 0; s < S; ++s) {
         f.only_species = s;
         f.queue = aux ? w.ctl + CTL_QUEUE + s : nullptr;   // (zeroed with the control block by the bucketing)
         launch_fused(shaped[s], (unsigned)grid, lds, (aux && (s & 1)) ? aux : stream, f);
     }
-    if (ov) {
-        ANIHIP_CHECK_HIP(hipEventRecord(ov->join, aux));
-        ANIHIP_CHECK_HIP(hipStreamWaitEvent(stream, ov->join, 0));
+    if (aux) {
+        hipError_t join_of_aux_stream = hipEventRecord(join, aux);
+        if (join_of_aux_stream == hipSuccess) join_of_aux_stream = hipStreamWaitEvent(stream, join, 0);
+        if (join_of_aux_stream != hipSuccess) (void)hipStreamSynchronize(aux);
+        ANIHIP_CHECK_HIP(join_of_aux_stream);
     }
     return 0;
 }
@@ -2346,7 +2319,7 @@ static int fb_fused(const FbCall &c, const FbPlan &p, const MlpWorkspace &w)
         f.tile_tab = w.tile_tab2; f.tile_rows = w.tile_rows2; f.queue = w.ctl + CTL_QUEUE;
     }
     if (p.shaped) {
-        if (int rc = fb_fused_per_species(c.stream, w, f, grid, lds)) return rc;
+        if (int rc = fb_fused_per_species(c.stream, d, w, f, grid, lds)) return rc;
     } else {
         launch_fused(p.variant, (unsigned)grid, lds, c.stream, f);
     }
@@ -2414,6 +2387,9 @@ extern "C" int anihip_mlp_forward_backward(void *stream_, const anihip_mlp_desc 
     if (int rc = check_desc(d)) return rc;   // 1. validate
     ANIHIP_REQUIRE(species && aev && workspace && atomic_e, "null pointer argument");
     ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
+    ANIHIP_REQUIRE((d->aux_stream != nullptr) == (d->fork_event != nullptr) && (d->aux_stream != nullptr) == (d->join_event != nullptr),
+                   "aux_stream, fork_event and join_event of the descriptor: all three set or all three NULL");
+    ANIHIP_REQUIRE(!d->aux_stream || d->aux_stream != stream_, "aux_stream of the descriptor is the stream of the call");
     const FbCall c{(hipStream_t)stream_, d, n_atoms, lo, hi, hi - lo, species, aev, slab_mask, atomic_e, grad_aev, member_e};
     if (c.n == 0) return 0;
     const FbPlan plan = fb_plan(d, c.n, grad_aev != nullptr, slab_mask != nullptr);   // 2. plan (refusals before the first launch)

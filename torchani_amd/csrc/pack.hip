@@ -155,7 +155,7 @@ extern "C" int anihip_mlp_pack(void *stream, const anihip_mlp_shape *sh, const f
         if (hipMemcpy(stage.back().data(), p, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
         return stage.back().data();
     };
-    memset(desc, 0, sizeof(*desc));
+    memset(desc, 0, sizeof(*desc));   // (aux_stream, fork_event, join_event stay NULL: the caller's to fill)
     desc->num_species = S; desc->n_members = M; desc->aev_len = g.K0; desc->celu_alpha = sh->celu_alpha;
     desc->precision = sh->precision; desc->aev_radial_len = g.R; desc->flags = 0; desc->activation = sh->activation;
     const unsigned char *base = (const unsigned char *)out_buffer;   // what the descriptor points into

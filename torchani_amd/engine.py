@@ -817,6 +817,26 @@ class PackedNetworks:
         self._ws: tp.Optional[Tensor] = None
         self._train_ws: tp.Optional[Tensor] = None
         self._fast_training: tp.Optional[bool] = None
+        self._second: tp.Optional[tp.Tuple[torch.cuda.Stream, torch.cuda.Event, torch.cuda.Event]] = None
+
+    def _own_second_stream(self) -> None:
+        """The second stream of the per-species launches with its fork / join events (anihip_mlp_desc.aux_stream, include/anihip.h):
+        this pack's own, alive as long as the pack.  The library creates none; without them it keeps every launch on the caller's
+        stream, which costs the 4 % of the step that the scheme buys (per-species launches) -- hence no silent fallback.
+        (No copy of a pack can carry them along: ctypes refuses to copy or pickle the descriptor's pointers.)"""
+        self._second = None
+        self.desc.aux_stream = self.desc.fork_event = self.desc.join_event = None
+        if torch.cuda.is_current_stream_capturing():
+            return   # (nothing is created or recorded beside a capture: the library keeps a captured step on the caller's stream)
+        stream = torch.cuda.Stream(device=self.device)
+        fork, join = torch.cuda.Event(enable_timing=False), torch.cuda.Event(enable_timing=False)
+        fork.record(stream)   # (torch creates an event's handle at its first record)
+        join.record(stream)
+        handles = (stream.cuda_stream, fork.cuda_event, join.cuda_event)
+        if not all(handles):
+            raise RuntimeError("torch handed out a NULL stream or event handle for the per-species launches")
+        self._second = (stream, fork, join)
+        self.desc.aux_stream, self.desc.fork_event, self.desc.join_event = handles
 
     def array(self, ptr: int, shape: tp.Sequence[int], dtype: torch.dtype = torch.float32) -> Tensor:
         """View of one packed array (a pointer of ``desc``) inside the buffer anihip_mlp_pack filled."""
@@ -884,6 +904,11 @@ class PackedNetworks:
             fl |= tile_hint & tiles
         fl |= tile_hint & ~tiles   # (other switches a caller hands over with the hint, e.g. MLP_FLAG_BWD_TWO_PRODUCTS)
         self.desc.flags = fl   # (before the workspace queries: the flags choose the kernels)
+        stream = _stream()
+        # (lazily: member packs, training packs and small systems never see the flag and hold no stream.  torch hands streams out
+        # of a pool: should the caller's be this pack's second one, the pack draws another)
+        if fl & _lib.MLP_FLAG_SHAPED and (self._second is None or self.desc.aux_stream == stream):
+            self._own_second_stream()
         if chunk is None:
             # ONE call when its scratch is small -- the fused kernel with the layer-0 backward inside keeps everything but
             # ~100 B per atom in LDS: one persistent launch and one tail instead of one per 2^20 atoms (-0.5 ms per step at
@@ -904,7 +929,7 @@ class PackedNetworks:
             c1 = min(hi, c0 + step)
             ws = self.workspace(c1 - c0, want_grad)
             _lib.check(L.anihip_mlp_forward_backward(
-                _stream(), C.byref(self.desc), n, c0, c1, _ptr(species), _row_ptr(aev, rows0, self.aev_len),
+                stream, C.byref(self.desc), n, c0, c1, _ptr(species), _row_ptr(aev, rows0, self.aev_len),
                 _ptr(slab_mask), _ptr(ws), ws.numel(), _ptr(atomic_e),
                 _row_ptr(grad_aev, rows0, self.aev_len) if want_grad else None, _ptr(member_e)))
         return atomic_e, (grad_aev if want_grad else None), member_e
