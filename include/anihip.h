@@ -776,6 +776,58 @@ int anihip_md_bias_deposit(void *stream, const anihip_md_params *params, const a
 int anihip_md_bias_hills(void *stream, const anihip_md_bias *bias, int32_t list, int64_t n_points, const double *values,
                          double *out_V, double *out_dV);
 
+/* Holonomic constraints on internal coordinates for anihip_lbfgs_step (torchani_amd.geomopt.GeometryOptimizer(constraints=),
+ * csrc/geom_constraints.hip): the CVs above (ANIHIP_MD_CV_*, csrc/md_cv.h) held at targets, the way ASE's FixInternals works
+ * with its LBFGS.  Relaxed scans: every grid point is an entry of the batch with its own target.  Everything is fp64 on the
+ * fp32 coords read exactly (the optimizer has no low word).  Per entry c with its n <= ANIHIP_GEOM_MAX_CONSTRAINTS constraints:
+ *   w_i = 1 for active[i] != 0, else 0;  J_k = d s_k / d x with the columns of atoms of w = 0 zeroed (a constraint may sit on
+ *   a fixed atom, which anchors it);  G = J J^T, solved by Cholesky in the stored order; a pivot <= 1e-12 x the largest diagonal
+ *   element of G (or one that is not finite) is SINGULAR: a redundant pair of constraints, a constraint whose atoms are all
+ *   fixed, collinear atoms of an angle or dihedral.
+ * Tables, device memory (C = n_mol, A = atoms_per_mol, N = n_constraints):
+ *   offset       int32 [C + 1]  CSR: entry c owns the constraints offset[c] .. offset[c + 1] - 1
+ *   kind         int32 [N]      ANIHIP_MD_CV_*
+ *   atoms        int32 [N][4]   global atom index c A + i, distinct, all inside entry c; unused slots -1
+ *   target       fp64  [N]      Angstrom or rad
+ *   values       fp64  [N]      OUT: s_k;   multipliers fp64 [N]  OUT of the projection: lambda_k
+ *   iterations   int32 [C]      OUT of the restore
+ *   status       int32 [C]      ANIHIP_GEOM_* bits, OR-ed in and never cleared by the kernels
+ *   tolerance (HOST, > 0) and max_iterations (HOST, >= 1) of the restore.
+ *
+ * anihip_geom_constraints_project: solves G lambda = J f and writes, for every atom named by a constraint,
+ *   forces[i] = (float)((double)f_i - sum_k lambda_k J_k,i), the sum over k in constraint order (the first slot that names the
+ *   atom writes it); multipliers[k] = lambda_k, values[k] = s_k.  Atoms in no constraint are not written.  At a constrained
+ *   minimum f = J^T lambda, so the slope of the relaxed energy along a target is dE* / dt_k = -lambda_k (the torque of a
+ *   torsion profile).
+ * anihip_geom_constraints_restore: Newton iteration back onto the targets by the minimum-norm correction.  Loop: s and J at
+ *   x, r_k = s_k - t_k (wrapped into [-pi, pi) for a dihedral); stop when max |r| <= tolerance; else G mu = r,
+ *   x_i <- x_i - sum_k mu_k J_k,i, one iteration counted, at most max_iterations of them (then ANIHIP_GEOM_NOT_CONVERGED).
+ *   coords = (float)x for the atoms named, only if an iteration moved them; values[k] = s_k at the fp32 coordinates written
+ *   (the residual the caller can trust); iterations[c].
+ * One wave per entry, constraint k on lane k, G one element per lane, gradients and multipliers in LDS.  No atomics on memory
+ * and every sum in a fixed order: bit-identical run to run and wherever the entry sits in the batch.  An entry with a broken
+ * table (an offset that falls, leaves 0 .. N or spans more than 8 constraints; a kind outside the three; an atom outside the
+ * entry, repeated within a constraint, or missing) sets ANIHIP_GEOM_BAD_TABLE and writes nothing else; a singular entry sets
+ * ANIHIP_GEOM_SINGULAR and writes nothing else; one that does not converge sets its bit and is left unmoved.  Other entries
+ * proceed; entries without constraints return at once, and N = 0 launches nothing.  Null pointers, tolerance <= 0 and
+ * max_iterations < 1 return nonzero before any launch. */
+#define ANIHIP_GEOM_MAX_CONSTRAINTS 8
+#define ANIHIP_GEOM_BAD_TABLE 1
+#define ANIHIP_GEOM_SINGULAR 2
+#define ANIHIP_GEOM_NOT_CONVERGED 4
+typedef struct {
+    int32_t n_constraints, max_iterations;
+    double tolerance;
+    const int32_t *offset, *kind, *atoms;
+    const double *target;
+    double *values, *multipliers;
+    int32_t *iterations, *status;
+} anihip_geom_constraints;
+int anihip_geom_constraints_project(void *stream, int64_t n_mol, int64_t atoms_per_mol, const anihip_geom_constraints *tables,
+                                    const uint8_t *active, const float *coords, float *forces);
+int anihip_geom_constraints_restore(void *stream, int64_t n_mol, int64_t atoms_per_mol, const anihip_geom_constraints *tables,
+                                    const uint8_t *active, float *coords);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -7,6 +7,10 @@ and wraps.  HIP events around each part of every iteration; medians over the ite
   config2        256 molecules of A = 28 (tests/golden/cfg2_xyz13_28_ani2x.npz), batch mode (graph replay from the third call)
   conformers2560 those 256 molecules ten times over: 2560 conformers, 71 680 atom slots
   config3        the 46 357-atom solvated 1hz5 box, periodic, cell mode
+    python tools/geomopt_bench.py --constraints [--out profiles/geomopt_constraints_bench.txt]
+                                  the 2560 conformers with one dihedral constraint each (geomopt.CVConstraints) against the same
+                                  batch without: whole steps (optimizer, restore, evaluation, projection), the two optimizers
+                                  alternating in one process, median (fastest, slowest) ms per step over 7 repeats
 Bytes moved per L-BFGS step are estimated from the shapes (lbfgs_step_bytes), so that the achieved rate can be compared
 with HBM: S and Y read twice in fp32 and the fp64 m x m matrices of k_lb_solve, which outweigh S and Y for small molecules."""
 import argparse
@@ -59,6 +63,49 @@ def measure(name, model, sp, x, cell, pbc, iters, memory=100):
     return out
 
 
+def constraints_ab(model, sp, x, out_path, repeats=7, steps=30, memory=10):
+    """ms per step() of a constrained and an unconstrained optimizer on the same batch, alternating."""
+    from torchani_amd import md
+    from torchani_amd.geomopt import CVConstraints, GeometryOptimizer
+
+    assert bool((sp[:, :4] >= 0).all())
+    opts = {"unconstrained": GeometryOptimizer(model, sp, x, memory=memory),
+            "constrained": GeometryOptimizer(model, sp, x, memory=memory, constraints=CVConstraints(md.dihedral(0, 1, 2, 3)))}
+    for opt in opts.values():
+        opt.fmax = 0.0
+        for _ in range(5):   # (the third evaluation captures the automatic HIP graph)
+            opt.step()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in opts}
+    for _ in range(repeats):
+        for name, opt in opts.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                opt.step()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / steps)
+    opts["constrained"].raise_on_failed_constraints()
+    it = opts["constrained"].constraint_iterations
+    lines = [f"tools/geomopt_bench.py --constraints: {sp.shape[0]} conformers of A = {sp.shape[1]}, one dihedral constraint each, "
+             f"memory {memory}; step() = L-BFGS step (+ restore) + evaluation (+ projection); {repeats} repeats of {steps} steps, "
+             "the two optimizers alternating in one process; median (fastest, slowest) ms per step"]
+    for name, v in ms.items():
+        lines.append(f"  {name:14s} {np.median(v):.4f} ({min(v):.4f}, {max(v):.4f})")
+    lo = max(min(v) for v in ms.values())
+    hi = min(max(v) for v in ms.values())
+    lines.append(f"  difference of the medians {1e3 * (np.median(ms['constrained']) - np.median(ms['unconstrained'])):+.1f} us per step; "
+                 + ("the two ranges overlap: no difference is resolved" if lo <= hi else "the two ranges do not overlap"))
+    lines.append(f"  restore iterations of the last step: {int(it.min())} .. {int(it.max())}")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 def trace_summary(path, skip=101):
     """Median duration (us) of each k_lb_* kernel over its calls after the first `skip`, and their sum."""
     import collections
@@ -79,6 +126,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default="config2,conformers2560,config3")
     ap.add_argument("--trace-summary", default=None, metavar="CSV")
+    ap.add_argument("--constraints", action="store_true")
+    ap.add_argument("--out", default=None, metavar="TXT")
     args = ap.parse_args()
     if args.trace_summary:
         print(json.dumps(trace_summary(args.trace_summary)))
@@ -91,6 +140,11 @@ def main():
     res = {}
     with np.load(os.path.join(GOLD, "cfg2_xyz13_28_ani2x.npz")) as z:
         sp2, x2 = z["species"].astype(np.int64), z["coords"]
+    if args.constraints:
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="batch")
+        constraints_ab(model, torch.from_numpy(np.tile(sp2, (10, 1))).to(dev), torch.from_numpy(np.tile(x2, (10, 1, 1))).to(dev),
+                       args.out)
+        return
     if "config2" in want:
         model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="batch")
         res["config2"] = measure("config 2: 256 molecules, A = 28", model, torch.from_numpy(sp2).to(dev),

@@ -14,8 +14,8 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip"]
-HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", os.path.join("..", "..", "include", "anihip.h")]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "geom_constraints.hip"]
+HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
 MAX_SPECIES = 8
@@ -53,6 +53,8 @@ MD_BIAS_MAX_CVS = 16   # ANIHIP_MD_BIAS_MAX_CVS
 MD_BIAS_CHUNK = 1024   # ANIHIP_MD_BIAS_CHUNK: hills per workgroup of the hills kernel
 MD_CV_DISTANCE, MD_CV_ANGLE, MD_CV_DIHEDRAL = 0, 1, 2   # ANIHIP_MD_CV_*
 MD_BIAS_BAD_OFFSET, MD_BIAS_BAD_CV, MD_BIAS_BAD_LIST = 1, 2, 4   # ANIHIP_MD_BIAS_BAD_*
+GEOM_MAX_CONSTRAINTS = 8   # ANIHIP_GEOM_MAX_CONSTRAINTS
+GEOM_BAD_TABLE, GEOM_SINGULAR, GEOM_NOT_CONVERGED = 1, 2, 4   # ANIHIP_GEOM_*
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -163,6 +165,13 @@ class MdBias(C.Structure):
                 ("rank_in_list", C.c_void_p), ("members", C.c_void_p), ("list_entry", C.c_void_p), ("bias_factor", C.c_void_p),
                 ("used", C.c_void_p), ("dropped", C.c_void_p), ("centers", C.c_void_p), ("heights", C.c_void_p),
                 ("status", C.c_void_p)]
+
+
+class GeomConstraints(C.Structure):
+    """anihip_geom_constraints (include/anihip.h)."""
+    _fields_ = [("n_constraints", C.c_int32), ("max_iterations", C.c_int32), ("tolerance", C.c_double),
+                ("offset", C.c_void_p), ("kind", C.c_void_p), ("atoms", C.c_void_p), ("target", C.c_void_p),
+                ("values", C.c_void_p), ("multipliers", C.c_void_p), ("iterations", C.c_void_p), ("status", C.c_void_p)]
 
 
 class MlpShape(C.Structure):
@@ -333,6 +342,10 @@ def lib() -> C.CDLL:
     L.anihip_md_bias_hills.argtypes = [vp, C.POINTER(MdBias), i32, i64, vp, vp, vp]
     for name in ("anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills"):
         getattr(L, name).restype = C.c_int
+    L.anihip_geom_constraints_project.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp, vp]
+    L.anihip_geom_constraints_restore.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp]
+    for name in ("anihip_geom_constraints_project", "anihip_geom_constraints_restore"):
+        getattr(L, name).restype = C.c_int
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
@@ -374,6 +387,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift", "anihip_md_rp_estimators",
     "anihip_md_exchange",
     "anihip_md_bias_workspace_bytes", "anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills",
+    "anihip_geom_constraints_project", "anihip_geom_constraints_restore",
 ]
 
 

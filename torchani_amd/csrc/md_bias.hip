@@ -8,16 +8,16 @@
 //   k_md_bias_deposit_hills, k_md_bias_deposit_count   one thread per entry appends its hill, then one per list advances `used`
 //   k_md_bias_hills_points    one workgroup per point: V and dV/ds of one list, the chunks summed as above
 //
-// Everything is fp64 on x = coords + coords_lo.  No atomics on memory and every sum in a fixed order: two calls on the same
-// input are bit-identical, and an entry gives the same bits wherever it sits in the batch.  Tables live in device memory, so
+// Everything is fp64 on x = coords + coords_lo; the CV formulas are in md_cv.h, shared with geom_constraints.hip.  No atomics
+// on memory and every sum in a fixed order: two calls on the same input are bit-identical, and an entry gives the same bits wherever it sits in the batch.  Tables live in device memory, so
 // the kernels check every index they follow: an entry with a table out of range writes its status word and nothing else.
 #include "anihip_common.h"
+#include "md_cv.h"
 #include "md_sums.h"
 
 namespace anihip {
 
 constexpr int BIAS_CVS = ANIHIP_MD_BIAS_MAX_CVS, BIAS_CHUNK = ANIHIP_MD_BIAS_CHUNK;
-constexpr double BIAS_PI = 3.14159265358979323846, BIAS_TWO_PI = 2.0 * BIAS_PI;
 static_assert(4 * BIAS_CVS <= MD_BLOCK, "k_md_bias_apply has one thread per atom of every CV");
 
 struct BiasArgs {
@@ -28,20 +28,9 @@ struct BiasArgs {
     double *e_bias, *e_meta, *cv_values, *part;   // part: [C][n_chunks][3]
 };
 
-struct BiasCv {
-    int kind, n;
-    int32_t at[4];
-    double s, g[4][3];
-};
+using BiasCv = Cv;   // (md_cv.h)
 
-__device__ __forceinline__ double bias_wrap(double d) { return d - BIAS_TWO_PI * floor((d + BIAS_PI) / BIAS_TWO_PI); }
-
-__device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-__device__ __forceinline__ void cross3(const double (&a)[3], const double (&b)[3], double (&c)[3])
-{
-    c[0] = a[1] * b[2] - a[2] * b[1], c[1] = a[2] * b[0] - a[0] * b[2], c[2] = a[0] * b[1] - a[1] * b[0];
-}
+__device__ __forceinline__ double bias_wrap(double d) { return cv_wrap(d); }
 
 // the CVs and the list of entry c: 0, or the ANIHIP_MD_BIAS_BAD_* bit of the first table that is out of range (then n = 0, g = -1)
 __device__ __forceinline__ int bias_entry(const anihip_md_bias &b, int64_t c, int &lo, int &n, int &g)
@@ -67,22 +56,10 @@ __device__ __forceinline__ int bias_entry(const anihip_md_bias &b, int64_t c, in
 // kind and atoms of CV r of entry c: the atoms distinct and inside the entry
 __device__ __forceinline__ int bias_cv_load(const anihip_md_bias &b, int64_t A, int64_t c, int r, BiasCv &cv)
 {
-    cv.kind = b.kind[r];
-    if (cv.kind < ANIHIP_MD_CV_DISTANCE || cv.kind > ANIHIP_MD_CV_DIHEDRAL) return ANIHIP_MD_BIAS_BAD_CV;
-    cv.n = cv.kind + 2;
-    int bad = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        cv.at[k] = k < cv.n ? b.atoms[4 * (int64_t)r + k] : -1;
-        if (k < cv.n && (cv.at[k] < c * A || cv.at[k] >= (c + 1) * A)) bad = 1;
-#pragma unroll
-        for (int j = 0; j < k; ++j)
-            if (k < cv.n && cv.at[j] == cv.at[k]) bad = 1;
-    }
-    return bad ? ANIHIP_MD_BIAS_BAD_CV : 0;
+    return cv_load(b.kind, b.atoms, A, c, r, cv) ? 0 : ANIHIP_MD_BIAS_BAD_CV;
 }
 
-// s and its gradient on every atom (include/anihip.h has the formulas)
+// s and its gradient on every atom at x = coords + coords_lo (md_cv.h has the formulas)
 __device__ __forceinline__ void bias_cv_eval(const BiasArgs &a, BiasCv &cv)
 {
     double x[4][3];
@@ -90,49 +67,9 @@ __device__ __forceinline__ void bias_cv_eval(const BiasArgs &a, BiasCv &cv)
     for (int k = 0; k < 4; ++k) {
         const int64_t at = cv.at[k] < 0 ? cv.at[0] : cv.at[k];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            x[k][d] = (double)a.coords[3 * at + d] + (double)a.coords_lo[3 * at + d];
-            cv.g[k][d] = 0.0;
-        }
+        for (int d = 0; d < 3; ++d) x[k][d] = (double)a.coords[3 * at + d] + (double)a.coords_lo[3 * at + d];
     }
-    if (cv.kind == ANIHIP_MD_CV_DISTANCE) {
-        const double d[3] = {x[0][0] - x[1][0], x[0][1] - x[1][1], x[0][2] - x[1][2]};
-        cv.s = sqrt(dot3(d, d));
-#pragma unroll
-        for (int k = 0; k < 3; ++k) cv.g[0][k] = d[k] / cv.s, cv.g[1][k] = -(d[k] / cv.s);
-    } else if (cv.kind == ANIHIP_MD_CV_ANGLE) {
-        const double u[3] = {x[0][0] - x[1][0], x[0][1] - x[1][1], x[0][2] - x[1][2]};
-        const double v[3] = {x[2][0] - x[1][0], x[2][1] - x[1][1], x[2][2] - x[1][2]};
-        double n[3], un[3], nv[3];
-        cross3(u, v, n);
-        const double nn = sqrt(dot3(n, n));
-        cv.s = atan2(nn, dot3(u, v));
-        cross3(u, n, un);
-        cross3(n, v, nv);
-        const double fu = dot3(u, u) * nn, fv = dot3(v, v) * nn;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            cv.g[0][k] = un[k] / fu, cv.g[2][k] = nv[k] / fv;
-            cv.g[1][k] = -(cv.g[0][k] + cv.g[2][k]);
-        }
-    } else {
-        const double b1[3] = {x[1][0] - x[0][0], x[1][1] - x[0][1], x[1][2] - x[0][2]};
-        const double b2[3] = {x[2][0] - x[1][0], x[2][1] - x[1][1], x[2][2] - x[1][2]};
-        const double b3[3] = {x[3][0] - x[2][0], x[3][1] - x[2][1], x[3][2] - x[2][2]};
-        double n1[3], n2[3];
-        cross3(b1, b2, n1);
-        cross3(b2, b3, n2);
-        const double L2 = dot3(b2, b2), L = sqrt(L2);
-        cv.s = atan2(L * dot3(b1, n2), dot3(n1, n2));
-        const double fi = -L / dot3(n1, n1), fl = L / dot3(n2, n2), p = dot3(b1, b2) / L2, q = dot3(b3, b2) / L2;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double gi = fi * n1[k], gl = fl * n2[k];
-            cv.g[0][k] = gi, cv.g[3][k] = gl;
-            cv.g[1][k] = q * gl - (1.0 + p) * gi;
-            cv.g[2][k] = p * gi - (1.0 + q) * gl;
-        }
-    }
+    cv_eval(x, cv);
 }
 
 __device__ __forceinline__ int bias_hills_held(const anihip_md_bias &b, int g, int bound)

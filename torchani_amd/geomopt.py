@@ -18,10 +18,18 @@ with the host; ``run()`` reads the converged count and the neighbor overflow sta
 is an ``ANI`` model (``energies_and_forces`` with ``check_overflow=False`` and the same species tensor at every step, so small
 systems replay the automatic HIP graph) or a standalone pair potential of ``torchani_amd.potentials``, evaluated through its
 ``accumulate`` on its own neighbor rows without autograd.
+
+``constraints=CVConstraints(...)`` holds internal coordinates (the CVs of ``md.distance / angle / dihedral``) at targets, exactly
+and per entry: relaxed scans, every grid point an entry of the batch (``torsion_scan``).  It is ASE's ``FixInternals`` with its
+``LBFGS``, on the device (csrc/geom_constraints.hip, include/anihip.h has the definition): the forces the optimizer sees are
+projected onto the tangent space of the constraints, f <- f - J^T lambda with (J J^T) lambda = J f, and every step is followed
+by a Newton iteration back onto the targets along the minimum-norm correction.  At a constrained minimum the multipliers are
+the slope of the relaxed energy along the targets, dE* / dt_k = -lambda_k.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import typing as tp
 
 import torch
@@ -29,13 +37,16 @@ from torch import Tensor
 
 from . import _lib
 from .engine import _stream
-from .tuples import OptimizedGeometries
+from .md_bias import CV, _CV_NAMES, _per_entry
+from .tuples import OptimizedGeometries, TorsionScan
 from .units import HARTREE_TO_EV
 from .utils import pbc_tuple
 
 DEFAULT_ALPHA = 70.0 / HARTREE_TO_EV   # ASE LBFGS(alpha=70 eV / A^2), in Hartree / A^2
 DEFAULT_FMAX = 0.05 / HARTREE_TO_EV    # ASE Optimizer.run(fmax=0.05 eV / A), in Hartree / A
 MAX_MEMORY = _lib.LBFGS_MAX_MEMORY
+MAX_CONSTRAINTS = _lib.GEOM_MAX_CONSTRAINTS
+MAX_INITIAL_OFFSET = 0.1   # Angstrom or rad: the farthest an initial value may be from its target
 
 
 def lbfgs_workspace_bytes(n_mol: int, atoms_per_mol: int, memory: int) -> int:
@@ -118,6 +129,205 @@ class ModelEvaluator:
         m._raise_on_pair_overflow()
 
 
+class CVConstraints:
+    """Internal coordinates held at targets.  ``cvs``: a ``md.CV`` or a sequence of them (``md.distance``, ``md.angle``,
+    ``md.dihedral``; an index tensor with -1 leaves an entry without that constraint).  ``targets``: None holds the values of
+    the initial coordinates; else one number or [C] tensor per CV (Angstrom or rad).  Per-entry targets are a scan."""
+
+    def __init__(self, cvs, targets=None) -> None:
+        cvs = (cvs,) if isinstance(cvs, CV) else tuple(cvs)
+        if not all(isinstance(cv, CV) for cv in cvs):
+            raise ValueError("CVConstraints needs CVs: md.distance, md.angle or md.dihedral")
+        if targets is not None:
+            if isinstance(targets, (int, float)) or (isinstance(targets, Tensor) and len(cvs) == 1):
+                targets = (targets,)
+            targets = tuple(targets)
+            if len(targets) != len(cvs):
+                raise ValueError(f"targets must be None or one value per CV ({len(cvs)}), got {len(targets)}")
+        self.cvs, self.targets = cvs, targets
+
+
+class ConstraintTables(tp.NamedTuple):
+    """The tables of anihip_geom_constraints (include/anihip.h) on the host."""
+    offset: Tensor   # int32 [C + 1]
+    kind: Tensor     # int32 [N]
+    atoms: Tensor    # int32 [N, 4]: global atom index c A + i, -1 in the unused slots
+    target: Tensor   # fp64 [N]: NaN where the value of the initial coordinates is to be held
+    index: Tensor    # int64 [C, n_cv]: the row of CV r of entry c in the CSR arrays, -1: the entry does not have it
+
+
+def build_constraint_tables(species: Tensor, fixed: tp.Optional[Tensor], constraints: CVConstraints) -> ConstraintTables:
+    """Validate ``constraints`` for a batch of ``species`` [C, A] with the ``fixed`` atoms (bool [C, A] or None) and lay out
+    the tables of include/anihip.h.  Pure host torch; reads no device.  The constraints of an entry are ordered as the CVs were
+    given.  Raises ValueError for an index outside -1 .. A - 1, a constraint on a padding atom, a repeated atom, a constraint
+    with no free atom (all of its atoms fixed), the same CV object given twice, a target that is not finite, and more than 8
+    constraints in an entry."""
+    if not isinstance(constraints, CVConstraints):
+        raise ValueError(f"constraints must be a CVConstraints, got {type(constraints).__name__}")
+    species = species.detach().cpu()
+    if species.dim() != 2:
+        raise ValueError("expected species [C, A]")
+    Cn, A = species.shape
+    if fixed is not None and tuple(fixed.shape) != (Cn, A):
+        raise ValueError(f"fixed must be a bool mask of shape {(Cn, A)}, got {tuple(fixed.shape)}")
+    cvs = constraints.cvs
+    for r, cv in enumerate(cvs):
+        if any(cv is other for other in cvs[:r]):
+            raise ValueError(f"the same CV was given twice: constraint {r}, {_CV_NAMES[cv.kind]}")
+    R = len(cvs)
+    real = species >= 0
+    free = real if fixed is None else real & ~fixed.detach().cpu().to(torch.bool)
+    entry = torch.arange(Cn)
+    present = torch.zeros((Cn, R), dtype=torch.bool)
+    idx_all = torch.full((Cn, R, 4), -1, dtype=torch.int64)
+    targets = torch.full((Cn, R), float("nan"), dtype=torch.float64)
+    for r, cv in enumerate(cvs):
+        name, n = _CV_NAMES[cv.kind], len(cv.atoms)
+        cols = []
+        for i in cv.atoms:
+            if isinstance(i, Tensor):
+                if tuple(i.shape) != (Cn,):
+                    raise ValueError(f"{name}: an index tensor must have shape ({Cn},), got {tuple(i.shape)}")
+                cols.append(i.detach().cpu())
+            else:
+                if not 0 <= i < A:
+                    raise ValueError(f"{name}: atom index {i} is outside 0 .. {A - 1}")
+                cols.append(torch.full((Cn,), i, dtype=torch.int64))
+        idx = torch.stack(cols, dim=1)
+
+        def where(bad: Tensor) -> str:
+            c = int(bad.nonzero()[0])
+            return f"entry {c}, {name} of atoms {tuple(idx[c].tolist())}"
+
+        bad = ((idx < -1) | (idx >= A)).any(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"a constraint needs atom indices in 0 .. {A - 1}, or -1 in an index tensor for an entry without "
+                             f"it: {where(bad)}")
+        here = ~(idx == -1).any(dim=1)
+        at = idx.clamp(min=0)
+        bad = here & ~real[entry.view(-1, 1), at].all(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"constraint on a padding atom: {where(bad)}")
+        rep = torch.zeros(Cn, dtype=torch.bool)
+        for a in range(n):
+            for b in range(a):
+                rep |= idx[:, a] == idx[:, b]
+        bad = here & rep
+        if bool(bad.any()):
+            raise ValueError(f"a constraint needs {n} different atoms: {where(bad)}")
+        bad = here & ~free[entry.view(-1, 1), at].any(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"a constraint needs a free atom, all of these are fixed: {where(bad)}")
+        if constraints.targets is not None:
+            tr = _per_entry(constraints.targets[r], "a target", Cn)
+            bad = here & ~torch.isfinite(tr)
+            if bool(bad.any()):
+                raise ValueError(f"a target must be finite: {where(bad)}")
+            targets[:, r] = tr
+        present[:, r] = here
+        idx_all[:, r, :n] = idx
+    count = present.sum(dim=1)
+    if bool((count > MAX_CONSTRAINTS).any()):
+        c = int((count > MAX_CONSTRAINTS).nonzero()[0])
+        raise ValueError(f"entry {c} has {int(count[c])} constraints, more than {MAX_CONSTRAINTS}")
+    offset = torch.zeros(Cn + 1, dtype=torch.int64)
+    offset[1:] = torch.cumsum(count, 0)
+    ce, re = present.nonzero(as_tuple=True)   # (sorted by entry, then by CV: the CSR order)
+    index = torch.full((Cn, R), -1, dtype=torch.int64)
+    index[ce, re] = torch.arange(ce.numel())
+    kinds = torch.tensor([cv.kind for cv in cvs], dtype=torch.int32)
+    kind = kinds[re] if ce.numel() else torch.zeros(0, dtype=torch.int32)
+    atoms = idx_all[ce, re].view(-1, 4)
+    atoms = torch.where(atoms >= 0, atoms + (ce * A).view(-1, 1), atoms).to(torch.int32)
+    return ConstraintTables(offset.to(torch.int32), kind, atoms.contiguous(), targets[ce, re].contiguous(), index)
+
+
+def _cv_values(kind: int, x: Tensor) -> Tensor:
+    """The CV of include/anihip.h at x [..., n, 3] in torch (the dtype of x; the host side works in fp64)."""
+    if kind == _lib.MD_CV_DISTANCE:
+        return (x[..., 0, :] - x[..., 1, :]).norm(dim=-1)
+    if kind == _lib.MD_CV_ANGLE:
+        a, b = x[..., 0, :] - x[..., 1, :], x[..., 2, :] - x[..., 1, :]
+        return torch.atan2(torch.linalg.cross(a, b).norm(dim=-1), (a * b).sum(-1))
+    b1, b2, b3 = x[..., 1, :] - x[..., 0, :], x[..., 2, :] - x[..., 1, :], x[..., 3, :] - x[..., 2, :]
+    n1, n2 = torch.linalg.cross(b1, b2), torch.linalg.cross(b2, b3)
+    return torch.atan2(b2.norm(dim=-1) * (b1 * n2).sum(-1), (n1 * n2).sum(-1))
+
+
+def _wrap(d: Tensor) -> Tensor:
+    return d - 2.0 * math.pi * torch.floor((d + math.pi) / (2.0 * math.pi))
+
+
+def _table_values(tables: ConstraintTables, coordinates: Tensor) -> Tensor:
+    """fp64 [N]: the values of the constraints at coordinates [C, A, 3] (host)."""
+    x = coordinates.detach().cpu().to(torch.float64).reshape(-1, 3)
+    out = torch.zeros(tables.kind.numel(), dtype=torch.float64)
+    for kind in (_lib.MD_CV_DISTANCE, _lib.MD_CV_ANGLE, _lib.MD_CV_DIHEDRAL):
+        rows = (tables.kind == kind).nonzero().view(-1)
+        if rows.numel():
+            out[rows] = _cv_values(kind, x[tables.atoms[rows, :kind + 2].to(torch.int64)])
+    return out
+
+
+def _describe(tables: ConstraintTables, c: int, atoms_per_mol: int) -> str:
+    lo, hi = int(tables.offset[c]), int(tables.offset[c + 1])
+    parts = [f"{_CV_NAMES[int(tables.kind[r])]} of atoms "
+             f"{tuple(int(a) - c * atoms_per_mol for a in tables.atoms[r, :int(tables.kind[r]) + 2])}" for r in range(lo, hi)]
+    return f"entry {c} ({', '.join(parts)})"
+
+
+def fragment_mask(species: Tensor, coordinates: Tensor, j: int, k: int, scale: float = 1.25) -> Tensor:
+    """Bool [A]: the atoms on k's side of the bond j-k of one molecule, species [A] (atomic numbers, < 0: padding) and
+    coordinates [A, 3].  Two atoms are bonded if r < scale x the sum of their covalent radii (the table of the D3 potential,
+    Z <= 18).  Raises ValueError when the bond is in a ring: k's side reaches j."""
+    from .potentials import d3_reference_data
+
+    z = species.detach().cpu().to(torch.int64)
+    x = coordinates.detach().cpu().to(torch.float64)
+    if z.dim() != 1 or tuple(x.shape) != (z.shape[0], 3):
+        raise ValueError("expected species [A] and coordinates [A, 3] of one molecule")
+    A = z.shape[0]
+    if not (0 <= j < A and 0 <= k < A and j != k) or int(z[j]) < 0 or int(z[k]) < 0:
+        raise ValueError(f"j and k must be two different atoms in 0 .. {A - 1}, got {j} and {k}")
+    radius = torch.as_tensor(d3_reference_data()["covalent_radius"], dtype=torch.float64)
+    if int(z.max()) >= radius.numel() or bool((z == 0).any()):
+        raise ValueError(f"no covalent radius for atomic number {int(z.max()) if int(z.max()) >= radius.numel() else 0} "
+                         f"(the table covers 1 .. {radius.numel() - 1}; pass `moving` instead)")
+    real = z > 0
+    r = radius[z.clamp(min=0)]
+    bonded = (torch.cdist(x, x) < scale * (r.view(-1, 1) + r.view(1, -1))) & real.view(-1, 1) & real.view(1, -1)
+    bonded.fill_diagonal_(False)
+    bonded[j, k] = bonded[k, j] = False
+    mask = torch.zeros(A, dtype=torch.bool)
+    mask[k] = True
+    front = mask.clone()
+    while bool(front.any()):
+        front = bonded[front].any(dim=0) & ~mask
+        mask |= front
+    if bool(mask[j]):
+        raise ValueError(f"the bond {j}-{k} is in a ring: the side of atom {k} reaches atom {j}")
+    return mask.to(coordinates.device)
+
+
+def rotate_dihedral(coordinates: Tensor, atoms: tp.Sequence[int], angle: float, moving: Tensor) -> Tensor:
+    """coordinates [A, 3] with the atoms of ``moving`` (bool [A]) rotated rigidly about the axis j -> k so that the dihedral
+    i-j-k-l of ``atoms`` becomes ``angle`` (rad), in fp64 torch.  ``moving`` holds l and neither i nor j."""
+    i, j, k, l = (int(a) for a in atoms)   # noqa: E741
+    x = coordinates.detach().to(torch.float64)
+    moving = moving.to(device=x.device, dtype=torch.bool)
+    if x.dim() != 2 or x.shape[1] != 3 or tuple(moving.shape) != (x.shape[0],):
+        raise ValueError("expected coordinates [A, 3] and moving [A]")
+    if not bool(moving[l]) or bool(moving[i]) or bool(moving[j]):
+        raise ValueError(f"moving must hold atom l = {l} and neither i = {i} nor j = {j}")
+    delta = float(angle) - float(_cv_values(_lib.MD_CV_DIHEDRAL, x[[i, j, k, l]]))
+    u = x[k] - x[j]
+    u = u / u.norm()
+    v = x - x[k]
+    cs, sn = math.cos(delta), math.sin(delta)
+    rot = v * cs + torch.linalg.cross(u.expand_as(v), v) * sn + u * (v @ u).unsqueeze(-1) * (1.0 - cs)
+    return torch.where(moving.unsqueeze(-1), rot + x[k], x)
+
+
 class GeometryOptimizer:
     """L-BFGS minimization of the energy of every molecule of species [C, A], coordinates [C, A, 3] (Angstrom).
 
@@ -125,11 +335,19 @@ class GeometryOptimizer:
     Angstrom^2), damping: factor of every step, fixed: bool [C, A] atoms that never move.  Attributes: ``coordinates``
     (fp32, updated in place), ``energies`` [C] and ``forces`` [C, A, 3] at them, ``converged`` (bool [C]), ``n_steps``
     (int32 [C]) and ``last_step`` (fp32 [C, A, 3], the displacement the last step applied).
+
+    constraints: a ``CVConstraints``.  Construction restores the initial coordinates onto the targets (to
+    ``constraint_tolerance``, Angstrom or rad, in at most ``constraint_max_iterations`` Newton iterations) and refuses an initial
+    value more than 0.1 Angstrom or 0.1 rad off its target.  ``forces`` are then always the projected ones, so the convergence
+    tests see them; ``step()`` is the L-BFGS step, the restore and the evaluation (two launches more, no host
+    synchronization); ``last_step`` stays the L-BFGS displacement.  ``constraint_values()`` and ``constraint_multipliers()``
+    read the device.  A constraint may sit on a ``fixed`` atom, which anchors it.
     """
 
     def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
                  memory: int = 100, maxstep: float = 0.2, alpha: float = DEFAULT_ALPHA, damping: float = 1.0,
-                 fixed: tp.Optional[Tensor] = None) -> None:
+                 fixed: tp.Optional[Tensor] = None, constraints: tp.Optional[CVConstraints] = None,
+                 constraint_tolerance: float = 1e-8, constraint_max_iterations: int = 32) -> None:
         if species.dim() != 2 or tuple(coordinates.shape) != (species.shape[0], species.shape[1], 3):
             raise ValueError("expected species [C, A] and coordinates [C, A, 3]")
         if isinstance(memory, bool) or int(memory) != memory or not 1 <= memory <= MAX_MEMORY:
@@ -140,6 +358,30 @@ class GeometryOptimizer:
             raise ValueError("alpha and damping must be > 0")
         if fixed is not None and tuple(fixed.shape) != tuple(species.shape):
             raise ValueError(f"fixed must be a bool mask of shape {tuple(species.shape)}, got {tuple(fixed.shape)}")
+        tables = None
+        if constraints is not None:
+            if not constraint_tolerance > 0:
+                raise ValueError(f"constraint_tolerance must be > 0, got {constraint_tolerance}")
+            if isinstance(constraint_max_iterations, bool) or int(constraint_max_iterations) != constraint_max_iterations \
+                    or constraint_max_iterations < 1:
+                raise ValueError(f"constraint_max_iterations must be an integer >= 1, got {constraint_max_iterations}")
+            tables = build_constraint_tables(species, fixed, constraints)
+            if tables.kind.numel() == 0:
+                tables = None   # (CVs that are -1 in every entry: nothing to hold, nothing launched)
+        if tables is not None:
+            # (the values of the fp32 coordinates the optimizer will hold)
+            start = _table_values(tables, coordinates.detach().to(torch.float32))
+            target = torch.where(torch.isnan(tables.target), start, tables.target)
+            off = start - target
+            off = torch.where(tables.kind == _lib.MD_CV_DIHEDRAL, _wrap(off), off).abs()
+            if bool((off > MAX_INITIAL_OFFSET).any()):
+                r = int((off > MAX_INITIAL_OFFSET).nonzero()[0])
+                c = int((tables.offset[1:].to(torch.int64) > r).nonzero()[0])
+                raise ValueError(
+                    f"{_describe(tables, c, species.shape[1])}: an initial value is {float(off[r]):.3g} (Angstrom or rad) off its "
+                    f"target {float(target[r]):.6g}, more than {MAX_INITIAL_OFFSET}; a minimum-norm correction over a large angle "
+                    "would tear bonds: build the start with rotate_dihedral (or a rigid shift of a fragment)")
+            tables = tables._replace(target=target)
         if not (species.is_cuda and coordinates.is_cuda):
             raise ValueError("GeometryOptimizer needs tensors on a ROCm device (no CPU fallback)")
         dev = coordinates.device
@@ -159,11 +401,70 @@ class GeometryOptimizer:
         self.converged = torch.zeros(Cn, dtype=torch.bool, device=dev)
         self.n_steps = torch.zeros(Cn, dtype=torch.int32, device=dev)
         self.last_step = torch.zeros_like(self.coordinates)
+        self._tables, self._geom = tables, None
+        if tables is not None:
+            N = tables.kind.numel()
+            self._geom_dev = {k: getattr(tables, k).to(dev).contiguous() for k in ("offset", "kind", "atoms", "target", "index")}
+            nan = float("nan")
+            self._geom_values = torch.full((N,), nan, dtype=torch.float64, device=dev)
+            self._geom_multipliers = torch.full((N,), nan, dtype=torch.float64, device=dev)
+            self.constraint_iterations = torch.zeros(Cn, dtype=torch.int32, device=dev)
+            self._geom_status = torch.zeros(Cn, dtype=torch.int32, device=dev)
+            g = self._geom_dev
+            self._geom = _lib.GeomConstraints(
+                N, int(constraint_max_iterations), float(constraint_tolerance), g["offset"].data_ptr(), g["kind"].data_ptr(),
+                g["atoms"].data_ptr(), g["target"].data_ptr(), self._geom_values.data_ptr(), self._geom_multipliers.data_ptr(),
+                self.constraint_iterations.data_ptr(), self._geom_status.data_ptr())
+            self._restore()
+            self.raise_on_failed_constraints()
         self._evaluate()
 
     def _evaluate(self) -> None:
-        """energies and forces at the current coordinates, queued on the stream."""
+        """energies and forces at the current coordinates, queued on the stream; with constraints the forces are projected
+        onto the tangent space of the constraints (anihip_geom_constraints_project)."""
         self.energies, self.forces = self._model_eval(self.coordinates)
+        if self._geom is not None:
+            Cn, A = self.species.shape
+            _lib.check(_lib.lib().anihip_geom_constraints_project(
+                _stream(), Cn, A, C.byref(self._geom), self._active.data_ptr(), self.coordinates.data_ptr(),
+                self.forces.data_ptr()))
+
+    def _restore(self) -> None:
+        """The coordinates moved back onto the targets (anihip_geom_constraints_restore)."""
+        Cn, A = self.species.shape
+        _lib.check(_lib.lib().anihip_geom_constraints_restore(
+            _stream(), Cn, A, C.byref(self._geom), self._active.data_ptr(), self.coordinates.data_ptr()))
+
+    def _constraint_readout(self, name: str) -> Tensor:
+        if self._geom is None:
+            raise ValueError("this optimizer has no constraints")
+        flat, index = getattr(self, name), self._geom_dev["index"]
+        return torch.where(index >= 0, flat[index.clamp(min=0)], torch.full_like(flat[:1], float("nan")))
+
+    def constraint_values(self) -> Tensor:
+        """fp64 [C, n_cv]: the values of the constraints at the current coordinates, NaN where an entry does not have one."""
+        return self._constraint_readout("_geom_values")
+
+    def constraint_multipliers(self) -> Tensor:
+        """fp64 [C, n_cv]: lambda of the last projection, NaN where absent.  At a constrained minimum dE* / d target =
+        -lambda (Hartree / Angstrom or Hartree / rad)."""
+        return self._constraint_readout("_geom_multipliers")
+
+    def raise_on_failed_constraints(self) -> None:
+        """Raise if the constraints of an entry are singular or their restore did not converge (one host synchronization)."""
+        if self._geom is None:
+            return
+        status = self._geom_status.cpu()
+        if not bool(status.any()):
+            return
+        c = int(status.nonzero()[0])
+        bits = int(status[c])
+        what = [name for bit, name in ((_lib.GEOM_BAD_TABLE, "the tables are out of range"),
+                                       (_lib.GEOM_SINGULAR, "the constraints are singular (redundant constraints, or collinear "
+                                                            "atoms of an angle or dihedral)"),
+                                       (_lib.GEOM_NOT_CONVERGED, f"the restore did not reach the targets in "
+                                                                 f"{self._geom.max_iterations} iterations")) if bits & bit]
+        raise RuntimeError(f"GeometryOptimizer: {_describe(self._tables, c, self.species.shape[1])}: {'; '.join(what)}")
 
     def _lbfgs_step(self) -> None:
         """The optimizer step alone (anihip_lbfgs_step): coordinates, last_step, converged and n_steps updated."""
@@ -177,6 +478,8 @@ class GeometryOptimizer:
         """One optimizer step on the forces at the current coordinates (convergence tested against ``self.fmax``), then the
         energies and forces at the new coordinates.  No host synchronization."""
         self._lbfgs_step()
+        if self._geom is not None:
+            self._restore()
         self._evaluate()
 
     def raise_on_overflow(self) -> None:
@@ -193,10 +496,12 @@ class GeometryOptimizer:
             self.step()
             if (k + 1) % check_every == 0 or k + 1 == steps:
                 self.raise_on_overflow()
+                self.raise_on_failed_constraints()
                 if bool(self.converged.all()):
                     break
         if steps == 0:
             self.raise_on_overflow()
+            self.raise_on_failed_constraints()
         fm = (self.forces * self._active.unsqueeze(-1)).to(torch.float64).norm(dim=-1).amax(dim=1)
         self.converged |= fm < self.fmax
         return self.result()
@@ -209,8 +514,65 @@ class GeometryOptimizer:
 
 def optimize_geometry(model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None,
                       **kw) -> OptimizedGeometries:
-    """``GeometryOptimizer(model, species, coordinates, cell, pbc, memory=, maxstep=, alpha=, damping=, fixed=)
-    .run(fmax=, steps=, check_every=)``."""
+    """``GeometryOptimizer(model, species, coordinates, cell, pbc, memory=, maxstep=, alpha=, damping=, fixed=, constraints=,
+    constraint_tolerance=, constraint_max_iterations=).run(fmax=, steps=, check_every=)``."""
     run_kw = {k: kw.pop(k) for k in ("fmax", "steps", "check_every") if k in kw}
     _check_run_args(run_kw.get("fmax", DEFAULT_FMAX), run_kw.get("steps", 1000), run_kw.get("check_every", 10))
     return GeometryOptimizer(model, species, coordinates, cell, pbc, **kw).run(**run_kw)
+
+
+def torsion_scan(model, species: Tensor, coordinates: Tensor, dihedral, angles, moving: tp.Optional[Tensor] = None,
+                 **kw) -> TorsionScan:
+    """Relaxed torsion scan: for one molecule (species [A], coordinates [A, 3], ``dihedral`` four atom indices) or M of them
+    (species [M, A], coordinates [M, A, 3], ``dihedral`` four ints or int64 [M] tensors), the batch of M x len(angles) copies
+    with the dihedral rotated rigidly to each angle (rad; ``moving`` bool [A] or [M, A]: the atoms that turn with atom l, None:
+    ``fragment_mask`` of the bond j-k) is relaxed in one optimizer with the dihedral constrained per entry.  Keywords go to
+    ``GeometryOptimizer`` and to ``run``.  Open boundaries."""
+    from . import md_bias
+    from .potentials import _Standalone
+
+    single = species.dim() == 1
+    sp = species.unsqueeze(0) if single else species
+    x = coordinates.unsqueeze(0) if single else coordinates
+    if sp.dim() != 2 or tuple(x.shape) != (sp.shape[0], sp.shape[1], 3):
+        raise ValueError("expected species [A] and coordinates [A, 3], or species [M, A] and coordinates [M, A, 3]")
+    M, A = sp.shape
+    ang = torch.as_tensor(angles, dtype=torch.float64).detach().cpu().reshape(-1)
+    K = ang.numel()
+    if K < 1 or len(dihedral) != 4:
+        raise ValueError("torsion_scan needs four dihedral atoms and at least one angle")
+    quad = torch.stack([d.detach().cpu().to(torch.int64).expand(M) if isinstance(d, Tensor)
+                        else torch.full((M,), int(d), dtype=torch.int64) for d in dihedral], dim=1)
+    if bool(((quad < 0) | (quad >= A)).any()):
+        raise ValueError(f"dihedral atoms must be in 0 .. {A - 1}")
+    if moving is not None:
+        mv = moving.detach().cpu().to(torch.bool)
+        if tuple(mv.shape) not in ((A,), (M, A)):
+            raise ValueError(f"moving must be a bool mask of shape ({A},) or ({M}, {A}), got {tuple(mv.shape)}")
+        mv = mv.unsqueeze(0).expand(M, A) if mv.dim() == 1 else mv
+    x64 = x.detach().cpu().to(torch.float64)
+    start = torch.empty((M, K, A, 3), dtype=torch.float64)
+    for m in range(M):
+        if moving is None:
+            z = sp[m].detach().cpu()
+            # (a standalone pair potential takes atomic numbers; an ANI model element indices unless periodic_table_index)
+            if not isinstance(model, _Standalone) and not getattr(model, "periodic_table_index", False):
+                from .potentials import d3_reference_data
+
+                table = d3_reference_data()["symbols"]
+                numbers = torch.tensor([table.index(s) + 1 if s in table else 0 for s in model.symbols], dtype=torch.int64)
+                z = torch.where(z >= 0, numbers[z.clamp(min=0)], z)
+            mask = fragment_mask(z, x64[m], int(quad[m, 1]), int(quad[m, 2]))
+        else:
+            mask = mv[m]
+        for a in range(K):
+            start[m, a] = rotate_dihedral(x64[m], quad[m].tolist(), float(ang[a]), mask)
+    run_kw = {k: kw.pop(k) for k in ("fmax", "steps", "check_every") if k in kw}
+    _check_run_args(run_kw.get("fmax", DEFAULT_FMAX), run_kw.get("steps", 1000), run_kw.get("check_every", 10))
+    cv = md_bias.dihedral(*(quad[:, d].repeat_interleave(K) for d in range(4)))
+    opt = GeometryOptimizer(model, sp.repeat_interleave(K, dim=0), start.view(M * K, A, 3).to(x.device, x.dtype),
+                            constraints=CVConstraints([cv], [ang.repeat(M)]), **kw)
+    out = opt.run(**run_kw)
+    shape = (K,) if single else (M, K)
+    return TorsionScan(ang.to(x.device), out.energies.view(shape), out.coordinates.view(*shape, A, 3),
+                       out.converged.view(shape), -opt.constraint_multipliers()[:, 0].reshape(shape))

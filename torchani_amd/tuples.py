@@ -126,6 +126,18 @@ class OptimizedGeometries(tp.NamedTuple):
     n_steps: Tensor
 
 
+class TorsionScan(tp.NamedTuple):
+    """What geomopt.torsion_scan returns for M molecules and K angles: angles [K] (rad, the targets), energies [M, K]
+    (float64, Hartree) of the relaxed geometries coordinates [M, K, A, 3], converged (bool [M, K]) and torques [M, K]
+    (Hartree / rad) = dE* / d angle = minus the constraint's multiplier.  A scan of one molecule drops the M axis."""
+
+    angles: Tensor
+    energies: Tensor
+    coordinates: Tensor
+    converged: Tensor
+    torques: Tensor
+
+
 class SparseVibAnalysis(tp.NamedTuple):
     """What grad.sparse_vibrational_analysis returns for C molecules and k modes: freqs [C, k], modes [C, k, A, 3],
     fconstants [C, k] and rmasses [C, k] as in VibAnalysis (zero on padding atoms), eigenvalues [C, k] of the mass-weighted
