@@ -776,6 +776,107 @@ int anihip_md_bias_deposit(void *stream, const anihip_md_params *params, const a
 int anihip_md_bias_hills(void *stream, const anihip_md_bias *bias, int32_t list, int64_t n_points, const double *values,
                          double *out_V, double *out_dV);
 
+/* Group CVs of biased MD (torchani_amd.md.center, md.coordination; csrc/md_sites.hip): centres of groups of atoms and
+ * coordination numbers reach the kernels above as SITES, pseudo-atoms appended to every entry.  Entry c of A atoms becomes an
+ * extended entry of A' = A + V atoms, V = max_sites <= ANIHIP_MD_SITES_MAX: the extended arrays coords_ext, coords_lo_ext and
+ * forces_ext are fp32 [C][A'][3], site v of entry c is their atom c A' + A + v, and the CV tables of anihip_md_bias name it
+ * like any atom.  One evaluation is
+ *   anihip_md_sites_gather  ->  anihip_md_bias_apply(params with atoms_per_mol = A', the extended arrays)  ->  anihip_md_sites_spread
+ * and both calls here take params with atoms_per_mol = A.  All arithmetic is fp64 on x = coords + coords_lo, read exactly.
+ *
+ * Sites (site_kind):
+ *   ANIHIP_MD_SITE_CENTER  x_v = sum_i w_i x_i over group site_ref, plain unwrapped coordinates (no minimum image); the weights
+ *                          are the host's, fp64, summing to 1 (m_i / sum m, or 1 / n).  Stored as a two-float pair per
+ *                          component: hi = (float)x, lo = (float)(x - hi).
+ *   ANIHIP_MD_SITE_VALUE   carries the coordination number s >= 0 of row site_ref of the coordination tables as a DISTANCE:
+ *   ANIHIP_MD_SITE_ANCHOR  the anchor in slot v - 1 sits at exactly (0, 0, 0) and the value site in slot v at (s', 0, 0), s' =
+ *                          max(s, 2^-64) as a two-float pair.  ANIHIP_MD_CV_DISTANCE on (value, anchor) then returns
+ *                          sqrt(s' s') = s' exactly with the gradient exactly (+1, 0, 0) on the value site, so after
+ *                          anihip_md_bias_apply forces_ext[value].x = -dE/ds, rounded to fp32 by that kernel.  The floor keeps
+ *                          the gradient finite at s = 0 and lo out of the fp32 subnormals (the pair holds s to 2^-48 relative).
+ *                          This representation is internal to the three calls.
+ * Every site gets zero force in forces_ext; the real atoms carry the forces given.  Slots of kind ANIHIP_MD_SITE_NONE are not
+ * written.
+ *
+ * Coordination number of row q = (entry, group A, group B, slot of the value site, n) with coord_params[q] = (r0, d0, r_max, b):
+ *   s = sum_{i in A} sum_{j in B, j != i} sw(r_ij),   r_ij = |x_i - x_j| (minimum image along the directions with pbc != 0)
+ *   x = max(r - d0, 0) / r0,  base(r) = 1 / (1 + x^n), x^n by repeated multiplication, n an integer in 2 .. 32
+ *   sw(r) = (base(r) - b) / (1 - b) for r < r_max, 0 for r >= r_max;  b = base(r_max), or b = 0 with r_max = infinity
+ *   dsw/dr = -n x^(n-1) / (r0 (1 + x^n)^2) / (1 - b), 0 for r <= d0 and for r >= r_max
+ * A and B may overlap or coincide: the same atom on both sides is skipped, ordered pairs are counted as written.  Minimum image,
+ * rows of cell the lattice vectors:  d <- d - (rint(d cell^-1) masked by pbc) cell; the caller keeps r_max within half the
+ * smallest perpendicular width over the periodic directions, so the rounded image is the nearest wherever sw != 0.
+ *
+ * Tables, device memory unless marked HOST (C = n_entries, V = max_sites, Ng = n_groups, Nq = n_coord, Nm = n_members):
+ *   site_kind     int32 [C][V]      ANIHIP_MD_SITE_*;   site_ref int32 [C][V]  a group (centre) or a coordination row (anchor, value)
+ *   group_offset  int32 [Ng + 1]    CSR: group g owns group_atoms[group_offset[g] .. group_offset[g + 1] - 1]
+ *   group_atoms   int32 [n_group_atoms]  global atom indices c A + i, ascending within a group, all inside the entry of the site
+ *   group_weights fp64  [n_group_atoms]  w_i of a centre's group (not read for coordination groups)
+ *   coord         int32 [Nq][5]     (entry, group A, group B, slot v >= 1 of the value site, n);   coord_params fp64 [Nq][4]
+ *   member_offset int32 [C A + 1]   the inverse CSR: atom c A + i owns the rows member_offset[c A + i] .. member_offset[c A + i + 1] - 1
+ *   member_site   int32 [Nm][2]     (slot v, ANIHIP_MD_SITE_ROLE_*), in ascending slot order, side A before side B
+ *   member_weight fp64  [Nm]        w_i for ANIHIP_MD_SITE_ROLE_CENTER, else 0
+ *   status        int32 [C]         OUT of anihip_md_sites_gather: 0, or ANIHIP_MD_SITES_BAD_* bits
+ *   pbc, cell, inv_cell (HOST)      by value; cell and inv_cell row-major, not read without a periodic direction
+ *
+ * anihip_md_sites_gather, at most two launches:
+ *   coordination kernel  (only with Nq > 0) one workgroup per (row q, chunk of 256 atoms of A, tile of 256 atoms of B): one
+ *                        thread per atom of A loops over the tile in ascending order, the tile staged in LDS; the workgroup sum
+ *                        (lanes, then waves, in a fixed order) goes to workspace[q][chunk][tile]
+ *   gather kernel        per entry one workgroup per chunk of 256 real atoms, which copies coords, coords_lo and forces into
+ *                        the extended arrays, and one more for the sites: it checks every table the entry names (below), then
+ *                        writes the sites in slot order -- a centre by one sum (thread t adds the atoms t, t + 256, ... of the
+ *                        group in that order, then lanes and waves in a fixed order), a value site by its partial sums, the
+ *                        chunks in order and within a chunk the tiles in order
+ * anihip_md_sites_spread, one launch, one workgroup per (entry, chunk of 64 atoms), each atom i written once:
+ *   acc = (double)forces_ext[i]; through the atom's rows of the inverse CSR in order: a centre v adds w_i (double)forces_ext[v];
+ *   a coordination row with G = (double)forces_ext[value].x adds G sum_{j in the other group, j != i} dsw/dr(r_ij) (x_i - x_j)_mic
+ *   / r_ij, terms with dsw/dr = 0 left out (r = 0 is never divided by); an atom on both sides has a row for each.  The other
+ *   group is staged through LDS in tiles of 256 atoms and an atom has four threads, one for each quarter of every tile: each
+ *   adds its quarters in ascending order from 0 over all tiles, and the sum is (q0 + q1) + (q2 + q3).  forces[i] = (float)acc.
+ *   Atoms without rows get forces_ext[i] bit for bit.
+ * No atomics on memory: two calls on the same input are bit-identical, and an entry gives the same bits wherever it sits in
+ * the batch.
+ *
+ * Checks: the kernels range-check every index they follow.  An entry whose site table (a kind outside the four, a group or
+ * row out of range, a falling or overlong CSR offset, an anchor without its value site or the reverse, a row that names another
+ * entry or slot, n or the parameters out of range: ANIHIP_MD_SITES_BAD_SITE), group atoms (outside the entry:
+ * ANIHIP_MD_SITES_BAD_GROUP) or inverse table (ANIHIP_MD_SITES_BAD_MEMBER) is broken gets the bits in status; its sites are
+ * then placed at (v + 1, 0, 0) Angstrom so that the bias kernels see finite positions, and anihip_md_sites_spread, which reads
+ * status as the gather left it, leaves that entry's forces as they were: the model's.  Other entries proceed.  What the host
+ * can see (null pointers, V outside 1 .. ANIHIP_MD_SITES_MAX, a short workspace) returns nonzero before any launch.
+ * anihip_md_sites_workspace_bytes: Nq ceil(A / 256)^2 doubles. */
+#define ANIHIP_MD_SITES_MAX 64
+#define ANIHIP_MD_SITE_NONE 0
+#define ANIHIP_MD_SITE_CENTER 1
+#define ANIHIP_MD_SITE_ANCHOR 2
+#define ANIHIP_MD_SITE_VALUE 3
+#define ANIHIP_MD_SITE_ROLE_CENTER 0
+#define ANIHIP_MD_SITE_ROLE_A 1
+#define ANIHIP_MD_SITE_ROLE_B 2
+#define ANIHIP_MD_SITES_BAD_SITE 1
+#define ANIHIP_MD_SITES_BAD_GROUP 2
+#define ANIHIP_MD_SITES_BAD_MEMBER 4
+typedef struct {
+    int32_t n_entries, max_sites, n_groups, n_group_atoms, n_coord, n_members;
+    int32_t pbc[3];
+    int32_t reserved;   /* 0 */
+    double cell[9], inv_cell[9];
+    const int32_t *site_kind, *site_ref, *group_offset, *group_atoms;
+    const double *group_weights;
+    const int32_t *coord;
+    const double *coord_params;
+    const int32_t *member_offset, *member_site;
+    const double *member_weight;
+    int32_t *status;
+} anihip_md_sites;
+size_t anihip_md_sites_workspace_bytes(const anihip_md_params *params, const anihip_md_sites *sites);
+int anihip_md_sites_gather(void *stream, const anihip_md_params *params, const anihip_md_sites *sites, const float *coords,
+                           const float *coords_lo, const float *forces, float *coords_ext, float *coords_lo_ext,
+                           float *forces_ext, void *workspace, size_t workspace_bytes);
+int anihip_md_sites_spread(void *stream, const anihip_md_params *params, const anihip_md_sites *sites, const float *coords,
+                           const float *coords_lo, const float *forces_ext, float *forces);
+
 /* Holonomic constraints on internal coordinates for anihip_lbfgs_step (torchani_amd.geomopt.GeometryOptimizer(constraints=),
  * csrc/geom_constraints.hip): the CVs above (ANIHIP_MD_CV_*, csrc/md_cv.h) held at targets, the way ASE's FixInternals works
  * with its LBFGS.  Relaxed scans: every grid point is an entry of the batch with its own target.  Everything is fp64 on the

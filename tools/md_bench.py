@@ -29,6 +29,14 @@
                                                                            or a static 2-CV metadynamics bias of --hills hills
                                                                            per list, a list per molecule or one for all walkers
 
+    python tools/md_bench.py --bias sites --system molecules --langevin --repeats 7 ...
+    python tools/md_bench.py --bias coordination [--coordination-atoms 100] --side 10 --langevin --repeats 7 ...
+                                                                           group CVs (md.center, md.coordination): a restraint on
+                                                                           the distance between the centres of mass of the two
+                                                                           halves of every molecule, or on the coordination number
+                                                                           of all O against all H of the box (--coordination-atoms
+                                                                           N: the first N of each)
+
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
 median, the fastest and the slowest repeat are printed: the spread to hold a difference against.  Whenever the device integrator
@@ -189,6 +197,24 @@ def bench_bias(args, dev):
     if args.bias == "restraints":
         cv = M.dihedral(0, 1, 2, 3) if cell is None else M.distance(0, 3)
         bias, what = [M.Restraint(cv, 1.0 if cell is None else 3.0, 0.01)], "one restraint per system"
+    elif args.bias == "sites":
+        # the two halves of every system's atoms: one gather, one apply and one spread launch more per step
+        real = (sp >= 0).cpu()
+        first = real & (torch.arange(A).view(1, -1) < (real.sum(dim=1) // 2).view(-1, 1))
+        bias = [M.Restraint(M.distance(M.center(first), M.center(real & ~first)), 3.0, 0.01)]
+        what = "one restraint on a distance between two centres of mass per system"
+    elif args.bias == "coordination":
+        if cell is None:
+            raise SystemExit("--bias coordination is timed on --system water")
+        oxygen, hydrogen = (sp[0] == 3).cpu(), (sp[0] == 0).cpu()   # (ANI-2x element indices)
+        if args.coordination_atoms:
+            oxygen &= torch.cumsum(oxygen, 0) <= args.coordination_atoms
+            hydrogen &= torch.cumsum(hydrogen, 0) <= args.coordination_atoms
+        width = 1.0 / torch.linalg.inv(cell.double().cpu()).norm(dim=0).max().item()
+        r_max = min(6.0, 0.49 * width)
+        bias = [M.Restraint(M.coordination(oxygen, hydrogen, 1.3, n=6, r_max=r_max), 2.0 * int(oxygen.sum()), 1e-6)]
+        what = (f"one restraint on the coordination number of {int(oxygen.sum())} O against {int(hydrogen.sum())} H "
+                f"({int(oxygen.sum()) * int(hydrogen.sum())} pairs, r_max {r_max:.2f} A)")
     else:
         if cell is not None:
             raise SystemExit("--bias metadynamics is timed on --system molecules")
@@ -255,7 +281,9 @@ def main():
     ap.add_argument("--exchange-every", type=int, default=None,
                     help="temperature replica exchange with one attempt per this many steps against the same step without")
     ap.add_argument("--rungs", type=int, default=8, help="--exchange-every: replicas per ladder")
-    ap.add_argument("--bias", choices=("restraints", "metadynamics"), default=None,
+    ap.add_argument("--coordination-atoms", type=int, default=0,
+                    help="--bias coordination: the first N oxygens against the first N hydrogens (default: all against all)")
+    ap.add_argument("--bias", choices=("restraints", "metadynamics", "sites", "coordination"), default=None,
                     help="the device integrator with this bias against the same step without")
     ap.add_argument("--hills", type=int, default=1000, help="--bias metadynamics: hills held by every list")
     ap.add_argument("--shared-walkers", action="store_true", help="--bias metadynamics: every system a walker of one list")

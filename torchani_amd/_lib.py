@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "geom_constraints.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "geom_constraints.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -53,6 +53,10 @@ MD_BIAS_MAX_CVS = 16   # ANIHIP_MD_BIAS_MAX_CVS
 MD_BIAS_CHUNK = 1024   # ANIHIP_MD_BIAS_CHUNK: hills per workgroup of the hills kernel
 MD_CV_DISTANCE, MD_CV_ANGLE, MD_CV_DIHEDRAL = 0, 1, 2   # ANIHIP_MD_CV_*
 MD_BIAS_BAD_OFFSET, MD_BIAS_BAD_CV, MD_BIAS_BAD_LIST = 1, 2, 4   # ANIHIP_MD_BIAS_BAD_*
+MD_SITES_MAX = 64   # ANIHIP_MD_SITES_MAX
+MD_SITE_NONE, MD_SITE_CENTER, MD_SITE_ANCHOR, MD_SITE_VALUE = 0, 1, 2, 3   # ANIHIP_MD_SITE_*
+MD_SITE_ROLE_CENTER, MD_SITE_ROLE_A, MD_SITE_ROLE_B = 0, 1, 2   # ANIHIP_MD_SITE_ROLE_*
+MD_SITES_BAD_SITE, MD_SITES_BAD_GROUP, MD_SITES_BAD_MEMBER = 1, 2, 4   # ANIHIP_MD_SITES_BAD_*
 GEOM_MAX_CONSTRAINTS = 8   # ANIHIP_GEOM_MAX_CONSTRAINTS
 GEOM_BAD_TABLE, GEOM_SINGULAR, GEOM_NOT_CONVERGED = 1, 2, 4   # ANIHIP_GEOM_*
 
@@ -164,6 +168,17 @@ class MdBias(C.Structure):
                 ("meta_cv", C.c_void_p), ("inv_sigma2", C.c_void_p), ("height", C.c_void_p), ("list", C.c_void_p),
                 ("rank_in_list", C.c_void_p), ("members", C.c_void_p), ("list_entry", C.c_void_p), ("bias_factor", C.c_void_p),
                 ("used", C.c_void_p), ("dropped", C.c_void_p), ("centers", C.c_void_p), ("heights", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+class MdSites(C.Structure):
+    """anihip_md_sites (include/anihip.h)."""
+    _fields_ = [("n_entries", C.c_int32), ("max_sites", C.c_int32), ("n_groups", C.c_int32), ("n_group_atoms", C.c_int32),
+                ("n_coord", C.c_int32), ("n_members", C.c_int32), ("pbc", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("cell", C.c_double * 9), ("inv_cell", C.c_double * 9),
+                ("site_kind", C.c_void_p), ("site_ref", C.c_void_p), ("group_offset", C.c_void_p), ("group_atoms", C.c_void_p),
+                ("group_weights", C.c_void_p), ("coord", C.c_void_p), ("coord_params", C.c_void_p),
+                ("member_offset", C.c_void_p), ("member_site", C.c_void_p), ("member_weight", C.c_void_p),
                 ("status", C.c_void_p)]
 
 
@@ -342,6 +357,12 @@ def lib() -> C.CDLL:
     L.anihip_md_bias_hills.argtypes = [vp, C.POINTER(MdBias), i32, i64, vp, vp, vp]
     for name in ("anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills"):
         getattr(L, name).restype = C.c_int
+    L.anihip_md_sites_workspace_bytes.restype = sz
+    L.anihip_md_sites_workspace_bytes.argtypes = [C.POINTER(MdParams), C.POINTER(MdSites)]
+    L.anihip_md_sites_gather.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdSites), vp, vp, vp, vp, vp, vp, vp, sz]
+    L.anihip_md_sites_spread.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdSites), vp, vp, vp, vp]
+    for name in ("anihip_md_sites_gather", "anihip_md_sites_spread"):
+        getattr(L, name).restype = C.c_int
     L.anihip_geom_constraints_project.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp, vp]
     L.anihip_geom_constraints_restore.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp]
     for name in ("anihip_geom_constraints_project", "anihip_geom_constraints_restore"):
@@ -387,6 +408,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift", "anihip_md_rp_estimators",
     "anihip_md_exchange",
     "anihip_md_bias_workspace_bytes", "anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills",
+    "anihip_md_sites_workspace_bytes", "anihip_md_sites_gather", "anihip_md_sites_spread",
     "anihip_geom_constraints_project", "anihip_geom_constraints_restore",
 ]
 

@@ -37,7 +37,7 @@ from torch import Tensor
 
 from . import _lib
 from .engine import _stream
-from .md_bias import CV, _CV_NAMES, _per_entry
+from .md_bias import CV, _CV_NAMES, _per_entry, has_sites
 from .tuples import OptimizedGeometries, TorsionScan
 from .units import HARTREE_TO_EV
 from .utils import pbc_tuple
@@ -138,6 +138,9 @@ class CVConstraints:
         cvs = (cvs,) if isinstance(cvs, CV) else tuple(cvs)
         if not all(isinstance(cv, CV) for cv in cvs):
             raise ValueError("CVConstraints needs CVs: md.distance, md.angle or md.dihedral")
+        if any(has_sites(cv) for cv in cvs):
+            raise ValueError("CVConstraints does not support sites (md.center) or md.coordination: the constraints move "
+                             "atoms, and a site is not one")
         if targets is not None:
             if isinstance(targets, (int, float)) or (isinstance(targets, Tensor) and len(cvs) == 1):
                 targets = (targets,)

@@ -21,7 +21,9 @@ one launch that propagates the free ring polymer exactly in its normal modes wit
 launches swap the temperatures of neighboring rungs of every ladder by the Metropolis rule and rescale the velocities.
 ``bias=`` adds restraints on collective variables (``distance``, ``angle``, ``dihedral``; ``Restraint``) and ``Metadynamics`` to
 the forces between the evaluation and the kick (csrc/md_bias.hip): one launch more per evaluation, two with hills, and two per
-deposit.
+deposit.  ``center`` (the centre of a group of atoms, usable wherever a CV takes an atom) and ``coordination`` (a coordination
+number between two groups) enter the same kernels as sites appended to every entry (csrc/md_sites.hip): a gather in front of
+them, at most two launches, and a spread behind them, one.
 """
 from __future__ import annotations
 
@@ -33,8 +35,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .md_bias import (CV, BiasTables, DeviceBias, Metadynamics, Restraint, angle, build_bias_tables, dihedral,  # noqa: F401
-                      distance)
+from .md_bias import (CV, BiasTables, DeviceBias, Metadynamics, Restraint, Site, SiteTables, angle, build_bias_tables,  # noqa: F401
+                      build_site_tables, center, coordination, dihedral, distance)
 
 # CODATA 2018: 1 Ha = 4.3597447222071e-18 J, 1 amu = 1.66053906660e-27 kg  ->  (Ha / Angstrom) / amu in Angstrom / fs^2
 ACC_UNIT = 4.3597447222071e-18 / 1e-10 / 1.66053906660e-27 * 1e10 * 1e-30
@@ -392,7 +394,12 @@ class BatchedDynamics:
     height that the bias just computed gives (all walkers see the bias of before the round), and the hills act from the next
     evaluation on; nothing is deposited at construction.  ``step()`` raises on the host before a deposit that would not fit
     ``max_hills``.  A CV may sit on a fixed atom (an anchor).  ``pressure=`` with ``bias=`` raises: the bias has no virial here.
-    None, or a bias with no CV in any entry, launches nothing more and is bit-identical to the unbiased dynamics.
+    None, or a bias with no CV in any entry, launches nothing more and is bit-identical to the unbiased dynamics.  An index of
+    a CV may be a ``center(atoms, weights="mass" | None)`` of a group of atoms (mass weights are the ``masses`` given, or the
+    default ones), and ``coordination(group_a, group_b, r0, d0=0, n=6, r_max=None)`` is a CV like the others; its distances
+    take the minimum image of ``cell`` along ``pbc`` (then ``r_max`` is needed, at most half the smallest perpendicular width),
+    centres do not.  Up to 64 sites per entry, a centre one and a coordination number two.  A bias without any of them runs
+    the path it ran before, bit for bit.  ``run()`` reads the status of the site tables with its other periodic checks.
 
     Attributes: ``coordinates`` (fp32, updated in place; ``coordinates_lo`` is the residual of the two-float position),
     ``velocities`` (Angstrom / fs), ``forces`` and ``potential_energies`` at the coordinates, ``steps_done``.  ``step()`` never
@@ -456,11 +463,14 @@ class BatchedDynamics:
                 pressure = pressure.expand(Cn)
             if tuple(pressure.shape) != (Cn,):
                 raise ValueError(f"pressure must be a number or a tensor of shape ({Cn},), got {tuple(pressure.shape)}")
-        bias_tables = None
+        bias_tables = site_tables = None
         if bias is not None:
             if pressure is not None:
                 raise ValueError("pressure= with bias= is not supported: the bias has no virial here")
-            bias_tables = build_bias_tables(species, fixed, bias, temperature)
+            # (masses only where a mass-weighted centre asks for them: the masses given, not the 1 that fixed atoms get below)
+            site_tables, bias_tables = build_site_tables(
+                species, fixed, bias, temperature, cell=cell, pbc=pbc_tuple(pbc),
+                masses=lambda: masses if masses is not None else default_masses(model, species))
             self._check_bias(bias_tables)
         if not (species.is_cuda and coordinates.is_cuda):
             raise ValueError("BatchedDynamics needs tensors on a ROCm device (no CPU fallback)")
@@ -512,7 +522,8 @@ class BatchedDynamics:
         if constraints is not None and bool((constraints.pairs >= 0).any()):
             self._set_constraints(constraints, fixed, float(constraint_tolerance), int(constraint_max_iterations))
         # (a bias with no CV in any entry is no bias: nothing more is launched)
-        self._bias = DeviceBias(bias_tables, Cn, A, dev) if bias_tables is not None and bias_tables.kind.numel() else None
+        self._bias = (DeviceBias(bias_tables, Cn, A, dev, site_tables)
+                      if bias_tables is not None and bias_tables.kind.numel() else None)
         self.bias_energies = torch.zeros(Cn, dtype=torch.float64, device=dev) if self._bias is None else self._bias.bias_energies
         self._evaluate()
         if self.molecular:
@@ -690,6 +701,8 @@ class BatchedDynamics:
             if (k + 1) % check_every == 0 or k + 1 == n_steps:
                 self.raise_on_overflow()
                 self.raise_on_unconverged_constraints()
+                if self._bias is not None:
+                    self._bias.raise_on_bad_sites()
 
     # ---- velocities ------------------------------------------------------------------------------------------------
     def noise(self, step: int) -> Tensor:
