@@ -263,7 +263,7 @@ def test_general_grids_random_sweep(dev):
         S = int(rs.randint(1, 8))
         nR, nA, nZ = int(rs.choice([1, 3, 8, 16, 17, 32])), int(rs.choice([1, 2, 5, 8, 16])), int(rs.choice([1, 3, 4, 9, 16]))
         if (nR, nA, nZ) in ((16, 8, 4), (16, 4, 8)):
-            nR = 8   # (the published grids take the tuned kernels: tested elsewhere)
+            nR = 8   # (these sizes take the tuned kernels: random constants on them in tests/test_gpu_aev_constants.py)
         Rcr, Rca = float(rs.uniform(3.5, 5.5)), float(rs.uniform(2.5, 3.5))
         EtaR, EtaA, Zeta = float(rs.uniform(4, 25)), float(rs.uniform(4, 15)), float(rs.choice([1.0, 8.0, 14.1, 32.0]))
         ShfR = np.linspace(0.8, Rcr - 0.3, nR).astype(np.float32)

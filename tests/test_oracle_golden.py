@@ -141,7 +141,10 @@ def test_f32_port_close_to_f64(oracle64):
     assert np.abs(out["forces"] - g["forces"]).max() < 2e-5
 
 
-GRID_CASES = ["r8_a4z4_batch", "r24_a10z8_pbc", "r5_a3z5_dense"]
+GRID_CASES = ["r8_a4z4_batch", "r24_a10z8_pbc", "r5_a3z5_dense",
+              # constants off the published models' on the 16 / 8x4 / 4x8 grid sizes (tests/_aev_constants.py GOLDEN_RUNS,
+              # tests/golden/gen_golden_tuned_constants.py): pins the checker of tests/test_gpu_aev_constants.py
+              "tuned_bwd_ang_in", "tuned_g48_zeta1", "tuned_rca_eq_rcr"]
 
 
 def load_grid(name):
