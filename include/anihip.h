@@ -929,6 +929,82 @@ int anihip_geom_constraints_project(void *stream, int64_t n_mol, int64_t atoms_p
 int anihip_geom_constraints_restore(void *stream, int64_t n_mol, int64_t atoms_per_mol, const anihip_geom_constraints *tables,
                                     const uint8_t *active, float *coords);
 
+/* Saddle-point search of a batch of molecules (torchani_amd.geomopt.SaddleOptimizer, csrc/saddle.hip): partitioned
+ * rational-function optimization (P-RFO, Baker 1986) on a dense model Hessian that the caller replaces by the exact one every
+ * few steps and that the Bofill formula updates in between.  Everything is fp64 on the fp32 coords and forces read exactly;
+ * every molecule c of [n_mol][atoms_per_mol] = [C][A] on its own, n = 3 A.  A step of the caller is: project, a symmetric
+ * eigensolver on `projected` (eigenvalues ascending, eigenvectors in the columns), step, the energies and forces at the moved
+ * coords, accept.
+ *
+ * kind uint8 [C][A]: 0 = padding, 1 = a free atom, 2 = a fixed atom (real, never moves); a coordinate is ACTIVE when its atom
+ * is free, and g = -forces on the active coordinates, 0 elsewhere.  An entry is FROZEN when converged[c] != 0 or
+ * status[c] != 0: the three entry points leave it alone (its coords stay bit-identical, its last_step is zero).
+ *
+ * project: converged[c] |= max over the free atoms of |f_i| < fmax (then frozen).  Else the rigid motions of the entry are
+ *   orthonormalized (Gram-Schmidt, twice) into q_1 .. q_r, r <= 6: the three translations of the free atoms when the entry
+ *   has no fixed atom, and the three rotations about the free atoms' centroid when in addition periodic == 0; a vector whose
+ *   remainder falls to 1e-8 of its length is dropped (linear and one-atom entries).  With D the 0 / 1 diagonal of the active
+ *   coordinates, Q = [q_1 .. q_r], P = D - Q Q^T and mu = 1 + the largest row sum of |hessians[c]|:
+ *     gproj = P g  (kept in the workspace),  projected[c] = P H P + mu (I - P)   (H = hessians[c], taken as symmetric).
+ *   Every eigenvalue of the part that matters is below mu - 1; the inactive coordinates and the rigid motions sit at mu.
+ * step: g~ = V^T gproj.  The followed mode k is the lowest eigenvalue (follow == 0) or, for follow == 1, the mode with
+ *   the largest |V_k . modes[c]| among the eigenvalues below mu / 2 (ties: the lowest index).  Along k the step maximizes,
+ *   s~_k = -g~_k / (lam_k - gp), gp = (lam_k + sqrt(lam_k^2 + 4 g~_k^2)) / 2; along every other mode it minimizes,
+ *   s~_i = -g~_i / (lam_i - gm), gm the lowest root of gm = sum_{i != k} g~_i^2 / (gm - lam_i), which lies below
+ *   min(0, the smallest lam_i with g~_i != 0) and is found by bisection from the bracket [hi - 1.000001 |g~|, hi]; a mode with
+ *   g~_i == 0 gets s~_i = 0.  If |s~| > trust_radii[c] it is scaled to it; predicted = sum g~_i s~_i + lam_i s~_i^2 / 2.
+ *   s = V s~; on the active coordinates coords += (float)s, last_step = (float)s; the old coords are kept for accept, and so is
+ *   the displacement (new - old coords, exact in fp64) for the Bofill update.  eigenvalues[c] = lam_k, modes[c] = V_k.
+ * accept: e', f' = new_energies, new_forces (at the moved coords); energies and forces still hold those of the old coords.
+ *   |predicted| < energy_floor: accepted, the radius unchanged.  Else rho = (e' - e) / predicted; |rho - 1| > 1: REJECTED --
+ *   coords restored bit for bit, energies and forces left as they are, radius <- max(radius / 4, min_trust),
+ *   n_rejected[c] += 1.  Otherwise accepted, n_steps[c] += 1, and radius <- min(2 radius, max_trust) if |rho - 1| < 0.25 and
+ *   |s~| >= 0.99 radius, radius <- max(radius / 2, min_trust) if |rho - 1| > 0.75.  An accepted entry takes e', f' into
+ *   energies, forces.  With bofill != 0 its model Hessian is first updated in place, s the displacement, y = g' - g on the
+ *   active coordinates, xi = D (y - H s), phi = (xi.s)^2 / ((xi.xi) (s.s)) (0 when xi.s == 0):
+ *     H += phi xi xi^T / (xi.s) + (1 - phi) ((xi s^T + s xi^T) / (s.s) - (xi.s) s s^T / (s.s)^2),
+ *   skipped when xi.xi or s.s is zero; the update is symmetric bit for bit.
+ *
+ * status int32 [C], OR-ed in and never cleared: ANIHIP_SADDLE_BAD_TABLE (a kind above 2), ANIHIP_SADDLE_NONFINITE (a force,
+ * Hessian row, eigenvalue or new energy that is not finite), ANIHIP_SADDLE_NO_BRACKET (the bracket of gm did not hold).  The
+ * entry that sets a bit in step or accept is left at its old coords.
+ * workspace: anihip_saddle_workspace_bytes(n_mol, atoms_per_mol) bytes, 256-byte aligned regions in this order:
+ *   q, b fp64 [C][6][n] | gproj, displacement, xi fp64 [C][n] | old coords fp32 [C][n] | scalars fp64 [C][8]
+ * kept between the three calls of a step.  n <= ANIHIP_SADDLE_MAX_COORDS: one workgroup per molecule holds the six rigid
+ * vectors (project) or four vectors of n (step) in its LDS.  project and accept are two launches each (one workgroup per
+ * molecule, then a streaming pass over [C][n][n] by blocks of 16 rows), step is one; no allocation, no atomics, every sum
+ * in a fixed order: bit-identical run to run.  Null pointers and sizes out of range return nonzero before any launch. */
+#define ANIHIP_SADDLE_MAX_COORDS 768
+#define ANIHIP_SADDLE_BAD_TABLE 1
+#define ANIHIP_SADDLE_NONFINITE 2
+#define ANIHIP_SADDLE_NO_BRACKET 4
+typedef struct {
+    int32_t n_mol, atoms_per_mol;
+    int32_t periodic;   /* != 0: the rotations are not projected out */
+    int32_t follow;     /* 0: the lowest mode; 1: the largest overlap with modes[c] */
+    double fmax;        /* Hartree / Angstrom */
+    double max_trust, min_trust; /* Angstrom */
+    double energy_floor;         /* Hartree */
+    const uint8_t *kind;         /* [C][A] */
+    float *coords;               /* [C][A][3], moved in place */
+    double *energies;            /* [C] */
+    float *forces;               /* [C][A][3] */
+    double *hessians;            /* [C][n][n], the model Hessian */
+    double *trust_radii;         /* [C] */
+    double *eigenvalues;         /* [C] */
+    double *modes;               /* [C][n] */
+    float *last_step;            /* [C][A][3] */
+    uint8_t *accepted, *converged; /* [C] */
+    int32_t *n_steps, *n_rejected, *status; /* [C] */
+    void *workspace;
+    size_t workspace_bytes;
+} anihip_saddle;
+size_t anihip_saddle_workspace_bytes(int64_t n_mol, int64_t atoms_per_mol);   /* 0 + anihip_last_error() */
+int anihip_saddle_project(void *stream, const anihip_saddle *state, double *projected);
+int anihip_saddle_step(void *stream, const anihip_saddle *state, const double *eigenvalues, const double *eigenvectors);
+int anihip_saddle_accept(void *stream, const anihip_saddle *state, const double *new_energies, const float *new_forces,
+                         int32_t bofill);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -11,6 +11,11 @@ and wraps.  HIP events around each part of every iteration; medians over the ite
                                   the 2560 conformers with one dihedral constraint each (geomopt.CVConstraints) against the same
                                   batch without: whole steps (optimizer, restore, evaluation, projection), the two optimizers
                                   alternating in one process, median (fastest, slowest) ms per step over 7 repeats
+    python tools/geomopt_bench.py --saddle [--out profiles/saddle_bench.txt]
+                                  ms per step of geomopt.SaddleOptimizer split into the exact Hessian, anihip_saddle_project,
+                                  torch.linalg.eigh, anihip_saddle_step, the evaluation and anihip_saddle_accept, on config 2's 256
+                                  molecules and on the 90-atom dense90 molecule, hessian_every 1 and 5; HIP events around each
+                                  part, median (fastest, slowest) over 5 repeats of 10 steps
 Bytes moved per L-BFGS step are estimated from the shapes (lbfgs_step_bytes), so that the achieved rate can be compared
 with HBM: S and Y read twice in fp32 and the fp64 m x m matrices of k_lb_solve, which outweigh S and Y for small molecules."""
 import argparse
@@ -106,6 +111,92 @@ def constraints_ab(model, sp, x, out_path, repeats=7, steps=30, memory=10):
             f.write(text + "\n")
 
 
+SADDLE_PARTS = ("exact Hessian", "anihip_saddle_project", "torch.linalg.eigh", "anihip_saddle_step", "evaluation",
+                "anihip_saddle_accept")
+
+
+def saddle_parts(model, sp, x, hessian_every, repeats=5, steps=10):
+    """ms per step of each part of SaddleOptimizer.step() (its phases _refresh_hessians, _move and _judge taken apart), per
+    repeat of `steps` steps: {part: [ms per step, one per repeat]}.  fmax = 0: nothing converges."""
+    import ctypes
+
+    from torchani_amd import _lib
+    from torchani_amd.engine import _stream
+    from torchani_amd.geomopt import SaddleOptimizer
+
+    L = _lib.lib()
+    opt = SaddleOptimizer(model, sp, x, hessian_every=hessian_every)
+    opt.fmax = 0.0
+    for _ in range(hessian_every + 1):   # (warm-up: every shape once, the automatic HIP graph captured)
+        opt.step()
+    torch.cuda.synchronize()
+    out = {part: [] for part in SADDLE_PARTS + ("whole step",)}
+    for _ in range(repeats):
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(7)] for _ in range(steps)]
+        for k in range(steps):
+            st = opt._state
+            ev[k][0].record()
+            opt._refresh_hessians()
+            ev[k][1].record()
+            st.fmax, st.follow = 0.0, 0
+            opt._project(st, opt._projected)
+            ev[k][2].record()
+            lam, V = torch.linalg.eigh(opt._projected)
+            lam, V = lam.contiguous(), V.contiguous()
+            ev[k][3].record()
+            _lib.check(L.anihip_saddle_step(_stream(), ctypes.byref(st), lam.data_ptr(), V.data_ptr()))
+            ev[k][4].record()
+            e, f = opt._model_eval(opt.coordinates)
+            e, f = e.to(torch.float64).contiguous(), f.to(torch.float32).contiguous()
+            ev[k][5].record()
+            _lib.check(L.anihip_saddle_accept(_stream(), ctypes.byref(st), e.data_ptr(), f.data_ptr(),
+                                              int((opt._calls + 1) % hessian_every != 0)))
+            opt._calls += 1
+            ev[k][6].record()
+        torch.cuda.synchronize()
+        for i, part in enumerate(SADDLE_PARTS):
+            out[part].append(sum(ev[k][i].elapsed_time(ev[k][i + 1]) for k in range(steps)) / steps)
+        out["whole step"].append(sum(ev[k][0].elapsed_time(ev[k][6]) for k in range(steps)) / steps)
+    opt.raise_on_overflow()
+    opt.raise_on_status()
+    out["accepted"] = int(opt.n_steps.sum())
+    out["rejected"] = int(opt.n_rejected.sum())
+    return out
+
+
+def saddle_bench(out_path):
+    from torchani_amd.models import ANI2x
+
+    dev = torch.device("cuda:0")
+    cases = []
+    with np.load(os.path.join(GOLD, "cfg2_xyz13_28_ani2x.npz")) as z:
+        cases.append(("config 2: 256 molecules, A = 28 (3A = 84)", z["species"].astype(np.int64), z["coords"]))
+    with np.load(os.path.join(GOLD, "dense90_ani2x.npz")) as z:
+        cases.append(("dense90: 1 molecule, A = 90 (3A = 270)", z["species"].astype(np.int64), z["coords"]))
+    lines = ["tools/geomopt_bench.py --saddle: ms per step() of geomopt.SaddleOptimizer, HIP events around each part, "
+             "median (fastest, slowest) over 5 repeats of 10 steps; seeded ANI-2x x 8, fmax = 0"]
+    for name, sp, x in cases:
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="batch")
+        for h in (1, 5):
+            r = saddle_parts(model, torch.from_numpy(sp).to(dev), torch.from_numpy(x).to(dev), h)
+            whole = np.median(r["whole step"])
+            lines.append(f"{name}, hessian_every {h}: whole step {whole:.3f} ({min(r['whole step']):.3f}, "
+                         f"{max(r['whole step']):.3f}) ms; steps accepted {r['accepted']}, rejected {r['rejected']}")
+            new = 0.0
+            for part in SADDLE_PARTS:
+                v = r[part]
+                lines.append(f"  {part:22s} {np.median(v):8.4f} ({min(v):.4f}, {max(v):.4f})  {100 * np.median(v) / whole:5.1f} %")
+                if part.startswith("anihip_saddle"):
+                    new += np.median(v)
+            lines.append(f"  the three new entry points together: {new:.4f} ms = {100 * new / whole:.1f} % of the step")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 def trace_summary(path, skip=101):
     """Median duration (us) of each k_lb_* kernel over its calls after the first `skip`, and their sum."""
     import collections
@@ -127,10 +218,14 @@ def main():
     ap.add_argument("--only", default="config2,conformers2560,config3")
     ap.add_argument("--trace-summary", default=None, metavar="CSV")
     ap.add_argument("--constraints", action="store_true")
+    ap.add_argument("--saddle", action="store_true")
     ap.add_argument("--out", default=None, metavar="TXT")
     args = ap.parse_args()
     if args.trace_summary:
         print(json.dumps(trace_summary(args.trace_summary)))
+        return
+    if args.saddle:
+        saddle_bench(args.out)
         return
     assert args.iters > 101, "the history is full from iteration 101 on"
     from torchani_amd.models import ANI2x

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "geom_constraints.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "geom_constraints.hip", "saddle.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -59,6 +59,8 @@ MD_SITE_ROLE_CENTER, MD_SITE_ROLE_A, MD_SITE_ROLE_B = 0, 1, 2   # ANIHIP_MD_SITE
 MD_SITES_BAD_SITE, MD_SITES_BAD_GROUP, MD_SITES_BAD_MEMBER = 1, 2, 4   # ANIHIP_MD_SITES_BAD_*
 GEOM_MAX_CONSTRAINTS = 8   # ANIHIP_GEOM_MAX_CONSTRAINTS
 GEOM_BAD_TABLE, GEOM_SINGULAR, GEOM_NOT_CONVERGED = 1, 2, 4   # ANIHIP_GEOM_*
+SADDLE_MAX_COORDS = 768   # ANIHIP_SADDLE_MAX_COORDS
+SADDLE_BAD_TABLE, SADDLE_NONFINITE, SADDLE_NO_BRACKET = 1, 2, 4   # ANIHIP_SADDLE_*
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -187,6 +189,16 @@ class GeomConstraints(C.Structure):
     _fields_ = [("n_constraints", C.c_int32), ("max_iterations", C.c_int32), ("tolerance", C.c_double),
                 ("offset", C.c_void_p), ("kind", C.c_void_p), ("atoms", C.c_void_p), ("target", C.c_void_p),
                 ("values", C.c_void_p), ("multipliers", C.c_void_p), ("iterations", C.c_void_p), ("status", C.c_void_p)]
+
+
+class Saddle(C.Structure):
+    """anihip_saddle (include/anihip.h)."""
+    _fields_ = [("n_mol", C.c_int32), ("atoms_per_mol", C.c_int32), ("periodic", C.c_int32), ("follow", C.c_int32),
+                ("fmax", C.c_double), ("max_trust", C.c_double), ("min_trust", C.c_double), ("energy_floor", C.c_double),
+                ("kind", C.c_void_p), ("coords", C.c_void_p), ("energies", C.c_void_p), ("forces", C.c_void_p),
+                ("hessians", C.c_void_p), ("trust_radii", C.c_void_p), ("eigenvalues", C.c_void_p), ("modes", C.c_void_p),
+                ("last_step", C.c_void_p), ("accepted", C.c_void_p), ("converged", C.c_void_p), ("n_steps", C.c_void_p),
+                ("n_rejected", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 class MlpShape(C.Structure):
@@ -367,6 +379,13 @@ def lib() -> C.CDLL:
     L.anihip_geom_constraints_restore.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp]
     for name in ("anihip_geom_constraints_project", "anihip_geom_constraints_restore"):
         getattr(L, name).restype = C.c_int
+    L.anihip_saddle_workspace_bytes.restype = sz
+    L.anihip_saddle_workspace_bytes.argtypes = [i64, i64]
+    L.anihip_saddle_project.argtypes = [vp, C.POINTER(Saddle), vp]
+    L.anihip_saddle_step.argtypes = [vp, C.POINTER(Saddle), vp, vp]
+    L.anihip_saddle_accept.argtypes = [vp, C.POINTER(Saddle), vp, vp, i32]
+    for name in ("anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept"):
+        getattr(L, name).restype = C.c_int
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
@@ -410,6 +429,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_bias_workspace_bytes", "anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills",
     "anihip_md_sites_workspace_bytes", "anihip_md_sites_gather", "anihip_md_sites_spread",
     "anihip_geom_constraints_project", "anihip_geom_constraints_restore",
+    "anihip_saddle_workspace_bytes", "anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept",
 ]
 
 

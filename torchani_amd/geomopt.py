@@ -25,6 +25,10 @@ and per entry: relaxed scans, every grid point an entry of the batch (``torsion_
 projected onto the tangent space of the constraints, f <- f - J^T lambda with (J J^T) lambda = J f, and every step is followed
 by a Newton iteration back onto the targets along the minimum-norm correction.  At a constrained minimum the multipliers are
 the slope of the relaxed energy along the targets, dE* / dt_k = -lambda_k.
+
+``SaddleOptimizer`` / ``optimize_saddle`` search first-order saddle points (transition states) of a batch by partitioned
+rational-function optimization on the analytic Hessian with Bofill updates (csrc/saddle.hip); ``descend_from_saddle`` relaxes
+both sides of every saddle to the minima it connects.  Its class docstring has the step.
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ from torch import Tensor
 from . import _lib
 from .engine import _stream
 from .md_bias import CV, _CV_NAMES, _per_entry, has_sites
-from .tuples import OptimizedGeometries, TorsionScan
+from .tuples import OptimizedGeometries, OptimizedSaddles, TorsionScan
 from .units import HARTREE_TO_EV
 from .utils import pbc_tuple
 
@@ -47,6 +51,9 @@ DEFAULT_FMAX = 0.05 / HARTREE_TO_EV    # ASE Optimizer.run(fmax=0.05 eV / A), in
 MAX_MEMORY = _lib.LBFGS_MAX_MEMORY
 MAX_CONSTRAINTS = _lib.GEOM_MAX_CONSTRAINTS
 MAX_INITIAL_OFFSET = 0.1   # Angstrom or rad: the farthest an initial value may be from its target
+# 3A of SaddleOptimizer: one workgroup per molecule holds the six rigid vectors of 3A doubles (36 KiB of its LDS at the limit)
+SADDLE_MAX_COORDS = _lib.SADDLE_MAX_COORDS
+DEFAULT_NEGATIVE_TOL = 1e-4   # Hartree / Angstrom^2: eigenvalues below its negative count in OptimizedSaddles.n_negative
 
 
 def lbfgs_workspace_bytes(n_mol: int, atoms_per_mol: int, memory: int) -> int:
@@ -66,6 +73,15 @@ def lbfgs_workspace_bytes(n_mol: int, atoms_per_mol: int, memory: int) -> int:
     regions = [Cn * 4 * 4, Cn * 2 * M1 * 8, Cn * M1 * M1 * 8, Cn * M1 * M1 * 8, Cn * M1 * M1 * 8, Cn * M1 * 8,
                Cn * G * NV * 8, Cn * Gc * 8, Cn * n * 8, Cn * n_pad * 4, Cn * n_pad * 4, Cn * M1 * n_pad * 4,
                Cn * M1 * n_pad * 4]
+    return sum(-(-r // 256) * 256 for r in regions)
+
+
+def saddle_workspace_bytes(n_mol: int, atoms_per_mol: int) -> int:
+    """Bytes of the saddle optimizer's device workspace: the layout of csrc/saddle.hip (sd_layout), computed on the host."""
+    if n_mol < 1 or atoms_per_mol < 1 or 3 * atoms_per_mol > SADDLE_MAX_COORDS:
+        raise ValueError(f"n_mol and atoms_per_mol must be >= 1 and 3 atoms_per_mol <= {SADDLE_MAX_COORDS}")
+    Cn, n = int(n_mol), 3 * int(atoms_per_mol)
+    regions = [Cn * 6 * n * 8, Cn * 6 * n * 8, Cn * n * 8, Cn * n * 8, Cn * n * 8, Cn * n * 4, Cn * 8 * 8]
     return sum(-(-r // 256) * 256 for r in regions)
 
 
@@ -579,3 +595,290 @@ def torsion_scan(model, species: Tensor, coordinates: Tensor, dihedral, angles, 
     shape = (K,) if single else (M, K)
     return TorsionScan(ang.to(x.device), out.energies.view(shape), out.coordinates.view(*shape, A, 3),
                        out.converged.view(shape), -opt.constraint_multipliers()[:, 0].reshape(shape))
+
+
+_SADDLE_STATUS = ((_lib.SADDLE_BAD_TABLE, "the atom table is out of range"),
+                  (_lib.SADDLE_NONFINITE, "a force, energy, Hessian entry or eigenvalue is not finite"),
+                  (_lib.SADDLE_NO_BRACKET, "the bracket of the minimizing shift did not hold"))
+
+
+def _check_saddle_args(species: Tensor, coordinates: Tensor, fixed, mode, follow, hessian_every, trust, max_trust, min_trust,
+                       energy_floor, constraints, neighbors) -> None:
+    """The refusals of SaddleOptimizer that need neither the model nor a device."""
+    if species.dim() != 2 or tuple(coordinates.shape) != (species.shape[0], species.shape[1], 3):
+        raise ValueError("expected species [C, A] and coordinates [C, A, 3]")
+    if constraints is not None:
+        raise NotImplementedError("SaddleOptimizer does not support constraints on internal coordinates: the projected "
+                                  "Hessian would need their tangent space (use fixed= to hold atoms)")
+    if neighbors is not None:
+        raise NotImplementedError("SaddleOptimizer does not support external neighbor lists: the exact Hessian is built on the "
+                                  "engine's own neighbor rows")
+    if 3 * species.shape[1] > SADDLE_MAX_COORDS:
+        raise ValueError(f"3A = {3 * species.shape[1]} coordinates per molecule exceed SADDLE_MAX_COORDS = {SADDLE_MAX_COORDS} "
+                         "(dense Hessians and one workgroup per molecule: this is a method for small systems)")
+    if isinstance(hessian_every, bool) or int(hessian_every) != hessian_every or hessian_every < 1:
+        raise ValueError(f"hessian_every must be an integer >= 1, got {hessian_every}")
+    for name, v in (("trust", trust), ("max_trust", max_trust), ("min_trust", min_trust)):
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError(f"{name} must be a finite trust radius > 0 (Angstrom), got {v}")
+    if not min_trust <= trust <= max_trust:
+        raise ValueError(f"trust radii must satisfy min_trust <= trust <= max_trust, got {min_trust}, {trust}, {max_trust}")
+    if not (math.isfinite(energy_floor) and energy_floor >= 0):
+        raise ValueError(f"energy_floor must be finite and >= 0, got {energy_floor}")
+    if follow not in ("lowest", "overlap"):
+        raise ValueError(f"follow must be 'lowest' or 'overlap', got {follow!r}")
+    if fixed is not None and tuple(fixed.shape) != tuple(species.shape):
+        raise ValueError(f"fixed must be a bool mask of shape {tuple(species.shape)}, got {tuple(fixed.shape)}")
+    if mode is not None and tuple(mode.shape) != tuple(coordinates.shape):
+        raise ValueError(f"mode must have the shape of the coordinates {tuple(coordinates.shape)}, got {tuple(mode.shape)}")
+
+
+def _check_saddle_model(model) -> None:
+    """D3 has no second derivative (the NotImplementedError of the Hessian drivers); trainable networks are refused like
+    grad.hessians refuses them."""
+    from .grad import _pair_potentials_without_hessians
+
+    pots = _pair_potentials_without_hessians(model)
+    if pots:
+        raise NotImplementedError(f"the pair potential(s) {', '.join(pots)} have no second derivative with respect to the "
+                                  "coordinates: Hessians of this model are not available, so no saddle search")
+    parameters = getattr(model, "parameters", None)
+    if callable(parameters) and any(p.requires_grad for p in parameters()):
+        raise RuntimeError("SaddleOptimizer needs a model with frozen parameters (requires_grad_(False)): a search on networks "
+                           "that are being trained is not meaningful")
+
+
+class SaddleOptimizer:
+    """Search for a first-order saddle point (a transition state) of every molecule of species [C, A], coordinates [C, A, 3]
+    (Angstrom; energies in Hartree): partitioned rational-function optimization (P-RFO, Baker 1986) on a dense model Hessian
+    that is the analytic one every ``hessian_every`` calls of ``step()`` and is updated by the Bofill formula in between.  The
+    step maximizes along one Hessian mode and minimizes along all the others.  The whole batch is stepped at once; the
+    per-molecule arithmetic is fp64 in libanihip (csrc/saddle.hip; include/anihip.h has the definition).
+
+    One ``step()``, per entry that is neither converged nor stopped by a status bit:
+
+    1. on calls 0, h, 2h, ... the model Hessian becomes the exact, symmetrized one (the direction loop of
+       ``grad.energies_forces_and_hessians``).  This comes before the convergence test of 2., so an entry that turns out
+       converged on such a call still had its Hessian computed and counted in ``n_hessians``;
+    2. ``converged |= max |f_i| < fmax`` over the free atoms; a converged entry is frozen, bit for bit;
+    3. the Hessian and the gradient are projected onto the complement of the inactive coordinates (padding, ``fixed``), of
+       the translations (when the entry has no fixed atom) and of the rotations (when in addition nothing is periodic); the
+       projected-out directions get the eigenvalue mu = 1 + the largest row sum of |H|;
+    4. ``torch.linalg.eigh`` of the projected Hessians in fp64.  This is the one place every step may synchronize with the
+       host (the eigensolver checks its own convergence); calls with an exact Hessian also read the neighbor overflow word;
+    5. the followed mode is the lowest (``follow="lowest"``) or the one of largest overlap with the mode followed before
+       (``follow="overlap"``); ``mode`` [C, A, 3] chooses it by overlap on the first call, whatever ``follow``;
+    6. the P-RFO step, scaled to the trust radius (``trust_radii``, Angstrom: the length of the whole step vector);
+    7. one evaluation at the moved coordinates; with rho = the actual over the predicted energy change the step is rejected
+       when |rho - 1| > 1 (coordinates, energies and forces stay those of before, the radius is quartered, ``n_rejected`` += 1)
+       and accepted otherwise (``n_steps`` += 1; the radius doubles up to ``max_trust`` for |rho - 1| < 0.25 on a full-length
+       step and halves down to ``min_trust`` for |rho - 1| > 0.75).  A predicted change below ``energy_floor`` is accepted as
+       it is: fp32 energies cannot judge it.
+
+    P-RFO climbs the chosen mode whatever its curvature.  From a start whose lowest Hessian eigenvalue is positive it climbs
+    the softest mode, which can lead anywhere (a Lennard-Jones cluster dissociates): start where the wanted negative curvature
+    already exists, such as the top of a ``torsion_scan``, or pass ``mode=``.  The search is dense and per molecule: 3A is at
+    most SADDLE_MAX_COORDS.  Not supported: constraints on internal coordinates, external neighbor lists, variable cells, D3
+    (ANI-2dr, no second derivative), trainable networks.
+
+    Attributes (device tensors): ``coordinates`` (fp32, in place), ``energies`` [C], ``forces`` [C, A, 3], ``hessians`` (the
+    model Hessian, fp64 [C, 3A, 3A]), ``last_step`` (fp32, the displacement last tried), ``trust_radii``, ``eigenvalues`` (of
+    the followed mode), ``modes`` [C, A, 3] (fp64), ``accepted``, ``converged`` (bool [C]), ``n_steps``, ``n_rejected``,
+    ``n_hessians`` (int32 [C]) and ``status`` (int32 [C], see ``raise_on_status``).
+    """
+
+    def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
+                 fixed: tp.Optional[Tensor] = None, mode: tp.Optional[Tensor] = None, follow: str = "lowest",
+                 hessian_every: int = 5, trust: float = 0.05, max_trust: float = 0.15, min_trust: float = 1e-4,
+                 energy_floor: float = 1e-7, constraints=None, neighbors=None) -> None:
+        _check_saddle_args(species, coordinates, fixed, mode, follow, hessian_every, trust, max_trust, min_trust,
+                           energy_floor, constraints, neighbors)
+        _check_saddle_model(model)
+        if not (species.is_cuda and coordinates.is_cuda):
+            raise ValueError("SaddleOptimizer needs tensors on a ROCm device (no CPU fallback)")
+        dev = coordinates.device
+        Cn, A = species.shape
+        n = 3 * A
+        self._model_eval = ModelEvaluator(model, species, cell, pbc)
+        self.model, self.species, self.cell, self.pbc = model, species, cell, self._model_eval.pbc
+        self._pbc_arg = pbc
+        self._dtype = coordinates.dtype
+        self.follow, self.hessian_every = follow, int(hessian_every)
+        self.fmax = DEFAULT_FMAX
+        self.coordinates = coordinates.detach().to(torch.float32).clone().contiguous()
+        kind = (species >= 0).to(torch.uint8)
+        if fixed is not None:
+            kind = kind + ((species >= 0) & fixed.to(device=dev, dtype=torch.bool)).to(torch.uint8)
+        self._kind = kind.contiguous()   # 0: padding, 1: free, 2: fixed
+        self._free = self._kind == 1
+        periodic = cell is not None and any(self.pbc)
+        self.hessians = torch.zeros((Cn, n, n), dtype=torch.float64, device=dev)
+        # (a frozen entry's projected Hessian is never written: the eigensolver still sees a matrix)
+        self._projected = torch.eye(n, dtype=torch.float64, device=dev).repeat(Cn, 1, 1)
+        self.trust_radii = torch.full((Cn,), float(trust), dtype=torch.float64, device=dev)
+        self.eigenvalues = torch.zeros(Cn, dtype=torch.float64, device=dev)
+        self.modes = torch.zeros((Cn, A, 3), dtype=torch.float64, device=dev)
+        self._have_mode = mode is not None
+        if mode is not None:
+            self.modes.copy_(mode.detach().to(device=dev, dtype=torch.float64))
+        self.last_step = torch.zeros_like(self.coordinates)
+        self.accepted = torch.zeros(Cn, dtype=torch.bool, device=dev)
+        self.converged = torch.zeros(Cn, dtype=torch.bool, device=dev)
+        self.n_steps = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.n_rejected = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.n_hessians = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self._workspace = torch.zeros(saddle_workspace_bytes(Cn, A), dtype=torch.uint8, device=dev)
+        self._calls = 0
+        e, f = self._model_eval(self.coordinates)
+        self.energies, self.forces = e.to(torch.float64).clone(), f.to(torch.float32).clone().contiguous()
+        self._state = self._struct(int(periodic), float(max_trust), float(min_trust), float(energy_floor))
+
+    def _struct(self, periodic: int, max_trust: float, min_trust: float, energy_floor: float) -> "_lib.Saddle":
+        Cn, A = self.species.shape
+        return _lib.Saddle(
+            Cn, A, periodic, 0, float(self.fmax), max_trust, min_trust, energy_floor, self._kind.data_ptr(),
+            self.coordinates.data_ptr(), self.energies.data_ptr(), self.forces.data_ptr(), self.hessians.data_ptr(),
+            self.trust_radii.data_ptr(), self.eigenvalues.data_ptr(), self.modes.data_ptr(), self.last_step.data_ptr(),
+            self.accepted.data_ptr(), self.converged.data_ptr(), self.n_steps.data_ptr(), self.n_rejected.data_ptr(),
+            self.status.data_ptr(), self._workspace.data_ptr(), self._workspace.numel())
+
+    def _exact_hessians(self) -> Tensor:
+        """fp64 [C, 3A, 3A]: the symmetrized analytic Hessian at the current coordinates."""
+        from . import grad
+
+        x = self.coordinates.clone()
+        inp = grad._second_order_inputs(self.model, self.species, x, self.cell, self._pbc_arg, "Hessians")
+        H = grad._dense_hessian_columns(inp, x.device).to(torch.float64)
+        return 0.5 * (H + H.transpose(1, 2))
+
+    def _project(self, state: "_lib.Saddle", projected: Tensor) -> None:
+        _lib.check(_lib.lib().anihip_saddle_project(_stream(), C.byref(state), projected.data_ptr()))
+
+    def _refresh_hessians(self) -> None:
+        """On calls 0, h, 2h, ...: the model Hessian of every entry that has not converged becomes the exact one."""
+        if self._calls % self.hessian_every == 0:
+            H = self._exact_hessians()
+            self.hessians.copy_(torch.where(self.converged.view(-1, 1, 1), self.hessians, H))
+            self.n_hessians += (~self.converged).to(torch.int32)
+
+    def _move(self) -> None:
+        """The convergence test, the projection, the eigensolver and the P-RFO step: the coordinates moved."""
+        st = self._state
+        st.fmax = float(self.fmax)
+        st.follow = int(self._have_mode and (self._calls == 0 or self.follow == "overlap"))
+        self._project(st, self._projected)
+        lam, V = torch.linalg.eigh(self._projected)
+        lam, V = lam.contiguous(), V.contiguous()
+        _lib.check(_lib.lib().anihip_saddle_step(_stream(), C.byref(st), lam.data_ptr(), V.data_ptr()))
+        self._have_mode = self._have_mode or self.follow == "overlap"
+
+    def _judge(self) -> None:
+        """The evaluation at the moved coordinates (kept as ``trial_energies``, ``trial_forces``), then accept or reject, and
+        the Bofill update unless the next call brings an exact Hessian."""
+        e, f = self._model_eval(self.coordinates)
+        self.trial_energies, self.trial_forces = e.to(torch.float64).contiguous(), f.to(torch.float32).contiguous()
+        update = int((self._calls + 1) % self.hessian_every != 0)
+        _lib.check(_lib.lib().anihip_saddle_accept(_stream(), C.byref(self._state), self.trial_energies.data_ptr(),
+                                                   self.trial_forces.data_ptr(), update))
+        self._calls += 1
+
+    def step(self) -> None:
+        """One step as described in the class docstring (convergence tested against ``self.fmax``)."""
+        self._refresh_hessians()
+        self._move()
+        self._judge()
+
+    def raise_on_overflow(self) -> None:
+        """Raise if a neighbor row of the last evaluation overflowed (one host synchronization)."""
+        self._model_eval.raise_on_overflow()
+
+    def raise_on_status(self) -> None:
+        """Raise if the kernels stopped an entry: a table out of range, a value that is not finite, a bracket that did not
+        hold (one host synchronization)."""
+        status = self.status.cpu()
+        if not bool(status.any()):
+            return
+        c = int(status.nonzero()[0])
+        what = [name for bit, name in _SADDLE_STATUS if int(status[c]) & bit]
+        raise RuntimeError(f"SaddleOptimizer: entry {c}: {'; '.join(what)}")
+
+    def run(self, fmax: float = DEFAULT_FMAX, steps: int = 200, check_every: int = 10,
+            negative_tol: float = DEFAULT_NEGATIVE_TOL) -> OptimizedSaddles:
+        """At most ``steps`` calls of ``step()`` until every entry has max |f_i| < fmax (Hartree / Angstrom).  The host reads
+        the converged flags, the status words and the overflow status every ``check_every`` steps and after the last one;
+        entries whose final forces are below fmax count as converged."""
+        _check_run_args(fmax, steps, check_every)
+        self.fmax = float(fmax)
+        for k in range(steps):
+            self.step()
+            if (k + 1) % check_every == 0 or k + 1 == steps:
+                self.raise_on_overflow()
+                self.raise_on_status()
+                if bool(self.converged.all()):
+                    break
+        if steps == 0:
+            self.raise_on_overflow()
+        fm = (self.forces * self._free.unsqueeze(-1)).to(torch.float64).norm(dim=-1).amax(dim=1)
+        self.converged |= fm < self.fmax
+        return self.result(negative_tol)
+
+    def result(self, negative_tol: float = DEFAULT_NEGATIVE_TOL) -> OptimizedSaddles:
+        """The current state as OptimizedSaddles (copies).  One exact Hessian at the current coordinates, projected as in a
+        step, gives ``n_negative`` (eigenvalues below -negative_tol) and the followed eigenpair: the lowest, or with
+        ``follow="overlap"`` or a ``mode`` the one of largest overlap with ``modes``."""
+        if not negative_tol >= 0:
+            raise ValueError(f"negative_tol must be >= 0, got {negative_tol}")
+        Cn, A = self.species.shape
+        dev = self.coordinates.device
+        H = self._exact_hessians().contiguous()
+        projected = torch.empty_like(H)
+        none = torch.zeros(Cn, dtype=torch.bool, device=dev)
+        state = self._struct(self._state.periodic, self._state.max_trust, self._state.min_trust, self._state.energy_floor)
+        state.fmax = 0.0   # (no entry is skipped as converged)
+        state.hessians, state.converged = H.data_ptr(), none.data_ptr()
+        status = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        state.status = status.data_ptr()
+        scratch = torch.zeros_like(self._workspace)   # (the optimizer's own workspace stays as the last step left it)
+        state.workspace = scratch.data_ptr()
+        self._project(state, projected)
+        if bool(status.any()):
+            self.status |= status
+            self.raise_on_status()
+        lam, V = torch.linalg.eigh(projected)
+        n_negative = (lam < -float(negative_tol)).sum(dim=1)
+        pick = torch.zeros(Cn, dtype=torch.int64, device=dev)
+        if self._have_mode:
+            mu = 1.0 + H.abs().sum(dim=2).amax(dim=1, keepdim=True)
+            ov = (V.transpose(1, 2) @ self.modes.view(Cn, 3 * A, 1)).squeeze(2).abs()
+            pick = torch.where(lam < 0.5 * mu, ov, torch.full_like(ov, -1.0)).argmax(dim=1)
+        eig = lam.gather(1, pick.view(-1, 1)).squeeze(1)
+        modes = V.gather(2, pick.view(-1, 1, 1).expand(Cn, 3 * A, 1)).squeeze(2).view(Cn, A, 3)
+        return OptimizedSaddles(self.species, self.coordinates.to(self._dtype, copy=True), self.energies.clone(),
+                                self.forces.to(self._dtype, copy=True), self.converged.clone(), self.n_steps.clone(), eig,
+                                modes.contiguous(), n_negative)
+
+
+def optimize_saddle(model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None,
+                    **kw) -> OptimizedSaddles:
+    """``SaddleOptimizer(model, species, coordinates, cell, pbc, fixed=, mode=, follow=, hessian_every=, trust=, max_trust=,
+    min_trust=, energy_floor=).run(fmax=, steps=, check_every=, negative_tol=)``."""
+    run_kw = {k: kw.pop(k) for k in ("fmax", "steps", "check_every", "negative_tol") if k in kw}
+    _check_run_args(run_kw.get("fmax", DEFAULT_FMAX), run_kw.get("steps", 200), run_kw.get("check_every", 10))
+    return SaddleOptimizer(model, species, coordinates, cell, pbc, **kw).run(**run_kw)
+
+
+def descend_from_saddle(model, species: Tensor, saddles: OptimizedSaddles, delta: float = 0.05,
+                        **kw) -> tp.Tuple[OptimizedGeometries, OptimizedGeometries]:
+    """The two minima a saddle point connects: every entry of ``saddles`` is displaced by +delta and by -delta (Angstrom)
+    along its ``modes`` vector and the 2C copies are relaxed as one batch by ``optimize_geometry`` (keywords, ``cell`` and
+    ``pbc`` among them, go there).  Returns (forward, backward).  This is a relaxation, not a reaction path."""
+    if not (math.isfinite(delta) and delta > 0):
+        raise ValueError(f"delta must be finite and > 0, got {delta}")
+    x = saddles.coordinates
+    Cn = x.shape[0]
+    d = float(delta) * saddles.modes.to(x.dtype)
+    if "fixed" in kw and kw["fixed"] is not None:
+        kw["fixed"] = kw["fixed"].repeat(2, 1)
+    out = optimize_geometry(model, species.repeat(2, 1), torch.cat([x + d, x - d]), **kw)
+    return (OptimizedGeometries(*(t[:Cn] for t in out)), OptimizedGeometries(*(t[Cn:] for t in out)))

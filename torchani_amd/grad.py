@@ -224,8 +224,16 @@ def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, re
     standalone pair potential (``torchani_amd.potentials``) may stand in for the model, on its own rows.  Energies and
     forces are those of grad.energies_and_forces.  Results are detached (any model: frozen or trainable parameters);
     ``retain_graph`` is accepted for the reference's signature."""
-    ef, species32, nnp, nbrs, eng, aev, packed, g, pairs = _second_order_inputs(model, species, coordinates, cell, pbc,
-                                                                                "Hessians")
+    inp = _second_order_inputs(model, species, coordinates, cell, pbc, "Hessians")
+    H = _dense_hessian_columns(inp, coordinates.device)
+    return EnergiesForcesHessians(inp.ef.energies, inp.ef.forces, H.to(coordinates.dtype))
+
+
+def _dense_hessian_columns(inp: _SecondOrderInputs, device: torch.device) -> Tensor:
+    """The direction loop of energies_forces_and_hessians on what _second_order_inputs computed: float32 [C, 3A, 3A], the
+    unit directions in chunks of hessian_chunk_size(...) through the second-order kernels (shared with
+    geomopt.SaddleOptimizer, which wants the Hessian at its own coordinates)."""
+    _, species32, nnp, nbrs, eng, aev, packed, g, pairs = inp
     with torch.no_grad():
         Cn, A = species32.shape
         N = Cn * A
@@ -235,12 +243,12 @@ def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, re
         else:
             K = hessian_chunk_size(Cn, A, 0, 0)
         n = 3 * A
-        H = torch.zeros((Cn, n, n), dtype=torch.float32, device=coordinates.device)
-        mol0 = torch.arange(Cn, device=coordinates.device) * A
+        H = torch.zeros((Cn, n, n), dtype=torch.float32, device=device)
+        mol0 = torch.arange(Cn, device=device) * A
         for j0 in range(0, n, K):
             j1 = min(n, j0 + K)
-            k = torch.arange(j1 - j0, device=coordinates.device)
-            t = torch.zeros((j1 - j0, N, 3), dtype=torch.float32, device=coordinates.device)
+            k = torch.arange(j1 - j0, device=device)
+            t = torch.zeros((j1 - j0, N, 3), dtype=torch.float32, device=device)
             jj = k + j0
             t[k.view(-1, 1), (mol0.view(1, -1) + (jj // 3).view(-1, 1)), (jj % 3).view(-1, 1)] = 1.0
             if nnp:
@@ -254,7 +262,7 @@ def energies_forces_and_hessians(model, species: Tensor, coordinates: Tensor, re
             for pot, rows in pairs:
                 pot.hvp(species32, rows, t, out)
             H[:, :, j0:j1] = out.view(j1 - j0, Cn, n).permute(1, 2, 0)
-    return EnergiesForcesHessians(ef.energies, ef.forces, H.to(coordinates.dtype))
+    return H
 
 
 def _sparse_hessian_pairs(model) -> tp.List[tp.Any]:

@@ -126,6 +126,24 @@ class OptimizedGeometries(tp.NamedTuple):
     n_steps: Tensor
 
 
+class OptimizedSaddles(tp.NamedTuple):
+    """What geomopt.SaddleOptimizer.run / geomopt.optimize_saddle return: coordinates [C, A, 3] in the input dtype, energies [C]
+    (float64) and forces [C, A, 3] at them, converged (bool [C]), n_steps (int32 [C], the accepted steps), and from one exact
+    Hessian at the final geometry, projected like the optimizer's: eigenvalues [C] (float64, Hartree / Angstrom^2) and modes
+    [C, A, 3] (float64, unit vectors) of the followed mode, and n_negative (int64 [C]), the number of eigenvalues below
+    -negative_tol.  A converged entry with n_negative != 1 is a stationary point of another index."""
+
+    species: Tensor
+    coordinates: Tensor
+    energies: Tensor
+    forces: Tensor
+    converged: Tensor
+    n_steps: Tensor
+    eigenvalues: Tensor
+    modes: Tensor
+    n_negative: Tensor
+
+
 class TorsionScan(tp.NamedTuple):
     """What geomopt.torsion_scan returns for M molecules and K angles: angles [K] (rad, the targets), energies [M, K]
     (float64, Hartree) of the relaxed geometries coordinates [M, K, A, 3], converged (bool [M, K]) and torques [M, K]
