@@ -1005,6 +1005,90 @@ int anihip_saddle_step(void *stream, const anihip_saddle *state, const double *e
 int anihip_saddle_accept(void *stream, const anihip_saddle *state, const double *new_energies, const float *new_forces,
                          int32_t bofill);
 
+/* Reaction paths of a batch of molecules (torchani_amd.geomopt.ReactionPathFollower, csrc/irc.hip): the intrinsic reaction
+ * coordinate, the steepest-descent path in mass-weighted coordinates q = M^1/2 x, integrated by the local quadratic
+ * approximation (LQA, Page & McIver 1988) on a dense Cartesian model Hessian as the saddle search keeps it (exact every few
+ * points, Bofill-updated in between).  Everything is fp64 on the fp32 coords and forces read exactly; every molecule c of [C][A] on its
+ * own, n = 3 A <= ANIHIP_SADDLE_MAX_COORDS.  A point of the caller is: project, a symmetric eigensolver on `projected`
+ * (eigenvalues ascending, eigenvectors in the columns), step, the energies and forces at the moved coords, commit.
+ *
+ * kind as in anihip_saddle; masses fp64 [C][A] in amu.  w = m^-1/2 on the active coordinates and 0 elsewhere, W = diag(w),
+ * g = -forces on the active coordinates.  An entry is FROZEN when reason[c] != 0 (done) or status[c] != 0: the three entry
+ * points leave it alone (coords, energies, forces, hessians, counters and path stay bit-identical, its last_step is zero).
+ *
+ * project: the rigid motions of the entry in mass-weighted coordinates, sqrt(m_i) e_a (when the entry has no fixed atom) and
+ *   sqrt(m_i) e_a x (x_i - x_com) about the centre of mass of the free atoms (when in addition periodic == 0), are
+ *   orthonormalized as in anihip_saddle_project (Gram-Schmidt twice, a vector dropped when its remainder falls to 1e-8 of its
+ *   length) into Q.  With H_q = W H W, D the 0 / 1 diagonal of the active coordinates, P = D - Q Q^T and mu = 1 + the largest
+ *   row sum of |H_q|:
+ *     gproj = P W g  (kept in the workspace),  projected[c] = P H_q P + mu (I - P).
+ *   A mass of a real atom (kind 1 or 2) that is not finite and positive sets ANIHIP_IRC_BAD_TABLE.
+ * step: g~ = V^T gproj.
+ *   The first point from a saddle, n_points[c] == 0 and direction != NULL: dq = +-step V_0 (the lowest eigenvector), the sign
+ *   that of V_0 . (M^1/2 direction[c]) over the active coordinates, + when that overlap is zero; the arc increment is step.
+ *   Otherwise the path of the quadratic model through the point, dq/dt = -(gproj + H' dq): q(t) = q_0 + V alpha(t),
+ *     alpha_i(t) = -g~_i (1 - e^(-lam_i t)) / lam_i   (-g~_i t for lam_i == 0),   ds/dt = (sum g~_i^2 e^(-2 lam_i t))^1/2,
+ *   followed to the time t with s(t) = step, |s(t) - step| <= 1e-9 step.  A mode with g~_i == 0 does not move; if none moves
+ *   the step and the arc increment are zero.  If every moving mode has lam_i > 0 and s(T) < step at T = 40 / min lam_i, the
+ *   step LANDS on the minimum of the model: alpha_i = -g~_i / lam_i and the arc increment is s(T).  s is integrated by 16-point
+ *   Gauss-Legendre panels whose widths grow by sqrt(2) from min(0.01 / max |lam_i|, step / |g~|) (over the moving modes), t is
+ *   found by Newton's iteration on s(t) - step inside the bracketing panel, bisection when it leaves the bracket.
+ *   dx = W V alpha; on the active coordinates coords += (float)dx, last_step = (float)dx; the old coords are kept for commit,
+ *   and so is the displacement (new - old coords, exact in fp64) for the Bofill update.  The arc increment handed to commit
+ *   is the larger of the one above and the mass-weighted length of that displacement, |M^1/2 (new - old coords)|: the
+ *   rounding of the fp32 coordinates can lengthen a straight or a very short step by an ulp of a coordinate, and the arc
+ *   lengths of a path are never shorter than the chords between its stored points.
+ * commit: e', f' = new_energies, new_forces (at the moved coords); energies and forces still hold those of the old coords.
+ *   e' > e + energy_floor: the coords are restored bit for bit, nothing is appended, reason[c] = ANIHIP_IRC_ENERGY_ROSE.
+ *   Otherwise, with bofill != 0 the model Hessian is updated in place by the formula of anihip_saddle_accept (s the Cartesian
+ *   displacement, y = g' - g on the active coordinates, the same skips, symmetric bit for bit); then e', f' are taken into
+ *   energies, forces, arc_lengths[c] grows by the arc increment, and the point is appended: path_coords[c][k] = coords,
+ *   path_energies[c][k] = e', path_arcs[c][k] = arc_lengths[c] at k = n_points[c]++.  Then reason[c] = ANIHIP_IRC_MINIMUM when
+ *   max over the free atoms of |f'_i| < fmax or the step was zero, else ANIHIP_IRC_PATH_FULL when n_points[c] == max_points.
+ *
+ * status int32 [C], OR-ed in and never cleared: ANIHIP_IRC_BAD_TABLE (a kind above 2, a bad mass), ANIHIP_IRC_NONFINITE (a
+ * force, coordinate, Hessian row, eigenvalue, step or new energy that is not finite), ANIHIP_IRC_NO_ROOT (no bracket of t, or
+ * the iteration did not reach the tolerance).  The entry that sets a bit in step or commit is left at its old coords.
+ * workspace: anihip_irc_workspace_bytes(n_mol, atoms_per_mol) bytes, 256-byte aligned regions in this order:
+ *   q, b fp64 [C][6][n] | gproj, w, displacement, xi fp64 [C][n] | old coords fp32 [C][n] | scalars fp64 [C][8]
+ * kept between the three calls of a point; commit must follow a step on the same state.  project and commit are two launches
+ * each (one workgroup of 256 threads per molecule, then a streaming pass over [C][n][n] by blocks of 16 rows), step is one; no
+ * allocation, no atomics, every sum in a fixed order: bit-identical run to run.  Null pointers (direction excepted) and sizes
+ * out of range return nonzero before any launch. */
+#define ANIHIP_IRC_BAD_TABLE 1
+#define ANIHIP_IRC_NONFINITE 2
+#define ANIHIP_IRC_NO_ROOT 4
+#define ANIHIP_IRC_MINIMUM 1
+#define ANIHIP_IRC_ENERGY_ROSE 2
+#define ANIHIP_IRC_PATH_FULL 3
+typedef struct {
+    int32_t n_mol, atoms_per_mol;
+    int32_t periodic;   /* != 0: the rotations are not projected out */
+    int32_t max_points; /* the capacity of the path of an entry */
+    double step;        /* Angstrom amu^1/2: the arc length of a point */
+    double fmax;        /* Hartree / Angstrom */
+    double energy_floor;         /* Hartree */
+    const uint8_t *kind;         /* [C][A] */
+    const double *masses;        /* [C][A], amu */
+    float *coords;               /* [C][A][3], moved in place */
+    double *energies;            /* [C] */
+    float *forces;               /* [C][A][3] */
+    double *hessians;            /* [C][n][n], the Cartesian model Hessian */
+    const double *direction;     /* [C][n] or NULL */
+    float *last_step;            /* [C][A][3] */
+    double *arc_lengths;         /* [C], cumulative */
+    int32_t *n_points, *reason, *status; /* [C] */
+    float *path_coords;          /* [C][max_points][A][3] */
+    double *path_energies, *path_arcs;   /* [C][max_points] */
+    void *workspace;
+    size_t workspace_bytes;
+} anihip_irc;
+size_t anihip_irc_workspace_bytes(int64_t n_mol, int64_t atoms_per_mol);   /* 0 + anihip_last_error() */
+int anihip_irc_project(void *stream, const anihip_irc *state, double *projected);
+int anihip_irc_step(void *stream, const anihip_irc *state, const double *eigenvalues, const double *eigenvectors);
+int anihip_irc_commit(void *stream, const anihip_irc *state, const double *new_energies, const float *new_forces,
+                      int32_t bofill);
+
 /* anihip_aev_backward plus the virial of the back-propagated scalar,
  *   virial[3a + b] = sum over central atoms lo <= i < hi and their neighbors j of (d E_i / d d_ij)[a] * d_ij[b]
  * (fp64 [9], OVERWRITTEN; d_ij = the displacement stored in the row): the reference's "fdotr" virial

@@ -16,6 +16,10 @@ and wraps.  HIP events around each part of every iteration; medians over the ite
                                   torch.linalg.eigh, anihip_saddle_step, the evaluation and anihip_saddle_accept, on config 2's 256
                                   molecules and on the 90-atom dense90 molecule, hessian_every 1 and 5; HIP events around each
                                   part, median (fastest, slowest) over 5 repeats of 10 steps
+    python tools/geomopt_bench.py --irc [--out profiles/irc_bench.txt]
+                                  the same for a point of geomopt.ReactionPathFollower: the exact Hessian, anihip_irc_project,
+                                  torch.linalg.eigh, anihip_irc_step, the evaluation and anihip_irc_commit; fmax = 0 and no
+                                  energy test, so that every entry takes every point
 Bytes moved per L-BFGS step are estimated from the shapes (lbfgs_step_bytes), so that the achieved rate can be compared
 with HBM: S and Y read twice in fp32 and the fp64 m x m matrices of k_lb_solve, which outweigh S and Y for small molecules."""
 import argparse
@@ -197,6 +201,93 @@ def saddle_bench(out_path):
             f.write(text + "\n")
 
 
+IRC_PARTS = ("exact Hessian", "anihip_irc_project", "torch.linalg.eigh", "anihip_irc_step", "evaluation", "anihip_irc_commit")
+ANI2X_MASSES = (1.008, 12.011, 14.007, 15.999, 32.06, 18.998, 35.45)   # H C N O S F Cl, the element indices of ANI-2x
+
+
+def irc_parts(model, sp, x, hessian_every, repeats=5, steps=10):
+    """ms per point of each part of ReactionPathFollower.step() (its phases _refresh_hessians, _move and _judge taken apart),
+    per repeat of `steps` points: {part: [ms per point, one per repeat]}."""
+    import ctypes
+
+    from torchani_amd import _lib
+    from torchani_amd.engine import _stream
+    from torchani_amd.geomopt import ReactionPathFollower
+
+    L = _lib.lib()
+    masses = torch.tensor(ANI2X_MASSES + (0.0,), dtype=torch.float64, device=sp.device)[sp]
+    total = hessian_every + 1 + repeats * steps
+    opt = ReactionPathFollower(model, sp, x, masses=masses, hessian_every=hessian_every, step=0.02, max_points=total + 1,
+                               fmax=0.0, energy_floor=1e30)
+    for _ in range(hessian_every + 1):   # (warm-up: every shape once, the automatic HIP graph captured)
+        opt.step()
+    torch.cuda.synchronize()
+    out = {part: [] for part in IRC_PARTS + ("whole point",)}
+    st = opt._state
+    for _ in range(repeats):
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(7)] for _ in range(steps)]
+        for k in range(steps):
+            ev[k][0].record()
+            opt._refresh_hessians()
+            ev[k][1].record()
+            _lib.check(L.anihip_irc_project(_stream(), ctypes.byref(st), opt._projected.data_ptr()))
+            ev[k][2].record()
+            lam, V = torch.linalg.eigh(opt._projected)
+            lam, V = lam.contiguous(), V.contiguous()
+            ev[k][3].record()
+            _lib.check(L.anihip_irc_step(_stream(), ctypes.byref(st), lam.data_ptr(), V.data_ptr()))
+            ev[k][4].record()
+            e, f = opt._model_eval(opt.coordinates)
+            e, f = e.to(torch.float64).contiguous(), f.to(torch.float32).contiguous()
+            ev[k][5].record()
+            _lib.check(L.anihip_irc_commit(_stream(), ctypes.byref(st), e.data_ptr(), f.data_ptr(),
+                                           int((opt._calls + 1) % hessian_every != 0)))
+            opt._calls += 1
+            ev[k][6].record()
+        torch.cuda.synchronize()
+        for i, part in enumerate(IRC_PARTS):
+            out[part].append(sum(ev[k][i].elapsed_time(ev[k][i + 1]) for k in range(steps)) / steps)
+        out["whole point"].append(sum(ev[k][0].elapsed_time(ev[k][6]) for k in range(steps)) / steps)
+    opt.raise_on_overflow()
+    opt.raise_on_status()
+    out["points"] = opt.n_points.cpu().tolist()
+    assert min(out["points"]) == total, "an entry stopped early"
+    return out
+
+
+def irc_bench(out_path):
+    from torchani_amd.models import ANI2x
+
+    dev = torch.device("cuda:0")
+    cases = []
+    with np.load(os.path.join(GOLD, "cfg2_xyz13_28_ani2x.npz")) as z:
+        cases.append(("config 2: 256 molecules, A = 28 (3A = 84)", z["species"].astype(np.int64), z["coords"]))
+    with np.load(os.path.join(GOLD, "dense90_ani2x.npz")) as z:
+        cases.append(("dense90: 1 molecule, A = 90 (3A = 270)", z["species"].astype(np.int64), z["coords"]))
+    lines = ["tools/geomopt_bench.py --irc: ms per point (step()) of geomopt.ReactionPathFollower, HIP events around each part, "
+             "median (fastest, slowest) over 5 repeats of 10 points; seeded ANI-2x x 8, step 0.02, fmax = 0, no energy test"]
+    for name, sp, x in cases:
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist="batch")
+        for h in (1, 5):
+            r = irc_parts(model, torch.from_numpy(sp).to(dev), torch.from_numpy(x).to(dev), h)
+            whole = np.median(r["whole point"])
+            lines.append(f"{name}, hessian_every {h}: whole point {whole:.3f} ({min(r['whole point']):.3f}, "
+                         f"{max(r['whole point']):.3f}) ms")
+            new = 0.0
+            for part in IRC_PARTS:
+                v = r[part]
+                lines.append(f"  {part:22s} {np.median(v):8.4f} ({min(v):.4f}, {max(v):.4f})  {100 * np.median(v) / whole:5.1f} %")
+                if part.startswith("anihip_irc"):
+                    new += np.median(v)
+            lines.append(f"  the three new entry points together: {new:.4f} ms = {100 * new / whole:.1f} % of the point")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 def trace_summary(path, skip=101):
     """Median duration (us) of each k_lb_* kernel over its calls after the first `skip`, and their sum."""
     import collections
@@ -219,6 +310,7 @@ def main():
     ap.add_argument("--trace-summary", default=None, metavar="CSV")
     ap.add_argument("--constraints", action="store_true")
     ap.add_argument("--saddle", action="store_true")
+    ap.add_argument("--irc", action="store_true")
     ap.add_argument("--out", default=None, metavar="TXT")
     args = ap.parse_args()
     if args.trace_summary:
@@ -226,6 +318,9 @@ def main():
         return
     if args.saddle:
         saddle_bench(args.out)
+        return
+    if args.irc:
+        irc_bench(args.out)
         return
     assert args.iters > 101, "the history is full from iteration 101 on"
     from torchani_amd.models import ANI2x

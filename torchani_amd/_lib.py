@@ -14,8 +14,8 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "geom_constraints.hip", "saddle.hip"]
-HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", os.path.join("..", "..", "include", "anihip.h")]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "geom_constraints.hip", "saddle.hip", "irc.hip"]
+HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", "saddle_common.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
 MAX_SPECIES = 8
@@ -61,6 +61,8 @@ GEOM_MAX_CONSTRAINTS = 8   # ANIHIP_GEOM_MAX_CONSTRAINTS
 GEOM_BAD_TABLE, GEOM_SINGULAR, GEOM_NOT_CONVERGED = 1, 2, 4   # ANIHIP_GEOM_*
 SADDLE_MAX_COORDS = 768   # ANIHIP_SADDLE_MAX_COORDS
 SADDLE_BAD_TABLE, SADDLE_NONFINITE, SADDLE_NO_BRACKET = 1, 2, 4   # ANIHIP_SADDLE_*
+IRC_BAD_TABLE, IRC_NONFINITE, IRC_NO_ROOT = 1, 2, 4   # ANIHIP_IRC_* (status bits)
+IRC_RUNNING, IRC_MINIMUM, IRC_ENERGY_ROSE, IRC_PATH_FULL = 0, 1, 2, 3   # ANIHIP_IRC_* (reasons; 0: not done)
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -199,6 +201,17 @@ class Saddle(C.Structure):
                 ("hessians", C.c_void_p), ("trust_radii", C.c_void_p), ("eigenvalues", C.c_void_p), ("modes", C.c_void_p),
                 ("last_step", C.c_void_p), ("accepted", C.c_void_p), ("converged", C.c_void_p), ("n_steps", C.c_void_p),
                 ("n_rejected", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class Irc(C.Structure):
+    """anihip_irc (include/anihip.h)."""
+    _fields_ = [("n_mol", C.c_int32), ("atoms_per_mol", C.c_int32), ("periodic", C.c_int32), ("max_points", C.c_int32),
+                ("step", C.c_double), ("fmax", C.c_double), ("energy_floor", C.c_double),
+                ("kind", C.c_void_p), ("masses", C.c_void_p), ("coords", C.c_void_p), ("energies", C.c_void_p),
+                ("forces", C.c_void_p), ("hessians", C.c_void_p), ("direction", C.c_void_p), ("last_step", C.c_void_p),
+                ("arc_lengths", C.c_void_p), ("n_points", C.c_void_p), ("reason", C.c_void_p), ("status", C.c_void_p),
+                ("path_coords", C.c_void_p), ("path_energies", C.c_void_p), ("path_arcs", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 class MlpShape(C.Structure):
@@ -386,6 +399,13 @@ def lib() -> C.CDLL:
     L.anihip_saddle_accept.argtypes = [vp, C.POINTER(Saddle), vp, vp, i32]
     for name in ("anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept"):
         getattr(L, name).restype = C.c_int
+    L.anihip_irc_workspace_bytes.restype = sz
+    L.anihip_irc_workspace_bytes.argtypes = [i64, i64]
+    L.anihip_irc_project.argtypes = [vp, C.POINTER(Irc), vp]
+    L.anihip_irc_step.argtypes = [vp, C.POINTER(Irc), vp, vp]
+    L.anihip_irc_commit.argtypes = [vp, C.POINTER(Irc), vp, vp, i32]
+    for name in ("anihip_irc_project", "anihip_irc_step", "anihip_irc_commit"):
+        getattr(L, name).restype = C.c_int
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
@@ -430,6 +450,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_sites_workspace_bytes", "anihip_md_sites_gather", "anihip_md_sites_spread",
     "anihip_geom_constraints_project", "anihip_geom_constraints_restore",
     "anihip_saddle_workspace_bytes", "anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept",
+    "anihip_irc_workspace_bytes", "anihip_irc_project", "anihip_irc_step", "anihip_irc_commit",
 ]
 
 

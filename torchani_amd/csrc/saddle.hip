@@ -14,21 +14,11 @@
 //   k_sd_bofill   blocks of 16 rows: the rank-two update, a streaming pass over [C][n][n]
 //
 // No atomics and every sum in a fixed order: bit-identical run to run.  A frozen entry (converged, or with a status bit) costs
-// an early exit in every kernel.
-#include "anihip_common.h"
+// an early exit in every kernel.  The Gram-Schmidt, the rank-12 correction and the two Bofill passes are device functions of
+// saddle_common.h, which irc.hip shares.
+#include "saddle_common.h"
 
 namespace anihip {
-
-constexpr int SD_THREADS = 256;
-constexpr int SD_WAVES = SD_THREADS / WAVE;
-constexpr int SD_ROWS = 16;                       // rows per workgroup of the streaming passes
-constexpr int SD_MAX_N = ANIHIP_SADDLE_MAX_COORDS;
-constexpr int SD_PER_LANE = SD_MAX_N / WAVE;      // coordinates per lane of wave 0
-constexpr int SD_Q = 6;
-constexpr double SD_RANK_TOL = 1e-8;
-static_assert(SD_MAX_N % WAVE == 0, "whole lanes");
-
-static inline size_t sd_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct SdLayout {
     int64_t n;
@@ -75,27 +65,6 @@ struct SdArgs {
     const double *e_new;       // accept
     const float *f_new;
 };
-
-__device__ __forceinline__ double sd_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ double sd_wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
-__device__ __forceinline__ double sd_wave_min(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off));
-    return v;
-}
 
 __device__ __forceinline__ bool sd_frozen(const SdArgs &a, int64_t c) { return a.converged[c] != 0 || a.status[c] != 0; }
 
@@ -179,51 +148,8 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_basis(SdArgs a)
 #pragma unroll
             for (int j = 0; j < SD_Q; ++j) s_q[j][d] = v[j];
         }
-        // classical Gram-Schmidt, twice, against the vectors kept so far (a dropped one is zero and takes nothing away)
-        for (int j = 0; j < SD_Q; ++j) {
-            double len2 = 0.0;
-#pragma unroll
-            for (int m = 0; m < SD_PER_LANE; ++m) len2 = fma(s_q[j][lane + WAVE * m], s_q[j][lane + WAVE * m], len2);
-            len2 = sd_wave_sum(len2);
-            for (int pass = 0; pass < 2; ++pass) {
-                double dot[SD_Q];
-                for (int l = 0; l < j; ++l) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int m = 0; m < SD_PER_LANE; ++m) acc = fma(s_q[l][lane + WAVE * m], s_q[j][lane + WAVE * m], acc);
-                    dot[l] = sd_wave_sum(acc);
-                }
-                for (int l = 0; l < j; ++l) {
-#pragma unroll
-                    for (int m = 0; m < SD_PER_LANE; ++m) s_q[j][lane + WAVE * m] -= dot[l] * s_q[l][lane + WAVE * m];
-                }
-            }
-            double rem2 = 0.0;
-#pragma unroll
-            for (int m = 0; m < SD_PER_LANE; ++m) rem2 = fma(s_q[j][lane + WAVE * m], s_q[j][lane + WAVE * m], rem2);
-            rem2 = sd_wave_sum(rem2);
-            const bool keep = rem2 > SD_RANK_TOL * SD_RANK_TOL * len2;
-            const double sc = keep ? 1.0 / sqrt(rem2) : 0.0;
-#pragma unroll
-            for (int m = 0; m < SD_PER_LANE; ++m) s_q[j][lane + WAVE * m] *= sc;
-        }
-        // gproj = P g
-        double dot[SD_Q];
-        for (int l = 0; l < SD_Q; ++l) {
-            double acc = 0.0;
-#pragma unroll
-            for (int m = 0; m < SD_PER_LANE; ++m) acc = fma(s_q[l][lane + WAVE * m], g[m], acc);
-            dot[l] = sd_wave_sum(acc);
-        }
-#pragma unroll
-        for (int m = 0; m < SD_PER_LANE; ++m) {
-            const int64_t d = lane + WAVE * m;
-            if (d >= n) continue;
-            double v = g[m];
-            for (int l = 0; l < SD_Q; ++l) v -= dot[l] * s_q[l][d];
-            gp[d] = v;
-            for (int l = 0; l < SD_Q; ++l) gq[l * n + d] = s_q[l][d];
-        }
+        sd_gram_schmidt(s_q, lane);
+        sd_project_gradient(s_q, g, lane, n, gp, gq);   // gproj = P g
     }
     __syncthreads();
 
@@ -257,28 +183,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_basis(SdArgs a)
         return;
     }
     const double mu = 1.0 + rowmax;
-    // M = Q^T W, one wave per element
-    for (int p = wave; p < SD_Q * SD_Q; p += SD_WAVES) {
-        const int l = p / SD_Q, m = p % SD_Q;
-        double acc = 0.0;
-        for (int64_t k = lane; k < n; k += WAVE) acc = fma(s_q[l][k], gb[m * n + k], acc);
-        acc = sd_wave_sum(acc);
-        if (lane == 0) s_m[l][m] = acc;
-    }
-    __syncthreads();
-    // B = W - Q (M + M^T) / 4 - mu Q / 2:  P H P + mu Q Q^T = D H D - Q B^T - B Q^T
-    for (int64_t d = tid; d < n; d += SD_THREADS) {
-        double w[SD_Q];
-#pragma unroll
-        for (int l = 0; l < SD_Q; ++l) w[l] = gb[l * n + d];
-#pragma unroll
-        for (int l = 0; l < SD_Q; ++l) {
-            double v = w[l] - 0.5 * mu * s_q[l][d];
-#pragma unroll
-            for (int m = 0; m < SD_Q; ++m) v -= 0.25 * (s_m[m][l] + s_m[l][m]) * s_q[m][d];
-            gb[l * n + d] = v;
-        }
-    }
+    sd_rank12_correction(s_q, s_m, gb, mu, n, tid, lane, wave);
     if (tid == 0) a.scal[c * 8 + SC_MU] = mu;
 }
 
@@ -293,22 +198,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_project(SdArgs a, int64_t blo
     const double mu = a.scal[c * 8 + SC_MU];
     const double *H = a.H + c * n * n;
     double *out = a.projected + c * n * n;
-    for (int r = wave; r < SD_ROWS; r += SD_WAVES) {
-        const int64_t i = rb * SD_ROWS + r;
-        if (i >= n) break;
-        const bool ai = kind[i / 3] == 1;
-        double qi[SD_Q], bi[SD_Q];
-#pragma unroll
-        for (int l = 0; l < SD_Q; ++l) qi[l] = gq[l * n + i], bi[l] = gb[l * n + i];
-        for (int64_t k = lane; k < n; k += WAVE) {
-            const bool ak = kind[k / 3] == 1;
-            double v = ai && ak ? H[i * n + k] : 0.0;
-            if (i == k && !ai) v = mu;
-#pragma unroll
-            for (int l = 0; l < SD_Q; ++l) v -= qi[l] * gb[l * n + k] + bi[l] * gq[l * n + k];
-            out[i * n + k] = v;
-        }
-    }
+    sd_project_rows(kind, gq, gb, mu, H, nullptr, out, n, rb, lane, wave);
 }
 
 __global__ __launch_bounds__(SD_THREADS) void k_sd_step(SdArgs a)
@@ -512,36 +402,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_accept(SdArgs a)
         for (int64_t d = tid; d < SD_MAX_N; d += SD_THREADS) s_s[d] = d < n ? a.disp[c * n + d] : 0.0, s_xi[d] = 0.0;
         __syncthreads();
         const double *H = a.H + c * n * n;
-        for (int64_t i = wave; i < n; i += SD_WAVES) {
-            if (kind[i / 3] != 1) continue;   // (wave-uniform)
-            double acc = 0.0;
-            for (int64_t k = lane; k < n; k += WAVE) acc = fma(H[i * n + k], s_s[k], acc);
-            acc = sd_wave_sum(acc);
-            if (lane == 0) s_xi[i] = ((double)f[i] - (double)fn[i]) - acc;   // y = g' - g = f - f'
-        }
-        __syncthreads();
-        if (wave == 0) {
-            double xs = 0.0, xx = 0.0, ss = 0.0;
-#pragma unroll
-            for (int m = 0; m < SD_PER_LANE; ++m) {
-                const double s = s_s[lane + WAVE * m], xi = s_xi[lane + WAVE * m];
-                xs = fma(xi, s, xs), xx = fma(xi, xi, xx), ss = fma(s, s, ss);
-            }
-            xs = sd_wave_sum(xs), xx = sd_wave_sum(xx), ss = sd_wave_sum(ss);
-            if (lane == 0) {
-                const bool upd = xx > 0.0 && ss > 0.0 && isfinite(xx) && isfinite(ss);
-                double c1 = 0.0, c2 = 0.0, c3 = 0.0;
-                if (upd) {
-                    const double phi = xs == 0.0 ? 0.0 : xs * xs / (xx * ss);
-                    c1 = xs == 0.0 ? 0.0 : phi / xs;
-                    c2 = (1.0 - phi) / ss;
-                    c3 = (1.0 - phi) * xs / (ss * ss);
-                }
-                scal[SC_C1] = c1, scal[SC_C2] = c2, scal[SC_C3] = c3, scal[SC_UPDATE] = upd ? 1.0 : 0.0;
-            }
-        }
-        for (int64_t d = tid; d < n; d += SD_THREADS) a.xi[c * n + d] = s_xi[d];
-        __syncthreads();   // (the old forces were read above)
+        sd_bofill_scalars(kind, H, f, fn, s_s, s_xi, a.xi + c * n, scal + SC_C1, n, tid, lane, wave);
     } else if (tid == 0) {
         scal[SC_UPDATE] = 0.0;
     }
@@ -565,18 +426,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_bofill(SdArgs a, int64_t bloc
     const double c1 = scal[SC_C1], c2 = scal[SC_C2], c3 = scal[SC_C3];
     const double *s = a.disp + c * n, *xi = a.xi + c * n;
     double *H = a.H + c * n * n;
-    for (int r = wave; r < SD_ROWS; r += SD_WAVES) {
-        const int64_t i = rb * SD_ROWS + r;
-        if (i >= n) break;
-        const double si = s[i], xii = xi[i];
-        for (int64_t k = lane; k < n; k += WAVE) {
-            const double sk = s[k], xik = xi[k];
-            // each term is symmetric in i and k bit for bit: contraction is off in this kernel, since a fused multiply-add
-            // would round xi_i s_k + s_i xi_k differently from xi_k s_i + s_k xi_i
-            const double up = (c1 * (xii * xik) + c2 * (xii * sk + si * xik)) - c3 * (si * sk);
-            H[i * n + k] = H[i * n + k] + up;
-        }
-    }
+    sd_bofill_rows(H, s, xi, c1, c2, c3, n, rb, lane, wave);
 }
 
 static int sd_args(const anihip_saddle *state, SdArgs &a, int64_t &C)

@@ -29,6 +29,10 @@ the slope of the relaxed energy along the targets, dE* / dt_k = -lambda_k.
 ``SaddleOptimizer`` / ``optimize_saddle`` search first-order saddle points (transition states) of a batch by partitioned
 rational-function optimization on the analytic Hessian with Bofill updates (csrc/saddle.hip); ``descend_from_saddle`` relaxes
 both sides of every saddle to the minima it connects.  Its class docstring has the step.
+
+``ReactionPathFollower`` / ``follow_reaction_path`` trace the intrinsic reaction coordinate from every saddle to both sides: the
+steepest-descent path in mass-weighted coordinates by the local quadratic approximation on the same model Hessian
+(csrc/irc.hip), the points of every path kept on the device.
 """
 from __future__ import annotations
 
@@ -42,7 +46,7 @@ from torch import Tensor
 from . import _lib
 from .engine import _stream
 from .md_bias import CV, _CV_NAMES, _per_entry, has_sites
-from .tuples import OptimizedGeometries, OptimizedSaddles, TorsionScan
+from .tuples import OptimizedGeometries, OptimizedSaddles, ReactionPaths, TorsionScan
 from .units import HARTREE_TO_EV
 from .utils import pbc_tuple
 
@@ -648,6 +652,17 @@ def _check_saddle_model(model) -> None:
                            "that are being trained is not meaningful")
 
 
+def _exact_hessians(model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor], pbc) -> Tensor:
+    """fp64 [C, 3A, 3A]: the symmetrized analytic Hessian at the coordinates (the direction loop of
+    ``grad.energies_forces_and_hessians``)."""
+    from . import grad
+
+    x = coordinates.clone()
+    inp = grad._second_order_inputs(model, species, x, cell, pbc, "Hessians")
+    H = grad._dense_hessian_columns(inp, x.device).to(torch.float64)
+    return 0.5 * (H + H.transpose(1, 2))
+
+
 class SaddleOptimizer:
     """Search for a first-order saddle point (a transition state) of every molecule of species [C, A], coordinates [C, A, 3]
     (Angstrom; energies in Hartree): partitioned rational-function optimization (P-RFO, Baker 1986) on a dense model Hessian
@@ -745,12 +760,7 @@ class SaddleOptimizer:
 
     def _exact_hessians(self) -> Tensor:
         """fp64 [C, 3A, 3A]: the symmetrized analytic Hessian at the current coordinates."""
-        from . import grad
-
-        x = self.coordinates.clone()
-        inp = grad._second_order_inputs(self.model, self.species, x, self.cell, self._pbc_arg, "Hessians")
-        H = grad._dense_hessian_columns(inp, x.device).to(torch.float64)
-        return 0.5 * (H + H.transpose(1, 2))
+        return _exact_hessians(self.model, self.species, self.coordinates, self.cell, self._pbc_arg)
 
     def _project(self, state: "_lib.Saddle", projected: Tensor) -> None:
         _lib.check(_lib.lib().anihip_saddle_project(_stream(), C.byref(state), projected.data_ptr()))
@@ -882,3 +892,225 @@ def descend_from_saddle(model, species: Tensor, saddles: OptimizedSaddles, delta
         kw["fixed"] = kw["fixed"].repeat(2, 1)
     out = optimize_geometry(model, species.repeat(2, 1), torch.cat([x + d, x - d]), **kw)
     return (OptimizedGeometries(*(t[:Cn] for t in out)), OptimizedGeometries(*(t[Cn:] for t in out)))
+
+
+def irc_workspace_bytes(n_mol: int, atoms_per_mol: int) -> int:
+    """Bytes of the path follower's device workspace: the layout of csrc/irc.hip (irc_layout), computed on the host."""
+    if n_mol < 1 or atoms_per_mol < 1 or 3 * atoms_per_mol > SADDLE_MAX_COORDS:
+        raise ValueError(f"n_mol and atoms_per_mol must be >= 1 and 3 atoms_per_mol <= {SADDLE_MAX_COORDS}")
+    Cn, n = int(n_mol), 3 * int(atoms_per_mol)
+    regions = [Cn * 6 * n * 8, Cn * 6 * n * 8, Cn * n * 8, Cn * n * 8, Cn * n * 8, Cn * n * 8, Cn * n * 4, Cn * 8 * 8]
+    return sum(-(-r // 256) * 256 for r in regions)
+
+
+IRC_REASONS = {_lib.IRC_RUNNING: "running", _lib.IRC_MINIMUM: "minimum", _lib.IRC_ENERGY_ROSE: "energy rose",
+               _lib.IRC_PATH_FULL: "path full"}
+_IRC_STATUS = ((_lib.IRC_BAD_TABLE, "the atom table or a mass is out of range"),
+               (_lib.IRC_NONFINITE, "a force, energy, Hessian entry, eigenvalue or step is not finite"),
+               (_lib.IRC_NO_ROOT, "the time of the arc length was not found"))
+
+
+class ReactionPathFollower:
+    """Follow the intrinsic reaction coordinate (IRC) of every entry of species [C, A], coordinates [C, A, 3] (Angstrom;
+    energies in Hartree, masses in amu): the steepest-descent path in mass-weighted coordinates q = M^1/2 x, integrated in
+    points of arc length ``step`` (Angstrom amu^1/2) by the local quadratic approximation (LQA, Page & McIver 1988) on a dense
+    model Hessian that is the analytic one every ``hessian_every`` calls of ``step()`` and is updated by the Bofill formula in
+    between.  The whole batch advances at once; the per-molecule arithmetic is fp64 in libanihip (csrc/irc.hip; include/anihip.h
+    has the definition).
+
+    One ``step()``, per entry that is neither done nor stopped by a status bit:
+
+    1. on calls 0, h, 2h, ... the model Hessian becomes the exact, symmetrized one;
+    2. the mass-weighted Hessian and gradient are projected onto the complement of the inactive coordinates (padding,
+       ``fixed``), of the translations (when the entry has no fixed atom) and of the rotations (when in addition nothing is
+       periodic);
+    3. ``torch.linalg.eigh`` of the projected Hessians in fp64: the one place every point may synchronize with the host;
+    4. the first point of an entry with a ``direction`` [C, A, 3] (a Cartesian vector, such as ``OptimizedSaddles.modes``) is
+       ``step`` along the lowest mode, to the side of the direction.  Every other point follows the steepest-descent path of
+       the quadratic model for the arc length ``step``, or to the model's minimum if that is nearer;
+    5. one evaluation at the moved coordinates.  If the energy rose by more than ``energy_floor`` the point is dropped, the
+       coordinates are restored and the entry is done (reason "energy rose": the step is too long for the valley); else the
+       point is appended to the path, and the entry is done when max |f_i| < ``fmax`` over the free atoms (reason "minimum")
+       or its ``max_points`` are used up (reason "path full").
+
+    There is no step-size control and no corrector: halve ``step`` for a more accurate path.  The limits are SaddleOptimizer's:
+    3A is at most SADDLE_MAX_COORDS, no constraints on internal coordinates, external neighbor lists, variable cells, D3 or
+    trainable networks.
+
+    Attributes (device tensors): ``coordinates`` (fp32, in place), ``energies`` [C], ``forces`` [C, A, 3], ``hessians`` (fp64
+    [C, 3A, 3A]), ``last_step`` (fp32), ``arc_lengths`` [C], ``n_points``, ``reasons`` (IRC_REASONS), ``n_hessians``, ``status``
+    (int32 [C]), ``path_coordinates`` [C, max_points, A, 3] (fp32), ``path_energies``, ``path_arc_lengths`` [C, max_points].
+    """
+
+    def __init__(self, model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None, pbc=None, *,
+                 masses: tp.Optional[Tensor] = None, direction: tp.Optional[Tensor] = None, step: float = 0.05,
+                 max_points: int = 128, hessian_every: int = 5, fmax: float = DEFAULT_FMAX, energy_floor: float = 1e-7,
+                 fixed: tp.Optional[Tensor] = None, constraints=None, neighbors=None) -> None:
+        _check_saddle_args(species, coordinates, fixed, None, "lowest", hessian_every, 1.0, 1.0, 1.0, energy_floor,
+                           constraints, neighbors)
+        if direction is not None and tuple(direction.shape) != tuple(coordinates.shape):
+            raise ValueError(f"direction must have the shape of the coordinates {tuple(coordinates.shape)}, got "
+                             f"{tuple(direction.shape)}")
+        if not (math.isfinite(step) and step > 0):
+            raise ValueError(f"step must be a finite arc length > 0 (Angstrom amu^1/2), got {step}")
+        if isinstance(max_points, bool) or int(max_points) != max_points or max_points < 1:
+            raise ValueError(f"max_points must be an integer >= 1, got {max_points}")
+        if not fmax >= 0:
+            raise ValueError(f"fmax must be >= 0, got {fmax}")
+        if masses is not None and tuple(masses.shape) != tuple(species.shape):
+            raise ValueError(f"masses must have the shape of species {tuple(species.shape)}, got {tuple(masses.shape)}")
+        _check_saddle_model(model)
+        if not (species.is_cuda and coordinates.is_cuda):
+            raise ValueError("ReactionPathFollower needs tensors on a ROCm device (no CPU fallback)")
+        if masses is None:
+            from .md import default_masses
+
+            masses = default_masses(model, species)
+        dev = coordinates.device
+        Cn, A = species.shape
+        n = 3 * A
+        self._model_eval = ModelEvaluator(model, species, cell, pbc)
+        self.model, self.species, self.cell, self.pbc = model, species, cell, self._model_eval.pbc
+        self._pbc_arg = pbc
+        self._dtype = coordinates.dtype
+        self.hessian_every, self.max_points = int(hessian_every), int(max_points)
+        self.coordinates = coordinates.detach().to(torch.float32).clone().contiguous()
+        kind = (species >= 0).to(torch.uint8)
+        if fixed is not None:
+            kind = kind + ((species >= 0) & fixed.to(device=dev, dtype=torch.bool)).to(torch.uint8)
+        self._kind = kind.contiguous()   # 0: padding, 1: free, 2: fixed
+        self.masses = masses.detach().to(device=dev, dtype=torch.float64).contiguous()
+        self._direction = None if direction is None else direction.detach().to(device=dev, dtype=torch.float64).contiguous()
+        self.hessians = torch.zeros((Cn, n, n), dtype=torch.float64, device=dev)
+        # (a frozen entry's projected Hessian is never written: the eigensolver still sees a matrix)
+        self._projected = torch.eye(n, dtype=torch.float64, device=dev).repeat(Cn, 1, 1)
+        self.last_step = torch.zeros_like(self.coordinates)
+        self.arc_lengths = torch.zeros(Cn, dtype=torch.float64, device=dev)
+        self.n_points = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.reasons = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.n_hessians = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(Cn, dtype=torch.int32, device=dev)
+        self.path_coordinates = torch.full((Cn, self.max_points, A, 3), math.nan, dtype=torch.float32, device=dev)
+        self.path_energies = torch.full((Cn, self.max_points), math.nan, dtype=torch.float64, device=dev)
+        self.path_arc_lengths = torch.full((Cn, self.max_points), math.nan, dtype=torch.float64, device=dev)
+        self._workspace = torch.zeros(irc_workspace_bytes(Cn, A), dtype=torch.uint8, device=dev)
+        self._calls = 0
+        e, f = self._model_eval(self.coordinates)
+        self.energies, self.forces = e.to(torch.float64).clone(), f.to(torch.float32).clone().contiguous()
+        self.start_coordinates, self.start_energies = self.coordinates.clone(), self.energies.clone()
+        periodic = cell is not None and any(self.pbc)
+        self._state = _lib.Irc(
+            Cn, A, int(periodic), self.max_points, float(step), float(fmax), float(energy_floor), self._kind.data_ptr(),
+            self.masses.data_ptr(), self.coordinates.data_ptr(), self.energies.data_ptr(), self.forces.data_ptr(),
+            self.hessians.data_ptr(), None if self._direction is None else self._direction.data_ptr(),
+            self.last_step.data_ptr(), self.arc_lengths.data_ptr(), self.n_points.data_ptr(), self.reasons.data_ptr(),
+            self.status.data_ptr(), self.path_coordinates.data_ptr(), self.path_energies.data_ptr(),
+            self.path_arc_lengths.data_ptr(), self._workspace.data_ptr(), self._workspace.numel())
+
+    @property
+    def done(self) -> Tensor:
+        """bool [C]: the entries that take no further points."""
+        return (self.reasons != 0) | (self.status != 0)
+
+    def _refresh_hessians(self) -> None:
+        """On calls 0, h, 2h, ...: the model Hessian of every entry that is not done becomes the exact one."""
+        if self._calls % self.hessian_every == 0:
+            H = _exact_hessians(self.model, self.species, self.coordinates, self.cell, self._pbc_arg)
+            done = self.done
+            self.hessians.copy_(torch.where(done.view(-1, 1, 1), self.hessians, H))
+            self.n_hessians += (~done).to(torch.int32)
+
+    def _move(self) -> None:
+        """The projection, the eigensolver and the first point or the LQA step: the coordinates moved."""
+        st = self._state
+        _lib.check(_lib.lib().anihip_irc_project(_stream(), C.byref(st), self._projected.data_ptr()))
+        lam, V = torch.linalg.eigh(self._projected)
+        lam, V = lam.contiguous(), V.contiguous()
+        _lib.check(_lib.lib().anihip_irc_step(_stream(), C.byref(st), lam.data_ptr(), V.data_ptr()))
+
+    def _judge(self) -> None:
+        """The evaluation at the moved coordinates (kept as ``trial_energies``, ``trial_forces``), then the commit, and the
+        Bofill update unless the next call brings an exact Hessian."""
+        e, f = self._model_eval(self.coordinates)
+        self.trial_energies, self.trial_forces = e.to(torch.float64).contiguous(), f.to(torch.float32).contiguous()
+        update = int((self._calls + 1) % self.hessian_every != 0)
+        _lib.check(_lib.lib().anihip_irc_commit(_stream(), C.byref(self._state), self.trial_energies.data_ptr(),
+                                                self.trial_forces.data_ptr(), update))
+        self._calls += 1
+
+    def step(self) -> None:
+        """One point as described in the class docstring."""
+        self._refresh_hessians()
+        self._move()
+        self._judge()
+
+    def raise_on_overflow(self) -> None:
+        """Raise if a neighbor row of the last evaluation overflowed (one host synchronization)."""
+        self._model_eval.raise_on_overflow()
+
+    def raise_on_status(self) -> None:
+        """Raise if the kernels stopped an entry: a table out of range, a value that is not finite, an arc length whose time
+        was not found (one host synchronization)."""
+        status = self.status.cpu()
+        if not bool(status.any()):
+            return
+        c = int(status.nonzero()[0])
+        what = [name for bit, name in _IRC_STATUS if int(status[c]) & bit]
+        raise RuntimeError(f"ReactionPathFollower: entry {c}: {'; '.join(what)}")
+
+    def run(self, steps: tp.Optional[int] = None, check_every: int = 10) -> None:
+        """At most ``steps`` calls of ``step()`` (default: ``max_points``, which ends every entry) until every entry is done.
+        The host reads the reasons, the status words and the overflow status every ``check_every`` calls and after the last."""
+        steps = self.max_points if steps is None else steps
+        if steps < 0 or check_every < 1:
+            raise ValueError("steps must be >= 0 and check_every >= 1")
+        for k in range(steps):
+            self.step()
+            if (k + 1) % check_every == 0 or k + 1 == steps:
+                self.raise_on_overflow()
+                self.raise_on_status()
+                if bool((self.reasons != 0).all()):
+                    break
+
+    def result(self) -> tp.Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        """Copies of the paths so far: coordinates [C, max_points, A, 3] in the input dtype, energies and arc lengths
+        [C, max_points] (NaN beyond ``n_points``), n_points and reasons [C]."""
+        return (self.path_coordinates.to(self._dtype, copy=True), self.path_energies.clone(), self.path_arc_lengths.clone(),
+                self.n_points.clone(), self.reasons.clone())
+
+
+def follow_reaction_path(model, species: Tensor, saddles: OptimizedSaddles, cell: tp.Optional[Tensor] = None, pbc=None,
+                         **kw) -> ReactionPaths:
+    """The reaction path through every saddle of ``saddles``: forward (along ``saddles.modes``) and backward as one batch of 2C
+    entries of ``ReactionPathFollower`` (its keywords; ``steps=`` and ``check_every=`` go to ``run``).  Every saddle must be
+    ``converged`` with ``n_negative == 1``."""
+    run_kw = {k: kw.pop(k) for k in ("steps", "check_every") if k in kw}
+    if "direction" in kw:
+        raise ValueError("follow_reaction_path takes the directions from saddles.modes")
+    ok = (saddles.converged & (saddles.n_negative == 1)).cpu()
+    if not bool(ok.all()):
+        c = int((~ok).nonzero()[0])
+        raise ValueError(f"entry {c} is not a first-order saddle point: converged {bool(saddles.converged[c])}, n_negative "
+                         f"{int(saddles.n_negative[c])} (follow_reaction_path starts from converged saddles with one negative "
+                         "eigenvalue)")
+    x = saddles.coordinates
+    Cn, A = species.shape
+    for name in ("masses", "fixed"):
+        if kw.get(name) is not None:
+            kw[name] = kw[name].repeat(2, 1)
+    follower = ReactionPathFollower(model, species.repeat(2, 1), torch.cat([x, x]), cell, pbc,
+                                    direction=torch.cat([saddles.modes, -saddles.modes]), **kw)
+    follower.run(**run_kw)
+    xs, es, arcs, n_points, reasons = follower.result()
+    P = follower.max_points
+    nan = math.nan
+    coordinates = torch.full((Cn, 2 * P + 1, A, 3), nan, dtype=xs.dtype, device=x.device)
+    energies = torch.full((Cn, 2 * P + 1), nan, dtype=torch.float64, device=x.device)
+    arc_lengths = torch.full((Cn, 2 * P + 1), nan, dtype=torch.float64, device=x.device)
+    coordinates[:, P] = follower.start_coordinates[:Cn].to(xs.dtype)
+    energies[:, P] = follower.start_energies[:Cn]
+    arc_lengths[:, P] = 0.0
+    coordinates[:, P + 1:], energies[:, P + 1:], arc_lengths[:, P + 1:] = xs[:Cn], es[:Cn], arcs[:Cn]
+    coordinates[:, :P], energies[:, :P], arc_lengths[:, :P] = xs[Cn:].flip(1), es[Cn:].flip(1), -arcs[Cn:].flip(1)
+    return ReactionPaths(species, coordinates, energies, arc_lengths, n_points[:Cn].clone(), n_points[Cn:].clone(),
+                         torch.stack([reasons[:Cn], reasons[Cn:]], dim=1))

@@ -144,6 +144,23 @@ class OptimizedSaddles(tp.NamedTuple):
     n_negative: Tensor
 
 
+class ReactionPaths(tp.NamedTuple):
+    """What geomopt.follow_reaction_path returns for C saddles followed for at most P = max_points points to each side:
+    coordinates [C, 2P + 1, A, 3] in the input dtype, energies and arc_lengths [C, 2P + 1] (float64; Hartree and Angstrom
+    amu^1/2).  Index P is the saddle (arc length 0); the forward points (along the saddle's ``modes``) sit at P + 1, P + 2, ...,
+    the backward points at P - 1, P - 2, ... with negative arc lengths; unused slots are NaN.  n_forward, n_backward (int32
+    [C]) count the points of each side, reasons (int32 [C, 2], forward then backward) tell why each side ended
+    (geomopt.IRC_REASONS)."""
+
+    species: Tensor
+    coordinates: Tensor
+    energies: Tensor
+    arc_lengths: Tensor
+    n_forward: Tensor
+    n_backward: Tensor
+    reasons: Tensor
+
+
 class TorsionScan(tp.NamedTuple):
     """What geomopt.torsion_scan returns for M molecules and K angles: angles [K] (rad, the targets), energies [M, K]
     (float64, Hartree) of the relaxed geometries coordinates [M, K, A, 3], converged (bool [M, K]) and torques [M, K]
