@@ -1,7 +1,9 @@
 """Batched L-BFGS geometry optimization (torchani_amd.geomopt, anihip_lbfgs_step) on the MI355X: lock-step parity of every
 step against the fp64 two-loop reference (tests/_geomopt_ref.py) on padded ANI-2x batches, a periodic box and the 46 357-atom
 solvated box; the Lennard-Jones minima of LJ13 and LJ7; the optimized LJ13 through the Hessian and vibrational analysis;
-fixed atoms, convergence checked by an independent evaluation, bit-identical runs and no host synchronization in step()."""
+fixed atoms, convergence checked by an independent evaluation, bit-identical runs and no host synchronization in step().
+The shape edges of anihip_lbfgs_step itself (every width of k_lb_dots, memory 1 and 256, ring wrap-around, an atom cut by a chunk
+boundary, hundreds of molecules in mixed states) are tested through the entry point in tests/test_gpu_lbfgs_entry.py."""
 import os
 
 import numpy as np
