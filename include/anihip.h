@@ -877,6 +877,50 @@ int anihip_md_sites_gather(void *stream, const anihip_md_params *params, const a
 int anihip_md_sites_spread(void *stream, const anihip_md_params *params, const anihip_md_sites *sites, const float *coords,
                            const float *coords_lo, const float *forces_ext, float *forces);
 
+/* Observables accumulated along a trajectory on the device (torchani_amd.md.RadialDistribution, MeanSquaredDisplacement,
+ * VelocityAutocorrelation; csrc/md_observe.hip).  Neither call reads on the host.
+ *
+ * anihip_md_rdf_accumulate adds one sample of a pair-distance histogram to `counts` from neighbor rows (meta, ent: the format
+ * above, lo = 0, of all N = n_mol atoms_per_mol atoms; ent_capacity = float4 entries that `ent` holds).  With
+ * r = sqrt(dx^2 + dy^2 + dz^2) taken in fp64 from the fp32 row entry,
+ *   counts[c][p][b] += #{row entries (i -> j): i in entry c, species[i] = a_p, species_j = b_p, r < r_max,
+ *                        floor(r (bins / r_max)) = b}
+ * (b = bins - 1 if rounding carries the product to bins), c = 0 for per_entry = 0, where the counters are [n_pairs][bins], and
+ * c = i / atoms_per_mol for per_entry = 1, [n_mol][n_pairs][bins].  pair_slot (HOST, 64 x int8) maps 8 s_i + s_j to the pair p
+ * or to -1; species (int32 [N], element indices 0 .. 7 as the rows carry them; < 0: padding, skipped).  Ordered pairs and
+ * periodic images, an atom's own image included, count once each, as the rows hold them.  n_pairs in 1 .. 8, bins in
+ * 1 .. 1024, n_pairs bins <= 8192.  One wave per central atom, lanes over its row, a histogram of uint32 in LDS per
+ * workgroup, added to `counts` (uint64) with integer atomics, non-zero bins only, whenever the workgroup's entry changes
+ * (per_entry) and at its end: integer sums, so the result does not depend on the order of arrival.  A row that the builder
+ * zeroed for overflow contributes nothing; the builder's status word says so.
+ *
+ * anihip_md_corr_accumulate takes sample k = `sample` (0, 1, ...) of a multiple-time-origin correlation over a ring of the
+ * last M = lags samples.  The atoms are named by a gather table: gather int32 [n_mol][G] (G = max_atoms), the index within
+ * its entry of the g-th atom, -1 past the entry's atoms; gather_species int32 [n_mol][G] in 0 .. n_species - 1 (anything else:
+ * the slot is skipped), sorted by species within an entry for speed, not for correctness.
+ *   ANIHIP_MD_CORR_MSD   y = (double)x[i] + (double)x_lo[i]  (x_lo NULL: 0), ring of double [M][n_mol][3][G]
+ *   ANIHIP_MD_CORR_VACF  y = x[i], ring of float [M][n_mol][3][G]
+ * The call writes y into slot k mod M and then, for every lag l = 0 .. min(k, M - 1), with y' of slot (k - l) mod M,
+ *   MSD   S[c][s][l] += sum_{g of entry c, species s} |y - y'|^2
+ *   VACF  S[c][s][l] += sum_{g of entry c, species s} y . y'        (S: double [n_mol][n_species][M], products in fp64)
+ * No atomics: one thread per gather slot, workgroups of 256 slots; per lag the terms of a species are summed over the 64
+ * lanes of a wave by a butterfly, then over the four waves in order, to workspace[c][chunk][s][l]; a second launch adds the
+ * chunks in ascending order to S.  Two calls on the same input give the same bits.  A gather index outside
+ * 0 .. atoms_per_mol - 1 is skipped.  lags in 1 .. 65536, n_species in 1 .. 8.
+ * anihip_md_corr_workspace_bytes: n_mol ceil(G / 256) n_species M doubles. */
+#define ANIHIP_MD_CORR_MSD 0
+#define ANIHIP_MD_CORR_VACF 1
+#define ANIHIP_MD_RDF_MAX_PAIRS 8
+#define ANIHIP_MD_RDF_MAX_BINS 1024
+int anihip_md_rdf_accumulate(void *stream, const anihip_md_params *params, int32_t n_pairs, int32_t bins, double r_max,
+                             int32_t per_entry, const int8_t *pair_slot, const int32_t *species, const uint32_t *meta,
+                             const float *ent, int64_t ent_capacity, uint64_t *counts);
+size_t anihip_md_corr_workspace_bytes(int64_t n_mol, int64_t max_atoms, int64_t lags, int64_t n_species);
+int anihip_md_corr_accumulate(void *stream, const anihip_md_params *params, int32_t kind, int32_t lags, int32_t n_species,
+                              int32_t max_atoms, int64_t sample, const int32_t *gather, const int32_t *gather_species,
+                              const float *x, const float *x_lo, void *ring, double *S, void *workspace,
+                              size_t workspace_bytes);
+
 /* Holonomic constraints on internal coordinates for anihip_lbfgs_step (torchani_amd.geomopt.GeometryOptimizer(constraints=),
  * csrc/geom_constraints.hip): the CVs above (ANIHIP_MD_CV_*, csrc/md_cv.h) held at targets, the way ASE's FixInternals works
  * with its LBFGS.  Relaxed scans: every grid point is an entry of the batch with its own target.  Everything is fp64 on the

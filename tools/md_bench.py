@@ -36,6 +36,10 @@
                                                                            halves of every molecule, or on the coordination number
                                                                            of all O against all H of the box (--coordination-atoms
                                                                            N: the first N of each)
+    python tools/md_bench.py --observe series trajectory rdf msd vacf [--observe-every 10] [--lags 512] --langevin --repeats 7 ...
+                                                                           observers (md.TimeSeries ... md.VelocityAutocorrelation):
+                                                                           the step with each attached against the step without,
+                                                                           the cost per sample next to the bytes it has to move
 
 --system water is the periodic water box of bench.py (3 side^3 atoms); --system molecules is BASELINE config 2's batch of 256
 molecules.  With --repeats R every (neighbor list, integrator) pair is timed R times, the integrators alternating, and the
@@ -248,6 +252,76 @@ def bench_bias(args, dev):
           f"{'separate' if apart else 'overlap: no difference can be claimed'}")
 
 
+def make_observer(name, args, cell):
+    """One observer of --observe, sampling every --observe-every steps."""
+    from torchani_amd import md as M
+
+    every = args.observe_every
+    if name == "series":
+        return M.TimeSeries(("potential", "kinetic", "temperature"), every=every, capacity=4096, on_full="wrap")
+    if name == "trajectory":
+        return M.Trajectory(every=every, capacity=8, velocities=True, on_full="wrap")
+    if name == "rdf":
+        pairs = [("O", "O"), ("O", "H")] if cell is not None else [("C", "C"), ("C", "H")]
+        return M.RadialDistribution(pairs, r_max=args.rdf_rmax, bins=200, every=every)
+    cls = M.MeanSquaredDisplacement if name == "msd" else M.VelocityAutocorrelation
+    return cls(lags=args.lags, every=every, max_bytes=1 << 36)
+
+
+def observer_bytes(name, obs, d):
+    """The bytes one sample of ``obs`` has to move, from shapes (the estimate the measured cost is held against)."""
+    n = d.species.numel()
+    if name == "series":
+        return sum(b[0].numel() * 8 * 2 for b in obs._buffers.values()), "reads and writes of the series' values"
+    if name == "trajectory":
+        return 2 * 2 * n * 3 * 4, "coordinates and velocities read and written once"
+    if name == "rdf":   # the rows of the current coordinates, read once; the build that writes them is in the cost, not in the bytes
+        rows = obs._engine.neighbors(obs._species32, d.coordinates, d.cell, d.pbc, mode=obs._mode, row_cap=256)
+        entries = int(((rows.meta[:, 1] & 0xFFFF) + ((rows.meta[:, 1] >> 16) & 0xFFFF)).sum())
+        return entries * 16 + n * (6 * 4 + 4), f"{entries} row entries of 16 B read once (the cost includes building the rows)"
+    slots = min(obs.n_samples, obs.lags)
+    per = obs._gather.numel() * 3 * obs.bytes_per_value
+    return (slots + 1) * per, f"{slots} ring slots of {per} B read, one written"
+
+
+def bench_observers(args, dev):
+    """BatchedDynamics with one observer of --observe attached against the same step without, in one process, the repeats
+    alternating: the cost of a sample is the difference of the medians times --observe-every."""
+    from torchani_amd import md as M
+    from torchani_amd.models import ANI2x
+
+    sp, x, cell, pbc, lists = load_system(args, dev)
+    nl = args.neighborlist or lists[0]
+    masses = torch.tensor(ELEMENT_MASSES, device=dev)[sp.clamp(min=0)]
+    Cn, A = sp.shape
+    temperature = 300.0 if args.langevin else None
+    drivers, observers = {}, {}
+    for kind in ["none"] + list(args.observe):
+        model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=nl, row_capacity=256)
+        d = M.BatchedDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1)
+        d.set_temperature(300.0)
+        if kind != "none":
+            observers[kind] = d.attach(make_observer(kind, args, cell))
+        d.run(max(args.warmup, 2 * args.observe_every))
+        drivers[kind] = d
+    times = {kind: [] for kind in drivers}
+    for _ in range(args.repeats):
+        for kind, d in drivers.items():
+            times[kind].append(timed(d, args.steps))
+    t = {kind: np.array(v) * 1e3 for kind, v in times.items()}
+    n_atoms = int((sp >= 0).sum())
+    for kind in drivers:
+        print(f"{nl:17s} observer {kind:10s} {Cn} x {A} atoms ({n_atoms} real), dt {args.dt:g} fs: {np.median(t[kind]):.3f} ms/step "
+              f"(fastest {t[kind].min():.3f}, slowest {t[kind].max():.3f} of {len(t[kind])} repeats of {args.steps} steps)")
+    for kind, obs in observers.items():
+        apart = t[kind].min() > t["none"].max() or t[kind].max() < t["none"].min()
+        per_sample = (np.median(t[kind]) - np.median(t["none"])) * 1e3 * args.observe_every
+        nbytes, what = observer_bytes(kind, obs, drivers[kind])
+        rate = f"{nbytes / (per_sample * 1e-6) / 1e9:.1f} GB/s of that estimate" if per_sample > 0 else "no cost resolved"
+        print(f"{kind}: {per_sample:+.1f} us per sample (medians, one sample per {args.observe_every} steps), {obs.n_samples} samples; "
+              f"{nbytes} B to move ({what}): {rate}; the ranges {'separate' if apart else 'overlap: no difference can be claimed'}")
+
+
 def timed(md, steps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -287,6 +361,11 @@ def main():
                     help="the device integrator with this bias against the same step without")
     ap.add_argument("--hills", type=int, default=1000, help="--bias metadynamics: hills held by every list")
     ap.add_argument("--shared-walkers", action="store_true", help="--bias metadynamics: every system a walker of one list")
+    ap.add_argument("--observe", nargs="+", choices=("series", "trajectory", "rdf", "msd", "vacf"), default=None,
+                    help="the device integrator with each of these observers attached against the same step without")
+    ap.add_argument("--observe-every", type=int, default=10, help="--observe: steps between samples")
+    ap.add_argument("--lags", type=int, default=512, help="--observe msd / vacf: lags held")
+    ap.add_argument("--rdf-rmax", type=float, default=5.0, help="--observe rdf: r_max, Angstrom")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--force-verlet", action="store_true",
@@ -305,6 +384,10 @@ def main():
         if args.hills < 0:
             ap.error("--hills must be >= 0")
         return bench_bias(args, dev)
+    if args.observe is not None:
+        if args.observe_every < 1 or args.lags < 1:
+            ap.error("--observe-every and --lags must be >= 1")
+        return bench_observers(args, dev)
     sp, x, cell, pbc, lists = load_system(args, dev)
     if args.neighborlist is not None and args.system == "water":
         lists = (args.neighborlist,)

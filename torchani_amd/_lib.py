@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "geom_constraints.hip", "saddle.hip", "irc.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "md_observe.hip", "geom_constraints.hip", "saddle.hip", "irc.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", "saddle_common.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -57,6 +57,8 @@ MD_SITES_MAX = 64   # ANIHIP_MD_SITES_MAX
 MD_SITE_NONE, MD_SITE_CENTER, MD_SITE_ANCHOR, MD_SITE_VALUE = 0, 1, 2, 3   # ANIHIP_MD_SITE_*
 MD_SITE_ROLE_CENTER, MD_SITE_ROLE_A, MD_SITE_ROLE_B = 0, 1, 2   # ANIHIP_MD_SITE_ROLE_*
 MD_SITES_BAD_SITE, MD_SITES_BAD_GROUP, MD_SITES_BAD_MEMBER = 1, 2, 4   # ANIHIP_MD_SITES_BAD_*
+MD_CORR_MSD, MD_CORR_VACF = 0, 1   # ANIHIP_MD_CORR_*
+MD_RDF_MAX_PAIRS, MD_RDF_MAX_BINS = 8, 1024   # ANIHIP_MD_RDF_MAX_*
 GEOM_MAX_CONSTRAINTS = 8   # ANIHIP_GEOM_MAX_CONSTRAINTS
 GEOM_BAD_TABLE, GEOM_SINGULAR, GEOM_NOT_CONVERGED = 1, 2, 4   # ANIHIP_GEOM_*
 SADDLE_MAX_COORDS = 768   # ANIHIP_SADDLE_MAX_COORDS
@@ -388,6 +390,12 @@ def lib() -> C.CDLL:
     L.anihip_md_sites_spread.argtypes = [vp, C.POINTER(MdParams), C.POINTER(MdSites), vp, vp, vp, vp]
     for name in ("anihip_md_sites_gather", "anihip_md_sites_spread"):
         getattr(L, name).restype = C.c_int
+    L.anihip_md_rdf_accumulate.argtypes = [vp, C.POINTER(MdParams), i32, i32, C.c_double, i32, vp, vp, vp, vp, i64, vp]
+    L.anihip_md_corr_workspace_bytes.restype = sz
+    L.anihip_md_corr_workspace_bytes.argtypes = [i64, i64, i64, i64]
+    L.anihip_md_corr_accumulate.argtypes = [vp, C.POINTER(MdParams), i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, sz]
+    for name in ("anihip_md_rdf_accumulate", "anihip_md_corr_accumulate"):
+        getattr(L, name).restype = C.c_int
     L.anihip_geom_constraints_project.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp, vp]
     L.anihip_geom_constraints_restore.argtypes = [vp, i64, i64, C.POINTER(GeomConstraints), vp, vp]
     for name in ("anihip_geom_constraints_project", "anihip_geom_constraints_restore"):
@@ -448,6 +456,7 @@ EXPORTED_SYMBOLS = [
     "anihip_md_exchange",
     "anihip_md_bias_workspace_bytes", "anihip_md_bias_apply", "anihip_md_bias_deposit", "anihip_md_bias_hills",
     "anihip_md_sites_workspace_bytes", "anihip_md_sites_gather", "anihip_md_sites_spread",
+    "anihip_md_rdf_accumulate", "anihip_md_corr_workspace_bytes", "anihip_md_corr_accumulate",
     "anihip_geom_constraints_project", "anihip_geom_constraints_restore",
     "anihip_saddle_workspace_bytes", "anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept",
     "anihip_irc_workspace_bytes", "anihip_irc_project", "anihip_irc_step", "anihip_irc_commit",

@@ -24,6 +24,8 @@ the forces between the evaluation and the kick (csrc/md_bias.hip): one launch mo
 deposit.  ``center`` (the centre of a group of atoms, usable wherever a CV takes an atom) and ``coordination`` (a coordination
 number between two groups) enter the same kernels as sites appended to every entry (csrc/md_sites.hip): a gather in front of
 them, at most two launches, and a spread behind them, one.
+``attach(observer)`` samples a trajectory on the device inside ``step()`` (md_observe.py, csrc/md_observe.hip): ``TimeSeries``,
+``Trajectory``, ``RadialDistribution``, ``MeanSquaredDisplacement`` and ``VelocityAutocorrelation``.
 """
 from __future__ import annotations
 
@@ -37,6 +39,8 @@ from torch import Tensor
 from . import _lib
 from .md_bias import (CV, BiasTables, DeviceBias, Metadynamics, Restraint, Site, SiteTables, angle, build_bias_tables,  # noqa: F401
                       build_site_tables, center, coordination, dihedral, distance)
+from .md_observe import (MeanSquaredDisplacement, Observer, RadialDistribution, TimeSeries, Trajectory,  # noqa: F401
+                         VelocityAutocorrelation)
 
 # CODATA 2018: 1 Ha = 4.3597447222071e-18 J, 1 amu = 1.66053906660e-27 kg  ->  (Ha / Angstrom) / amu in Angstrom / fs^2
 ACC_UNIT = 4.3597447222071e-18 / 1e-10 / 1.66053906660e-27 * 1e10 * 1e-30
@@ -401,6 +405,11 @@ class BatchedDynamics:
     centres do not.  Up to 64 sites per entry, a centre one and a coordination number two.  A bias without any of them runs
     the path it ran before, bit for bit.  ``run()`` reads the status of the site tables with its other periodic checks.
 
+    ``attach(observer)`` has ``step()`` sample an observer of md_observe.py whenever ``steps_done % observer.every == 0``, on the
+    state the step leaves behind (after the kick, a deposit and, in ``ReplicaExchangeDynamics``, the attempt) and without a host
+    read; ``run()`` reads the observers' status words with its other periodic checks.  Without observers ``step()`` launches and
+    allocates what it did before them.
+
     Attributes: ``coordinates`` (fp32, updated in place; ``coordinates_lo`` is the residual of the two-float position),
     ``velocities`` (Angstrom / fs), ``forces`` and ``potential_energies`` at the coordinates, ``steps_done``.  ``step()`` never
     synchronizes with the host; ``run()`` reads the neighbor overflow status every ``check_every`` steps.
@@ -518,6 +527,7 @@ class BatchedDynamics:
         self._kinetic_stale = False
         self._mb_draws = 0
         self.steps_done = 0
+        self._observers: tp.List[Observer] = []
         self._clusters = None
         if constraints is not None and bool((constraints.pairs >= 0).any()):
             self._set_constraints(constraints, fixed, float(constraint_tolerance), int(constraint_max_iterations))
@@ -668,9 +678,24 @@ class BatchedDynamics:
         else:
             _lib.check(_lib.lib().anihip_md_barostat(*args))
 
+    def attach(self, observer: Observer) -> Observer:
+        """Have ``step()`` sample ``observer`` (``TimeSeries``, ``Trajectory``, ``RadialDistribution``,
+        ``MeanSquaredDisplacement``, ``VelocityAutocorrelation``) whenever ``steps_done % observer.every == 0``; returns it."""
+        if not isinstance(observer, Observer):
+            raise ValueError(f"attach() takes an observer of torchani_amd.md, got {type(observer).__name__}")
+        observer._attach(self)
+        self._observers.append(observer)
+        return observer
+
     def step(self) -> None:
-        """One time step: drift, the barostat's move if there is one, energies and forces at the new coordinates, kick.  No
-        host synchronization."""
+        """One time step (``_advance``), then the samples of the observers that are due.  No host synchronization."""
+        self._advance()
+        for observer in self._observers:
+            if self.steps_done % observer.every == 0:
+                observer._sample(self)
+
+    def _advance(self) -> None:
+        """Drift, the barostat's move if there is one, energies and forces at the new coordinates, kick, deposit."""
         if self.barostat and self._kinetic_stale:
             # velocities set since the last kick: the barostat takes the kinetic energy of before the drift, the same sum as
             # kinetic_energies() on the device, no host read
@@ -703,6 +728,8 @@ class BatchedDynamics:
                 self.raise_on_unconverged_constraints()
                 if self._bias is not None:
                     self._bias.raise_on_bad_sites()
+                for observer in self._observers:
+                    observer.raise_on_status()
 
     # ---- velocities ------------------------------------------------------------------------------------------------
     def noise(self, step: int) -> Tensor:
@@ -1133,10 +1160,10 @@ class ReplicaExchangeDynamics(BatchedDynamics):
         rung = self._rung_of[self._members].long()
         self.temperature.index_copy_(0, self._members, self.rung_temperatures[self._member_ladders, rung])
 
-    def step(self) -> None:
-        """The inherited step, then one exchange attempt when ``steps_done`` is a multiple of ``exchange_every``.  No host
-        synchronization."""
-        super().step()
+    def _advance(self) -> None:
+        """The inherited step, then one exchange attempt when ``steps_done`` is a multiple of ``exchange_every``: observers
+        sample what the attempt leaves behind.  No host synchronization."""
+        super()._advance()
         if self.exchange_every and self.steps_done % self.exchange_every == 0:
             self._exchange()
 
