@@ -1144,6 +1144,36 @@ int anihip_aev_backward_virial(void *stream, const anihip_aev_params *p, const f
                                const float *ent, const float *grad_aev, const uint32_t *slab_mask,
                                int32_t flags, float *grad_coords, double *virial, uint32_t *status);
 
+/* The heat flux of a strictly local potential, E = sum_i E_i with E_i a function of the displacements of row i alone.  With
+ * eps_i = 1/2 m_i |v_i|^2 + e_i, differentiating sum_i r_i eps_i along the equations of motion gives
+ *   J = sum_i eps_i v_i - sum_i q_i,   q_i = sum_{j in row i} d_ij (g_ij . v_j),   g_ij = d E_i / d d_ij
+ * (d_ij = the displacement stored in the row; the product does not depend on its sign convention, and no absolute position
+ * enters, so it holds under periodic boundaries).  anihip_aev_backward_flux is the AEV backward with that contraction in place
+ * of the scatter into forces: flux_atoms fp32 [n_atoms][3], the rows lo <= i < hi OVERWRITTEN with q_i (zero for an atom
+ * without neighbors or with species < 0), every other row untouched; vectors fp32 [n_atoms][3] are gathered by neighbor index.
+ * grad_aev is d (sum_i E_i) / d aev as for anihip_aev_backward.  Every term is evaluated as an own term of row i: flags and
+ * slab_mask are accepted for the siblings' signature and not used (ANIHIP_BWD_SYMMETRIC would fold a neighbor's share, which
+ * multiplies another vector, into the pair).  No global atomics and nothing pushed to other atoms.  On the 16 / 8x4 / 4x8 grids
+ * every sum has a fixed order and two calls on the same input are bit-identical by construction.  On any other grid the general
+ * kernel adds the angular terms of a row into LDS with float atomics of the one wave that owns the row, as its force variant
+ * does: the order is the hardware's order of the lanes of one instruction, which was observed to repeat, not guaranteed to. */
+int anihip_aev_backward_flux(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms, int64_t lo,
+                             int64_t hi, const int32_t *species, const uint32_t *meta, const float *ent,
+                             const float *grad_aev, const uint32_t *slab_mask, int32_t flags, const float *vectors,
+                             float *flux_atoms, uint32_t *status);
+
+/* The three sums of J per entry: flux fp64 [C][3][3], OVERWRITTEN, in Hartree Angstrom / fs,
+ *   flux[c][0] = sum_i 1/2 m_i |v_i|^2 v_i / ANIHIP_MD_ACC_UNIT   (kinetic convective)
+ *   flux[c][1] = sum_i e_i v_i                                     (potential convective)
+ *   flux[c][2] = - sum_i q_i                                       (virial term)
+ * over the atoms with species >= 0.  masses fp32 [C][A] (amu), atomic_energies fp64 [C][A] (Hartree), species int32 [C][A],
+ * velocities and flux_atoms fp32 [C][A][3].  fp64 sums in a fixed order, no atomics.  workspace:
+ * anihip_md_heat_flux_workspace_bytes(n_mol, atoms_per_mol) bytes of scratch (needed for atoms_per_mol > 256). */
+size_t anihip_md_heat_flux_workspace_bytes(int64_t n_mol, int64_t atoms_per_mol);   /* 0 + anihip_last_error() */
+int anihip_md_heat_flux(void *stream, const anihip_md_params *params, const float *masses, const double *atomic_energies,
+                        const int32_t *species, const float *velocities, const float *flux_atoms, double *flux,
+                        void *workspace, size_t workspace_bytes);
+
 /* ---------------------------------------------------------------------------------------------
  * Per-species MLP ensemble: replaces mnp::run (csrc/mnp.cpp:238-265; forward :32-136, input-gradient
  * backward :138-232) and BmmEnsemble (nn/_infer.py:61-216).

@@ -36,7 +36,7 @@
                                                                            halves of every molecule, or on the coordination number
                                                                            of all O against all H of the box (--coordination-atoms
                                                                            N: the first N of each)
-    python tools/md_bench.py --observe series trajectory rdf msd vacf [--observe-every 10] [--lags 512] --langevin --repeats 7 ...
+    python tools/md_bench.py --observe series trajectory rdf msd vacf heatflux hfacf [--observe-every 10] [--lags 512] --langevin --repeats 7 ...
                                                                            observers (md.TimeSeries ... md.VelocityAutocorrelation):
                                                                            the step with each attached against the step without,
                                                                            the cost per sample next to the bytes it has to move
@@ -264,6 +264,10 @@ def make_observer(name, args, cell):
     if name == "rdf":
         pairs = [("O", "O"), ("O", "H")] if cell is not None else [("C", "C"), ("C", "H")]
         return M.RadialDistribution(pairs, r_max=args.rdf_rmax, bins=200, every=every)
+    if name == "heatflux":
+        return M.HeatFlux(every=every, capacity=4096, on_full="wrap")
+    if name == "hfacf":
+        return M.HeatFluxAutocorrelation(lags=args.lags, every=every)
     cls = M.MeanSquaredDisplacement if name == "msd" else M.VelocityAutocorrelation
     return cls(lags=args.lags, every=every, max_bytes=1 << 36)
 
@@ -279,6 +283,8 @@ def observer_bytes(name, obs, d):
         rows = obs._engine.neighbors(obs._species32, d.coordinates, d.cell, d.pbc, mode=obs._mode, row_cap=256)
         entries = int(((rows.meta[:, 1] & 0xFFFF) + ((rows.meta[:, 1] >> 16) & 0xFFFF)).sum())
         return entries * 16 + n * (6 * 4 + 4), f"{entries} row entries of 16 B read once (the cost includes building the rows)"
+    if name in ("heatflux", "hfacf"):   # one more evaluation of the model: held against the step, not against bytes
+        return 0, "one evaluation of the model's flux stage"
     slots = min(obs.n_samples, obs.lags)
     per = obs._gather.numel() * 3 * obs.bytes_per_value
     return (slots + 1) * per, f"{slots} ring slots of {per} B read, one written"
@@ -301,7 +307,11 @@ def bench_observers(args, dev):
         d = M.BatchedDynamics(model, sp, x, cell, pbc, dt=args.dt, masses=masses, temperature=temperature, seed=1)
         d.set_temperature(300.0)
         if kind != "none":
-            observers[kind] = d.attach(make_observer(kind, args, cell))
+            try:
+                observers[kind] = d.attach(make_observer(kind, args, cell))
+            except ValueError as err:   # (hfacf on open molecules: no volume)
+                print(f"{kind}: refused ({err})")
+                continue
         d.run(max(args.warmup, 2 * args.observe_every))
         drivers[kind] = d
     times = {kind: [] for kind in drivers}
@@ -318,8 +328,44 @@ def bench_observers(args, dev):
         per_sample = (np.median(t[kind]) - np.median(t["none"])) * 1e3 * args.observe_every
         nbytes, what = observer_bytes(kind, obs, drivers[kind])
         rate = f"{nbytes / (per_sample * 1e-6) / 1e9:.1f} GB/s of that estimate" if per_sample > 0 else "no cost resolved"
+        if kind in ("heatflux", "hfacf"):
+            rate = f"{per_sample * 1e-3 / np.median(t['none']):.2f} steps"
         print(f"{kind}: {per_sample:+.1f} us per sample (medians, one sample per {args.observe_every} steps), {obs.n_samples} samples; "
               f"{nbytes} B to move ({what}): {rate}; the ranges {'separate' if apart else 'overlap: no difference can be claimed'}")
+
+
+def bench_flux_backward(args, dev):
+    """The flux backward's own time against the force backward on the same rows and dE/dAEV (events around each launch, the two
+    alternating)."""
+    from torchani_amd.models import ANI2x
+
+    sp, x, cell, pbc, lists = load_system(args, dev)
+    model = ANI2x(seed=0, device=dev, periodic_table_index=False, neighborlist=args.neighborlist or lists[0], row_capacity=256)
+    aevc, eng = model.aev_computer, model.aev_computer.engine()
+    sp32, n = sp.to(torch.int32).contiguous(), sp.numel()
+    c32 = x.to(torch.float32).contiguous()
+    v = torch.randn((n, 3), device=dev) * 0.01
+    nbrs = aevc.neighbor_rows(sp32, c32, cell, pbc, lo=0, hi=n)
+    packed = model.neural_networks._pack(dev, None)
+    mask = torch.empty(n, dtype=torch.int32, device=dev)
+    aev = eng.forward(sp32, nbrs, slab_mask=mask, shard_rows=True)
+    _, grad_aev, _ = packed.forward_backward(sp32, aev, lo=0, hi=n, want_grad=True, slab_mask=mask, shard_rows=True)
+    acc = torch.zeros((n, 3), device=dev)
+    runs = {"force backward": lambda: eng.backward(sp32, nbrs, grad_aev, grad_coords=acc, shard_rows=True, slab_mask=mask),
+            "flux backward": lambda: eng.backward_flux(sp32, nbrs, grad_aev, v, slab_mask=mask, shard_rows=True)}
+    t = {k: [] for k in runs}
+    for r in range(args.repeats + 2):
+        for k, f in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            torch.cuda.synchronize()
+            if r >= 2:
+                t[k].append(a.elapsed_time(b))
+    for k, v_ in t.items():
+        print(f"{k:15s} {n} atoms: {np.median(v_):.3f} ms (fastest {min(v_):.3f}, slowest {max(v_):.3f} of {len(v_)}; the flux "
+              "backward includes the allocation of its [N, 3] result)")
 
 
 def timed(md, steps):
@@ -361,7 +407,8 @@ def main():
                     help="the device integrator with this bias against the same step without")
     ap.add_argument("--hills", type=int, default=1000, help="--bias metadynamics: hills held by every list")
     ap.add_argument("--shared-walkers", action="store_true", help="--bias metadynamics: every system a walker of one list")
-    ap.add_argument("--observe", nargs="+", choices=("series", "trajectory", "rdf", "msd", "vacf"), default=None,
+    ap.add_argument("--observe", nargs="+", choices=("series", "trajectory", "rdf", "msd", "vacf", "heatflux", "hfacf"),
+                    default=None,
                     help="the device integrator with each of these observers attached against the same step without")
     ap.add_argument("--observe-every", type=int, default=10, help="--observe: steps between samples")
     ap.add_argument("--lags", type=int, default=512, help="--observe msd / vacf: lags held")
@@ -387,7 +434,10 @@ def main():
     if args.observe is not None:
         if args.observe_every < 1 or args.lags < 1:
             ap.error("--observe-every and --lags must be >= 1")
-        return bench_observers(args, dev)
+        bench_observers(args, dev)
+        if "heatflux" in args.observe:
+            bench_flux_backward(args, dev)
+        return
     sp, x, cell, pbc, lists = load_system(args, dev)
     if args.neighborlist is not None and args.system == "water":
         lists = (args.neighborlist,)

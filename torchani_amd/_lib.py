@@ -294,6 +294,12 @@ def lib() -> C.CDLL:
     L.anihip_mlp_input_hvp.argtypes = [vp, C.POINTER(MlpDesc), i64, vp, vp, i64, vp, vp, sz, vp]
     L.anihip_mlp_input_hvp.restype = C.c_int
     L.anihip_aev_backward_virial.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.anihip_aev_backward_flux.argtypes = [vp, C.POINTER(AevParams), vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.anihip_aev_backward_flux.restype = C.c_int
+    L.anihip_md_heat_flux_workspace_bytes.restype = sz
+    L.anihip_md_heat_flux_workspace_bytes.argtypes = [i64, i64]
+    L.anihip_md_heat_flux.argtypes = [vp, C.POINTER(MdParams), vp, vp, vp, vp, vp, vp, vp, sz]
+    L.anihip_md_heat_flux.restype = C.c_int
     L.anihip_mlp_workspace_bytes.restype = sz
     L.anihip_mlp_workspace_bytes.argtypes = [C.POINTER(MlpDesc), i64]
     L.anihip_mlp_forward_backward_workspace_bytes.restype = sz
@@ -460,6 +466,7 @@ EXPORTED_SYMBOLS = [
     "anihip_geom_constraints_project", "anihip_geom_constraints_restore",
     "anihip_saddle_workspace_bytes", "anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept",
     "anihip_irc_workspace_bytes", "anihip_irc_project", "anihip_irc_step", "anihip_irc_commit",
+    "anihip_aev_backward_flux", "anihip_md_heat_flux_workspace_bytes", "anihip_md_heat_flux",
 ]
 
 

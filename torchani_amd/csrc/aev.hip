@@ -1021,13 +1021,20 @@ __device__ __forceinline__ void push_grad(float *grad_coords, size_t at, int com
 //   angular, NA shifts: ONE anchor c = NA / 2 - 1 and powers of gu = exp2(2 D x), gd = 1 / gu; f_c is common to all NA terms and
 //   multiplies the contracted sums once:  sum_u w_u f_u (1, x - m D) = f_c (X, x X - Y), (X, Y) = sum (w_u gu^m) (K_m, m D K_m):
 //   3 exponentials and 2 NA - 3 products instead of NA exponentials and 3 NA products.
-template <int NA, int NZ, bool VIRIAL, bool FIXED, bool REC>
+// FLUX (anihip_aev_backward_flux): no forces at all.  Every finished per-neighbor gradient g_ij = d E_i / d d_ij is contracted
+// with the neighbor's row of `vectors` instead of being pushed:  q_i = sum_j d_ij (g_ij . v_j), three per-lane sums where VIRIAL
+// keeps six, one wave sum per central atom and one plain store of three floats to grad_coords[i] (the caller's flux_atoms).  The
+// radial gather is compiled out -- every term is an own term, as on an asymmetric list --, because the two shares of a gathered
+// pair multiply different vectors (v_j for the own share, v_i with d reversed for the neighbor's).  No atomics, fixed order.
+template <int NA, int NZ, bool VIRIAL, bool FIXED, bool REC, bool FLUX = false>
 __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
     AevArgs a, const float *__restrict__ tab, int64_t lo64, int64_t hi64,
     const int32_t *__restrict__ species, const uint32_t *__restrict__ meta,
     const float4 *__restrict__ ent, const float *__restrict__ grad_aev, float *__restrict__ grad_coords,
-    double *__restrict__ virial, const uint32_t *__restrict__ slab_mask, int64_t glo64, int64_t ghi64)
+    double *__restrict__ virial, const uint32_t *__restrict__ slab_mask, int64_t glo64, int64_t ghi64,
+    const float *__restrict__ vectors)
 {
+    static_assert(!FLUX || (!VIRIAL && !FIXED), "the flux variant accumulates neither a virial nor fixed-point forces");
     // (32-bit atom indices inside the kernel -- rows hold 28-bit neighbor indices anyway: a 64-bit "less than" is a vector
     // compare whose operands end up spilled)
     const int lo = (int)lo64, hi = (int)hi64, glo = (int)glo64, ghi = (int)ghi64;
@@ -1145,6 +1152,7 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
         const uint32_t start = h.start;
         const int spi = h.sp;
         float sx = 0.f, sy = 0.f, sz_ = 0.f;   // minus the gradient on the central atom, per lane
+        float qx = 0.f, qy = 0.f, qz = 0.f;    // FLUX: d_ij (g_ij . v_j), per lane
         if (!skip) {
             v4f_ *st4 = reinterpret_cast<v4f_ *>(stage);
             st4[lane] = gr0;
@@ -1177,7 +1185,14 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
                 const uint32_t wbits = __float_as_uint(d.w);
                 const int jn = ve ? (int)(wbits & IDX_MASK) : lo;
                 // the neighbor's block for MY species: issued first, consumed at the end of the pass
-                const bool inrow = ve && jn >= glo && jn < ghi;   // (empty range: asymmetric list, push everything)
+                const bool inrow = FLUX ? false : (ve && jn >= glo && jn < ghi);   // (empty range: asymmetric list, push everything)
+                float wx = 0.f, wy = 0.f, wz = 0.f;   // FLUX: the vector of a radial-only neighbor, consumed at the end of the pass
+                if constexpr (FLUX) {
+                    if (ve && e >= nA) {
+                        const float *vj_ = vectors + 3 * (size_t)jn;
+                        wx = vj_[0]; wy = vj_[1]; wz = vj_[2];
+                    }
+                }
                 float4 G0 = make_float4(0.f, 0.f, 0.f, 0.f), G1 = G0, G2 = G0, G3 = G0;
                 uint32_t jmask = 0xFFFFFFFFu;
                 if (inrow) {
@@ -1267,9 +1282,14 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
                         af[e] = make_float4(ca.x, ca.y, inv, d.w);
                         if (!gat) { gx[e] = Gx; gy[e] = Gy; gz[e] = Gz; }   // pushed with the angular part (plane 0)
                     } else if (!gat) {
-                        push_grad<FIXED>(grad_coords, (size_t)jn, 0, Gx);
-                        push_grad<FIXED>(grad_coords, (size_t)jn, 1, Gy);
-                        push_grad<FIXED>(grad_coords, (size_t)jn, 2, Gz);
+                        if constexpr (FLUX) {
+                            const float gv = Gx * wx + Gy * wy + Gz * wz;
+                            qx += gv * d.x; qy += gv * d.y; qz += gv * d.z;
+                        } else {
+                            push_grad<FIXED>(grad_coords, (size_t)jn, 0, Gx);
+                            push_grad<FIXED>(grad_coords, (size_t)jn, 1, Gy);
+                            push_grad<FIXED>(grad_coords, (size_t)jn, 2, Gz);
+                        }
                     }
                 }
             }
@@ -1280,6 +1300,12 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
         q.request();   // (the position of the atom after i2: granted by the end of this atom)
         ANIHIP_BWD_ISSUE(i1, h)
         hw_next = hdr_load(meta, species, i2, i2 < hi);
+        if constexpr (FLUX) {   // the row is overwritten: zero for an atom without neighbors or with species < 0
+            if (skip && lane == 0) {
+                float *o = grad_coords + 3 * (size_t)i;
+                o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+            }
+        }
         if (skip) continue;
         wave_sync();
         TR_STAMP(3)   // prefetch issue
@@ -1449,6 +1475,13 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
             }
             const float4 fa = af[e];
             const size_t jat = (size_t)(__float_as_uint(fa.w) & IDX_MASK);
+            if constexpr (FLUX) {
+                const float *vj_ = vectors + 3 * jat;
+                const float4 u = nb[e];   // unit vector, 0.5 qA r
+                const float gv = (x * vj_[0] + y * vj_[1] + z * vj_[2]) * (u.w * (2.0f / qA));
+                qx += gv * u.x; qy += gv * u.y; qz += gv * u.z;
+                continue;
+            }
             push_grad<FIXED>(grad_coords, jat, 0, x);
             push_grad<FIXED>(grad_coords, jat, 1, y);
             push_grad<FIXED>(grad_coords, jat, 2, z);
@@ -1461,11 +1494,19 @@ __global__ __launch_bounds__(BWD_WPB * WAVE, ANIHIP_BWD_WAVES) void k_aev_bwd(
                 vxy += x * dy; vxz += x * dz; vyz += y * dz;
             }
         }
-        sx = wave_sum(sx); sy = wave_sum(sy); sz_ = wave_sum(sz_);
-        if (lane == 0) {
-            push_grad<FIXED>(grad_coords, (size_t)i, 0, -sx);
-            push_grad<FIXED>(grad_coords, (size_t)i, 1, -sy);
-            push_grad<FIXED>(grad_coords, (size_t)i, 2, -sz_);
+        if constexpr (FLUX) {
+            qx = wave_sum(qx); qy = wave_sum(qy); qz = wave_sum(qz);
+            if (lane == 0) {
+                float *o = grad_coords + 3 * (size_t)i;
+                o[0] = qx; o[1] = qy; o[2] = qz;
+            }
+        } else {
+            sx = wave_sum(sx); sy = wave_sum(sy); sz_ = wave_sum(sz_);
+            if (lane == 0) {
+                push_grad<FIXED>(grad_coords, (size_t)i, 0, -sx);
+                push_grad<FIXED>(grad_coords, (size_t)i, 1, -sy);
+                push_grad<FIXED>(grad_coords, (size_t)i, 2, -sz_);
+            }
         }
         wave_sync();
         TR_STAMP(5)   // phase 3: atomics issued
@@ -1498,7 +1539,7 @@ int aev_jvp_generic_items(hipStream_t stream, Dir M, const anihip_aev_params *p,
                           const int32_t *row_dir, float *daev);
 int aev_backward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                          const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
-                         float *grad_coords, double *virial, bool fixed);
+                         float *grad_coords, double *virial, bool fixed, const float *vectors = nullptr);
 
 // the grids the tuned kernels are built for: 16 radial shifts, 8 x 4 (ANI-2x) or 4 x 8 (ANI-1x) angular terms
 static bool tuned_grid(const anihip_aev_params *p)
@@ -1759,10 +1800,10 @@ static int aev_backward(void *stream, const anihip_aev_params *p, const float *t
 #define ANIHIP_LAUNCH_BWD(NA_, NZ_, VIR_, FIX_)                                                                              \
     if (rec)                                                                                                                 \
         hipLaunchKernelGGL((k_aev_bwd<NA_, NZ_, VIR_, FIX_, true>), grid, block, 0, st, a, table, lo, hi, species, meta, e4, \
-                           grad_aev, grad_coords, virial, slab_mask, glo, ghi);                                              \
+                           grad_aev, grad_coords, virial, slab_mask, glo, ghi, (const float *)nullptr);                      \
     else                                                                                                                     \
         hipLaunchKernelGGL((k_aev_bwd<NA_, NZ_, VIR_, FIX_, false>), grid, block, 0, st, a, table, lo, hi, species, meta, e4, \
-                           grad_aev, grad_coords, virial, slab_mask, glo, ghi)
+                           grad_aev, grad_coords, virial, slab_mask, glo, ghi, (const float *)nullptr)
     const int variant = (p->n_shf_a == 8 ? 0 : 4) + (virial ? 2 : 0) + (fixed ? 1 : 0);
     switch (variant) {
         case 0: ANIHIP_LAUNCH_BWD(8, 4, false, false); break;
@@ -1800,6 +1841,40 @@ extern "C" int anihip_aev_backward_virial(void *stream, const anihip_aev_params 
     ANIHIP_REQUIRE(virial, "null pointer argument");
     return aev_backward(stream, p, table, n_atoms, lo, hi, species, meta, ent, grad_aev, grad_coords, virial,
                         slab_mask, flags);
+}
+
+// q_i = sum_j d_ij (d E_i / d d_ij . vectors[j]) of the central atoms lo..hi (k_aev_bwd<.., FLUX>): rows are overwritten, nothing
+// else is written.  Every term is an own term (ANIHIP_BWD_SYMMETRIC in flags is ignored: see the kernel), and a slab mask,
+// which only qualifies what the radial gather may read of OTHER rows, is not needed; it is accepted for the siblings' signature.
+extern "C" int anihip_aev_backward_flux(void *stream, const anihip_aev_params *p, const float *table, int64_t n_atoms,
+                                        int64_t lo, int64_t hi, const int32_t *species, const uint32_t *meta,
+                                        const float *ent, const float *grad_aev, const uint32_t *slab_mask, int32_t flags,
+                                        const float *vectors, float *flux_atoms, uint32_t *status)
+{
+    (void)status; (void)flags; (void)slab_mask;
+    ANIHIP_REQUIRE(p && table && species && meta && ent && grad_aev && vectors && flux_atoms, "null pointer argument");
+    ANIHIP_REQUIRE(0 <= lo && lo <= hi && hi <= n_atoms, "central range outside 0..n_atoms");
+    if (!tuned_grid(p))
+        return aev_backward_generic((hipStream_t)stream, p, table, lo, hi, species, meta, ent, grad_aev, flux_atoms, nullptr,
+                                    false, vectors);
+    AevArgs a;
+    if (int rc = make_args(p, &a)) return rc;
+    if (hi == lo) return 0;
+    dim3 grid(persistent_blocks(hi - lo, BWD_WPB, (ANIHIP_BWD_WAVES * 4 + BWD_WPB - 1) / BWD_WPB)), block(BWD_WPB * WAVE);
+    const float4 *e4 = (const float4 *)ent;
+    hipStream_t st = (hipStream_t)stream;
+    const bool rec = (p->flags & ANIHIP_AEV_REC_BWD) != 0 && ANIHIP_BWD_REC;
+#define ANIHIP_LAUNCH_FLUX(NA_, NZ_, REC_)                                                                                   \
+    hipLaunchKernelGGL((k_aev_bwd<NA_, NZ_, false, false, REC_, true>), grid, block, 0, st, a, table, lo, hi, species, meta, \
+                       e4, grad_aev, flux_atoms, (double *)nullptr, (const uint32_t *)nullptr, (int64_t)0, (int64_t)0, vectors)
+    if (p->n_shf_a == 8) {
+        if (rec) ANIHIP_LAUNCH_FLUX(8, 4, true); else ANIHIP_LAUNCH_FLUX(8, 4, false);
+    } else {
+        if (rec) ANIHIP_LAUNCH_FLUX(4, 8, true); else ANIHIP_LAUNCH_FLUX(4, 8, false);
+    }
+#undef ANIHIP_LAUNCH_FLUX
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 #ifdef ANIHIP_TRACE

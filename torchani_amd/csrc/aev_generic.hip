@@ -244,14 +244,18 @@ __device__ __forceinline__ void gen_push(float *grad_coords, size_t at, int comp
     }
 }
 
-template <bool VIRIAL, bool FIXED>
+// FLUX (anihip_aev_backward_flux): the per-neighbor sums are contracted with vectors[j] instead of being pushed, and
+// grad_coords[i] (the caller's flux_atoms) is overwritten with q_i = sum_j d_ij (g_ij . v_j); no global atomics (the angular phase
+// keeps its LDS float atomics of the one wave that owns the row)
+template <bool VIRIAL, bool FIXED, bool FLUX = false>
 __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_bwd_gen(GenArgs a, const float *__restrict__ tab, int64_t lo,
                                                                 int64_t hi, const int32_t *__restrict__ species,
                                                                 const uint32_t *__restrict__ meta,
                                                                 const float4 *__restrict__ ent,
                                                                 const float *__restrict__ grad_aev,
                                                                 float *__restrict__ grad_coords,
-                                                                double *__restrict__ virial)
+                                                                double *__restrict__ virial,
+                                                                const float *__restrict__ vectors)
 {
     __shared__ float4 s_ur[GEN_WPB][MAXR];
     __shared__ float2 s_fca[GEN_WPB][MAXR];
@@ -267,6 +271,12 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_bwd_gen(GenArgs a, const
 #pragma unroll
     for (int q = 0; q < 9; ++q) vir[q] = 0.f;
     for (int64_t i = lo + blockIdx.x * (int64_t)GEN_WPB + wib; i < hi; i += nw) {
+        if constexpr (FLUX) {   // the row is overwritten: zero for an atom without neighbors or with species < 0
+            if (lane == 0) {
+                float *o = grad_coords + 3 * (size_t)i;
+                o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+            }
+        }
         if (species[i] < 0) continue;
         const GenHdr h = gen_hdr(meta, i);
         const int nR = h.nA + h.nF;
@@ -364,6 +374,22 @@ __global__ __launch_bounds__(GEN_WPB * WAVE) void k_aev_bwd_gen(GenArgs a, const
             o1 += n1;
         }
         wave_sync();
+        if constexpr (FLUX) {
+            float qx = 0.f, qy = 0.f, qz = 0.f;
+            for (int e = lane; e < nR; e += WAVE) {
+                const float *vj = vectors + 3 * (size_t)st.jat[e];
+                const float4 U = st.ur[e];
+                const float gv = (gx[e] * vj[0] + gy[e] * vj[1] + gz[e] * vj[2]) * U.w;
+                qx += gv * U.x; qy += gv * U.y; qz += gv * U.z;
+            }
+            qx = wave_sum(qx); qy = wave_sum(qy); qz = wave_sum(qz);
+            if (lane == 0) {   // (after the zeros above, same lane: stores of one lane to one address stay in order)
+                float *o = grad_coords + 3 * (size_t)i;
+                o[0] = qx; o[1] = qy; o[2] = qz;
+            }
+            wave_sync();
+            continue;
+        }
         // ---- push: every neighbor its sum, the central atom minus the total ----
         for (int e = lane; e < nR; e += WAVE) {
             const size_t jn = (size_t)st.jat[e];
@@ -451,7 +477,7 @@ int aev_jvp_generic_items(hipStream_t stream, Dir M, const anihip_aev_params *p,
 
 int aev_backward_generic(hipStream_t stream, const anihip_aev_params *p, const float *table, int64_t lo, int64_t hi,
                          const int32_t *species, const uint32_t *meta, const float *ent, const float *grad_aev,
-                         float *grad_coords, double *virial, bool fixed)
+                         float *grad_coords, double *virial, bool fixed, const float *vectors)
 {
     GenArgs a;
     if (int rc = gen_args(p, &a)) return rc;
@@ -460,8 +486,11 @@ int aev_backward_generic(hipStream_t stream, const anihip_aev_params *p, const f
     const float4 *e4 = (const float4 *)ent;
 #define ANIHIP_LAUNCH_GEN(VIR_, FIX_)                                                                                \
     hipLaunchKernelGGL((k_aev_bwd_gen<VIR_, FIX_>), grid, block, 0, stream, a, table, lo, hi, species, meta, e4, grad_aev, \
-                       grad_coords, virial)
-    if (virial) {
+                       grad_coords, virial, (const float *)nullptr)
+    if (vectors) {
+        hipLaunchKernelGGL((k_aev_bwd_gen<false, false, true>), grid, block, 0, stream, a, table, lo, hi, species, meta, e4,
+                           grad_aev, grad_coords, virial, vectors);
+    } else if (virial) {
         if (fixed) ANIHIP_LAUNCH_GEN(true, true); else ANIHIP_LAUNCH_GEN(true, false);
     } else {
         if (fixed) ANIHIP_LAUNCH_GEN(false, true); else ANIHIP_LAUNCH_GEN(false, false);

@@ -11,7 +11,10 @@
 //                     every species the wave holds, the four waves added in order in tiles of 64 lags
 //   k_md_corr_finish  S[c][s][l] += the chunks' partial sums in ascending order
 //
-// The correlation kernels use no atomics and sum in a fixed order: two calls on the same input are bit-identical.  Tables live in
+//   k_md_heat_flux    the three sums of the heat flux per entry (kinetic convective, potential convective, virial term) from
+//                     per-atom inputs: chunks stride over the atoms of an entry, md_block_sum, k_md_heat_flux_finish adds the chunks
+//
+// The correlation and heat-flux kernels use no atomics and sum in a fixed order: two calls on the same input are bit-identical.  Tables live in
 // device memory, so the kernels check every index they follow.
 #include "anihip_common.h"
 #include "md_sums.h"
@@ -188,9 +191,97 @@ __global__ __launch_bounds__(MD_BLOCK) void k_md_corr_finish(CorrArgs a, int L)
     }
 }
 
+// ---- heat flux: the three sums of J per entry ------------------------------------------------------------------------------
+struct FluxArgs {
+    int64_t A;
+    int32_t n_mol, n_chunks;
+    const float *mass, *vel, *flux_atoms;
+    const double *energy;
+    const int32_t *species;
+    double *part, *out;
+};
+
+constexpr int FLUX_MAX_CHUNKS = 1024;   // chunks of an entry: each strides over its atoms
+
+// chunk k of entry c: atoms k MD_BLOCK + t, + n_chunks MD_BLOCK, ...; nine sums per thread, workgroup sum in a fixed order
+__global__ __launch_bounds__(MD_BLOCK) void k_md_heat_flux(FluxArgs a)
+{
+    const int c = blockIdx.x / a.n_chunks, chunk = blockIdx.x % a.n_chunks;
+    double s[9];
+#pragma unroll
+    for (int w = 0; w < 9; ++w) s[w] = 0.0;
+    for (int64_t i = (int64_t)chunk * MD_BLOCK + threadIdx.x; i < a.A; i += (int64_t)a.n_chunks * MD_BLOCK) {
+        const int64_t at = (int64_t)c * a.A + i;
+        if (a.species[at] < 0) continue;
+        const double vx = (double)a.vel[3 * at], vy = (double)a.vel[3 * at + 1], vz = (double)a.vel[3 * at + 2];
+        const double ke = 0.5 * (double)a.mass[at] * (vx * vx + vy * vy + vz * vz) * (1.0 / ANIHIP_MD_ACC_UNIT);
+        const double e = a.energy[at];
+        s[0] += ke * vx; s[1] += ke * vy; s[2] += ke * vz;
+        s[3] += e * vx; s[4] += e * vy; s[5] += e * vz;
+        s[6] -= (double)a.flux_atoms[3 * at]; s[7] -= (double)a.flux_atoms[3 * at + 1]; s[8] -= (double)a.flux_atoms[3 * at + 2];
+    }
+    md_block_sum<9>(s);
+    if (threadIdx.x == 0) {
+        double *dst = a.n_chunks == 1 ? a.out + (int64_t)c * 9 : a.part + ((int64_t)c * a.n_chunks + chunk) * 9;
+#pragma unroll
+        for (int w = 0; w < 9; ++w) dst[w] = s[w];
+    }
+}
+
+// out[c][w] = the chunks' partial sums in ascending order
+__global__ __launch_bounds__(MD_BLOCK) void k_md_heat_flux_finish(FluxArgs a)
+{
+    const int64_t w = blockIdx.x * (int64_t)MD_BLOCK + threadIdx.x;
+    if (w >= (int64_t)a.n_mol * 9) return;
+    const int64_t c = w / 9, q = w % 9;
+    double acc = 0.0;
+    for (int k = 0; k < a.n_chunks; ++k) acc += a.part[(c * a.n_chunks + k) * 9 + q];
+    a.out[w] = acc;
+}
+
+static int flux_chunks(int64_t atoms_per_mol)
+{
+    return (int)std::min<int64_t>((atoms_per_mol + MD_BLOCK - 1) / MD_BLOCK, FLUX_MAX_CHUNKS);
+}
+
 }  // namespace anihip
 
 using namespace anihip;
+
+extern "C" size_t anihip_md_heat_flux_workspace_bytes(int64_t n_mol, int64_t atoms_per_mol)
+{
+    if (n_mol < 1 || atoms_per_mol < 1) {
+        set_error("anihip_md_heat_flux_workspace_bytes: n_mol and atoms_per_mol must be >= 1");
+        return 0;
+    }
+    return (size_t)n_mol * (size_t)flux_chunks(atoms_per_mol) * 9 * sizeof(double);
+}
+
+extern "C" int anihip_md_heat_flux(void *stream, const anihip_md_params *params, const float *masses, const double *atomic_energies,
+                                   const int32_t *species, const float *velocities, const float *flux_atoms, double *flux,
+                                   void *workspace, size_t workspace_bytes)
+{
+    ANIHIP_REQUIRE(params && masses && atomic_energies && species && velocities && flux_atoms && flux, "null pointer argument");
+    ANIHIP_REQUIRE(params->n_mol >= 1 && params->atoms_per_mol >= 1, "n_mol and atoms_per_mol must be >= 1");
+    FluxArgs a{};
+    a.A = params->atoms_per_mol, a.n_mol = params->n_mol, a.n_chunks = flux_chunks(params->atoms_per_mol);
+    ANIHIP_REQUIRE((int64_t)a.n_mol * a.n_chunks < ((int64_t)1 << 31), "entries x chunks must stay below 2^31");
+    if (a.n_chunks > 1) {
+        const size_t need = anihip_md_heat_flux_workspace_bytes(a.n_mol, a.A);
+        ANIHIP_REQUIRE(workspace && workspace_bytes >= need, "workspace holds %zu bytes, %zu needed", workspace_bytes, need);
+    }
+    a.mass = masses, a.vel = velocities, a.flux_atoms = flux_atoms, a.energy = atomic_energies, a.species = species;
+    a.part = (double *)workspace, a.out = flux;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_md_heat_flux, dim3((unsigned)(a.n_mol * a.n_chunks)), dim3(MD_BLOCK), 0, st, a);
+    ANIHIP_CHECK_HIP(hipGetLastError());
+    if (a.n_chunks > 1) {
+        hipLaunchKernelGGL(k_md_heat_flux_finish, dim3((unsigned)(((int64_t)a.n_mol * 9 + MD_BLOCK - 1) / MD_BLOCK)),
+                           dim3(MD_BLOCK), 0, st, a);
+        ANIHIP_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
 
 extern "C" int anihip_md_rdf_accumulate(void *stream, const anihip_md_params *params, int32_t n_pairs, int32_t bins, double r_max,
                                         int32_t per_entry, const int8_t *pair_slot, const int32_t *species, const uint32_t *meta,

@@ -623,6 +623,30 @@ class AevEngine:
             _lib.check(_lib.lib().anihip_aev_backward_virial(*args, _ptr(virial), _ptr(nbrs.status)))
         return grad_coords
 
+    def backward_flux(self, species: Tensor, nbrs: NeighborRows, grad_aev: Tensor, vectors: Tensor,
+                      slab_mask: tp.Optional[Tensor] = None, shard_rows: bool = False) -> Tensor:
+        """q [N, 3] (float32): q_i = sum_j d_ij (g_ij . vectors[j]) over the neighbors j of the central atoms of nbrs, with
+        g_ij = d(sum grad_aev * aev_i)/d d_ij and d_ij the displacement stored in the row (anihip_aev_backward_flux) -- the
+        virial term of the heat flux when ``vectors`` are the velocities.  Rows outside nbrs.lo..nbrs.hi are zero.  Nothing is
+        scattered: no global atomics; a fixed order and the same bits run to run on the tuned grids (a general grid adds a row's
+        angular terms with LDS float atomics of one wave, whose order was observed to repeat, not guaranteed to).
+        shard_rows / slab_mask as for ``backward`` (every term is an own
+        term of its row, so the flags, which qualify what is read of other rows, are not needed)."""
+        _require_cuda(species, grad_aev, vectors, slab_mask)
+        n = species.numel()
+        assert grad_aev.dtype == torch.float32 and grad_aev.is_contiguous()
+        assert grad_aev.numel() == ((nbrs.hi - nbrs.lo) if shard_rows else n) * self.L
+        assert vectors.dtype == torch.float32 and vectors.is_contiguous() and vectors.numel() == 3 * n
+        if slab_mask is not None:
+            assert slab_mask.dtype == torch.int32 and slab_mask.numel() == n and slab_mask.is_contiguous()
+        alloc = torch.empty if (nbrs.lo == 0 and nbrs.hi == n) else torch.zeros
+        out = alloc((n, 3), dtype=torch.float32, device=species.device)
+        _lib.check(_lib.lib().anihip_aev_backward_flux(
+            _stream(), C.byref(self.params), _ptr(self.table(species.device)), n, nbrs.lo, nbrs.hi, _ptr(species),
+            _ptr(nbrs.meta), _ptr(nbrs.ent), _row_ptr(grad_aev, nbrs.lo if shard_rows else 0, self.L), _ptr(slab_mask), 0,
+            _ptr(vectors), _ptr(out), _ptr(nbrs.status)))
+        return out
+
 
 FIXED_SCALE = 2.0 ** -32
 

@@ -31,6 +31,7 @@ import typing as tp
 import torch
 from torch import Tensor
 
+from .tuples import HeatFlux
 from .tuples import (BlockHessian, EnergiesForces, EnergiesForcesHessians, EnergiesForcesSparseHessians,
                      EnergiesForcesStrainHessians, ForcesHessians, SparseVibAnalysis, VibAnalysis)
 from . import units as _units
@@ -758,6 +759,41 @@ def energies_and_forces(model, species: Tensor, coordinates: Tensor, cell: tp.Op
     if not keep_vars:
         energies = energies.detach()
     return EnergiesForces(energies, f)
+
+
+def heat_flux(model, species: Tensor, coordinates: Tensor, velocities: Tensor, masses: tp.Optional[Tensor] = None,
+              cell: tp.Optional[Tensor] = None, pbc: tp.Optional[Tensor] = None,
+              include_self_energies: bool = False) -> HeatFlux:
+    """The heat flux of an ANI model at one phase-space point, ``HeatFlux(total, kinetic, convective, virial, atomic)`` in
+    Hartree Angstrom / fs (velocities in Angstrom / fs, masses in amu, by default the standard atomic weights).
+
+    With eps_i = 1/2 m_i |v_i|^2 + e_i, differentiating sum_i r_i eps_i along the equations of motion gives
+    J = sum_i eps_i v_i - sum_i q_i,  q_i = sum_{j in row i} d_ij (dE_i/d d_ij . v_j): ``kinetic`` and ``convective`` are the two
+    halves of the first sum, ``virial`` is the second with its sign and ``atomic`` holds the rows q_i.  ANI is strictly local
+    (E_i depends on the displacements of row i alone), so this is exact, needs no absolute positions and holds under periodic
+    boundaries.  e_i is the ensemble-mean network output.  ``include_self_energies=True`` adds the self energy c_{s_i} to e_i,
+    i.e. sum_i c_{s_i} v_i to the flux: in a one-component system that is a constant times the conserved momentum, in a mixture
+    it is a gauge choice (it changes the flux but not the conductivity of a converged Green-Kubo integral), so it is off by
+    default.  One extra evaluation of the model (networks forward and backward), no forces.
+
+    Raises RuntimeError, like ``energies_and_forces``, if an atom has more neighbors than a row holds (one host read, none
+    where no row can overflow): the builder zeroes such a row and the flux would be silently wrong.
+
+    Refused: models with pair potentials (ANI-2xr, ANI-2dr, anything added from ``potentials``), whose pair halves have no
+    flux kernel yet, and a program with more than one rank in torch.distributed's default group (every rank would evaluate
+    the whole system)."""
+    from .md import default_masses
+
+    if not hasattr(model, "heat_flux_terms"):
+        raise NotImplementedError(f"heat flux: {type(model).__name__} has no flux kernel (standalone pair potentials are pair "
+                                  "potentials: only ANI network models are supported)")
+    model._refuse_heat_flux()
+    if masses is None:
+        masses = torch.where(species >= 0, default_masses(model, species).to(torch.float32), torch.ones((), device=species.device))
+    J, q = model.heat_flux_terms(species, coordinates, velocities, masses, cell, pbc, include_self_energies)
+    if not model._overflow_impossible(species, cell, pbc_tuple(pbc)):
+        model.last_flux_neighbors.raise_on_overflow()
+    return HeatFlux(J.sum(dim=1), J[:, 0], J[:, 1], J[:, 2], q)
 
 
 def single_point(model, species: Tensor, coordinates: Tensor, cell: tp.Optional[Tensor] = None,

@@ -25,7 +25,8 @@ deposit.  ``center`` (the centre of a group of atoms, usable wherever a CV takes
 number between two groups) enter the same kernels as sites appended to every entry (csrc/md_sites.hip): a gather in front of
 them, at most two launches, and a spread behind them, one.
 ``attach(observer)`` samples a trajectory on the device inside ``step()`` (md_observe.py, csrc/md_observe.hip): ``TimeSeries``,
-``Trajectory``, ``RadialDistribution``, ``MeanSquaredDisplacement`` and ``VelocityAutocorrelation``.
+``Trajectory``, ``RadialDistribution``, ``MeanSquaredDisplacement``, ``VelocityAutocorrelation``, ``HeatFlux`` and
+``HeatFluxAutocorrelation`` (the last two evaluate the model once more per sample).
 """
 from __future__ import annotations
 
@@ -39,8 +40,8 @@ from torch import Tensor
 from . import _lib
 from .md_bias import (CV, BiasTables, DeviceBias, Metadynamics, Restraint, Site, SiteTables, angle, build_bias_tables,  # noqa: F401
                       build_site_tables, center, coordination, dihedral, distance)
-from .md_observe import (MeanSquaredDisplacement, Observer, RadialDistribution, TimeSeries, Trajectory,  # noqa: F401
-                         VelocityAutocorrelation)
+from .md_observe import (HeatFlux, HeatFluxAutocorrelation, MeanSquaredDisplacement, Observer,  # noqa: F401
+                         RadialDistribution, TimeSeries, Trajectory, VelocityAutocorrelation)
 
 # CODATA 2018: 1 Ha = 4.3597447222071e-18 J, 1 amu = 1.66053906660e-27 kg  ->  (Ha / Angstrom) / amu in Angstrom / fs^2
 ACC_UNIT = 4.3597447222071e-18 / 1e-10 / 1.66053906660e-27 * 1e10 * 1e-30
@@ -680,7 +681,7 @@ class BatchedDynamics:
 
     def attach(self, observer: Observer) -> Observer:
         """Have ``step()`` sample ``observer`` (``TimeSeries``, ``Trajectory``, ``RadialDistribution``,
-        ``MeanSquaredDisplacement``, ``VelocityAutocorrelation``) whenever ``steps_done % observer.every == 0``; returns it."""
+        ``MeanSquaredDisplacement``, ``VelocityAutocorrelation``, ``HeatFlux``, ``HeatFluxAutocorrelation``) whenever ``steps_done % observer.every == 0``; returns it."""
         if not isinstance(observer, Observer):
             raise ValueError(f"attach() takes an observer of torchani_amd.md, got {type(observer).__name__}")
         observer._attach(self)

@@ -4,7 +4,8 @@
 kick, after a metadynamics deposit and after a replica-exchange attempt.  A sample queues work on the stream and never reads on
 the host; ``run()`` reads the observers' status words with its other periodic checks.  ``TimeSeries`` and ``Trajectory`` are
 plain copies into device rings; ``RadialDistribution``, ``MeanSquaredDisplacement`` and ``VelocityAutocorrelation`` run the
-kernels of csrc/md_observe.hip (include/anihip.h has their exact definitions).
+kernels of csrc/md_observe.hip (include/anihip.h has their exact definitions).  ``HeatFlux`` and ``HeatFluxAutocorrelation``
+evaluate the model's flux stage at a sample (anihip_aev_backward_flux, anihip_md_heat_flux): one extra evaluation each.
 """
 from __future__ import annotations
 
@@ -535,3 +536,171 @@ class VelocityAutocorrelation(_Correlation):
         if L < 2:
             raise ValueError("spectrum() needs at least two lags with an origin")
         return cosine_spectrum(self.vacf()[..., :L], self.every * self._need_attached().dt, window)
+
+
+# ---- heat flux -------------------------------------------------------------------------------------------------------------
+def _check_flux(dyn, name: str) -> None:
+    """What the heat-flux observers refuse (host only): everything whose forces carry a flux the model's flux stage does not
+    compute, and models without that stage."""
+    from . import md
+
+    if isinstance(dyn, md.RingPolymerDynamics):
+        raise ValueError(f"{name} is not available on RingPolymerDynamics: the beads are not trajectories, and their springs carry "
+                         "a flux of their own")
+    if dyn._clusters is not None:
+        raise ValueError(f"{name} is not available with constraints: the constraint forces carry a heat flux that is not computed")
+    if dyn._bias is not None:
+        raise ValueError(f"{name} is not available with a bias: the bias forces carry a heat flux that is not computed")
+    if dyn._model_eval.standalone or not hasattr(dyn.model, "heat_flux_terms"):
+        raise ValueError(f"{name}: {type(dyn.model).__name__} is a pair potential, and the pair halves have no flux kernel yet")
+    try:
+        dyn.model._refuse_heat_flux()
+    except NotImplementedError as err:
+        raise ValueError(f"{name}: {err}") from None
+
+
+def _flux_of(dyn) -> Tensor:
+    """J [C, 3, 3] fp64 of the state the dynamics holds (coordinates and velocities of the same instant: after the kick).  One
+    evaluation of the model's flux stage on the stream, no host read."""
+    return dyn.model.heat_flux_terms(dyn.species, dyn.coordinates, dyn.velocities, dyn.masses, dyn.cell, dyn.pbc)[0]
+
+
+class HeatFlux(_Ring):
+    """A device ring of the heat flux J [capacity, C, 3, 3] (fp64, Hartree Angstrom / fs): per entry the kinetic convective
+    term sum_i 1/2 m_i |v_i|^2 v_i, the potential convective term sum_i e_i v_i (e_i: the ensemble-mean network output, no self
+    energies) and the virial term -sum_i sum_j d_ij (dE_i/d d_ij . v_j) -- ``grad.heat_flux`` has the definitions.  A sample
+    evaluates the model's flux stage at the coordinates and velocities held, both after the kick: ONE EXTRA EVALUATION of the
+    model per sample (neighbor rows, AEVs, networks forward and backward, the flux backward in place of the force backward),
+    about the cost of a step; the step itself is untouched.  Works on open molecules and in cells.
+
+    Refused at ``attach``: RingPolymerDynamics, constraints and a bias (their forces carry a flux that is not computed), and
+    models with pair potentials."""
+
+    def __init__(self, every: int, capacity: int, on_full: str = "raise") -> None:
+        super().__init__(every, capacity, on_full)
+        self._buf = None
+
+    def _check(self, dyn) -> None:
+        _check_flux(dyn, "HeatFlux")
+
+    def _allocate(self, dyn) -> None:
+        self._buf = torch.zeros((self.capacity, dyn.species.shape[0], 3, 3), dtype=torch.float64, device=dyn.coordinates.device)
+
+    def _sample(self, dyn) -> None:
+        k = self._slot(dyn)
+        self._buf[k].copy_(_flux_of(dyn))
+
+    def values(self) -> Tensor:
+        """fp64 [n, C, 3, 3], oldest first: (kinetic, convective, virial) x (x, y, z)."""
+        self._need_attached()
+        return self._ordered(self._buf)
+
+    def total(self) -> Tensor:
+        """fp64 [n, C, 3]: J, the sum of the three terms."""
+        return self.values().sum(dim=2)
+
+
+class HeatFluxAutocorrelation(Observer):
+    """<J(0) . J(t)> over multiple time origins, and the Green-Kubo thermal conductivity from it.  Every ``every`` steps the
+    total heat flux J [C, 3] (see ``HeatFlux``: one extra evaluation of the model per sample) goes into a device ring of the
+    last ``lags`` samples and its dot products with the ring are added to the sums [C, lags] (fp64): plain torch on the stream,
+    the ring slot and the lags that exist come from the host-side sample count, nothing is read on the host.
+
+    ``hfacf()`` [C, lags] is the average over the origins (``origins()``, NaN at a lag without one) in (Hartree Angstrom / fs)^2,
+    ``thermal_conductivity()`` its running integral 1 / (3 V k_B T^2) int_0^t <J(0) . J(s)> ds in W / (m K).
+
+    Refused at ``attach``: what ``HeatFlux`` refuses, a barostat (V and J's normalization move with the cell) and a cell that
+    is not periodic in all three directions (no volume)."""
+
+    def __init__(self, lags: int, every: int) -> None:
+        super().__init__(every)
+        self.lags = _positive_int(lags, "lags")
+        self._ring = self._sums = None
+        self._dt = None
+
+    def _check(self, dyn) -> None:
+        name = "HeatFluxAutocorrelation"
+        _check_flux(dyn, name)
+        if dyn.barostat:
+            raise ValueError(f"{name} is not available with a barostat: the volume that normalizes the conductivity moves")
+        if dyn.cell is None or dyn.pbc is None or not all(dyn.pbc):
+            raise ValueError(f"{name} needs a cell that is periodic in all three directions: an open system has no volume to "
+                             "normalize the conductivity by (HeatFlux records J without one)")
+
+    def _allocate(self, dyn) -> None:
+        self._init_buffers(dyn.species.shape[0], dyn.coordinates.device, dyn.dt)
+        self._temp_sum = torch.zeros(dyn.species.shape[0], dtype=torch.float64, device=dyn.coordinates.device)
+
+    def _init_buffers(self, n_entries: int, device, dt: float) -> None:
+        self._ring = torch.zeros((self.lags, n_entries, 3), dtype=torch.float64, device=device)
+        self._sums = torch.zeros((n_entries, self.lags), dtype=torch.float64, device=device)
+        self._lag_index = torch.arange(self.lags, device=device)
+        self._dt = float(dt)
+
+    def _push(self, j: Tensor) -> None:
+        """One sample J [C, 3] (fp64, on the device of the ring): ring slot k mod M, then S[c, l] += J . ring[(k - l) mod M] for
+        the lags l = 0 .. min(k, M - 1) that exist, k the host-side sample count."""
+        k, M = self.n_samples, self.lags
+        cur = k % M
+        self._ring[cur].copy_(j)
+        n = min(k, M - 1) + 1
+        slots = torch.remainder(cur - self._lag_index[:n], M)
+        self._sums[:, :n] += (self._ring.index_select(0, slots) * self._ring[cur]).sum(dim=-1).t()
+        self.n_samples += 1
+
+    def _sample(self, dyn) -> None:
+        self._temp_sum.add_(dyn.temperatures())
+        self._push(_flux_of(dyn).sum(dim=1))
+
+    def reset(self) -> None:
+        super().reset()
+        if self._sums is not None:
+            self._sums.zero_()
+            self._ring.zero_()
+            if self._dyn is not None:
+                self._temp_sum.zero_()
+
+    # ---- results -------------------------------------------------------------------------------------------------------
+    def _need_buffers(self) -> None:
+        if self._sums is None:
+            raise ValueError("attach the observer to a dynamics first: dyn.attach(observer)")
+
+    def origins(self) -> Tensor:
+        """int64 [M] (host): time origins per lag."""
+        return origins(self.n_samples, self.lags)
+
+    def times(self) -> Tensor:
+        """fp64 [M] (host): l every dt, in fs."""
+        self._need_buffers()
+        return torch.arange(self.lags, dtype=torch.float64) * (self.every * self._dt)
+
+    def hfacf(self) -> Tensor:
+        """fp64 [C, M], (Hartree Angstrom / fs)^2: <J(0) . J(l every dt)>, NaN at a lag without an origin."""
+        self._need_buffers()
+        n_l = self.origins().to(self._sums.device).double()
+        return torch.where(n_l > 0, self._sums / n_l.clamp(min=1.0), torch.full_like(self._sums, float("nan")))
+
+    def mean_temperatures(self) -> Tensor:
+        """fp64 [C], K: the mean of ``temperatures()`` over the samples."""
+        self._need_attached()
+        return self._temp_sum / max(self.n_samples, 1)
+
+    def thermal_conductivity(self, temperature=None, volume=None) -> Tensor:
+        """fp64 [C, M], W / (m K): kappa(t_l) = 1 / (3 V k_B T^2) int_0^{t_l} <J(0) . J(s)> ds by the trapezoid rule over the
+        lags.  T: ``temperature`` (a number or [C]), else the thermostat's target, else -- NVE -- the mean kinetic temperature
+        of the samples.  V: ``volume`` (Angstrom^3), else the cell's.  A running integral: read it where it has reached its
+        plateau and before the noise of the tail takes over; NaN from the first lag without an origin on."""
+        from .md import KB_HARTREE
+        from .units import HARTREE_PER_ANGSTROM_FS_KELVIN_TO_WATT_PER_METER_KELVIN as TO_SI
+
+        h = self.hfacf()
+        dev = h.device
+        if temperature is None:
+            dyn = self._need_attached()
+            temperature = dyn.temperature.double() if dyn.langevin else self.mean_temperatures()
+        if volume is None:
+            volume = self._need_attached().volumes()
+        T = torch.as_tensor(temperature, dtype=torch.float64, device=dev).reshape(-1, 1)
+        V = torch.as_tensor(volume, dtype=torch.float64, device=dev).reshape(-1, 1)
+        integral = (torch.cumsum(h, dim=1) - 0.5 * (h[:, :1] + h)) * (self.every * self._dt)
+        return integral * (TO_SI / (3.0 * KB_HARTREE)) / (V * T * T)

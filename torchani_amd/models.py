@@ -16,6 +16,7 @@ from __future__ import annotations
 import math
 import typing as tp
 import warnings
+from ctypes import byref as C_byref
 
 import numpy as np
 import torch
@@ -553,6 +554,83 @@ class ANI(torch.nn.Module):
             energies = energy_forces_finish(given, atomic_e, sae, acc, lo, hi)
         aevc._last_neighbors = nbrs
         return _LocalStage(net_e, atomic_e, energies, virial)
+
+    def _flux_stage(self, species: Tensor, c32: Tensor, v32: Tensor, cell, pbc_t,
+                    order: tp.Optional[tp.Tuple[int, ...]], tile_hint: int) -> tp.Tuple[Tensor, Tensor, tp.Any]:
+        """The sibling of ``_local_stage`` behind the heat flux, for all atoms of one rank: neighbor rows -> AEV rows and slab
+        flags -> networks forward + backward -> AevEngine.backward_flux.  Returns (net_e [n] fp32, q [n, 3] fp32, the neighbor
+        rows, whose status word says whether a row overflowed) with q_i = sum_j d_ij (dE_i/d d_ij . v_j).  It writes nothing the force step reads: buffers of its own, not the engine's kept
+        AEV rows, and ``last_neighbors`` stays the step's."""
+        aevc = self.aev_computer
+        eng = aevc.engine()
+        dev = c32.device
+        n = species.numel()
+        nbrs = aevc.neighbor_rows(species, c32, cell, pbc_t, lo=0, hi=n)
+        packed = self.neural_networks._pack(dev, order)
+        slab_mask = None
+        plain = self._plain_slabs(eng, packed)
+        if packed.radial_len == 16 * eng.params.num_species and eng.tuned and eng.n_slabs <= 32:
+            slab_mask = torch.empty(n, dtype=torch.int32, device=dev)
+        elif plain:
+            slab_mask = torch.zeros(n, dtype=torch.int32, device=dev)
+        aev = eng.forward(species, nbrs, slab_mask=slab_mask, shard_rows=True)
+        net_e, grad_aev, _ = packed.forward_backward(species, aev, lo=0, hi=n, want_grad=True, chunk=self.mlp_chunk,
+                                                     slab_mask=slab_mask, shard_rows=True, tile_hint=tile_hint,
+                                                     plain_slabs=plain)
+        if plain:
+            slab_mask = None
+        q = eng.backward_flux(species, nbrs, grad_aev, v32, slab_mask=slab_mask, shard_rows=True)
+        return net_e, q, nbrs
+
+    def _refuse_heat_flux(self, group=None) -> None:
+        """The heat flux is refused on the host where a term of it has no kernel."""
+        pairs = [k for k, p in self.potentials.items() if k != "nnp" and p._enabled]
+        if pairs:
+            raise NotImplementedError(f"heat flux: the model has pair potentials ({', '.join(pairs)}), whose pair halves have no "
+                                      "flux kernel yet -- only the network part (ANI-1x, ANI-2x, ...) is supported")
+        # (the group given, or the default group of a program that has one: every rank would evaluate the whole system)
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            raise NotImplementedError("heat flux: more than one rank is not supported (the rows of a shard would need the "
+                                      "velocities of its halo)")
+
+    @torch.no_grad()
+    def heat_flux_terms(self, species: Tensor, coords: Tensor, velocities: Tensor, masses: Tensor,
+                        cell: tp.Optional[Tensor] = None, pbc=None, include_self_energies: bool = False,
+                        group=None) -> tp.Tuple[Tensor, Tensor]:
+        """(J [C, 3, 3] fp64: kinetic convective, potential convective, virial term; q [C, A, 3] fp32) -- grad.heat_flux
+        and md.HeatFlux document the definitions.  masses fp32 [C, A] on the device.  No host synchronization for systems
+        below 16 384 atoms; above, what ``energies_and_forces`` reads once per species tensor.  The neighbor rows of the evaluation
+        are kept as ``last_flux_neighbors``: the status word of a row over capacity (zeroed by the builder) is theirs, read by
+        ``grad.heat_flux``; an observer's sample sits at the coordinates of the step, whose rows ``run()`` checks."""
+        from .engine import _ptr, _stream
+
+        self._refuse_heat_flux(group)
+        if not coords.is_cuda:
+            raise ValueError("torchani_amd's engine needs tensors on a ROCm device (no CPU fallback)")
+        pbc_t = pbc_tuple(pbc)
+        species32 = self._elem_idxs(species).to(torch.int32).contiguous()
+        Cn, A = species32.shape
+        c32 = coords.detach().to(torch.float32).contiguous()
+        v32 = velocities.detach().to(torch.float32).contiguous()
+        m32 = masses.detach().to(device=c32.device, dtype=torch.float32).contiguous()
+        if tuple(v32.shape) != (Cn, A, 3) or tuple(m32.shape) != (Cn, A):
+            raise ValueError(f"expected velocities {(Cn, A, 3)} and masses {(Cn, A)}")
+        hint = 0 if torch.cuda.is_current_stream_capturing() else self._tile_hint(species, species32, species32.numel())
+        if self.two_product_backward:
+            hint |= _lib.MLP_FLAG_BWD_TWO_PRODUCTS
+        sp_e, order = self._engine_species(species32, species)
+        net_e, q, self.__dict__["last_flux_neighbors"] = self._flux_stage(sp_e, c32, v32.view(-1, 3), cell, pbc_t, order, hint)
+        e64 = net_e.view(Cn, A).to(torch.float64)
+        if include_self_energies and self.energy_shifter._enabled:
+            e64 = e64 + self._sae64(c32.device)[species32.clamp(min=0).long()]
+        e64 = e64.contiguous()
+        out = torch.empty((Cn, 3, 3), dtype=torch.float64, device=c32.device)
+        params = _lib.MdParams(Cn, A, 0, 0, 1.0, 0, 0)
+        ws = torch.empty(_lib.lib().anihip_md_heat_flux_workspace_bytes(Cn, A), dtype=torch.uint8, device=c32.device)
+        _lib.check(_lib.lib().anihip_md_heat_flux(_stream(), C_byref(params), _ptr(m32), _ptr(e64), _ptr(species32), _ptr(v32),
+                                                  _ptr(q), _ptr(out), _ptr(ws), ws.numel()))
+        return out, q.view(Cn, A, 3)
 
     # ---- one big system on several ranks: spatial shards + halo (parallel.SpatialShards) ---------------------------
     partition = "spatial"   # "index": contiguous index ranges + one all-reduce of the whole force array (round-2 scheme)

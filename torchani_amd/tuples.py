@@ -57,6 +57,18 @@ class FusedEnergiesForces(tp.NamedTuple):
     virial: tp.Optional[Tensor] = None   # [3,3] float64 Hartree (stress=True): dE/d strain; stress = virial / volume
 
 
+class HeatFlux(tp.NamedTuple):
+    """What grad.heat_flux returns, in Hartree Angstrom / fs: total = kinetic + convective + virial [C, 3] (float64), the
+    convective terms sum_i 1/2 m_i |v_i|^2 v_i and sum_i e_i v_i, the virial term -sum_i q_i, and atomic [C, A, 3] (float32),
+    the rows q_i = sum_j d_ij (dE_i/d d_ij . v_j)."""
+
+    total: Tensor
+    kinetic: Tensor
+    convective: Tensor
+    virial: Tensor
+    atomic: Tensor
+
+
 class SpeciesForces(tp.NamedTuple):
     """members_forces: energies [M, C], forces [M, C, A, 3] (torchani/tuples.py)."""
 

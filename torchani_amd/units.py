@@ -34,6 +34,11 @@ SQRT_MHESSIAN_TO_INVCM = math.sqrt(HARTREE_TO_JOULE / AMU_TO_KG) / ANGSTROM_TO_M
 SQRT_MHESSIAN_TO_MILLIEV = SQRT_MHESSIAN_TO_INVCM * INVCM_TO_EV * 1000.0
 # Hartree / Angstrom^2 -> mDyne / Angstrom (~4.36)
 MHESSIAN_TO_FCONST = HARTREE_TO_JOULE * NEWTON_TO_MILLIDYNE / ANGSTROM_TO_METER
+# thermal conductivity from a Green-Kubo integral in the units of the MD engine: J in Hartree Angstrom / fs, V in Angstrom^3,
+# t in fs and k_B in Hartree / K (md.KB_HARTREE) give  1 / (3 V k_B T^2) int <J(0) . J(t)> dt  in Hartree / (Angstrom fs K).
+# With the CODATA 2018 Hartree of md.ACC_UNIT, 1 Ha = 4.3597447222071e-18 J, 1 Angstrom = 1e-10 m and 1 fs = 1e-15 s:
+# 1 Ha / (Angstrom fs K) = 4.3597447222071e-18 J / (1e-10 m 1e-15 s K) = 4.3597447222071e7 W / (m K)
+HARTREE_PER_ANGSTROM_FS_KELVIN_TO_WATT_PER_METER_KELVIN = 4.3597447222071e-18 / (1e-10 * 1e-15)
 
 # older names of the reference
 HARTREE_TO_KCALMOL = HARTREE_TO_KCALPERMOL
