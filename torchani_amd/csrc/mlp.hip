@@ -2149,13 +2149,21 @@ static int cu_count(int *n_cus)
 }
 
 // the fused network kernel's arguments common to inference and training (the species' networks, the workspace, the AEV
-// rows); returns the dynamic LDS bytes of tiles of `rows` atoms
-static size_t fused_args(const anihip_mlp_desc *d, const MlpWorkspace &w, const float *aev, int rows, FusedArgs &f)
+// rows); *lds_bytes = the dynamic LDS bytes of tiles of `rows` atoms
+static int fused_args(const anihip_mlp_desc *d, const MlpWorkspace &w, const float *aev, int rows, FusedArgs &f, size_t *lds_bytes)
 {
     size_t lds = 0;
     for (int s = 0; s < d->num_species; ++s) {
         const anihip_species_net &nn = d->net[s];
         FusedSpecies &fs = f.sp[s];
+        // The kernel folds the operand scales into constants of its epilogues and undoes them by exponent arithmetic
+        // (csrc/mlp_fused.hip: FOLD, pow2_recip), which is exact for powers of two only.  The library's packers choose such
+        // scales (csrc/pack.hip: ldexpf); a caller's own planes must do the same.
+        for (int l = 0; l < 3; ++l) {
+            int e = 0;
+            ANIHIP_REQUIRE(frexpf(nn.wh_scale[l], &e) == 0.5f && e > -125 && e < 127,
+                           "species %d layer %d: the fp16 weight scale %g is no power of two", s, l, (double)nn.wh_scale[l]);
+        }
         fs.H1 = nn.dims[1]; fs.H2 = nn.dims[2]; fs.H3 = nn.dims[3];
         fs.w0 = (const _Float16 *)nn.whf[0];
         fs.w1 = (const _Float16 *)nn.whf[1]; fs.w2 = (const _Float16 *)nn.whf[2];
@@ -2171,7 +2179,8 @@ static size_t fused_args(const anihip_mlp_desc *d, const MlpWorkspace &w, const 
     f.kp_rad = d->aev_radial_len; f.n_slabs = layer0_width(d, true) / 32;
     f.tile_tab = w.tile_tab; f.tile_rows = w.tile_rows; f.member_part = w.member_part;
     f.S = d->num_species; f.M = d->n_members; f.alpha = d->celu_alpha; f.inv_alpha = 1.0f / d->celu_alpha;
-    return lds;
+    *lds_bytes = lds;
+    return 0;
 }
 
 // what k_fused_finish (or the extra workgroups of k_gemm_l0s) needs to sum the per-member energies of the fused kernel
@@ -2287,7 +2296,8 @@ static int fb_fused(const FbCall &c, const FbPlan &p, const MlpWorkspace &w)
 {
     const anihip_mlp_desc *d = c.d;
     FusedArgs f{};
-    const size_t lds = fused_args(d, w, c.aev, FUSED_ROWS, f);
+    size_t lds = 0;
+    if (fused_args(d, w, c.aev, FUSED_ROWS, f, &lds)) return 1;
     f.slab_mask = p.mask_tab ? c.slab_mask : nullptr;
     f.d0 = p.fused_l0b ? nullptr : w.act[0]; f.ld0 = w.ld[0]; f.d0_tm = p.d0_tm ? 1 : 0;
     f.want_grad = c.grad_aev ? 1 : 0; f.l0b = p.fused_l0b ? 1 : 0; f.grad_aev = c.grad_aev;
@@ -2459,7 +2469,8 @@ static int train_forward_fused(hipStream_t stream, const anihip_mlp_desc *d, int
     const int ani_species = (lo == 0 && hi == n_atoms && kp_rad == 16 * S && kp_rad > 0) ? S : 0;
     launch_tile_table(stream, w.ctl, S, w.perm, nullptr, all_slabs, (int)tiles, FUSED_ROWS, w.tile_tab, w.tile_rows, ani_species);
     FusedArgs f{};
-    const size_t lds = fused_args(d, w, aev, FUSED_ROWS, f);
+    size_t lds = 0;
+    if (fused_args(d, w, aev, FUSED_ROWS, f, &lds)) return 1;
     f.slab_mask = nullptr;
     f.d0 = dlt[0]; f.ld0 = w.ld[0]; f.d0_tm = 0;
     f.want_grad = 1; f.owner = 0; f.l0b = 0; f.grad_aev = nullptr;

@@ -57,11 +57,41 @@ __device__ __forceinline__ float wave_max_nonneg(float v)
     return __int_as_float(max(m01, m23));
 }
 
+// A register that NO instruction of this path reads, defined without an instruction: the empty asm is a definition to the
+// compiler (the value is whatever the register held), so an array is "defined at every join" and nothing of an earlier
+// item or row block stays live through it -- without the v_mov zero fills that did the same.  Only for values whose every reader
+// sits under the wave-uniform condition of the writer that did define them (rule v: the audited sites).
+template <class T>
+__device__ __forceinline__ void never_read(T &x)
+{
+    asm volatile("" : "=v"(x));   // (volatile: equal empty statements are otherwise merged into one value and copied)
+}
+
+// (four floats of an array as ONE 128-bit definition: defined one by one, the derivative arrays cost two more vector registers
+// in the 192- and 224-wide instantiations)
+__device__ __forceinline__ void never_read4(float *x)
+{
+    v4f t;
+    never_read(t);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = t[i];
+}
+
 __device__ __forceinline__ float pow2_scale_for(float mx)
 {
     if (!(mx > 0.f)) return 1.0f;
     const int e = (int)(__float_as_uint(mx) >> 23) - 127;
     return __uint_as_float((unsigned)(127 + 13 - e) << 23);
+}
+
+// 1 / s of a NORMAL power of two s with an exponent of 2^-126 .. 2^126: one integer subtraction on the exponent field.  There
+// x * pow2_recip(s) is x / s bit for bit -- both are x with its exponent moved -- where the division is a sequence of ten vector
+// instructions.  (pow2_scale_for leaves that range for maxima below about 2^-113, where 140 - e no longer fits the exponent
+// field: its result is then no power of two and neither form means anything, before and after this function.  The host checks
+// the weight scales; s2 .. s4 come from the pack's bounds, which for any trained network are far inside the range.)
+__device__ __forceinline__ float pow2_recip(float s)
+{
+    return __uint_as_float(0x7F000000u - __float_as_uint(s));
 }
 
 // ---- GEMM machinery of the fused kernel: v_mfma_f32_16x16x32_f16 ----------------------------------------------------------
@@ -460,6 +490,10 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
     using C = FusedCfg<RB, NB>;
     static_assert(NB == 1, "the 16 x 16 x 32 machinery is written for one column block per wave");
     constexpr int NW = C::NW, ROWS = C::ROWS, D = C::DEPTH, SLAB = C::SLAB, NE = RB * NB;
+    // Power-of-two operand scales folded into constants the epilogues multiply by anyway (put_acc's PRE form; DESIGN section 3,
+    // rule iv).  Not in the training instantiation, which stores the unscaled activations and gradients from the same
+    // registers; FOLD1 (act1) is written for CELU.
+    constexpr bool FOLD = !TRAIN, FOLD1 = FOLD && ACT == 0;
     typedef WRing<D> Ring;
     extern __shared__ __attribute__((aligned(16))) _Float16 fsm_all[];
     unsigned *s_tab = reinterpret_cast<unsigned *>(fsm_all);
@@ -641,12 +675,14 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         fetch_group(vb);
     };
     // (an item that needs no slabs still DEFINES the registers: a path that leaves them undefined would carry the previous
-    // item's values around the item loop and hold 24 VGPRs through every phase)
+    // item's values around the item loop and hold 24 VGPRs through every phase.  Defined without an instruction: the next
+    // item is another member of a tile whose operand is kept, so it stages nothing and runs one pair of slabs -- it neither
+    // stores nor refetches them before the end of its own phase 5 defines them again)
     auto no_aev = [&]() {
 #pragma unroll
         for (int j = 0; j < FR_GROUP; ++j) {
-            va[j] = v4f{0.f, 0.f, 0.f, 0.f};
-            vb[j] = v4f{0.f, 0.f, 0.f, 0.f};
+            never_read(va[j]);
+            never_read(vb[j]);
         }
     };
     // first D weight fragments of layer 0 of an item
@@ -774,7 +810,11 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             return __uint_as_float(s_max);
         };
         // acc * scale -> split planes of X (row stride ldx): this lane's runs of 4 columns of its unit
-        auto put_acc = [&](_Float16 *X, int plane, int ldx, float scale, const FusedUnit &u) {
+        // PRE (std::true_type): the accumulators already carry the scale -- every operand scale is a power of two, and the
+        // epilogue that formed them folded it into a constant it multiplies by anyway (same bits, no v_pk_mul_f32 here); `scale`
+        // is then unused
+        auto put_acc = [&](_Float16 *X, int plane, int ldx, float scale, const FusedUnit &u, auto pre_) {
+            constexpr bool PRE = decltype(pre_)::value;
             // this lane's run 0 of the unit (halves from X), formed ONCE per call and opaque from there on: the eight runs of a row
             // block differ from it by compile-time multiples of ldx and of 16 columns (the swizzle touches bit 0 of the chunk index
             // only, the column half adds two chunks) -- immediates of the ds_write.  Left visible, the whole sum is rebuilt from
@@ -794,16 +834,21 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         typedef float v2f_ __attribute__((ext_vector_type(2)));
                         typedef _Float16 h2_ __attribute__((ext_vector_type(2)));
                         const v2f_ x = v2f_{ACC(acc[rb], 4 * q + e), ACC(acc[rb], 4 * q + e + 1)};
-                        const h2_ h = __builtin_convertvector(x * scale, h2_);
+                        const h2_ h = __builtin_convertvector(PRE ? x : x * scale, h2_);
                         hi[e] = h[0];
                         hi[e + 1] = h[1];
                         // (written out: left to itself hipcc converts hi back to fp32 and packs again, 2 more
                         // instructions per pair)
                         h2_ l;
-                        asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]"
-                            : "=v"(l) : "v"(x[0]), "v"(scale), "v"(h));
-                        asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-                            : "+v"(l) : "v"(x[1]), "v"(scale), "v"(h));
+                        if constexpr (PRE) {
+                            asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x[0]), "v"(h));
+                            asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x[1]), "v"(h));
+                        } else {
+                            asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]"
+                                : "=v"(l) : "v"(x[0]), "v"(scale), "v"(h));
+                            asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+                                : "+v"(l) : "v"(x[1]), "v"(scale), "v"(h));
+                        }
                         lo[e] = l[0];
                         lo[e + 1] = l[1];
                     }
@@ -920,8 +965,12 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         const float ia_log2e = inv_alpha * 1.44269504f;
         // two elements at a time: bias + scale, the exponent argument and alpha (e - 1) as packed fp32 operations
         typedef float v2f __attribute__((ext_vector_type(2)));
-        auto celu_d2 = [&](float a0, float a1, float osc, float b0, float b1, float &y0, float &y1, float &dd0,
-                           float &dd1) {
+        // (tsc, al: the exponent's factor and alpha.  ia_log2e and alpha for the activation itself; an epilogue that wants
+        // S x activation for a power of two S passes osc S, b S, ia_log2e / S and alpha S: every intermediate is S times what it
+        // was -- scaling by a power of two commutes with the rounding of fma, mul and med3 -- and the exponent's argument, hence the
+        // derivative, is the same bit for bit)
+        auto celu_d2 = [&](float a0, float a1, float osc, float b0, float b1, float tsc, float al, float &y0, float &y1,
+                           float &dd0, float &dd1) {
             const v2f x = v2f{a0, a1} * osc + v2f{b0, b1};
             if constexpr (ACT == 1) {
                 // gelu(x) = x Phi(x), gelu'(x) = Phi(x) + x phi(x)   (torch.nn.GELU(), approximate = 'none')
@@ -931,13 +980,23 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                 const v2f y = x * ph, d = ph + x * g2;
                 y0 = y.x; y1 = y.y; dd0 = d.x; dd1 = d.y;
             } else {
-                const v2f t = x * ia_log2e;
+                const v2f t = x * tsc;
                 const v2f e = v2f{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                const v2f y = e * alpha - alpha;
+                const v2f y = e * al - al;
                 dd0 = fminf(e.x, 1.0f);
                 dd1 = fminf(e.y, 1.0f);
                 y0 = __builtin_amdgcn_fmed3f(x.x, y.x, 0.f);
                 y1 = __builtin_amdgcn_fmed3f(x.y, y.y, 0.f);
+            }
+        };
+        // The derivatives of a row block the wave has no unit in: nobody reads them, they are defined for the join.  Without an
+        // instruction in the instantiations with phase 5 (the large-system kernels); the others keep the zero fill -- there the
+        // empty definitions cost the GELU instantiation two vector registers
+        auto no_deriv = [&](float (&d)[16]) {
+#pragma unroll
+            for (int r = 0; r < 16; r += 4) {
+                if constexpr (L0B) never_read4(&d[r]);
+                else d[r] = d[r + 1] = d[r + 2] = d[r + 3] = 0.f;
             }
         };
         float d0f[NE][16];   // celu'(act0) of this lane's elements
@@ -962,17 +1021,15 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         for (int r = 0; r < 16; r += 2) {
                             const int i = rb * NB + nb;
                             float v0, v1;
-                            celu_d2(ACC(acc[i], r), ACC(acc[i], r + 1), oscale, bias0[nb][r], bias0[nb][r + 1], v0, v1, d0f[i][r],
-                                    d0f[i][r + 1]);
+                            celu_d2(ACC(acc[i], r), ACC(acc[i], r + 1), oscale, bias0[nb][r], bias0[nb][r + 1], ia_log2e, alpha, v0, v1,
+                                    d0f[i][r], d0f[i][r + 1]);
                             ACC(acc[i], r) = v0;
                             ACC(acc[i], r + 1) = v1;
                             if (NB == 1 || nb < u1.nba) vmax = __builtin_fmaxf(vmax, __builtin_fmaxf(v0, v1));
                         }
-                } else {   // (defined on every path, like the rings)
+                } else {   // (defined on every path, like the rings; read under rb < u1.nrb only: phase 4)
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) d0f[rb * NB + nb][r] = 0.f;
+                    for (int nb = 0; nb < NB; ++nb) no_deriv(d0f[rb * NB + nb]);
                 }
             }
             if constexpr (TRAIN) store_rows(ka->tr_act[0], ka->tr_ld[0], H1, u1);
@@ -991,7 +1048,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             ANIHIP_STAMP(trace, 24);
         }
         const float s0 = pow2_scale_for(a0max);
-        put_acc(X0, x0_plane, ld0, s0, u1);
+        put_acc(X0, x0_plane, ld0, s0, u1, std::false_type{});   // (the one scale that waits for the tile maximum)
         ANIHIP_STAMP(trace, 25);
         // the scales of the inner GEMM operands follow from a0max and the weight-norm bounds: no more reductions
         const float s1 = pow2_scale_for(__builtin_fmaf(a0max, bnd[0], bnd[1]));   // |act1| <= a0max ||W1||_inf + |b1|
@@ -1013,7 +1070,17 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         fr_ring<D>(r2, fs->w2, (int64_t)(H3 >> 5) * (H2 >> 4) * 2 * FRAG, m, H2 >> 4, u3.cb, lane, u3.nba);
         float d1f[NE][16];   // celu'(act1) of this lane's elements
         {
-            const float oscale = fs->is1 / s0;
+            // FOLD1: act1 leaves the activation as s1 act1 (celu_d2), the split takes it as it is
+            const float f1 = FOLD1 ? s1 : 1.0f;
+            // (the exponent's factor keeps its division: with pow2_recip here the 192- or the 224-wide instantiation, whichever way
+            // it is written, takes two more vector registers -- tried five ways, profiles/fused_isa_budget.txt)
+            const float oscale = fs->is1 * pow2_recip(s0) * f1, tsc1 = FOLD1 ? ia_log2e / s1 : ia_log2e, al1 = alpha * f1;
+            if constexpr (FOLD1) {   // (sixteen entries, eight registers: the two row halves of a column half share theirs)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) bias1[nb][r] *= s1;
+            }
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 if (rb < u2.nrb) {   // (one branch per row block: see the layer-0 epilogue)
@@ -1023,21 +1090,19 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         for (int r = 0; r < 16; r += 2) {
                             const int i = rb * NB + nb;
                             float y0, y1;
-                            celu_d2(ACC(acc[i], r), ACC(acc[i], r + 1), oscale, bias1[nb][r], bias1[nb][r + 1], y0, y1, d1f[i][r],
-                                    d1f[i][r + 1]);
+                            celu_d2(ACC(acc[i], r), ACC(acc[i], r + 1), oscale, bias1[nb][r], bias1[nb][r + 1], tsc1, al1, y0, y1,
+                                    d1f[i][r], d1f[i][r + 1]);
                             ACC(acc[i], r) = y0;
                             ACC(acc[i], r + 1) = y1;
                         }
-                } else {   // (defined on every path, like the rings)
+                } else {   // (defined on every path, like the rings; read under rb < u2.nrb only: phase 3)
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) d1f[rb * NB + nb][r] = 0.f;
+                    for (int nb = 0; nb < NB; ++nb) no_deriv(d1f[rb * NB + nb]);
                 }
             }
             if constexpr (TRAIN) store_rows(ka->tr_act[1], ka->tr_ld[1], H2, u2);
             ANIHIP_STAMP(trace, 26);
-            put_acc(X1, x1_plane, ld1, s1, u2);
+            put_acc(X1, x1_plane, ld1, s1, u2, std::bool_constant<FOLD1>{});
             ANIHIP_STAMP(trace, 27);
         }
         __syncthreads();  // X1 complete; every wave is done reading X0 -> XU reusable
@@ -1057,8 +1122,14 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             // e = sum_col act2 * w3 (+ b3): per-lane partial over its columns of each of its two rows of a row block, the four
             // lanes of a row (c4 = 0..3) combined with two lane swaps, the waves through LDS in a fixed order (deterministic sum).
             // seed: d act2 = w3 * celu'(act2) / M, kept in the accumulators
-            const float osc2 = fs->is2 / s1;
-            const float invM = 1.0f / (float)Mi;
+            const float osc2 = fs->is2 * pow2_recip(s1);
+            // FOLD: the seed leaves as s2 d act2 -- s2 goes into the factor 1 / M of the output weights, once per item
+            const float invM = 1.0f / (float)Mi * (FOLD ? s2 : 1.0f);
+            float w3m[NB][16];   // (sixteen entries, eight registers)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) w3m[nb][r] = invM * w3[nb][r];
             float e_loc[RB];   // [row block]: lanes with c4 = rt hold the sum of row half rt
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
@@ -1070,11 +1141,11 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         for (int r = 0; r < 16; r += 2) {
                             const int i = rb * NB + nb, rt = (r >> 2) & 1;
                             float y0, y1, dy0, dy1;
-                            celu_d2(ACC(acc[i], r), ACC(acc[i], r + 1), osc2, bias2[nb][r], bias2[nb][r + 1], y0, y1, dy0, dy1);
+                            celu_d2(ACC(acc[i], r), ACC(acc[i], r + 1), osc2, bias2[nb][r], bias2[nb][r + 1], ia_log2e, alpha, y0, y1, dy0, dy1);
                             e[rt] = __builtin_fmaf(y0, w3[nb][r], e[rt]);
                             e[rt] = __builtin_fmaf(y1, w3[nb][r + 1], e[rt]);
-                            ACC(acc[i], r) = invM * w3[nb][r] * dy0;
-                            ACC(acc[i], r + 1) = invM * w3[nb][r + 1] * dy1;
+                            ACC(acc[i], r) = w3m[nb][r] * dy0;
+                            ACC(acc[i], r + 1) = w3m[nb][r + 1] * dy1;
                             if constexpr (TRAIN) {   // act2 leaves from here (the accumulators take the backward seed)
                                 const int row = urow(u3, rb, r >> 2);
                                 float *dst = ka->tr_act[2] + (int64_t)(p0 + min(row, n_rows - 1)) * ka->tr_ld[2] + (int64_t)m * H3 +
@@ -1103,7 +1174,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             }
             if constexpr (TRAIN) store_rows(ka->tr_dlt[2], ka->tr_ld[2], H3, u3);
             ANIHIP_STAMP(trace, 28);
-            if (ka->want_grad) put_acc(X2, x2_plane, ld2, s2, u3);   // (XU: X0 is dead since the last barrier)
+            if (ka->want_grad) put_acc(X2, x2_plane, ld2, s2, u3, std::bool_constant<FOLD>{});   // (XU: X0 is dead since the last barrier)
             ANIHIP_STAMP(trace, 29);
         }
         __syncthreads();
@@ -1126,18 +1197,23 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         fr_ring<D>(r4, fs->w1t, (int64_t)(H1 >> 5) * (H2 >> 4) * 2 * FRAG, m, H2 >> 4, u1.cb, lane, u1.nba);
         if (ka->want_grad) {
             if (u2.nrb > 0) {
-                const float osc3 = fs->is2 / s2;
+                // FOLD: the accumulators take the derivative only; the two powers of two, the GEMM's scale back and the split's
+                // scale, are one scalar that the split multiplies by
+                const float osc3 = fs->is2 * pow2_recip(s2);
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
                     if (rb >= u2.nrb) continue;
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) ACC(acc[rb * NB + nb], r) *= osc3 * d1f[rb * NB + nb][r];
+                        for (int r = 0; r < 16; ++r) {
+                            if constexpr (FOLD) ACC(acc[rb * NB + nb], r) *= d1f[rb * NB + nb][r];
+                            else ACC(acc[rb * NB + nb], r) *= osc3 * d1f[rb * NB + nb][r];
+                        }
                 }
                 if constexpr (TRAIN) store_rows(ka->tr_dlt[1], ka->tr_ld[1], H2, u2);
                 ANIHIP_STAMP(trace, 30);
-                put_acc(X1, x1_plane, ld1, s3, u2);   // (X1: its last readers finished before the previous barrier)
+                put_acc(X1, x1_plane, ld1, FOLD ? osc3 * s3 : s3, u2, std::false_type{});   // (X1: its last readers finished before the previous barrier)
                 ANIHIP_STAMP(trace, 31);
             }
         }
@@ -1192,18 +1268,26 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
             ring5(max(slab, 0));   // (travels during the epilogue below; requested behind it instead: no faster, measured)
             ANIHIP_STAMP(trace, 16);
             if (ka->want_grad && u1.nrb > 0) {
-                const float osc4 = fs->is1 / s3;
+                // (as in phase 3: the derivative here, osc4 s4 in the split -- without `if constexpr (FOLD)`: phase 5 does not exist
+                // in the training instantiation, static_assert(!TRAIN || !L0B) above, so FOLD is true here.  Row blocks the wave has
+                // no unit in are skipped: their derivative registers are not defined by any instruction)
+                static_assert(FOLD, "phase 4 of the phase-5 instantiations hands its scales to put_acc");
+                const float osc4 = fs->is1 * pow2_recip(s3);
 #pragma unroll
-                for (int i = 0; i < NE; ++i)
+                for (int rb = 0; rb < RB; ++rb) {
+                    if (rb >= u1.nrb) continue;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) ACC(acc[i], r) *= osc4 * d0f[i][r];
-                put_acc(X0, x0_plane, ld0, s4, u1);
+                    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) ACC(acc[rb * NB + nb], r) *= d0f[rb * NB + nb][r];
+                }
+                put_acc(X0, x0_plane, ld0, osc4 * s4, u1, std::false_type{});
             }
             ANIHIP_STAMP(trace, 17);
             __syncthreads();   // d act0 complete
             ANIHIP_STAMP(trace, 13);
             if (ka->want_grad) {
-                const float osc5 = fs->is0 / s4;
+                const float osc5 = fs->is0 * pow2_recip(s4);
                 // (wave-uniform) a single-pass tile in owner order over single tiles: the members' sum stays in registers (gsum) and
                 // only the last member needs the row pointers (LDS reads + 64-bit address arithmetic: 1.3 k clocks per item)
                 const bool regsum_tile = nact <= 4 && ka->owner == 1;
@@ -1245,7 +1329,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
                         }
                     } else {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) prev[t] = v4f{0.f, 0.f, 0.f, 0.f};
+                        for (int t = 0; t < 4; ++t) never_read(prev[t]);   // (the sums below take gsum under the same `regsum`)
                     }
                     v4f acc5[4];
                     ANIHIP_STAMP(trace, 19);
@@ -1301,7 +1385,7 @@ __global__ __launch_bounds__(64 * (8 / NB), 2) void k_mlp_fused(FusedArgs g)
         // every wave is done with the LDS of this item: the next one may stage its slabs
         __syncthreads();
         if (ka->want_grad && u1.nrb > 0) {
-            const float osc4 = fs->is1 / s3;
+            const float osc4 = fs->is1 * pow2_recip(s3);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 if (rb >= u1.nrb) continue;
