@@ -371,6 +371,40 @@ int anihip_block_hessian_prepare(void *stream, int64_t n_atoms, int64_t nnz, con
 int anihip_block_hessian_spmm(void *stream, int64_t n_atoms, int32_t m, const int64_t *coff, const int32_t *rows,
                               const float *ablocks, const float *x, float *y);
 
+/* Phonons from the block-sparse Hessian of a supercell (csrc/phonons.hip, torchani_amd/phonons.py).  The supercell is
+ * r1 x r2 x r3 copies of a primitive cell of n_basis atoms in cell-major order: atom ((l1 r2 + l2) r3 + l3) n_basis + b.
+ * All three functions compute in fp64, write every output element once without atomics (two calls give the same bits) and
+ * read nothing on the host.
+ *
+ * anihip_phonon_fold: the compact force constants.  coff, rows, ablocks are the outputs of anihip_block_hessian_prepare
+ * called with unit masses.  Compact entry e < m is (ent_b[e], ent_j[e]): basis atom b and the supercell atom j of a block of
+ * the home cell's column of b, i.e. the pair (b; b' = j mod n_basis, cell of j).  phi fp64 [m][3][3] gets
+ * phi[e][x][y] = mean over the r1 r2 r3 translations t (t3 fastest, summed in that order) of the symmetrized block
+ * d^2 E / d r_(b, t) x  d r_(b', cell of j + t mod repeats) y, each found by a binary search in its column's sorted rows;
+ * missing int32 [m] counts the translations whose block is not stored (they count as zero), defect fp64 [m] is the
+ * largest |block - mean| over translations and components.  An entry with ent_b or ent_j out of range gets zeros and
+ * missing = r1 r2 r3.  With boff int32 [n_basis + 1] (the entries of basis atom b are boff[b] .. boff[b + 1]) and diag_entry
+ * int32 [n_basis] (the entry (b; b, 0), -1: none) a second launch imposes the acoustic sum rule:
+ * phi[diag_entry[b]] = -(S + S^T) / 2, S the sum of b's other entries.  Both NULL: no sum rule.
+ *
+ * anihip_phonon_dynmat: D(q)_(3b+x),(3b'+y) = (m_b m_b')^-1/2 sum_e phi[e][x][y] exp(2 pi i q . nvec[e]) over the entries of
+ * (b, b'), which must be contiguous: poff int32 [n_basis^2 + 1] holds the run of pair b n_basis + b'.  q fp64 [n_q][3] in
+ * fractional reciprocal coordinates, nvec int32 [m][3] the lattice vector of each entry, masses fp64 [n_basis] (amu).  dmat:
+ * n_q x 3 n_basis x 3 n_basis complex numbers as interleaved (re, im) fp64 pairs.  dderiv (may be NULL), [n_q][3] such
+ * matrices: the derivatives with respect to the Cartesian wave vector (rad / Angstrom), each term times i rvec[e][a],
+ * rvec fp64 [m][3] = nvec times the primitive lattice (Angstrom).  The phase is sincospi(2 frac(q . nvec)).
+ *
+ * anihip_phonon_dos: dos[k] = sum_i weights[i] G_sigma(f_first + k df - freqs[i]), k < bins, G_sigma the unit-area Gaussian;
+ * freqs, weights fp64 [n_modes]. */
+int anihip_phonon_fold(void *stream, int32_t n_basis, int32_t r1, int32_t r2, int32_t r3, const int64_t *coff,
+                       const int32_t *rows, const float *ablocks, int32_t m, const int32_t *ent_b, const int32_t *ent_j,
+                       const int32_t *boff, const int32_t *diag_entry, double *phi, int32_t *missing, double *defect);
+int anihip_phonon_dynmat(void *stream, int32_t n_basis, int64_t n_q, const int32_t *poff, const int32_t *nvec,
+                         const double *phi, const double *rvec, const double *masses, const double *q, double *dmat,
+                         double *dderiv);
+int anihip_phonon_dos(void *stream, int64_t n_modes, const double *freqs, const double *weights, double f_first, double df,
+                      double sigma, int32_t bins, double *dos);
+
 /* L-BFGS geometry optimization of a batch of molecules (torchani_amd.geomopt, csrc/lbfgs.hip): one step of ASE's LBFGS
  * without line search for every molecule c of [n_mol][atoms_per_mol] that has not converged.  active uint8 [C][A] (0: padding
  * or fixed atom: its force is taken as zero, it never moves), coords fp32 [C][A][3] (x_k, moved IN PLACE to x_k+1), forces

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "md_observe.hip", "geom_constraints.hip", "saddle.hip", "irc.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "md_observe.hip", "geom_constraints.hip", "saddle.hip", "irc.hip", "phonons.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", "saddle_common.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -420,6 +420,11 @@ def lib() -> C.CDLL:
     L.anihip_irc_commit.argtypes = [vp, C.POINTER(Irc), vp, vp, i32]
     for name in ("anihip_irc_project", "anihip_irc_step", "anihip_irc_commit"):
         getattr(L, name).restype = C.c_int
+    L.anihip_phonon_fold.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_phonon_dynmat.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.anihip_phonon_dos.argtypes = [vp, i64, vp, vp, C.c_double, C.c_double, C.c_double, i32, vp]
+    for name in ("anihip_phonon_fold", "anihip_phonon_dynmat", "anihip_phonon_dos"):
+        getattr(L, name).restype = C.c_int
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
@@ -467,6 +472,7 @@ EXPORTED_SYMBOLS = [
     "anihip_saddle_workspace_bytes", "anihip_saddle_project", "anihip_saddle_step", "anihip_saddle_accept",
     "anihip_irc_workspace_bytes", "anihip_irc_project", "anihip_irc_step", "anihip_irc_commit",
     "anihip_aev_backward_flux", "anihip_md_heat_flux_workspace_bytes", "anihip_md_heat_flux",
+    "anihip_phonon_fold", "anihip_phonon_dynmat", "anihip_phonon_dos",
 ]
 
 

@@ -227,6 +227,58 @@ def block_hessian_spmm(op: BlockOperator, x: Tensor, out: tp.Optional[Tensor] = 
     return y
 
 
+def phonon_fold(op: BlockOperator, n_basis: int, repeats: tp.Sequence[int], ent_b: Tensor, ent_j: Tensor,
+                boff: tp.Optional[Tensor] = None, diag_entry: tp.Optional[Tensor] = None) -> tp.Tuple[Tensor, Tensor, Tensor]:
+    """anihip_phonon_fold: (phi fp64 [m, 3, 3], missing int32 [m], defect fp64 [m]) of the compact entries (ent_b, ent_j)
+    int32 [m] over the unit-mass operator of a supercell of repeats copies of n_basis atoms.  boff int32 [n_basis + 1] and
+    diag_entry int32 [n_basis] impose the acoustic sum rule."""
+    _require_cuda(op.coff, op.rows, op.ablocks, ent_b, ent_j, boff, diag_entry)
+    r1, r2, r3 = (int(r) for r in repeats)
+    m = int(ent_b.numel())
+    if op.n_atoms != n_basis * r1 * r2 * r3 or int(ent_j.numel()) != m:
+        raise ValueError("the operator does not belong to this supercell, or ent_b and ent_j differ in length")
+    for t in (ent_b, ent_j, boff, diag_entry):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError("the compact pattern must be contiguous int32 tensors")
+    dev = op.ablocks.device
+    phi = torch.empty((m, 3, 3), dtype=torch.float64, device=dev)
+    missing = torch.empty(m, dtype=torch.int32, device=dev)
+    defect = torch.empty(m, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().anihip_phonon_fold(_stream(), n_basis, r1, r2, r3, _ptr(op.coff), _ptr(op.rows), _ptr(op.ablocks), m,
+                                             _ptr(ent_b), _ptr(ent_j), _ptr(boff), _ptr(diag_entry), _ptr(phi), _ptr(missing),
+                                             _ptr(defect)))
+    return phi, missing, defect
+
+
+def phonon_dynmat(n_basis: int, poff: Tensor, nvec: Tensor, phi: Tensor, rvec: Tensor, masses: Tensor, q: Tensor,
+                  derivatives: bool = False) -> tp.Tuple[Tensor, tp.Optional[Tensor]]:
+    """anihip_phonon_dynmat: D complex128 [Q, 3n, 3n] (a view of the interleaved fp64 output, no copy) and, with derivatives,
+    dD / dk complex128 [Q, 3, 3n, 3n] for q fp64 [Q, 3]."""
+    _require_cuda(poff, nvec, phi, rvec, masses, q)
+    Q, d = int(q.shape[0]), 3 * n_basis
+    for t, dt in ((poff, torch.int32), (nvec, torch.int32), (phi, torch.float64), (rvec, torch.float64),
+                  (masses, torch.float64), (q, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError("anihip_phonon_dynmat takes contiguous int32 patterns and float64 values")
+    dmat = torch.empty((Q, d, d, 2), dtype=torch.float64, device=q.device)
+    dder = torch.empty((Q, 3, d, d, 2), dtype=torch.float64, device=q.device) if derivatives else None
+    _lib.check(_lib.lib().anihip_phonon_dynmat(_stream(), n_basis, Q, _ptr(poff), _ptr(nvec), _ptr(phi), _ptr(rvec),
+                                               _ptr(masses), _ptr(q), _ptr(dmat), _ptr(dder)))
+    return torch.view_as_complex(dmat), (None if dder is None else torch.view_as_complex(dder))
+
+
+def phonon_dos(freqs: Tensor, weights: Tensor, f_first: float, df: float, sigma: float, bins: int) -> Tensor:
+    """anihip_phonon_dos: fp64 [bins], sum_i weights[i] G_sigma(f_first + k df - freqs[i]) for freqs, weights fp64 [M]."""
+    _require_cuda(freqs, weights)
+    if freqs.dtype != torch.float64 or weights.dtype != torch.float64 or freqs.shape != weights.shape:
+        raise ValueError("freqs and weights must be float64 tensors of one shape")
+    freqs, weights = freqs.contiguous(), weights.contiguous()
+    out = torch.empty(int(bins), dtype=torch.float64, device=freqs.device)
+    _lib.check(_lib.lib().anihip_phonon_dos(_stream(), freqs.numel(), _ptr(freqs), _ptr(weights), float(f_first), float(df),
+                                            float(sigma), int(bins), _ptr(out)))
+    return out
+
+
 class AevEngine:
     """Neighbor rows + AEV forward/backward for one set of AEV constants."""
 

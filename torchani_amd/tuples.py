@@ -275,3 +275,105 @@ class EnergiesForcesStrainHessians(tp.NamedTuple):
     virial: Tensor
     strain_hessians: Tensor
     internal_strain: Tensor
+
+
+class Supercell(tp.NamedTuple):
+    """What phonons.supercell returns: r1 x r2 x r3 copies of a primitive cell of n atoms, N = r1 r2 r3 n atoms in cell-major
+    order (atom ((l1 r2 + l2) r3 + l3) n + b).  species [1, N], coordinates [1, N, 3] (built in float64 as tau_b + l . a, cast
+    once to the input dtype), cell [3, 3] (rows r_k a_k), basis int32 [N] (b) and lattice int32 [N, 3] (l) of every atom,
+    repeats, and the primitive data in float64: primitive_species [n], primitive_coordinates [n, 3], primitive_cell [3, 3]."""
+
+    species: Tensor
+    coordinates: Tensor
+    cell: Tensor
+    basis: Tensor
+    lattice: Tensor
+    repeats: tp.Tuple[int, int, int]
+    primitive_species: Tensor
+    primitive_coordinates: Tensor
+    primitive_cell: Tensor
+
+
+class ForceConstants(tp.NamedTuple):
+    """Compact force constants of a crystal (phonons.force_constants): entry e is the 3 x 3 block phi[e] = Phi(b; b', n)
+    (Hartree / Angstrom^2, float64) between basis atom b = ent_b[e] in some cell and basis atom b' = ent_bp[e] in the cell
+    displaced by the lattice vector nvec[e] (int32 [m, 3]; rvec = nvec @ cell in Angstrom).  The entries are sorted by (b, b'):
+    those of basis atom b are boff[b] .. boff[b + 1], those of the pair (b, b') poff[b n + b'] .. poff[b n + b' + 1] (int32).
+    cell [3, 3], positions [n, 3] and masses [n] (amu) are the primitive cell's, in float64.  exact: every perpendicular width
+    of the supercell exceeds four radial cutoffs, so D(q) is exact at any q and not only at commensurate ones.
+    translation_defect: the largest deviation of a translated block from its mean over max |phi|; n_missing: translated
+    blocks that were not stored.  energy (Hartree) and max_force (Hartree / Angstrom) are the supercell's (None when built
+    from a Hessian alone): a max_force that is not small means the frequencies are not those of a minimum."""
+
+    cell: Tensor
+    positions: Tensor
+    masses: Tensor
+    repeats: tp.Tuple[int, int, int]
+    boff: Tensor
+    poff: Tensor
+    ent_b: Tensor
+    ent_bp: Tensor
+    nvec: Tensor
+    rvec: Tensor
+    phi: Tensor
+    exact: bool
+    translation_defect: float
+    n_missing: int
+    energy: tp.Optional[Tensor] = None
+    max_force: tp.Optional[Tensor] = None
+
+    @property
+    def n_basis(self) -> int:
+        return int(self.masses.numel())
+
+
+class PhononModes(tp.NamedTuple):
+    """What phonons.modes returns for Q wave vectors of a crystal with n basis atoms: q [Q, 3] (fractional), frequencies
+    [Q, 3n] in the unit asked for (ascending, imaginary ones negative), eigenvalues [Q, 3n] of D(q) (Hartree / (amu
+    Angstrom^2)), eigenvectors complex128 [Q, 3n, 3n] (columns; None unless asked for) and group_velocities [Q, 3n, 3]
+    (Angstrom / fs; None unless asked for)."""
+
+    q: Tensor
+    frequencies: Tensor
+    eigenvalues: Tensor
+    eigenvectors: tp.Optional[Tensor]
+    group_velocities: tp.Optional[Tensor]
+
+
+class PhononThermodynamics(tp.NamedTuple):
+    """Harmonic thermodynamics per primitive cell at temperatures [T] (K): zero_point_energy (Hartree, a scalar tensor),
+    free_energy [T] (Helmholtz, Hartree), entropy [T] and heat_capacity [T] (C_v; Hartree / K), and n_imaginary, the number
+    of modes of the mesh with f <= 0, which are left out of every sum."""
+
+    temperatures: Tensor
+    zero_point_energy: Tensor
+    free_energy: Tensor
+    entropy: Tensor
+    heat_capacity: Tensor
+    n_imaginary: int
+
+
+class PhononMesh:
+    """Frequencies on a Monkhorst-Pack mesh (phonons.mesh): q [Q, 3], weights [Q] (sum 1, q and -q merged), frequencies
+    [Q, 3n] in ``unit`` and eigenvalues [Q, 3n] of D(q)."""
+
+    def __init__(self, q: Tensor, weights: Tensor, frequencies: Tensor, eigenvalues: Tensor, unit: str) -> None:
+        self.q = q
+        self.weights = weights
+        self.frequencies = frequencies
+        self.eigenvalues = eigenvalues
+        self.unit = unit
+
+    def dos(self, bins: int, f_max: tp.Optional[float] = None, sigma: tp.Optional[float] = None,
+            f_min: float = 0.0) -> tp.Tuple[Tensor, Tensor]:
+        """(centres [bins], g [bins]) of the Gaussian-smeared density of states g(f) = sum_{q, nu} w_q G_sigma(f - f_{q nu})
+        per primitive cell and frequency unit, on the regular centres f_min + (k + 1/2) (f_max - f_min) / bins.  f_max
+        defaults to 1.05 x the largest frequency, sigma to two bin widths."""
+        from . import phonons
+
+        return phonons.dos(self, bins, f_max=f_max, sigma=sigma, f_min=f_min)
+
+    def thermodynamics(self, temperatures) -> PhononThermodynamics:
+        from . import phonons
+
+        return phonons.thermodynamics(self, temperatures)
