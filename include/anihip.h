@@ -1208,6 +1208,75 @@ int anihip_md_heat_flux(void *stream, const anihip_md_params *params, const floa
                         const int32_t *species, const float *velocities, const float *flux_atoms, double *flux,
                         void *workspace, size_t workspace_bytes);
 
+/* The multistate Bennett acceptance ratio estimator (MBAR; binless WHAM is the same equations) on recorded series
+ * (torchani_amd.md.MBAR; csrc/mbar.hip).  K thermodynamic states, N samples pooled from all of them, N_k of them drawn in state
+ * k (N_k = 0: a state that was not sampled, a target).  In the STRUCTURED mode a state is an inverse temperature and one
+ * restraint row per CV column, a sample its potential energy E_n and its CV values s_nr, and the reduced potential is
+ *   u_k(x_n) = beta_k (E_n + sum_r 1/2 k_kr e^2),   e = max(0, |d| - hw_kr),   d = s_nr - c_kr
+ * with d wrapped into [-pi, pi) for a column of kind ANIHIP_MD_CV_DIHEDRAL, the sum over r in ascending order from 0: the
+ * restraint energy of anihip_md_bias_apply, operation for operation.  In the DENSE mode (u_kn not null) u_k(x_n) = u_kn[k][n].
+ * The N x K matrix never exists in the structured mode.  The fields of the struct, device pointers unless marked HOST:
+ *   n_samples (HOST) N >= 1;  n_states (HOST) K >= 1;  n_cvs (HOST) R in 0 .. ANIHIP_MD_BIAS_MAX_CVS
+ *   beta       fp64 [K]        1 / Hartree                  n_k     fp64 [K]   counts >= 0, at least one > 0
+ *   restraint  fp64 [K][R][3]  (center, k >= 0, half_width >= 0)       cv_kind int32 [R]  ANIHIP_MD_CV_*
+ *   energy     fp64 [N] or NULL (zeros)                     cv      fp64 [N][R]
+ *   u_kn       fp64 [K][N] or NULL; when given, beta, restraint, cv_kind, energy and cv are not read
+ *   status     int32 [1]  OUT: 0, or ANIHIP_MBAR_BAD_* bits.  anihip_mbar_iterate and anihip_mbar_log_weights first check what
+ *              they are about to read (every table, and the samples of the call) and rewrite status; a call that leaves it
+ *              non-zero writes NOTHING else to its outputs.
+ *
+ * anihip_mbar_iterate runs n_iter >= 1 self-consistent iterations from f_in fp64 [K] without a host read, three launches
+ * each, and leaves the last f in f_out fp64 [K] (may be f_in) and max_k |f' - f| of the last iteration in delta fp64 [1]:
+ *   launch 1   d_n = lse over the states with N_j > 0 of (ln N_j + f_j - u_j(x_n)), for every n.  Two samples per thread; the
+ *              state table is staged in LDS in tiles of at most 32 KB (sized from the LDS of a CU, not from K) and read by
+ *              broadcast; one running (max, sum) pair per sample, one exp per (state, sample)
+ *   launch 2   a workgroup owns the samples c S .. c S + S - 1 of chunk c, S = min(2048, 64 floor(6144 / (2 + R') / 64)) with R' = R rounded up to 0, 1, 2, 4, 8 or 16, staged in
+ *              LDS; its waves deal the states, a wave holds a state's row in registers and walks the chunk twice: the
+ *              maximum m of -u_k(x_n) - d_n, then the sum s of exp(. - m), lane l taking the samples l, l + 64, ... and the
+ *              lanes reduced by xor butterflies.  (m, s) goes to workspace[c][k]
+ *   launch 3   one workgroup: M_k = max_c m, f'_k = -(M_k + ln sum_c s exp(m - M_k)) with c ascending, then f'_k - f'_0
+ * fp64 throughout, every log-sum-exp against a maximum, no floating-point atomics, every sum in a fixed order: two calls on
+ * the same input give the same bits.
+ *
+ * anihip_mbar_log_weights with target = a state index, or ANIHIP_MBAR_TARGET_EXTERNAL and the state given as target_beta fp64 [1]
+ * and target_restraint fp64 [R][3] (dense mode: its row target_u fp64 [N]): out fp64 [n_count] = -u_t(x_n) - d_n - ln Z for
+ * n_first <= n < n_first + n_count, with d_n from f as in launch 1 and ln Z the log-sum-exp over ALL N samples (chunks of 1024,
+ * combined in chunk order): the log-sum-exp of the N log weights is 0 whatever f.  With ANIHIP_MBAR_TARGET_ALL: out fp64
+ * [n_count][K] = f_k - u_k(x_n) - d_n for every state, normalized when f is self-consistent; only the slab is evaluated (the
+ * host accumulates W^T W over slabs).  workspace: anihip_mbar_workspace_bytes bytes (0 + anihip_last_error() for a bad problem),
+ * the same for both.
+ *
+ * anihip_mbar_histogram: log weights fp64 [N] binned along one or two columns (HOST: columns, lo, hi, bins, one per column)
+ * of cv fp64 [N][cv_stride].  A sample is in range when lo <= s < hi in every column, its bin min(bins - 1, (int)((s - lo) bins
+ * / (hi - lo))), the first column the slow index; a NaN weight is out of range.  out fp64 [bins_0 bins_1] = lse of the log weights
+ * of the bin (-inf when empty), counts int64 the samples per bin; both OVERWRITTEN.  Bin maxima by integer atomics on an
+ * order-preserving key, then sums against them per chunk of samples, the chunks added in ascending order: the same bits at
+ * every call.  At most ANIHIP_MBAR_MAX_BINS bins in all. */
+#define ANIHIP_MBAR_BAD_COUNTS 1    /* a count that is negative or not finite, or no count above 0 */
+#define ANIHIP_MBAR_BAD_SAMPLES 2   /* an energy, a CV value or a dense u that is not finite */
+#define ANIHIP_MBAR_BAD_STATES 4    /* beta or a restraint row not finite, k or half_width < 0, a kind that is none of the three */
+#define ANIHIP_MBAR_TARGET_EXTERNAL (-1)
+#define ANIHIP_MBAR_TARGET_ALL (-2)
+#define ANIHIP_MBAR_MAX_BINS 4096
+typedef struct {
+    int64_t n_samples;
+    int32_t n_states, n_cvs;
+    const double *beta, *n_k, *restraint;
+    const int32_t *cv_kind;
+    const double *energy, *cv, *u_kn;
+    int32_t *status;
+} anihip_mbar;
+size_t anihip_mbar_workspace_bytes(const anihip_mbar *problem);
+int anihip_mbar_iterate(void *stream, const anihip_mbar *problem, const double *f_in, int32_t n_iter, double *f_out,
+                        double *delta, void *workspace, size_t workspace_bytes);
+int anihip_mbar_log_weights(void *stream, const anihip_mbar *problem, const double *f, int32_t target, const double *target_beta,
+                            const double *target_restraint, const double *target_u, int64_t n_first, int64_t n_count,
+                            double *out, void *workspace, size_t workspace_bytes);
+size_t anihip_mbar_histogram_workspace_bytes(int64_t n_samples, int32_t n_bins);
+int anihip_mbar_histogram(void *stream, int64_t n_samples, const double *log_weights, const double *cv, int32_t cv_stride,
+                          int32_t n_columns, const int32_t *columns, const double *lo, const double *hi, const int32_t *bins,
+                          double *out, int64_t *counts, void *workspace, size_t workspace_bytes);
+
 /* ---------------------------------------------------------------------------------------------
  * Per-species MLP ensemble: replaces mnp::run (csrc/mnp.cpp:238-265; forward :32-136, input-gradient
  * backward :138-232) and BmmEnsemble (nn/_infer.py:61-216).

@@ -14,7 +14,7 @@ import typing as tp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TORCHANI_AMD_LIB") or os.path.join(_HERE, "libanihip.so")
-SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "md_observe.hip", "geom_constraints.hip", "saddle.hip", "irc.hip", "phonons.hip"]
+SOURCES = ["api.hip", "nbr.hip", "aev.hip", "aev_generic.hip", "aev_hess.hip", "mlp.hip", "mlp_fused.hip", "mlp_prep.hip", "pair.hip", "pack.hip", "train.hip", "hess_sparse.hip", "hess_modes.hip", "lbfgs.hip", "md.hip", "md_bias.hip", "md_sites.hip", "md_observe.hip", "geom_constraints.hip", "saddle.hip", "irc.hip", "phonons.hip", "mbar.hip"]
 HEADERS = ["anihip_common.h", "aev_gen.h", "hess_rows.h", "train.h", "mlp_fused.h", "mlp_prep.h", "md_sums.h", "md_cv.h", "saddle_common.h", os.path.join("..", "..", "include", "anihip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared"]
 
@@ -65,6 +65,9 @@ SADDLE_MAX_COORDS = 768   # ANIHIP_SADDLE_MAX_COORDS
 SADDLE_BAD_TABLE, SADDLE_NONFINITE, SADDLE_NO_BRACKET = 1, 2, 4   # ANIHIP_SADDLE_*
 IRC_BAD_TABLE, IRC_NONFINITE, IRC_NO_ROOT = 1, 2, 4   # ANIHIP_IRC_* (status bits)
 IRC_RUNNING, IRC_MINIMUM, IRC_ENERGY_ROSE, IRC_PATH_FULL = 0, 1, 2, 3   # ANIHIP_IRC_* (reasons; 0: not done)
+MBAR_BAD_COUNTS, MBAR_BAD_SAMPLES, MBAR_BAD_STATES = 1, 2, 4   # ANIHIP_MBAR_BAD_*
+MBAR_TARGET_EXTERNAL, MBAR_TARGET_ALL = -1, -2   # ANIHIP_MBAR_TARGET_*
+MBAR_MAX_BINS = 4096   # ANIHIP_MBAR_MAX_BINS
 
 
 def md_group_scratch_bytes(n_mol: int, atoms_per_mol: int) -> int:
@@ -214,6 +217,13 @@ class Irc(C.Structure):
                 ("arc_lengths", C.c_void_p), ("n_points", C.c_void_p), ("reason", C.c_void_p), ("status", C.c_void_p),
                 ("path_coords", C.c_void_p), ("path_energies", C.c_void_p), ("path_arcs", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class Mbar(C.Structure):
+    """anihip_mbar (include/anihip.h)."""
+    _fields_ = [("n_samples", C.c_int64), ("n_states", C.c_int32), ("n_cvs", C.c_int32),
+                ("beta", C.c_void_p), ("n_k", C.c_void_p), ("restraint", C.c_void_p), ("cv_kind", C.c_void_p),
+                ("energy", C.c_void_p), ("cv", C.c_void_p), ("u_kn", C.c_void_p), ("status", C.c_void_p)]
 
 
 class MlpShape(C.Structure):
@@ -425,6 +435,16 @@ def lib() -> C.CDLL:
     L.anihip_phonon_dos.argtypes = [vp, i64, vp, vp, C.c_double, C.c_double, C.c_double, i32, vp]
     for name in ("anihip_phonon_fold", "anihip_phonon_dynmat", "anihip_phonon_dos"):
         getattr(L, name).restype = C.c_int
+    L.anihip_mbar_workspace_bytes.restype = sz
+    L.anihip_mbar_workspace_bytes.argtypes = [C.POINTER(Mbar)]
+    L.anihip_mbar_iterate.argtypes = [vp, C.POINTER(Mbar), vp, i32, vp, vp, vp, sz]
+    L.anihip_mbar_log_weights.argtypes = [vp, C.POINTER(Mbar), vp, i32, vp, vp, vp, i64, i64, vp, vp, sz]
+    L.anihip_mbar_histogram_workspace_bytes.restype = sz
+    L.anihip_mbar_histogram_workspace_bytes.argtypes = [i64, i32]
+    L.anihip_mbar_histogram.argtypes = [vp, i64, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(i32), vp, vp, vp, sz]
+    for name in ("anihip_mbar_iterate", "anihip_mbar_log_weights", "anihip_mbar_histogram"):
+        getattr(L, name).restype = C.c_int
     for name in ("anihip_md_drift", "anihip_md_kick", "anihip_md_remove_drift", "anihip_md_noise",
                  "anihip_md_constrain_drift", "anihip_md_constrain_kick", "anihip_md_project_velocities",
                  "anihip_md_barostat", "anihip_md_group_terms", "anihip_md_barostat_groups", "anihip_md_rp_drift",
@@ -473,6 +493,8 @@ EXPORTED_SYMBOLS = [
     "anihip_irc_workspace_bytes", "anihip_irc_project", "anihip_irc_step", "anihip_irc_commit",
     "anihip_aev_backward_flux", "anihip_md_heat_flux_workspace_bytes", "anihip_md_heat_flux",
     "anihip_phonon_fold", "anihip_phonon_dynmat", "anihip_phonon_dos",
+    "anihip_mbar_workspace_bytes", "anihip_mbar_iterate", "anihip_mbar_log_weights", "anihip_mbar_histogram_workspace_bytes",
+    "anihip_mbar_histogram",
 ]
 
 

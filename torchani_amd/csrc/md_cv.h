@@ -13,8 +13,12 @@ struct Cv {
     double s, g[4][3];
 };
 
+// d less `period` times the number of turns that bring d into [-pi, pi): period = 2 pi wraps a difference of dihedrals, period = 0
+// leaves d as it is (a loop over columns of mixed kinds selects by the value, without a branch per column)
+__device__ __forceinline__ double cv_wrap_by(double d, double period) { return d - period * floor((d + CV_PI) / CV_TWO_PI); }
+
 // a difference of dihedrals brought into [-pi, pi)
-__device__ __forceinline__ double cv_wrap(double d) { return d - CV_TWO_PI * floor((d + CV_PI) / CV_TWO_PI); }
+__device__ __forceinline__ double cv_wrap(double d) { return cv_wrap_by(d, CV_TWO_PI); }
 
 __device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 

@@ -27,6 +27,8 @@ them, at most two launches, and a spread behind them, one.
 ``attach(observer)`` samples a trajectory on the device inside ``step()`` (md_observe.py, csrc/md_observe.hip): ``TimeSeries``,
 ``Trajectory``, ``RadialDistribution``, ``MeanSquaredDisplacement``, ``VelocityAutocorrelation``, ``HeatFlux`` and
 ``HeatFluxAutocorrelation`` (the last two evaluate the model once more per sample).
+``MBAR`` (md_mbar.py, csrc/mbar.hip) turns the series of umbrella windows and temperature ladders into free energies, potentials
+of mean force and averages reweighted to states that were not sampled, on the device.
 """
 from __future__ import annotations
 
@@ -40,6 +42,7 @@ from torch import Tensor
 from . import _lib
 from .md_bias import (CV, BiasTables, DeviceBias, Metadynamics, Restraint, Site, SiteTables, angle, build_bias_tables,  # noqa: F401
                       build_site_tables, center, coordination, dihedral, distance)
+from .md_mbar import MBAR, ThermodynamicStates  # noqa: F401
 from .md_observe import (HeatFlux, HeatFluxAutocorrelation, MeanSquaredDisplacement, Observer,  # noqa: F401
                          RadialDistribution, TimeSeries, Trajectory, VelocityAutocorrelation)
 

@@ -173,6 +173,15 @@ class ReactionPaths(tp.NamedTuple):
     reasons: Tensor
 
 
+class PMF(tp.NamedTuple):
+    """What md.MBAR.pmf returns: free_energy (float64, in kT, the minimum at 0, inf in empty bins) of shape [bins] or
+    [bins_0, bins_1], edges (a tuple of one float64 tensor [bins + 1] per column) and counts (int64, the samples per bin)."""
+
+    free_energy: Tensor
+    edges: tp.Tuple[Tensor, ...]
+    counts: Tensor
+
+
 class TorsionScan(tp.NamedTuple):
     """What geomopt.torsion_scan returns for M molecules and K angles: angles [K] (rad, the targets), energies [M, K]
     (float64, Hartree) of the relaxed geometries coordinates [M, K, A, 3], converged (bool [M, K]) and torques [M, K]
